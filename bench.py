@@ -18,6 +18,17 @@ CHOLMOD factorize/solve). The timed region starts with everything resident in
 HBM; steps continue the solve from the seed (no artificial repetition of a
 converged state).
 
+A plain run sets the problem up, warms up, times the --steps steps and prints the line: metric, value,
+unit, higher_is_better, dtype, ms_per_step (and the problem's sizes and the solver's counters). Everything
+else it measures takes runs of its own and comes with --full only: the board kernel's roofline and MFMA
+figures (event-timed steps behind the timed ones), the full solves, optimizer_callback() times, the steps
+without the Jacobian stream, the other BASELINE.json configurations, the CPU baseline and, at N > 1, the
+per-rank figures. --no-cpu-baseline, --no-full-solve and --no-configs leave parts of --full out.
+
+--dump-outputs DIR writes what the timed steps computed, as of the last one, into DIR/<name>.npy
+(float64): b_packed (the state), x (the residuals) and J_values (the CSR Jacobian's values), the last two
+as a fixed sample where they are large (dump_outputs()). At N > 1: rank 0's b_packed.
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -42,11 +53,15 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--cameras", type=int, default=8)
     ap.add_argument("--frames",  type=int, default=1000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline figure (roofline, full solves, configs[], CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed in their last step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline-iterations", type=int, default=4)
-    ap.add_argument("--no-full-solve", action="store_true")
+    ap.add_argument("--no-full-solve", action="store_true", help="with --full: skip the full solves and the callback times")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the other single-GPU BASELINE.json configurations (the line's configs[])")
+                    help="with --full: skip the other single-GPU BASELINE.json configurations (the line's configs[])")
     ap.add_argument("--only-config", default=None,
                     help="dev: time just this entry of configs[] (1, 2, 3, 4 or 5) and print it instead of the line")
     ap.add_argument("--sharded", action="store_true",
@@ -313,7 +328,8 @@ def spawn_ranks(ngpus):
     import socket
     import subprocess
     import torch
-    if torch.cuda.device_count() < ngpus and not ONE_DEVICE:
+    # (with ONE_DEVICE the launcher itself never opens the GPU: the ranks are the only processes that do)
+    if not ONE_DEVICE and torch.cuda.device_count() < ngpus:
         print(f"bench.py: --gpus {ngpus} but only {torch.cuda.device_count()} GPU(s) are visible", file=sys.stderr)
         return 2
     with socket.socket() as sk:
@@ -403,6 +419,84 @@ def main():
     sync_all()
     dt = time.perf_counter() - t0
     assert n == args.steps
+
+    dt_rank = dt
+    if sharded:
+        t = torch.tensor([dt], dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, problem, sharded)
+
+    result = dict(
+        metric  = "LM (dog-leg) iterations/sec, 8-cam x 1000-frame OPENCV8 calibration",
+        value   = args.steps/dt,
+        unit    = "iterations/s",
+        n_gpus  = world,
+        steps   = args.steps,
+        warmup  = args.warmup,
+        ms_per_step = 1e3*dt/args.steps,
+        higher_is_better = True,
+        scaling = "strong",
+        vs_baseline = None,
+        dtype   = "f64",
+        data    = "synthetic",
+        config  = dict(workload = workload,
+                       Nstate = problem.Nstate_global, Nmeasurements = problem.Nmeas_global,
+                       Nnz_J = problem.Nnz_global,
+                       parallelism = "single GPU" if not sharded else f"frames sharded over {world} GPU(s), one process per GPU, 2 {'host-staged (validation)' if ONE_DEVICE else 'RCCL'} all-reduces per trial step: [S|r|g_S||x|^2] ({problem.problem.Nstate} state variables: Nc^2+2Nc+2 doubles) and 4 scalars"),
+    )
+    if ONE_DEVICE:
+        result["transport"] = "host shared memory, all ranks on ONE device (MRCAL_AMD_BENCH_ONE_DEVICE=1): a check of the multi-rank path, NOT a measurement"
+    if args.full:
+        full_measurements(args, result, problem, oi, tr, sync_all, sharded, rank, world, dt_rank, torch,
+                          dist if sharded else None)
+    else:
+        st = problem.solver_stats()
+        result["solver"] = dict(evaluations = st["Nevaluations"], factorizations = st["Nfactorizations"],
+                                **({"collectives": st["Ncollectives"]} if sharded else {}))
+
+    problem.close()
+    if sharded:
+        dist.barrier()
+        dist.destroy_process_group()
+    if rank == 0:
+        # the ONE line, and the last thing on stdout (RCCL prints its banner at teardown)
+        sys.stdout.flush()
+        print(json.dumps(result), flush=True)
+    if sharded:
+        # RCCL writes a version banner to stdout when the process exits: keep the JSON line the last one
+        devnull = os.open(os.devnull, os.O_WRONLY)
+        os.dup2(devnull, 1)
+
+
+# --dump-outputs: at most this many float64 values per array (x: 24 MB, J's values: 24 MB); a larger array is
+# written as a fixed sample of its entries
+DUMP_MAX_VALUES = 3_000_000
+
+def dump_outputs(path, problem, sharded):
+    """What a caller of the timed path receives after its last step, as float64 .npy files: the state b_packed and,
+    on one GPU, the residuals x and the CSR Jacobian's values (J_values) at that state. An array of more than
+    DUMP_MAX_VALUES entries is written as the entries at sorted(numpy.random.default_rng(0).choice(size,
+    DUMP_MAX_VALUES, replace=False)): positions that depend on the array's size alone, the same in every run"""
+    import numpy as np
+    def sample(a):
+        if a.size <= DUMP_MAX_VALUES:
+            return a
+        return a[np.sort(np.random.default_rng(0).choice(a.size, size=DUMP_MAX_VALUES, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    out = dict(b_packed = problem.b_packed())
+    if not sharded:
+        out["x"] = sample(problem.x())
+        out["J_values"] = sample(problem.J().data)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def full_measurements(args, result, problem, oi, tr, sync_all, sharded, rank, world, dt_rank, torch, dist):
+    """--full: everything besides the headline figure, added to result. Runs after the timed steps (and after
+    --dump-outputs has read their state)"""
     # the dominant kernel's own duration: HIP event pairs around EVERY board launch of EXTRA further trial steps of
     # the same solve, behind the timed ones (as configs[] does)
     EXTRA = 16
@@ -411,12 +505,6 @@ def main():
     sync_all()
     nlaunch, ktot_ms, kmin_ms, kmax_ms = problem.jacobian_timing_end()
     TIMED_EVERY = 1
-
-    dt_rank = dt
-    if sharded:
-        t = torch.tensor([dt], dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
 
     st = problem.solver_stats()
     per_rank = None
@@ -481,23 +569,7 @@ def main():
     except Exception:
         mfma = None
 
-    result = dict(
-        metric  = "LM (dog-leg) iterations/sec, 8-cam x 1000-frame OPENCV8 calibration",
-        value   = args.steps/dt,
-        unit    = "iterations/s",
-        n_gpus  = world,
-        steps   = args.steps,
-        warmup  = args.warmup,
-        ms_per_step = 1e3*dt/args.steps,
-        higher_is_better = True,
-        scaling = "strong",
-        vs_baseline = None,
-        dtype   = "f64",
-        data    = "synthetic",
-        config  = dict(workload = workload,
-                       Nstate = problem.Nstate_global, Nmeasurements = problem.Nmeas_global,
-                       Nnz_J = problem.Nnz_global,
-                       parallelism = "single GPU" if not sharded else f"frames sharded over {world} GPU(s), one process per GPU, 2 {'host-staged (validation)' if ONE_DEVICE else 'RCCL'} all-reduces per trial step: [S|r|g_S||x|^2] ({problem.problem.Nstate} state variables: Nc^2+2Nc+2 doubles) and 4 scalars"),
+    result.update(
         roofline = dict(bound = "hbm",
                         kernel = "board_kernel<OPENCV,8,J,Gram> (residuals x, CSR Jacobian values, per-observation Gram on the FP64 matrix cores)",
                         achieved = achieved, peak = HBM_PEAK_GBS, unit = "GB/s",
@@ -525,8 +597,6 @@ def main():
         result["consistent"] = (len(set(r["collectives"] for r in per_rank)) == 1 and
                                 result["comm_world_observed"] in ([world], [-1]))
 
-    if ONE_DEVICE:
-        result["transport"] = "host shared memory, all ranks on ONE device (MRCAL_AMD_BENCH_ONE_DEVICE=1): a check of the multi-rank path, NOT a measurement"
     if rank == 0 and not args.no_full_solve and not sharded:
         # the second half of the metric: one full solve, seed to return, outlier rejection included - the drop-in
         # optimize() (round 6), the resident solve beside it, and both again in the product's no-stream mode
@@ -556,19 +626,6 @@ def main():
         if not sharded and not args.no_cpu_baseline:
             cb = cpu_baseline(oi, args.cpu_baseline_iterations)
         result["cpu_baseline"] = cb
-
-    problem.close()
-    if sharded:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        # the ONE line, and the last thing on stdout (RCCL prints its banner at teardown)
-        sys.stdout.flush()
-        print(json.dumps(result), flush=True)
-    if sharded:
-        # RCCL writes a version banner to stdout when the process exits: keep the JSON line the last one
-        devnull = os.open(os.devnull, os.O_WRONLY)
-        os.dup2(devnull, 1)
 
 
 if __name__ == "__main__":

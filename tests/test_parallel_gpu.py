@@ -22,6 +22,9 @@ pytestmark = pytest.mark.gpu
 
 
 SPLINED = "LENSMODEL_SPLINED_STEREOGRAPHIC_order=3_Nx=11_Ny=8_fov_x_deg=120"
+# the most ranks a test starts on the one device. The machines the GPU suite is checked on allow at most 6 processes with
+# the GPU open; with the test's own process this makes 5. (The metric-size cases ran over 8 ranks until round 6)
+MAX_RANKS = 4
 
 
 def _problem(amd_api, lensmodel="LENSMODEL_OPENCV8"):
@@ -287,26 +290,26 @@ def _rccl_world2_worker(rank, world, port, out_path):
         rec = dict(what=f"tests/test_parallel_gpu.py _rccl_world2_worker at world {world}: ShardedProblem(_driver='rccl'), one process per rank and device; "
                         "the all-reduces are the library's own (csrc/comm.cpp) timed alone on a stream with event pairs",
                    world=world, devices=torch.cuda.device_count(), device_name=torch.cuda.get_device_name(0), ranks=gathered)
-        for d in ("gpurun_out", "profiles"):
-            try:
-                with open(os.path.join(ROOT, d, f"r06_rccl_world{world}_measured.json"), "w") as fjson: json.dump(rec, fjson, indent=1)
-            except OSError:
-                pass
+        with open(os.path.join(os.path.dirname(out_path), f"rccl_world{world}_measured.json"), "w") as fjson:
+            json.dump(rec, fjson, indent=1)
         print(json.dumps(rec, indent=1))
     sp.close()
     dist.barrier()
     dist.destroy_process_group()
 
 
-def test_rccl_world2_on_two_devices(amd, tmp_path):
+def test_rccl_world2_on_two_devices(request, tmp_path):
     """The product path with MORE THAN ONE RANK: two processes, two GPUs, ShardedProblem(_driver="rccl") - the
-    collectives are ncclAllReduce calls issued by libmrcal_amd.so between its own kernel launches. Skips itself
-    on a one-GPU box (the boxes of this pool); runs the first time it finds two devices. Same optimum, outliers
+    collectives are ncclAllReduce calls issued by libmrcal_amd.so between its own kernel launches. Skips itself,
+    before anything else (the package fixture included), where fewer than two devices are visible; runs the first
+    time it finds two. Same optimum, outliers
     and cost as the single-GPU solve (the sums over two shards differ from the unsharded ones in the last bits,
     so the trajectories may differ by rounding: compared to the solve's own tolerance, not bit for bit)"""
     import torch
-    if torch.cuda.device_count() < 2:
-        pytest.skip(f"needs 2 GPUs, this box has {torch.cuda.device_count()}")
+    ndev = torch.cuda.device_count()
+    if ndev < 2:
+        pytest.skip(f"needs 2 GPUs, found {ndev}")
+    amd = request.getfixturevalue("amd")
     import torch.multiprocessing as mp
     from mrcal_amd.resident import Problem
     oi = _problem(amd._api)
@@ -327,8 +330,8 @@ def test_rccl_world2_on_two_devices(amd, tmp_path):
 def test_rccl_worker_measures_at_world1(amd, tmp_path):
     """The worker of the two-device test above, at world 1 on the one device this pool's boxes have: the same code - the
     RCCL communicator, the sharded solve, the timed steps, the event-timed all-reduces - so that the measuring part is known
-    to run before a box with two devices ever sees it; its record (gpurun_out/ and profiles/r06_rccl_world1_measured.json)
-    is what one-rank collectives cost. The solve must be the single-GPU solve's bits (test_rccl_world1... says the same)"""
+    to run before a box with two devices ever sees it; its record (rccl_world1_measured.json beside the worker's output, printed
+    too) is what one-rank collectives cost. The solve must be the single-GPU solve's bits (test_rccl_world1... says the same)"""
     import torch.multiprocessing as mp
     from mrcal_amd.resident import Problem
     oi = _problem(amd._api)
@@ -342,7 +345,7 @@ def test_rccl_worker_measures_at_world1(amd, tmp_path):
     assert bool(r["replicated"]) and int(r["Noutliers"]) == s1["Noutliers_board"]
     assert np.array_equal(r["b"], b1)
     import json
-    rec = json.load(open(os.path.join(ROOT, "profiles", "r06_rccl_world1_measured.json")))
+    rec = json.load(open(tmp_path / "rccl_world1_measured.json"))
     assert rec["world"] == 1 and "allreduce" in rec["ranks"][0], rec["ranks"][0]
 
 
@@ -350,11 +353,11 @@ def test_rccl_worker_measures_at_world1(amd, tmp_path):
 def test_sharded_metric_size_outliers_against_the_references_record(amd, tmp_path):
     """since round 5's arithmetic the 8-rank solve of the metric's problem and the single-GPU
     solve mark 7843 outliers each but not the same 7843 (one corner at the k-sigma line falls the other way) - and nothing
-    said which of the two the REFERENCE's mask equals. Here both are solved on the inputs the record of the reference's own
-    mrcal_optimize() was made from (tests/golden/reference_solve_ns_seed0.npz: 80 s of one core, in the build container)
-    and both masks are compared with the recorded one: the counts must agree, whatever differs must be a handful of corners
+    said which of the two the REFERENCE's mask equals. (The sharded solve here has MAX_RANKS ranks on the one device.) Here
+    both are solved on the inputs the record of the reference's own mrcal_optimize() was made from
+    (tests/golden/reference_solve_ns_seed0.npz: 80 s of one CPU core) and both masks are compared with the recorded one: the counts must agree, whatever differs must be a handful of corners
     AT the line, and the rms must be the reference's to 1e-5 - and no higher - where the marks are identical. Which of the two (or both)
-    reproduces the reference's marks corner by corner is printed and recorded, not imposed: the sums of eight shards and of
+    reproduces the reference's marks corner by corner is printed, not imposed: the sums of several shards and of
     one GPU are both legitimate roundings of the same numbers"""
     import torch.multiprocessing as mp
     from mrcal_amd.resident import Problem
@@ -368,31 +371,23 @@ def test_sharded_metric_size_outliers_against_the_references_record(amd, tmp_pat
     s1 = amd.optimize(**o1)
     mask_1 = (o1["observations_board"][..., 2] < 0).ravel()
     mask_r = np.unpackbits(rec["outlier_mask_packed"])[:mask_1.size].astype(bool)
-    out = str(tmp_path / "host8.npz")
+    out = str(tmp_path / "hostn.npz")
     port = 29700 + (os.getpid() % 250)
-    mp.spawn(_host_worker, args=(8, port, out, "metric_size_recorded"), nprocs=8, join=True)
+    mp.spawn(_host_worker, args=(MAX_RANKS, port, out, "metric_size_recorded"), nprocs=MAX_RANKS, join=True)
     r = np.load(out)
-    mask_8 = r["outlier_mask"]
-    d1, d8 = int((mask_1 != mask_r).sum()), int((mask_8 != mask_r).sum())
+    mask_n = r["outlier_mask"]
+    d1, dn = int((mask_1 != mask_r).sum()), int((mask_n != mask_r).sum())
     rms_r = float(rec["rms_reproj_error__pixels"])
-    print(f"outliers: reference {int(mask_r.sum())}, single GPU {int(mask_1.sum())} ({d1} marks differ), 8 ranks {int(mask_8.sum())} ({d8} marks differ); "
-          f"rms reference {rms_r!r}, single GPU {s1['rms_reproj_error__pixels']!r}, 8 ranks {float(r['rms'])!r}")
-    import json
-    recd = dict(problem="8 cameras x 1000 frames OPENCV8, seed 0 (bench.py's), inputs made with the reference's library",
-                outliers=dict(reference=int(mask_r.sum()), single_gpu=int(mask_1.sum()), ranks8_host_transport=int(mask_8.sum())),
-                marks_differing_from_the_references=dict(single_gpu=d1, ranks8_host_transport=d8),
-                rms=dict(reference=rms_r, single_gpu=float(s1["rms_reproj_error__pixels"]), ranks8_host_transport=float(r["rms"])))
-    for d in ("gpurun_out", "profiles"):
-        try:
-            with open(os.path.join(ROOT, d, "r06_ns_sharded_outliers_vs_reference.json"), "w") as f: json.dump(recd, f, indent=1)
-        except OSError: pass
+    print(f"outliers: reference {int(mask_r.sum())}, single GPU {int(mask_1.sum())} ({d1} marks differ), {MAX_RANKS} ranks {int(mask_n.sum())} ({dn} marks differ); "
+          f"rms reference {rms_r!r}, single GPU {s1['rms_reproj_error__pixels']!r}, {MAX_RANKS} ranks {float(r['rms'])!r}")
     assert bool(r["replicated"])
-    assert abs(int(mask_1.sum()) - int(mask_r.sum())) <= 2 and abs(int(mask_8.sum()) - int(mask_r.sum())) <= 2
-    assert d1 <= 4 and d8 <= 4, (d1, d8)
-    assert min(d1, d8) == 0, "neither the single-GPU nor the 8-rank solve reproduces the reference's marks corner by corner"
-    # (observed: 0 and 0 marks differ - both solves reproduce the reference's 7843 corner by corner -, and the rms of either is
-    #  1.5e-6 BELOW the recorded one: at this seed the restated libdogleg stops a little earlier in OPENCV8's flat valley)
-    for d, rms in ((d1, float(s1["rms_reproj_error__pixels"])), (d8, float(r["rms"]))):
+    assert abs(int(mask_1.sum()) - int(mask_r.sum())) <= 2 and abs(int(mask_n.sum()) - int(mask_r.sum())) <= 2
+    assert d1 <= 4 and dn <= 4, (d1, dn)
+    assert min(d1, dn) == 0, f"neither the single-GPU nor the {MAX_RANKS}-rank solve reproduces the reference's marks corner by corner"
+    # (observed with 8 ranks in round 6, and again with 4: 0 and 0 marks differ - both solves reproduce the reference's 7843 corner
+    #  by corner -, and the rms of either is 1.5e-6 BELOW the recorded one (at 4 ranks the same rms as the single GPU's to the
+    #  last digit printed): at this seed the restated libdogleg stops a little earlier in OPENCV8's flat valley)
+    for d, rms in ((d1, float(s1["rms_reproj_error__pixels"])), (dn, float(r["rms"]))):
         assert abs(rms - rms_r) < (1e-5 if d == 0 else 1e-4)*rms_r
         assert rms <= rms_r*(1. + 1e-9)
 
@@ -603,7 +598,7 @@ def _host_worker(rank, world, port, out_path, which):
 
 
 @pytest.mark.parametrize("which,world", (("boards", 2), ("boards_splined", 2), ("everything", 2), ("everything", 3),
-                                         ("fewer_frames_than_ranks", 3), ("metric_size", 8)))
+                                         ("fewer_frames_than_ranks", 3), ("metric_size", MAX_RANKS)))
 def test_cpp_sharded_solve_over_the_host_transport(amd, tmp_path, which, world):
     """The PRODUCT solver with more than one rank on a one-GPU box: ShardedProblem(_driver="host") is the C++
     sharded solve - the device-controlled step with its two all-reduces, mark_outliers() with its three, the
@@ -632,8 +627,8 @@ def test_cpp_sharded_solve_over_the_host_transport(amd, tmp_path, which, world):
         assert (r["ranges"][:,3] > r["ranges"][:,2]).all() and (r["ranges"][:,5] > r["ranges"][:,4]).all()
         assert s1["Noutliers_board"] > 0
     assert int(r["Noutliers"]) == s1["Noutliers_board"]
-    # (the metric's problem: 7843 outliers out of 800 000 corners in both - but since round 5 not the same 7843: the
-    #  eight shards' sums and the one GPU's differ in their last bits, and with this round's arithmetic
+    # (the metric's problem, as observed over 8 ranks in round 6: 7843 outliers out of 800 000 corners in both - but not
+    #  the same 7843: the eight shards' sums and the one GPU's differ in their last bits, and with this round's arithmetic
     #  (-ffp-contract=on) ONE corner at the k-sigma line is an outlier in the one solve and its neighbour in the other.
     #  Both solves converge (expected improvement 1e-10 at the end of either: tools/exp/dbg_sharded8.py); their costs
     #  differ by that corner's 12 units of 3.5 million. The other cases mark the same corners: 1e-9)
@@ -658,7 +653,7 @@ def test_bench_multi_rank_path_on_one_device(world):
     env = dict(os.environ, MRCAL_AMD_BENCH_ONE_DEVICE="1", MRCAL_AMD_HOST_COMM_TIMEOUT="120")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"): env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "6", "--warmup", "2",
-                        "--cameras", "3", "--frames", "40"], env=env, capture_output=True, text=True, timeout=600)
+                        "--cameras", "3", "--frames", "40", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)

@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 has() { [[ " $parts " == *" $1 "* ]]; }
 
 if has bench; then
-    python $R/bench.py > $O/${tag}_bench.json 2> $O/${tag}_bench.err
+    python $R/bench.py --full > $O/${tag}_bench.json 2> $O/${tag}_bench.err
 fi
 if has stats; then
     rm -rf /tmp/prof_ns

@@ -12,6 +12,6 @@ print('ms/step %.4f  it/s %.0f  kernel_ms %.4f frac %.3f | stream frac %s poses 
 PY
 for k in $(seq 1 $reps); do
   for v in "$@"; do
-    echo "[$v] $(env $v python bench.py --no-cpu-baseline --no-configs 2>/dev/null | python /tmp/ab_fmt.py)"
+    echo "[$v] $(env $v python bench.py --full --no-cpu-baseline --no-configs 2>/dev/null | python /tmp/ab_fmt.py)"
   done
 done | tee $O/ab_ns_env.txt
