@@ -795,6 +795,40 @@ bool   mrcal_amd_csr_A_Jt_J_At(int Nrows, int Ncols, const int32_t* Jp, const in
 /* (min diag L / max diag L)^2, like cholmod_rcond() */
 double mrcal_amd_factorization_rcond  (mrcal_amd_factorization_t* f);
 
+/* ---- projection uncertainty: mrcal.projection_uncertainty() ---------------
+   Reference: mrcal/model_analysis.py:1192-1517 (projection_uncertainty), :560-870
+   (_propagate_calibration_uncertainty), :491-557 (the estimate of the observed
+   pixel uncertainty). The cross-reprojection methods only; "mean-pcam" is not
+   provided.
+   _create() computes, at the problem's current state, the k x k matrix C with
+       Var(q) = sigma^2 G(p) C G(p)^T
+   (G: the 2 x k gradient of a projection with respect to this camera's optimized
+   intrinsics, for rrp its extrinsics, and the 6 rows of
+   mrcal_amd_problem_drt_cross_reprojection()), all of it on the device: x and J at
+   the state, K, the factorization of J*^T J*, k right-hand sides solved there, C.
+   Only K (6 x Nstate) and a few small records cross PCIe. The problem may be
+   changed or destroyed afterwards: the context keeps C, the camera's intrinsics and
+   pose, and sigma.
+   observed_pixel_uncertainty <= 0: sigma is estimated from the board and point
+   measurements at the state (RMS / sqrt(1 - Nstate/Nmeasurements)).
+   NULL on failure (mrcal_amd_last_error(): the reference's messages: triangulated
+   points present, rrp on a moving camera, a singular J^T J, a shard, ...).
+   _evaluate(): p_cam (N,3) host, out (N,4) for the covariance (row-major 2x2),
+   (N,) for the two standard deviations. Results are the same bits on every call */
+#define MRCAL_AMD_UNCERTAINTY_CROSS_REPROJECTION_CCP     0
+#define MRCAL_AMD_UNCERTAINTY_CROSS_REPROJECTION_RRP_JFP 1
+#define MRCAL_AMD_UNCERTAINTY_COVARIANCE                 0
+#define MRCAL_AMD_UNCERTAINTY_WORSTDIRECTION_STDEV       1
+#define MRCAL_AMD_UNCERTAINTY_RMS_STDEV                  2
+typedef struct mrcal_amd_uncertainty mrcal_amd_uncertainty_t;
+mrcal_amd_uncertainty_t* mrcal_amd_uncertainty_create(mrcal_amd_problem_t* problem, int icam_intrinsics, int method,
+                                                      double observed_pixel_uncertainty);
+bool   mrcal_amd_uncertainty_evaluate(mrcal_amd_uncertainty_t* u, const double* p_cam, int N, bool atinfinity, int what,
+                                      double* out);
+/* the sigma in use: the caller's, or the estimate */
+double mrcal_amd_uncertainty_observed_pixel_uncertainty(const mrcal_amd_uncertainty_t* u);
+void   mrcal_amd_uncertainty_destroy(mrcal_amd_uncertainty_t* u);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,7 @@
 # Builds mrcal_amd/libmrcal_amd.so for gfx950 (MI355X). hipcc cross-compiles
 # without a GPU present.
 #
-# Round 6: every source is its own translation unit, compiled side by side (as many at a time as there are cores,
+# Round 6: every source is its own translation unit, compiled side by side (as many at a time as there are cores, at most 16;
 # JOBS=n to say otherwise) into csrc/_build/, then linked: 25 s on eight cores where the one command took 64 (the
 # solver's kernels were ONE 6800-line unit until then: solver_kernels.hip, now assembly.hip ... factorization_solve.hip).
 #
@@ -25,9 +25,10 @@ for a in "$@"; do
 done
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=on -Wall -Wno-unused-function -Wno-unused-value -Wno-unused-result $DEV"
-SOURCES="kernels.hip splined_kernels.hip project_kernels.hip cholesky_large.hip assembly_splined.hip schur.hip assembly.hip step.hip factorization_solve.hip cholesky_lds.hip uncertainty.hip
+SOURCES="kernels.hip splined_kernels.hip project_kernels.hip cholesky_large.hip assembly_splined.hip schur.hip assembly.hip step.hip factorization_solve.hip cholesky_lds.hip uncertainty.hip projection_uncertainty.hip
          problem.cpp solver.cpp cabi_layout.cpp factorization.cpp unproject.cpp comm.cpp cameramodel_io.cpp"
-JOBS=${JOBS:-$(nproc)}
+# (at most 16 by default: a build box may report many more cores than a command is given)
+JOBS=${JOBS:-$(( $(nproc) < 16 ? $(nproc) : 16 ))}
 mkdir -p $OBJ
 rm -f $OBJ/*.o $OBJ/*.failed
 pids=()

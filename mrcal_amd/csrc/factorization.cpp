@@ -275,23 +275,32 @@ int  mrcal_amd_factorization_Nstate(const mrcal_amd_factorization_t* f) { return
 // xt[i,:] = (JtJ)^-1 bt[i,:], i in [0,Nrhs). Host pointers, C-contiguous (Nrhs,Nstate)
 // The right-hand sides go up in batches and the solutions come down in batches: a copy to or from pageable
 // host memory per right-hand side is a synchronization each, more than the six kernels of a solve take
-static bool solve_batched(mrcal_amd_factorization_t* f, int sys, const double* bt, int Nrhs, double* xt)
+// How many right-hand sides go in one batch, and the batch buffers for that many
+static int batch_prepare(mrcal_amd_factorization_t* f, int Nrhs, size_t* part_per_rhs)
 {
     const size_t n = (size_t)f->nd.Nstate;
-    if(Nrhs <= 0) return true;
     // <= 32 MB of right-hand sides each way, <= 256 MB of scratch (y, r and the partial sums of every right-hand side)
     const size_t per_rhs = fsolve_batch_scratch_doubles(f->nd, 1);
-    const size_t part_per_rhs = per_rhs - (size_t)f->nd.NE - (size_t)f->nd.Nc;
+    *part_per_rhs = per_rhs - (size_t)f->nd.NE - (size_t)f->nd.Nc;
     size_t cap = std::min<size_t>((size_t)Nrhs, ((size_t)32 << 20)/(n*sizeof(double) + 1));
     cap = std::min<size_t>(cap, ((size_t)256 << 20)/(per_rhs*sizeof(double) + 1));
     const int BATCH = (int)std::max<size_t>(1, std::min<size_t>(cap, 16384));
     if(f->batch_capacity < BATCH)
     {
         double *rb = NULL, *sb = NULL, *sc = NULL;
-        if(!f->alloc(&rb, (size_t)BATCH*n) || !f->alloc(&sb, (size_t)BATCH*n) || !f->alloc(&sc, (size_t)BATCH*per_rhs)) return false;
+        if(!f->alloc(&rb, (size_t)BATCH*n) || !f->alloc(&sb, (size_t)BATCH*n) || !f->alloc(&sc, (size_t)BATCH*per_rhs)) return 0;
         f->release(f->d_rhs_batch); f->release(f->d_sol_batch); f->release(f->d_batch_scratch);
         f->d_rhs_batch = rb; f->d_sol_batch = sb; f->d_batch_scratch = sc; f->batch_capacity = BATCH;
     }
+    return BATCH;
+}
+static bool solve_batched(mrcal_amd_factorization_t* f, int sys, const double* bt, int Nrhs, double* xt)
+{
+    const size_t n = (size_t)f->nd.Nstate;
+    if(Nrhs <= 0) return true;
+    size_t part_per_rhs = 0;
+    const int BATCH = batch_prepare(f, Nrhs, &part_per_rhs);
+    if(BATCH <= 0) return false;
     for(int i0 = 0; i0 < Nrhs; i0 += BATCH)
     {
         const int nb = std::min(BATCH, Nrhs - i0);
@@ -457,3 +466,28 @@ double mrcal_amd_factorization_rcond(mrcal_amd_factorization_t* f)
 }
 
 } // extern "C"
+
+// Internal (not in include/mrcal_amd.h): solve_batched() for right-hand sides that are already on the device and
+// solutions that stay there. Queued on the factorization's stream (factorization_stream()); nothing is synchronized.
+// projection_uncertainty.hip builds its right-hand sides on the device and reduces the solutions there
+namespace mrcal_amd {
+hipStream_t factorization_stream(mrcal_amd_factorization_t* f) { return f->stream; }
+bool factorization_solve_device(mrcal_amd_factorization_t* f, int sys, const double* d_bt, int Nrhs, double* d_xt)
+{
+    const size_t n = (size_t)f->nd.Nstate;
+    if(Nrhs <= 0) return true;
+    if(sys < 0 || sys > FSOLVE_Pt) { set_error("unknown system %d", sys); return false; }
+    size_t part_per_rhs = 0;
+    const int BATCH = batch_prepare(f, Nrhs, &part_per_rhs);
+    if(BATCH <= 0) return false;
+    for(int i0 = 0; i0 < Nrhs; i0 += BATCH)
+    {
+        const int nb = std::min(BATCH, Nrhs - i0);
+        double* y    = f->d_batch_scratch;
+        double* r    = y + (size_t)BATCH*f->nd.NE;
+        double* part = r + (size_t)BATCH*f->nd.Nc;
+        HIP_TRY(launch_fsolve_sys_batch(f->nd, f->F, sys, d_bt + (size_t)i0*n, d_xt + (size_t)i0*n, nb, y, r, part, part_per_rhs, f->stream), return false);
+    }
+    return true;
+}
+} // namespace mrcal_amd

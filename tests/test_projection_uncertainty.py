@@ -1,0 +1,453 @@
+"""projection_uncertainty() / ProjectionUncertainty / worst_direction_stdev() (mrcal/model_analysis.py:398-489,
+491-557, 560-870, 1192-1517): the cross-reprojection methods with the propagation on the device
+(csrc/projection_uncertainty.hip).
+
+The checker is the reference's formula restated densely in numpy, fed only by the reference's own compiled code
+(oracle/_ref/libmrcal_ref.so through the ref_api fixture): J from its optimizer_callback, K from its
+drt_cross_reprojection__dbpacked (uncertainty.c), dq/dp and dq/dintrinsics from its mrcal_project, dR/dr from its
+mrcal_R_from_r_full. From these it builds dq/db (N,2,Nstate), unpacks it, and applies the two branches of
+_propagate_calibration_uncertainty() with np.linalg.solve. Without a GPU the reduced form sigma^2 G C G^T that the
+kernels implement is held to that dense propagation."""
+import ctypes as C
+import os
+import numpy as np
+import pytest
+
+from conftest import ROOT, relative_error
+from mrcal_amd.synthetic import make_calibration_problem, copy_inputs
+
+GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
+
+
+def skew(p):
+    p = np.asarray(p)
+    z = np.zeros(p.shape[:-1])
+    return np.stack((np.stack(( z,        -p[...,2],  p[...,1]), -1),
+                     np.stack(( p[...,2],  z,        -p[...,0]), -1),
+                     np.stack((-p[...,1],  p[...,0],  z       ), -1)), -2)
+
+
+def ref_R_from_r(ref, r):
+    """R (3,3) and dR/dr (3,3,3) from the reference's poseutils.c"""
+    f = ref.lib.lib.mrcal_R_from_r_full
+    f.restype = None
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    R = np.zeros((3,3)); dR = np.zeros((3,3,3)); r = np.ascontiguousarray(r, dtype=float)
+    f(R.ctypes.data, 0, 0, dR.ctypes.data, 0, 0, 0, r.ctypes.data, 0)
+    return R, dR
+
+
+def sigma_estimate(ref, oi, x):
+    """_observed_pixel_uncertainty_from_inputs() with measurements_board() / measurements_point()"""
+    ss, n = 0.0, 0
+    ob = oi.get("observations_board")
+    if ob is not None and np.size(ob):
+        i0 = ref.measurement_index_boards(0, **oi)
+        xb = x[i0:i0 + ref.num_measurements_boards(**oi)].reshape(ob.shape[:-1] + (2,))[ob[..., 2] > 0]
+        ss += np.sum(xb*xb); n += xb.size
+    op = oi.get("observations_point")
+    if op is not None and np.size(op):
+        i0 = ref.measurement_index_points(0, **oi)
+        xp = x[i0:i0 + ref.num_measurements_points(**oi)].reshape(len(op), 2)[op[:, 2] > 0]
+        ss += np.sum(xp*xp); n += xp.size
+    return np.sqrt(ss/n) / np.sqrt(1 - ref.num_states(**oi)/n)
+
+
+class Checker:
+    """The reference's projection_uncertainty() restated densely, on the reference's compiled code"""
+
+    def __init__(self, ref, oi, icam, method):
+        self.ref, self.oi, self.icam, self.method = ref, oi, icam, method
+        b, x, J, _ = ref.optimizer_callback(no_factorization=True, **oi)
+        self.x, self.J = x, J
+        self.Nstate = J.shape[1]
+        self.Nreg = ref.num_measurements_regularization(**oi)
+        self.scale = np.ones(self.Nstate); ref.unpack_state(self.scale, **oi)
+        rrp = method == "cross-reprojection-rrp-Jfp"
+        self.K = ref.drt_cross_reprojection__dbpacked(icam_intrinsics=(-1 if rrp else icam), **oi)   # packed
+        self.lensmodel = oi["lensmodel"]
+        self.intrinsics = oi["intrinsics"][icam]
+        self.istate_i = ref.state_index_intrinsics(icam, **oi)
+        self.Nsi = ref.num_intrinsics_optimization_params(**oi)
+        self.arg0 = 4 if not oi.get("do_optimize_intrinsics_core", True) else 0
+        self.icam_e = ref.corresponding_icam_extrinsics(icam, **oi) if rrp else -1
+        self.rt = oi["rt_cam_ref"][self.icam_e] if self.icam_e >= 0 else np.zeros(6)
+        self.istate_e = ref.state_index_extrinsics(self.icam_e, **oi) if self.icam_e >= 0 else None
+        self.R, self.dR = ref_R_from_r(ref, self.rt[:3])
+        self.sigma_est = sigma_estimate(ref, oi, x)
+
+    def G_pieces(self, p, atinfinity):
+        """dq/dintrinsics (N,2,Nsi), dq/drt_cam_ref (N,2,6) or None, dq/dpref skew(pref) and -dq/dpref (N,2,6)"""
+        ref = self.ref
+        p = np.asarray(p, dtype=float).reshape(-1, 3)
+        _, dq_dp, dq_di = ref.project(p, self.lensmodel, self.intrinsics, get_gradients=True)
+        Gi = dq_di[..., self.arg0:self.arg0 + self.Nsi] if self.istate_i is not None else np.zeros(dq_dp.shape[:-1] + (0,))
+        Ge = None
+        if self.method == "cross-reprojection-rrp-Jfp":
+            t = self.rt[3:]
+            pref = (p if atinfinity else p - t) @ self.R          # R^T (p - t)
+            dq_dpref = dq_dp @ self.R
+            if self.istate_e is not None:
+                dpcam_dr = np.einsum('ijk,nj->nik', self.dR, pref)
+                Ge = np.concatenate((dq_dp @ dpcam_dr, np.zeros_like(dq_dp) if atinfinity else dq_dp), axis=-1)
+        else:
+            pref, dq_dpref = p, dq_dp
+        GK = np.concatenate((dq_dpref @ skew(pref), np.zeros_like(dq_dp) if atinfinity else -dq_dpref), axis=-1)
+        return Gi, Ge, GK
+
+    def dq_db_packed(self, p, atinfinity):
+        """dq/db* (N,2,Nstate): built unpacked as the reference does, then unpack_state()-ed"""
+        Gi, Ge, GK = self.G_pieces(p, atinfinity)
+        Kunpacked = self.K.copy(); self.ref.pack_state(Kunpacked, **self.oi)
+        d = np.zeros(Gi.shape[:-1] + (self.Nstate,))
+        if self.istate_i is not None:
+            d[..., self.istate_i:self.istate_i + self.Nsi] = Gi
+        if Ge is not None:
+            d[..., self.istate_e:self.istate_e + 6] = Ge
+        d += GK @ Kunpacked
+        return d * self.scale
+
+    def dense(self, p, atinfinity, sigma):
+        """_propagate_calibration_uncertainty(), both branches, np.linalg.solve: (N,2,2)"""
+        dF = self.dq_db_packed(p, atinfinity)
+        N = dF.shape[0]
+        JtJ = (self.J.T @ self.J).toarray()
+        A = np.linalg.solve(JtJ, dF.reshape(-1, self.Nstate).T)             # (Nstate, 2N)
+        if self.Nreg > 0:
+            Jo = self.J[:self.J.shape[0] - self.Nreg]
+            JotJo = (Jo.T @ Jo).toarray()
+            B = JotJo @ A
+            V = np.einsum('sni,snj->nij', A.reshape(self.Nstate, N, 2), B.reshape(self.Nstate, N, 2))
+        else:
+            V = np.einsum('nis,snj->nij', dF, A.reshape(self.Nstate, N, 2))
+        return V * sigma*sigma
+
+    def C(self):
+        """C = M X - (J*[reg] X)^T (J*[reg] X), X = (J*^T J*)^-1 M^T: what the device computes"""
+        rows = []
+        if self.istate_i is not None:
+            for j in range(self.Nsi):
+                r = np.zeros(self.Nstate); r[self.istate_i + j] = self.scale[self.istate_i + j]; rows.append(r)
+        if self.istate_e is not None:
+            for j in range(6):
+                r = np.zeros(self.Nstate); r[self.istate_e + j] = self.scale[self.istate_e + j]; rows.append(r)
+        M = np.vstack(rows + [self.K])
+        JtJ = (self.J.T @ self.J).toarray()
+        X = np.linalg.solve(JtJ, M.T)
+        C = M @ X
+        if self.Nreg > 0:
+            JX = self.J[self.J.shape[0] - self.Nreg:] @ X
+            C = C - JX.T @ JX
+        return C
+
+    def reduced(self, p, atinfinity, sigma):
+        Gi, Ge, GK = self.G_pieces(p, atinfinity)
+        G = np.concatenate([Gi] + ([Ge] if Ge is not None else []) + [GK], axis=-1)
+        return G @ self.C() @ np.swapaxes(G, -1, -2) * sigma*sigma
+
+
+def reduce_what(V, what):
+    if what == "covariance":
+        return V
+    if what == "worstdirection-stdev":
+        a, b, c = V[..., 0,0], V[..., 1,0], V[..., 1,1]
+        return np.sqrt((a+c)/2 + np.sqrt((a-c)*(a-c)/4 + b*b))
+    return np.sqrt((V[..., 0,0] + V[..., 1,1])/2)
+
+
+# ------------------------------------------------------------------ problems ---
+def board_problem(api, Ncameras=3, lensmodel="LENSMODEL_OPENCV8", seed=3, **kw):
+    """boards, warp, regularization, an outlier"""
+    oi, _ = make_calibration_problem(api, Ncameras=Ncameras, Nframes=8, lensmodel=lensmodel,
+                                     object_width_n=8, object_height_n=7, seed=seed, **kw)
+    oi["observations_board"][1, 2, 1:3, 2] = -1.
+    return oi
+
+
+def points_problem():
+    """discrete points only (tests/test_uncertainty.py's problem): 3 cameras, one at the reference"""
+    rng = np.random.RandomState(5)
+    Ncam, Np = 3, 12
+    W, H = 4000, 2200
+    intr = np.tile(np.array((1500., 1500., (W-1)/2., (H-1)/2., -0.01, 0.02, 1e-3, -2e-3)), (Ncam,1))
+    rt_cam_ref = np.array(((0.01, -0.02, 0.03, -0.5, 0.02, 0.01), (-0.02, 0.01, 0.02, -1.0, -0.03, 0.02)))
+    pts = np.column_stack((rng.uniform(-1, 2, Np), rng.uniform(-1, 1, Np), rng.uniform(4, 9, Np)))
+    idx, obs = [], []
+    for ip in range(Np):
+        for ic in range(Ncam):
+            idx.append((ip, ic, ic-1))
+            obs.append((rng.uniform(800, 3000), rng.uniform(500, 1700), rng.uniform(0.5, 1.0)))
+    obs = np.array(obs); obs[4,2] = -1.
+    return dict(intrinsics=intr, lensmodel="LENSMODEL_OPENCV4",
+                imagersizes=np.tile(np.array((W,H), dtype=np.int32), (Ncam,1)),
+                rt_cam_ref=rt_cam_ref, points=pts, Npoints_fixed=2,
+                observations_point=obs, indices_point_camintrinsics_camextrinsics=np.array(idx, dtype=np.int32),
+                do_optimize_intrinsics_core=True, do_optimize_intrinsics_distortions=True,
+                do_optimize_extrinsics=True, do_optimize_frames=True, do_optimize_calobject_warp=False,
+                do_apply_regularization=True, do_apply_outlier_rejection=False, verbose=False)
+
+
+def some_points(N=17, seed=0, z=(2., 20.)):
+    rng = np.random.RandomState(seed)
+    p = np.column_stack((rng.uniform(-0.5, 0.5, N), rng.uniform(-0.4, 0.4, N), np.ones(N)))
+    return p * rng.uniform(*z, N)[:, None]
+
+
+# ------------------------------------------------------------------ CPU ---
+def test_worst_direction_stdev_known_answer(amd):
+    assert amd.worst_direction_stdev(np.array(((1., -0.4), (-0.4, 0.5)))) == pytest.approx(1.105304960905736, rel=1e-15)
+
+
+@pytest.mark.parametrize("shape", ((2,2), (3,2,2), (4,1,1), (3,3), (5,4,4), (2,3,6,6)))
+def test_worst_direction_stdev_random(amd, shape):
+    """the shapes of the reference's test/test-worst_direction_stdev.py, against sqrt(max eigvalsh)"""
+    rng = np.random.RandomState(1)
+    N = shape[-1]
+    A = rng.normal(size=shape[:-1] + (N+2,))
+    cov = A @ np.swapaxes(A, -1, -2)
+    got = amd.worst_direction_stdev(cov)
+    want = np.sqrt(np.linalg.eigvalsh(cov)[..., -1])
+    assert np.shape(got) == shape[:-2]
+    assert np.abs(got - want).max() < 1e-12 * np.abs(want).max()
+
+
+REDUCED_CASES = [("boards", 0, "cross-reprojection-ccp", True), ("boards", 1, "cross-reprojection-ccp", True),
+                 ("boards", 2, "cross-reprojection-rrp-Jfp", True), ("boards", 0, "cross-reprojection-rrp-Jfp", True),
+                 ("boards", 1, "cross-reprojection-ccp", False), ("boards", 2, "cross-reprojection-rrp-Jfp", False),
+                 ("points", 0, "cross-reprojection-ccp", True), ("points", 2, "cross-reprojection-rrp-Jfp", True)]
+
+
+@pytest.mark.parametrize("what,icam,method,reg", REDUCED_CASES)
+def test_checker_reduced_form_is_the_dense_propagation(ref_api, what, icam, method, reg):
+    """sigma^2 G C G^T (what the kernels compute) == the reference's dense dq/db propagation: ccp and rrp,
+    atinfinity on and off, regularization on and off. (1e-8 of the largest entry: the two solve J^T J, whose
+    condition here reaches ~1e12, against different right-hand sides; what they leave is 1e-10..4e-9)"""
+    # (without regularization, a model with fewer parameters: OPENCV8 on these few frames is nearly singular then)
+    oi = board_problem(ref_api, Ncameras=3, lensmodel=("LENSMODEL_OPENCV8" if reg else "LENSMODEL_OPENCV4")) \
+        if what == "boards" else points_problem()
+    oi["do_apply_regularization"] = reg
+    ch = Checker(ref_api, oi, icam, method)
+    p = some_points(9)
+    for atinfinity in (False, True):
+        Vd = ch.dense(p, atinfinity, 0.7)
+        Vr = ch.reduced(p, atinfinity, 0.7)
+        assert np.abs(Vd - Vr).max() <= 1e-8 * np.abs(Vd).max(), (atinfinity, np.abs(Vd - Vr).max(), np.abs(Vd).max())
+
+
+def _model(amd, oi, icam):
+    return amd.cameramodel(optimization_inputs=oi, icam_intrinsics=icam)
+
+
+def test_refusals_before_any_device_work(amd, ref_api, monkeypatch):
+    """the reference's refusals, raised before a problem is made on the device"""
+    import mrcal_amd.resident as resident
+    def no_device(*a, **k): raise AssertionError("device work before the refusal")
+    monkeypatch.setattr(resident.Problem, "__init__", no_device)
+    oi = board_problem(ref_api, Ncameras=2)
+    m = _model(amd, oi, 1)
+    with pytest.raises(Exception, match="Unknown uncertainty method"):
+        amd.projection_uncertainty(np.array((0., 0., 1.)), m, method="bogus")
+    with pytest.raises(Exception, match="'what' kwarg must be in"):
+        amd.projection_uncertainty(np.array((0., 0., 1.)), m, what="bogus")
+    with pytest.raises(Exception, match="mean-pcam.*not implemented"):
+        amd.projection_uncertainty(np.array((0., 0., 1.)), m, method="mean-pcam")
+    m0 = amd.cameramodel(m); m0.optimization_inputs_reset()
+    with pytest.raises(Exception, match="optimization_inputs are unavailable"):
+        amd.projection_uncertainty(np.array((0., 0., 1.)), m0)
+    # a moving camera: one camera, every frame seen from a pose of its own
+    oim = copy_inputs(oi)
+    idx = oim["indices_frame_camintrinsics_camextrinsics"].copy()
+    sel = idx[:, 1] == 1
+    idx[sel, 2] = np.arange(np.count_nonzero(sel))
+    idx[~sel, 2] = -1
+    oim["indices_frame_camintrinsics_camextrinsics"] = idx
+    oim["rt_cam_ref"] = np.tile(oi["rt_cam_ref"][:1], (np.count_nonzero(sel), 1))
+    with pytest.raises(Exception, match="I only handle stationary cameras for now"):
+        amd.projection_uncertainty(np.array((0., 0., 1.)),
+                                   amd.cameramodel(optimization_inputs=oim, icam_intrinsics=1, icam_extrinsics=0),
+                                   method="cross-reprojection-rrp-Jfp")
+
+
+# ------------------------------------------------------------------ GPU ---
+def _solved(amd, oi):
+    oi = copy_inputs(oi)
+    amd.optimize(**oi)
+    return oi
+
+
+def _compare(amd, ref_api, oi, icam, method, p, sigmas=(None, 0.5), whats=("covariance", "worstdirection-stdev", "rms-stdev"),
+             tol=1e-6):
+    ch = Checker(ref_api, oi, icam, method)
+    m = _model(amd, oi, icam)
+    worst = 0.0
+    for sigma in sigmas:
+        u = amd.ProjectionUncertainty(m, method=method, observed_pixel_uncertainty=sigma)
+        s = ch.sigma_est if sigma is None else sigma
+        assert relative_error(u.observed_pixel_uncertainty, s) < 1e-9
+        for atinfinity in (False, True):
+            V = ch.dense(p, atinfinity, s)
+            for what in whats:
+                got = u.evaluate(p, atinfinity=atinfinity, what=what)
+                want = reduce_what(V, what)
+                e = np.abs(got - want).max() / np.abs(want).max()
+                worst = max(worst, e)
+                assert e < tol, (sigma, atinfinity, what, e)
+        u.close()
+    return worst
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("icam", (0, 1, 2))
+def test_boards_against_checker(amd, ref_api, icam):
+    oi = _solved(amd, board_problem(amd._api, Ncameras=3))
+    _compare(amd, ref_api, oi, icam, "cross-reprojection-ccp", some_points(23, seed=icam))
+
+
+@pytest.mark.gpu
+def test_monocular_against_checker(amd, ref_api):
+    oi = _solved(amd, board_problem(amd._api, Ncameras=1))
+    _compare(amd, ref_api, oi, 0, "cross-reprojection-ccp", some_points(23))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("icam", (0, 2))
+def test_points_against_checker(amd, ref_api, icam):
+    _compare(amd, ref_api, points_problem(), icam, "cross-reprojection-ccp", some_points(23))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("icam", (0, 1, 2))
+def test_rrp_against_checker(amd, ref_api, icam):
+    oi = _solved(amd, board_problem(amd._api, Ncameras=3))
+    _compare(amd, ref_api, oi, icam, "cross-reprojection-rrp-Jfp", some_points(23, seed=5))
+    _compare(amd, ref_api, points_problem(), icam, "cross-reprojection-rrp-Jfp", some_points(23, seed=5))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lensmodel", ("LENSMODEL_CAHVORE_linearity=0.00", "LENSMODEL_CAHVOR", "LENSMODEL_STEREOGRAPHIC",
+                                       "LENSMODEL_SPLINED_STEREOGRAPHIC_order=3_Nx=8_Ny=6_fov_x_deg=80"))
+def test_lens_models_against_checker(amd, ref_api, lensmodel):
+    oi = board_problem(amd._api, Ncameras=2, lensmodel=lensmodel)
+    for method in ("cross-reprojection-ccp", "cross-reprojection-rrp-Jfp"):
+        _compare(amd, ref_api, oi, 1, method, some_points(23, seed=2), sigmas=(0.5,))
+
+
+@pytest.mark.gpu
+def test_partial_intrinsics_against_checker(amd, ref_api):
+    """do_optimize_intrinsics_core=False shifts the intrinsics columns; without the distortions only the core is left.
+    (With no intrinsics at all the reference's uncertainty.c refuses to make K)"""
+    for core, dist in ((False, True), (True, False)):
+        oi = board_problem(amd._api, Ncameras=2)
+        oi["do_optimize_intrinsics_core"], oi["do_optimize_intrinsics_distortions"] = core, dist
+        for method in ("cross-reprojection-ccp", "cross-reprojection-rrp-Jfp"):
+            _compare(amd, ref_api, oi, 1, method, some_points(11), sigmas=(0.5,))
+
+
+def _grid(amd, model, distance):
+    W, H = model.imagersize()
+    q = np.stack(np.meshgrid(np.linspace(0, W-1, 60), np.linspace(0, H-1, 40)), -1).reshape(-1, 2)
+    v = amd.unproject(q, *model.intrinsics(), normalize=True)
+    return v if distance is None else v*distance
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ("real_opencv8-0", "real_splined-0"))
+def test_real_data_grid_against_checker(amd, ref_api, name):
+    m = amd.cameramodel(os.path.join(GOLDEN_DIR, name + ".cameramodel"))
+    oi = {k: v for k, v in m.optimization_inputs().items() if not (isinstance(v, str) and v.startswith("ERROR:"))}
+    ch = Checker(ref_api, oi, m.icam_intrinsics(), "cross-reprojection-ccp")
+    u = amd.ProjectionUncertainty(m)
+    assert relative_error(u.observed_pixel_uncertainty, ch.sigma_est) < 1e-9
+    for distance, atinfinity in ((None, True), (5.0, False)):
+        p = _grid(amd, m, distance)
+        got = u.evaluate(p.reshape(40, 60, 3), atinfinity=atinfinity).reshape(-1, 2, 2)
+        # (the splined model's unprojection does not converge at a few of the imager's corners: those rows are NaN)
+        ok = np.isfinite(p).all(axis=-1)
+        assert np.count_nonzero(ok) > 0.9*len(p)
+        assert not np.isfinite(got[~ok]).any()
+        want = ch.dense(p[ok], atinfinity, ch.sigma_est)
+        # (beyond the splined model's valid region - the 28 corner rows the reference's own unproject() gives up
+        #  on - the reference's projection yields non-finite gradients: those rows have no checker)
+        fin = np.isfinite(want).all(axis=(-1, -2))
+        assert np.count_nonzero(fin) > 0.95*len(p)
+        want, got = want[fin], got[ok][fin]
+        e = np.abs(got - want).max() / np.abs(want).max()
+        assert e < 1e-6, e
+
+
+@pytest.mark.gpu
+def test_metric_problem_against_existing_primitives(amd):
+    """the bench's 8 x 1000 OPENCV8 problem (seed 0), solved; about 20 points against the reference's flow composed
+    from the already-pinned primitives: project(), drt_cross_reprojection__dbpacked(), solve_xt_JtJ_bt(),
+    _A_Jt_J_At__2()"""
+    api = amd._api
+    oi, _ = make_calibration_problem(api, Ncameras=8, Nframes=1000, seed=0)
+    amd.optimize(**oi)
+    icam = 3
+    m = _model(amd, oi, icam)
+    p = some_points(20, seed=7)
+    u = amd.ProjectionUncertainty(m, observed_pixel_uncertainty=0.3)
+    got = u.evaluate(p)
+    b, x, J, F = amd.optimizer_callback(**oi)
+    Nstate = J.shape[1]
+    Nreg = api.num_measurements_regularization(**oi)
+    K = amd.drt_cross_reprojection__dbpacked(icam_intrinsics=icam, **oi)
+    api.pack_state(K, **oi)
+    _, dq_dp, dq_di = amd.project(p, oi["lensmodel"], oi["intrinsics"][icam], get_gradients=True)
+    i0 = api.state_index_intrinsics(icam, **oi); Ni = api.num_intrinsics_optimization_params(**oi)
+    dq_db = np.zeros((len(p), 2, Nstate))
+    dq_db[..., i0:i0+Ni] = dq_di[..., :Ni]
+    dq_db += (dq_dp @ skew(p)) @ K[:3] - dq_dp @ K[3:]
+    api.unpack_state(dq_db, **oi)
+    for i in range(len(p)):
+        A = F.solve_xt_JtJ_bt(dq_db[i])
+        V = amd._A_Jt_J_At__2(A, J.indptr, J.indices, J.data, Nleading_rows_J=J.shape[0] - Nreg) * 0.3*0.3
+        assert np.abs(got[i] - V).max() < 1e-6 * np.abs(V).max(), i
+
+
+@pytest.mark.gpu
+def test_properties(amd, tmp_path):
+    oi = _solved(amd, board_problem(amd._api, Ncameras=3))
+    m = _model(amd, oi, 1)
+    p = some_points(31, seed=3)
+    # the same bits twice
+    a = amd.projection_uncertainty(p, m)
+    assert np.array_equal(a, amd.projection_uncertainty(p, m))
+    # a context reused over three distances == fresh one-shot calls
+    u = amd.ProjectionUncertainty(m)
+    v = p / np.linalg.norm(p, axis=-1, keepdims=True)
+    for d in (1., 10., 100.):
+        assert np.array_equal(u.evaluate(v*d), amd.projection_uncertainty(v*d, m))
+        assert np.array_equal(u.evaluate(v*d, atinfinity=True, what="rms-stdev"),
+                              amd.projection_uncertainty(v*d, m, atinfinity=True, what="rms-stdev"))
+    # atinfinity does not depend on the scale of p; far away approaches it
+    inf = u.evaluate(p, atinfinity=True)
+    assert np.abs(u.evaluate(p*7.5, atinfinity=True) - inf).max() < 1e-9*np.abs(inf).max()
+    far = u.evaluate(v*1e6)
+    assert np.abs(far - u.evaluate(v, atinfinity=True)).max() < 1e-4*np.abs(inf).max()
+    # Var scales as sigma^2
+    u1 = amd.ProjectionUncertainty(m, observed_pixel_uncertainty=1.0)
+    u3 = amd.ProjectionUncertainty(m, observed_pixel_uncertainty=3.0)
+    assert np.abs(u3.evaluate(p) - 9.*u1.evaluate(p)).max() < 1e-12*np.abs(u3.evaluate(p)).max()
+    # broadcast shapes
+    assert u.evaluate(p[0]).shape == (2, 2)
+    assert np.ndim(u.evaluate(p[0], what="worstdirection-stdev")) == 0
+    assert u.evaluate(p[:30].reshape(5, 6, 3)).shape == (5, 6, 2, 2)
+    assert u.evaluate(p[:30].reshape(5, 6, 3), what="rms-stdev").shape == (5, 6)
+    # p = 0 is non-finite without touching the others
+    pz = p.copy(); pz[4] = 0.
+    r = u.evaluate(pz)
+    assert not np.isfinite(r[4]).all()
+    keep = np.arange(len(p)) != 4
+    assert np.array_equal(r[keep], u.evaluate(p)[keep])
+    # moving the extrinsics and a round trip through a file changes nothing
+    m2 = amd.cameramodel(m)
+    rt = m2.rt_cam_ref().copy(); rt[3:] += (0.5, -0.2, 0.1); rt[:3] += 0.01
+    m2.rt_cam_ref(rt)
+    fn = str(tmp_path / "m.cameramodel")
+    m2.write(fn)
+    m3 = amd.cameramodel(fn)
+    for method in ("cross-reprojection-ccp", "cross-reprojection-rrp-Jfp"):
+        want = amd.projection_uncertainty(p, m, method=method)
+        got = amd.projection_uncertainty(p, m3, method=method)
+        assert np.abs(got - want).max() <= 1e-9*np.abs(want).max()
