@@ -608,7 +608,8 @@ bool  mrcal_amd_problem_gather_state(mrcal_amd_problem_t* problem);
    trial step the driver queues, on the problem's stream,
        enqueue(0,0) | all-reduce comm_buffer(0) | enqueue(0,1) | all-reduce comm_buffer(1)
    and never reads anything back in between. initial=1: the evaluation of the
-   starting point, after sharded_reset(). snapshot(slot)/wait(slot): a pinned copy
+   starting point. enqueue() refuses a problem sharded_reset() has not been called
+   on (mrcal_amd_last_error()). snapshot(slot)/wait(slot): a pinned copy
    of the control block, queued after a trial step and waited for a few steps
    later, tells the host when the device has declared the solve finished; wait()
    writes out[4] = { done, error, Nsteps_accepted, Ntrials }. finish() drains the
@@ -668,8 +669,8 @@ int   mrcal_amd_set_elimination(int policy);
    the plan needs; "lchol_sweep" = 1: the big Cholesky's solve by the backward sweep (the stable fallback the solver
    switches to by itself when a factor's diagonal spans more than 1e10); "lchol_fallback_log10" = k: that threshold as
    10^k. 0: not forced. Returns the previous value,
-   -1 for an unknown name. (Round 6: these were environment variables; the library reads six of those now -
-   MRCAL_AMD_GRAPH, _ELIMINATE, _RCCL, _LIB, _NO_ND, _NO_SPL_COMPACT - and MRCAL_AMD_DEBUG_SOLVER, which only prints) */
+   -1 for an unknown name. (Round 6: these were environment variables; the library reads five of those now -
+   MRCAL_AMD_ELIMINATE, _RCCL, _LIB, _NO_ND, _NO_SPL_COMPACT - and MRCAL_AMD_DEBUG_SOLVER, which only prints) */
 int   mrcal_amd_set_test_hook(const char* name, int value);
 /* Round 6: the big camera block's solve ends with d = -Y^T z, Y = L^-1 formed explicitly beside the panels: fast, and
    not backward stable - its error grows like n eps max/min of L's diagonal. The factorizations of a dog-leg pass leave

@@ -934,7 +934,7 @@ hipError_t launch_assemble(const DeviceProblem& P, const NormalDims& nd, const B
     // splined models: no per-observation Gram; every row goes through the generic path
     const bool by_rows = (P.lens_type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC);
     const int row0 = by_rows ? 0 : 2*P.W*P.H*P.Nobs_board;
-    if(P.Nobs_board > 0 && !by_rows)
+    if(problem_has_grams(P))
     {
         const int nframe_blocks = br.frame_hi - br.frame_lo;        // (the 6x6 eliminated blocks: frames, or cameras)
         FactorBuffers none; memset(&none, 0, sizeof(none));

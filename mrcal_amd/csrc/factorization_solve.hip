@@ -593,11 +593,6 @@ hipError_t launch_csr_A_Jt_J_At(int NX, int Nrows, int Nstate, const int32_t* Jp
     return hipGetLastError();
 }
 
-hipError_t launch_fsolve(const NormalDims& nd, const FactorBuffers& F,
-                         const double* b, double* x, hipStream_t stream)
-{
-    return launch_fsolve_sys(nd, F, FSOLVE_A, b, x, stream);
-}
 // The systems of cholmod_solve2() (same codes) against the kept factorization:
 // A x = b in state order; the others in factor order [E | S]: L x = b, L^T x = b,
 // L L^T x = b (D is the identity: this is an LL^T factorization, so LD == L,

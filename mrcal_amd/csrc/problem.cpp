@@ -90,7 +90,6 @@ mrcal_amd_problem::~mrcal_amd_problem()
     if(h_scalars)  hipHostFree(h_scalars);
     if(h_ctl_ring) hipHostFree(h_ctl_ring);
     for(hipEvent_t e : ctl_events) hipEventDestroy(e);
-    for(int i=0;i<3;i++) if(step_graph[i]) hipGraphExecDestroy(step_graph[i]);
     for(hipEvent_t e : ev_pool) hipEventDestroy(e);
     if(ev_j0)  hipEventDestroy(ev_j0);
     if(ev_j1)  hipEventDestroy(ev_j1);
@@ -711,8 +710,7 @@ bool problem_evaluate_ref(mrcal_amd_problem* P, const OpRef& R, bool with_jacobi
     B.choose = choose;
     // (round 6) a solve that was told to leave the Jacobian stream out: only the solver's own evaluations, and only
     // where the board kernel is the rows' one reader (never the splined models, whose assembly reads them back)
-    if(P->jfree_now && with_normal && with_jacobian && P->D.Nobs_board > 0 &&
-       P->D.lens_type != MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC)
+    if(P->jfree_now && with_normal && with_jacobian && problem_has_grams(P->D))
     {
         B.store_jacobian = false;
         if(parts & EVAL_PART_BOARD) P->jacobian_stale = true;
@@ -735,7 +733,7 @@ bool problem_evaluate_ref(mrcal_amd_problem* P, const OpRef& R, bool with_jacobi
     // back). So: none inside the solver's steps unless the benchmark asked for timings, and then only around
     // every ev_pool_stride-th launch; a host-driven evaluate() keeps its pair (last_jacobian_kernel_ms())
     hipEvent_t e0 = NULL, e1 = NULL;
-    if(with_jacobian && (parts & EVAL_PART_BOARD) && !P->capturing)
+    if(with_jacobian && (parts & EVAL_PART_BOARD))
     {
         if(P->ev_pool_enabled)
         {
@@ -1370,19 +1368,13 @@ double*  mrcal_amd_problem_dev_J_values(mrcal_amd_problem_t* p) { return problem
 int mrcal_amd_problem_set_jacobian_stream(mrcal_amd_problem_t* p, int stream)
 {
     const int old = p->solve_stores_jacobian ? 1 : 0;
-    if((stream != 0) != p->solve_stores_jacobian)
-    {
-        p->solve_stores_jacobian = (stream != 0);
-        // (the captured trial step has the board kernel's variant in it)
-        for(int i = 0; i < 3; i++)
-            if(p->step_graph[i]) { hipGraphExecDestroy(p->step_graph[i]); p->step_graph[i] = NULL; }
-    }
+    p->solve_stores_jacobian = (stream != 0);
     return old;
 }
 // does a solve of this problem go without the Jacobian stream when told to?
 int mrcal_amd_problem_jacobian_stream_is_optional(mrcal_amd_problem_t* p)
 {
-    return (p->D.Nobs_board > 0 && p->D.lens_type != MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC) ? 1 : 0;
+    return problem_has_grams(p->D) ? 1 : 0;
 }
 void*    mrcal_amd_problem_stream      (mrcal_amd_problem_t* p) { return (void*)p->stream; }
 

@@ -55,7 +55,6 @@ struct mrcal_amd_problem
     bool        solve_stores_jacobian = true;
     bool        jfree_now             = false;
     bool        jacobian_stale        = false;
-    bool        capturing = false;      // a hipGraph capture is in progress on the stream
     // optional: an event pair per Jacobian-kernel launch, to average over a timed region
     std::vector<hipEvent_t> ev_pool;
     int         ev_pool_used = 0;
@@ -111,9 +110,6 @@ struct mrcal_amd_problem
     mrcal_amd::SolverCtl*      snap_target = NULL;      // where the step being queued leaves its control-block snapshot
     std::vector<hipEvent_t>    ctl_events;
     bool                       ctl_initialized = false;
-    // one trial step captured as a graph: whole [0], or split around the board
-    // kernel ([1] before, [2] after) when that kernel is being timed with events
-    hipGraphExec_t             step_graph[3] = {NULL, NULL, NULL};
     mrcal_amd_solver_stats     stats;
 
     // op i, resolved by the host

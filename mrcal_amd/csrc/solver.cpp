@@ -7,8 +7,8 @@
 // restated in oracle/dogleg_restated.c (CPU checker); THIS file is the
 // product: the same algorithm with every vector/matrix operation AND the
 // scalar trust-region decisions on the GPU (solver_device.hpp, "dog-leg
-// control"). The host queues trial steps (one captured hipGraph each) and
-// polls a pinned snapshot of the device's control block a few steps behind.
+// control"). The host queues trial steps and polls a pinned snapshot of the
+// device's control block a few steps behind.
 //
 // mrcal's solver settings (mrcal.c:6296-6299): Jt_x_threshold 0,
 // update_threshold 1e-7, trustregion_threshold 0, max_iterations 300; the rest
@@ -106,15 +106,29 @@ bool ctl_reset(mrcal_amd_problem* P, const DoglegParameters& prm, bool check_ter
     return true;
 }
 
-Step2Args step2_args(mrcal_amd_problem* P)
+// The arguments of the fused step's launchers and the step's layout: decided here, once per queued step
+Step2Args step2_args(mrcal_amd_problem* P, bool initial)
 {
     Step2Args a;
     a.P = &P->D; a.nd = &P->nd; a.br = &P->br; a.plan = &P->plan;
     a.ops = P->d_ops; a.ctl = P->d_ctl; a.F = &P->F; a.gram = P->d_gram;
     a.Jp = P->d_Jp; a.Ji = P->d_Ji; a.step = P->d_step; a.is_leader = P->is_leader;
     a.comm2 = (P->comm != NULL || P->sharded_external) ? P->d_comm : NULL;
-    a.snap  = P->capturing ? NULL : P->snap_target;
+    a.snap  = P->snap_target;
     a.side = P->side_stream; a.ev_fork = P->ev_fork; a.ev_join = P->ev_join;
+    a.initial    = initial;
+    a.with_grams = problem_has_grams(P->D);
+    // Does the end-of-trial logic (step2_finish) ride in the reduction's launch (round 5)? On a single GPU the tail it
+    // reads - g_S, |x|^2, the block elimination's status - is complete when the reduction's last workgroup has written it,
+    // and that workgroup can decide the trial there and then, beside the others: the factorization's first launch starts
+    // on its matrix at once (and may be several workgroups: the dissection's). Sharded, the tail is summed over the ranks
+    // behind that launch. (With the backward sweep - FactorBuffers::use_sweep - the end-of-trial logic and the verdict are
+    // launches of their own.)
+    a.finish_rides = a.comm2 == NULL && !P->F.use_sweep;
+    // (where the host has provided for the dissection's launches - learn_likely_size() -, the reduction fills the
+    //  dissection's matrices with more workgroups, and the factorization goes through those launches)
+    a.nd_launches  = a.finish_rides && P->F.ndMA != NULL && P->F.cperm_cur != NULL && P->F.nd_lim.rounds > 0;
+    a.S_packed     = a.finish_rides && step2_chol_in_lds(P->nd);
     return a;
 }
 
@@ -129,19 +143,44 @@ bool step_collective(mrcal_amd_problem* P, int which)
     return mrcal_amd_comm_allreduce_sum(P->comm, P->d_comm, 4, (void*)P->stream);
 }
 
+// x, J and the Grams at the point the step evaluates: the starting point, or the trial point chosen from the current one
+// (the prologue launch carries the choice - dogleg_choose.hpp -, or launch_step2_choose runs in front of the evaluation)
+bool enqueue_evaluation(mrcal_amd_problem* P, const Step2Args& a)
+{
+    const int parts = EVAL_PART_PROLOGUE | EVAL_PART_ZERO | EVAL_PART_BOARD | EVAL_PART_REST;
+    if(a.initial) return problem_evaluate_ref(P, OpRef{ P->d_ops, &a.ctl->ib, NULL }, true, true, parts);
+    const OpRef Rto = { P->d_ops, &a.ctl->ia, solver_ctl_skip_eval2(a.ctl) };
+    if(prologue_takes_choose(P->D))
+    {
+        const ChooseArgs ca = step2_choose_args(a);
+        return problem_evaluate_ref(P, Rto, true, true, parts, NULL, &ca);
+    }
+    HIP_TRY(launch_step2_choose(a, P->stream), return false);
+    return problem_evaluate_ref(P, Rto, true, true, parts);
+}
+
+// The rest of the step: assemble -> reduce -> sum 0 -> factor -> sum 1. segment -1: all of it; for a caller that does
+// the sums over the shards itself, 0: up to the first sum, 1: from there to the second
+bool enqueue_factorization(mrcal_amd_problem* P, const Step2Args& a, int segment)
+{
+    if(segment != 1)
+    {
+        bool forked = false;
+        HIP_TRY(launch_step2_assemble(a, P->stream, &forked), return false);
+        HIP_TRY(launch_step2_reduce(a, P->stream, forked), return false);
+    }
+    if(segment == -1 && !step_collective(P, 0)) return false;
+    if(segment != 0) HIP_TRY(launch_step2_factor(a, P->stream), return false);
+    if(segment == -1 && !step_collective(P, 1)) return false;
+    return true;
+}
+
 // x, J, the normal equations, g, |x|^2, the Cauchy step and (unless the Cauchy
 // step already leaves the trust region) the Gauss-Newton step at the starting point
 bool enqueue_initial_point(mrcal_amd_problem* P)
 {
-    const OpRef R = { P->d_ops, &P->d_ctl->ib, NULL };
-    if(!problem_evaluate_ref(P, R, true, true, EVAL_PART_PROLOGUE | EVAL_PART_ZERO | EVAL_PART_BOARD | EVAL_PART_REST)) return false;
-    const Step2Args a = step2_args(P);
-    HIP_TRY(launch_step2_assemble(a, true, P->stream), return false);
-    HIP_TRY(launch_step2_reduce(a, P->stream, 1), return false);
-    if(!step_collective(P, 0)) return false;
-    HIP_TRY(launch_step2_factor(a, true, P->stream), return false);
-    if(!step_collective(P, 1)) return false;
-    return true;
+    const Step2Args a = step2_args(P, true);
+    return enqueue_evaluation(P, a) && enqueue_factorization(P, a, -1);
 }
 
 // SolverCtl::error, in words
@@ -153,87 +192,11 @@ static const char* solver_error_text(int error)
                         "could not make JtJ positive definite";
 }
 // One trial step of the dog-leg, entirely queued: every decision is taken on
-// the device (step.hip, "the fused step"). segment: 0 = all of it;
-// 1 = up to the board kernel, 2 = the board kernel alone, 3 = after it
-bool enqueue_trial_step(mrcal_amd_problem* P, int segment)
+// the device (step.hip, "the fused step")
+bool enqueue_trial_step(mrcal_amd_problem* P)
 {
-    SolverCtl* ctl = P->d_ctl;
-    const Step2Args a = step2_args(P);
-    const OpRef Rto = { P->d_ops, &ctl->ia, solver_ctl_skip_eval2(ctl) };
-    if(segment == 0 || segment == 1)
-    {
-        // the step from the current point (its Gauss-Newton step was computed when the
-        // point was accepted); then the joint poses of the trial point
-        if(prologue_takes_choose(P->D))
-        {
-            // ONE launch: the prologue's workgroups choose the trial point they evaluate (dogleg_choose.hpp)
-            const ChooseArgs ca = step2_choose_args(a);
-            if(!problem_evaluate_ref(P, Rto, true, true, EVAL_PART_PROLOGUE | EVAL_PART_ZERO, NULL, &ca)) return false;
-        }
-        else
-        {
-            HIP_TRY(launch_step2_choose(a, P->stream), return false);
-            if(!problem_evaluate_ref(P, Rto, true, true, EVAL_PART_PROLOGUE | EVAL_PART_ZERO)) return false;
-        }
-    }
-    if(segment == 0 || segment == 2)
-        if(!problem_evaluate_ref(P, Rto, true, true, EVAL_PART_BOARD)) return false;
-    if(segment == 0 || segment == 3)
-    {
-        if(!problem_evaluate_ref(P, Rto, true, true, EVAL_PART_REST)) return false;
-        HIP_TRY(launch_step2_assemble(a, false, P->stream), return false);
-        HIP_TRY(launch_step2_reduce(a, P->stream, 0), return false);
-        if(!step_collective(P, 0)) return false;
-        HIP_TRY(launch_step2_factor(a, false, P->stream), return false);
-        if(!step_collective(P, 1)) return false;
-    }
-    return true;
-}
-
-bool capture_segment(mrcal_amd_problem* P, int segment, hipGraphExec_t* exec)
-{
-    hipGraph_t graph = NULL;
-    HIP_TRY(hipStreamBeginCapture(P->stream, hipStreamCaptureModeThreadLocal), return false);
-    P->capturing = true;
-    const bool ok = enqueue_trial_step(P, segment);
-    P->capturing = false;
-    hipError_t e = hipStreamEndCapture(P->stream, &graph);
-    if(!ok || e != hipSuccess || graph == NULL)
-    {
-        if(graph) hipGraphDestroy(graph);
-        set_error("could not capture the solver step into a HIP graph: %s", hipGetErrorString(e));
-        return false;
-    }
-    HIP_TRY(hipGraphInstantiate(exec, graph, NULL, NULL, 0), { hipGraphDestroy(graph); return false; });
-    hipGraphDestroy(graph);
-    return true;
-}
-
-// Queues one trial step: eagerly, or (MRCAL_AMD_GRAPH=1) as ONE captured graph;
-// when the board kernel is being timed with per-launch events, as graph |
-// event | kernel | event | graph. Graphs are captured on first use
-bool queue_trial_step(mrcal_amd_problem* P)
-{
-    // Measured (8 cameras x 1000 frames, when a step was 17 launches): queued
-    // eagerly 277 us, replayed as one graph 279 us, as graph|kernel|graph (when
-    // the board kernel is timed with events) 297 us. Eager is the default;
-    // MRCAL_AMD_GRAPH=1 selects the graph, which does not depend on the host
-    // keeping up with the queue. (Single GPU only: the all-reduces of the sharded
-    // step are not captured)
-    static const bool use_graph = (getenv("MRCAL_AMD_GRAPH") != NULL);
-    if(!use_graph || P->comm != NULL) return enqueue_trial_step(P, 0);
-    if(!P->ev_pool_enabled)
-    {
-        if(P->step_graph[0] == NULL && !capture_segment(P, 0, &P->step_graph[0])) return false;
-        HIP_TRY(hipGraphLaunch(P->step_graph[0], P->stream), return false);
-        return true;
-    }
-    if(P->step_graph[1] == NULL && !capture_segment(P, 1, &P->step_graph[1])) return false;
-    if(P->step_graph[2] == NULL && !capture_segment(P, 3, &P->step_graph[2])) return false;
-    HIP_TRY(hipGraphLaunch(P->step_graph[1], P->stream), return false);
-    if(!enqueue_trial_step(P, 2)) return false;
-    HIP_TRY(hipGraphLaunch(P->step_graph[2], P->stream), return false);
-    return true;
+    const Step2Args a = step2_args(P, false);
+    return enqueue_evaluation(P, a) && enqueue_factorization(P, a, -1);
 }
 
 bool read_ctl(mrcal_amd_problem* P, SolverCtl* c)
@@ -250,6 +213,12 @@ void absorb_ctl(mrcal_amd_problem* P, const SolverCtl& c)
     P->stats.lambda  = c.lambda;
     P->stats.norm2_x = c.norm2_x[c.ib];
     P->op[0].have_normal = P->op[1].have_normal = true;
+}
+
+// The splined models' camera block factored whole from here on: neither compacted (LcholCompact) nor dissected
+void compaction_off(mrcal_amd_problem* P)
+{
+    P->F.cperm_cur = NULL; P->plan.spl_compact = 0; P->plan.nd_lim = NULL; P->F.nd_lim.rounds = 0;
 }
 
 // The splined models' compacted camera block (LcholCompact): how many of its factorization's launches the host
@@ -271,8 +240,8 @@ static bool learn_likely_size(mrcal_amd_problem* P)
     // strip there is at that point - whether launches for it are provided or not. Launches for THAT plan are what the
     // factorizations of this solve get: rounds for the longer side, a border a panel larger than the separator; the plans
     // of later points are used where they fit (else the point goes the ordinary way through the same launches). Where
-    // that differs from what the last solve had, the trial step's graphs - the launches are in them - are made again
-    // (a solve from the seed and the solve after an outlier pass may well differ: the boxes move with the state)
+    // that differs from what the last solve had, the device's copy of the limits is replaced (a solve from the seed and
+    // the solve after an outlier pass may well differ: the boxes move with the state)
     if(P->F.ndMA != NULL && P->op[P->icur].ndp != NULL)
     {
         int h[NDH_WORDS];
@@ -297,8 +266,6 @@ static bool learn_likely_size(mrcal_amd_problem* P)
             HIP_TRY(launch_nd_plans_off(P->d_ops, P->nd.Nc, P->stream), return false);
             HIP_TRY(hipMemcpyAsync(P->F.nd_lim_dev, &P->F.nd_lim, sizeof(NdLimits), hipMemcpyHostToDevice, P->stream), return false);
             HIP_TRY(hipStreamSynchronize(P->stream), return false);       // (the source is this problem's member: let it be read)
-            for(int i = 0; i < 3; i++)
-                if(P->step_graph[i]) { hipGraphExecDestroy(P->step_graph[i]); P->step_graph[i] = NULL; }
         }
     }
     return true;
@@ -323,16 +290,11 @@ bool run_dogleg(mrcal_amd_problem* P, const DoglegParameters& prm)
     while(!done && nqueued < max_trials)
     {
         const int slot = nqueued % CTL_RING;
-        // the step's last kernel leaves the snapshot in the pinned ring itself (eager queueing; a captured
-        // graph has its arguments baked in and is followed by a copy instead)
-        static const bool use_graph = (getenv("MRCAL_AMD_GRAPH") != NULL);
-        const bool by_kernel = !use_graph || P->comm != NULL;
-        P->snap_target = by_kernel ? &P->h_ctl_ring[slot] : NULL;
-        const bool queued = queue_trial_step(P);
+        // the step's last kernel leaves the snapshot in the pinned ring itself
+        P->snap_target = &P->h_ctl_ring[slot];
+        const bool queued = enqueue_trial_step(P);
         P->snap_target = NULL;
         if(!queued) return false;
-        if(!by_kernel)
-            HIP_TRY(hipMemcpyAsync(&P->h_ctl_ring[slot], P->d_ctl, sizeof(SolverCtl), hipMemcpyDeviceToHost, P->stream), return false);
         HIP_TRY(hipEventRecord(P->ctl_events[slot], P->stream), return false);
         nqueued++;
         if(debug)
@@ -716,9 +678,7 @@ double mrcal_amd_problem_solve(mrcal_amd_problem_t* P, int max_iterations,
             if(P->last_ctl_error == 3 && P->plan.spl_compact)
             {
                 fprintf(stderr, "mrcal_amd: WARNING: %s. Solving this problem without the compaction of its camera block\n", solver_error_text(3));
-                P->F.cperm_cur = NULL; P->plan.spl_compact = 0; P->plan.nd_lim = NULL; P->F.nd_lim.rounds = 0;
-                for(int i = 0; i < 3; i++)
-                    if(P->step_graph[i]) { hipGraphExecDestroy(P->step_graph[i]); P->step_graph[i] = NULL; }
+                compaction_off(P);
                 last_error_string().clear();
                 continue;
             }
@@ -735,9 +695,7 @@ double mrcal_amd_problem_solve(mrcal_amd_problem_t* P, int max_iterations,
             fprintf(stderr, "mrcal_amd: WARNING: the diagonal of the camera block's Cholesky factor spans %.1e: this problem's steps go through "
                             "the backward sweep from here on instead of the explicit inverse (slower, backward stable)\n", 1.0/P->lchol_diag_ratio);
             P->F.use_sweep = 1;
-            P->F.cperm_cur = NULL; P->plan.spl_compact = 0; P->plan.nd_lim = NULL; P->F.nd_lim.rounds = 0;
-            for(int i = 0; i < 3; i++)
-                if(P->step_graph[i]) { hipGraphExecDestroy(P->step_graph[i]); P->step_graph[i] = NULL; }
+            compaction_off(P);
         }
         if(!P->L.sel.do_apply_outlier_rejection) break;
         bool found;
@@ -776,7 +734,7 @@ int mrcal_amd_problem_run_steps(mrcal_amd_problem_t* P, int Nsteps, double* trus
         if(!learn_likely_size(P)) return -1;
     }
     for(int n = 0; n < Nsteps; n++)
-        if(!queue_trial_step(P)) return -1;
+        if(!enqueue_trial_step(P)) return -1;
     SolverCtl c;
     if(!read_ctl(P, &c)) return -1;
     if(c.error) { set_error("%s", solver_error_text(c.error)); return -1; }
@@ -854,7 +812,7 @@ bool mrcal_amd_problem_attach_comm(mrcal_amd_problem_t* P, mrcal_amd_comm_t* com
     P->comm = comm;
     P->ctl_initialized = false;
     // (the ranks of a sharded solve sum their camera blocks entry by entry: no rank puts its own in another order)
-    P->F.cperm_cur = NULL; P->plan.spl_compact = 0; P->plan.nd_lim = NULL; P->F.nd_lim.rounds = 0;
+    compaction_off(P);
     return true;
 }
 // dev / tests: the nested-dissection order of a splined problem's camera block. out[0] rounds the host provides launches for
@@ -924,7 +882,7 @@ bool mrcal_amd_problem_sharded_reset(mrcal_amd_problem_t* P, int check_terminati
     if(max_iterations > 0)  prm.max_iterations = max_iterations;
     if(trustregion0 > 0.0)  prm.trustregion0   = trustregion0;
     P->sharded_external = true;     // the caller sums comm_buffer(0), comm_buffer(1) over the shards itself
-    P->F.cperm_cur = NULL; P->plan.spl_compact = 0; P->plan.nd_lim = NULL; P->F.nd_lim.rounds = 0;
+    compaction_off(P);
     P->stats.lambda = 0.0;          // a new run starts unregularized, like a new libdogleg context
     return ctl_reset(P, prm, check_termination != 0);
 }
@@ -932,43 +890,13 @@ bool mrcal_amd_problem_sharded_reset(mrcal_amd_problem_t* P, int check_terminati
 // segment 0: up to the first sum over the shards; 1: from there to the second
 bool mrcal_amd_problem_sharded_enqueue(mrcal_amd_problem_t* P, int initial, int segment)
 {
-    if(!P->ctl_initialized) { set_error("mrcal_amd_problem_sharded_reset() first"); return false; }
-    SolverCtl* ctl = P->d_ctl;
-    const bool init = initial != 0;
-    const Step2Args a = step2_args(P);
-    if(segment == 0)
-    {
-        if(init)
-        {
-            const OpRef R = { P->d_ops, &ctl->ib, NULL };
-            if(!problem_evaluate_ref(P, R, true, true, EVAL_PART_PROLOGUE | EVAL_PART_ZERO | EVAL_PART_BOARD | EVAL_PART_REST)) return false;
-        }
-        else
-        {
-            const OpRef Rto = { P->d_ops, &ctl->ia, solver_ctl_skip_eval2(ctl) };
-            const int parts = EVAL_PART_PROLOGUE | EVAL_PART_ZERO | EVAL_PART_BOARD | EVAL_PART_REST;
-            if(prologue_takes_choose(P->D))
-            {
-                const ChooseArgs ca = step2_choose_args(a);
-                if(!problem_evaluate_ref(P, Rto, true, true, parts, NULL, &ca)) return false;
-            }
-            else
-            {
-                HIP_TRY(launch_step2_choose(a, P->stream), return false);
-                if(!problem_evaluate_ref(P, Rto, true, true, parts)) return false;
-            }
-        }
-        HIP_TRY(launch_step2_assemble(a, init, P->stream), return false);
-        HIP_TRY(launch_step2_reduce(a, P->stream), return false);
-        return true;
-    }
-    if(segment == 1)
-    {
-        HIP_TRY(launch_step2_factor(a, init, P->stream), return false);
-        return true;
-    }
-    set_error("mrcal_amd_problem_sharded_enqueue(): segment %d", segment);
-    return false;
+    // (without the reset, after a solve(), the step's layout would be the single GPU's: the end of the trial and the packed
+    //  copy of S in the reduction's launch, on this shard's terms alone, before the caller's sums)
+    if(!P->ctl_initialized || !P->sharded_external) { set_error("mrcal_amd_problem_sharded_reset() first"); return false; }
+    if(segment != 0 && segment != 1) { set_error("mrcal_amd_problem_sharded_enqueue(): segment %d", segment); return false; }
+    const Step2Args a = step2_args(P, initial != 0);
+    if(segment == 0 && !enqueue_evaluation(P, a)) return false;
+    return enqueue_factorization(P, a, segment);
 }
 
 // the buffer to sum over the shards after segment 0 / 1

@@ -384,11 +384,7 @@ hipError_t launch_factor_local(const NormalDims& nd, const BlockRanges& br,
 hipError_t launch_solve_backsub(const NormalDims& nd, const BlockRanges& br,
                                 const OpRef& R, const FactorBuffers& F, const int* skip_also, bool keep_factor,
                                 hipStream_t stream);
-hipError_t launch_quadform(const NormalDims& nd, const OpRef& R, const double* v, double* out,
-                           hipStream_t stream);
 hipError_t launch_dot(int n, const double* a, const double* b, double* out, hipStream_t stream);
-hipError_t launch_axpby(int n, double alpha, const double* a, double beta, const double* b, double* y,
-                        hipStream_t stream);
 // part: scratch of outlier_partial_doubles() doubles (per-workgroup partial sums, added up in a fixed order)
 size_t     outlier_partial_doubles();
 hipError_t launch_outlier_stats(int Npoints_board, double thresh_sq, const double* x, const double* pool,
@@ -396,11 +392,8 @@ hipError_t launch_outlier_stats(int Npoints_board, double thresh_sq, const doubl
 hipError_t launch_mark_outliers(int Npoints_board, double thresh_sq, const double* x, double* pool,
                                 int* counts, hipStream_t stream);
 
-// solves against a kept factorization (F as left by launch_factor_local() +
-// launch_solve_backsub(keep_factor)): (JtJ) x = b, device vectors in state order
-hipError_t launch_fsolve(const NormalDims& nd, const FactorBuffers& F,
-                         const double* b, double* x, hipStream_t stream);
-// the systems of cholmod_solve2(), same codes (factorization_solve.hip explains the factor and its order)
+// solves against a kept factorization (F as left by launch_factor_local() + launch_solve_backsub(keep_factor)): the
+// systems of cholmod_solve2(), same codes (factorization_solve.hip explains the factor and its order)
 enum { FSOLVE_A = 0, FSOLVE_LDLt, FSOLVE_LD, FSOLVE_DLt, FSOLVE_L, FSOLVE_Lt, FSOLVE_D, FSOLVE_P, FSOLVE_Pt };
 hipError_t launch_fsolve_sys(const NormalDims& nd, const FactorBuffers& F, int sys,
                              const double* b, double* x, hipStream_t stream);
@@ -440,7 +433,6 @@ hipError_t launch_assemble_rows(const NormalDims& nd, const OpRef& R, int Nmeas,
 //   finish + Cholesky accept/reject, trust region; Cholesky of S if the point was accepted  (launch_step2_factor)
 //   backsub+quadform  the frame/point part of the Gauss-Newton step ; g^T N g of the new point
 //                     -- sharded: pack + all-reduce of comm2 (4 doubles) --
-// initial: the evaluation of the starting point (no choose, no accept)
 struct Step2Args
 {
     const DeviceProblem* P; const NormalDims* nd; const BlockRanges* br; const AssemblyPlan* plan;
@@ -450,21 +442,32 @@ struct Step2Args
     SolverCtl* snap;         // host-visible (pinned) copy of the control block to leave behind at the end of the step; NULL: none
     // a side stream with its fork and join events (NULL: none): _assemble may leave work there that _reduce waits for
     hipStream_t side; hipEvent_t ev_fork, ev_join;
+    // The step's layout, decided once (solver.cpp step2_args()); the launchers only read it
+    bool initial;            // the evaluation of the starting point (no choose, no accept)
+    bool with_grams;         // the board rows come with per-observation Grams (problem_has_grams()): the fused assembly
+    bool finish_rides;       // the end-of-trial logic rides in the reduction's launch
+    bool nd_launches;        // the dissection's launches follow the reduction (FactorBuffers::nd_lim)
+    bool S_packed;           // the reduction leaves a packed copy of S (factor_S_packed()) that the one-workgroup Cholesky reads
 };
+bool       step2_chol_in_lds(const NormalDims& nd);     // the camera block's Cholesky is the one-workgroup LDS one
 hipError_t launch_step2_choose(const Step2Args& a, hipStream_t stream);
 // the same as arguments, for an evaluation whose prologue launch carries the choice (EvalBuffers::choose)
 struct ChooseArgs;
 ChooseArgs step2_choose_args(const Step2Args& a);
-hipError_t launch_step2_assemble(const Step2Args& a, bool initial, hipStream_t stream);
+// *forked: work was left on the side stream; launch_step2_reduce(side_forked) joins it
+hipError_t launch_step2_assemble(const Step2Args& a, hipStream_t stream, bool* forked);
 // ... comm1 = [S | r | g_S | |x|^2 | status] (F.S, step2_comm1_doubles()) is this rank's summand after _reduce;
 // _factor expects it summed over the ranks, and leaves this rank's summand of comm2 (if a.comm2 is given)
-// initial (0 / 1; -1: not said): the reduction of a trial step / of the starting point - where the dissection's launches follow
-// (FactorBuffers::nd_lim), the end-of-trial logic rides in this launch and launch_step2_factor(a, initial) leaves it out
-hipError_t launch_step2_reduce(const Step2Args& a, hipStream_t stream, int initial = -1);
-hipError_t launch_step2_factor(const Step2Args& a, bool initial, hipStream_t stream);
+hipError_t launch_step2_reduce(const Step2Args& a, hipStream_t stream, bool side_forked);
+hipError_t launch_step2_factor(const Step2Args& a, hipStream_t stream);
 int64_t    step2_comm1_doubles(const NormalDims& nd);
 hipError_t launch_mask_state(const NormalDims& nd, const BlockRanges& br, bool is_leader, double* b, hipStream_t stream);
 const int* solver_ctl_skip_eval2(const SolverCtl* ctl);
+// the board rows come with per-observation Grams: every lens model but the splined one (whose assembly goes row by row)
+inline bool problem_has_grams(const DeviceProblem& P)
+{
+    return P.Nobs_board > 0 && P.lens_type != MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC;
+}
 // host-driven evaluation: deterministic block normal equations of the point R from the Grams (no elimination)
 // (with side and the two events: what only A, g of the camera block and |x|^2 wait for goes to the side stream,
 //  forked after the kernels Bt, D come from; *forked tells the caller to wait for ev_join before it reads those)

@@ -10,18 +10,6 @@ namespace mrcal_amd {
 
 // (quadform_body, backsub_eblock: step_device.hpp - cholesky_lds.hip runs them beside the factorization)
 __global__ __launch_bounds__(256)
-void quadform_kernel(NormalDims nd, OpRef R, const double* __restrict__ v_in, int v_is_g,
-                     double* __restrict__ out_in, int out_in_scalars_at, int nout)
-{
-    if(opref_skip(R)) return;
-    const OpDev& O = opref_get(R);
-    const double* __restrict__ v   = v_is_g ? O.g : v_in;
-    double*       __restrict__ out = (out_in != NULL) ? out_in : (O.scalars + out_in_scalars_at);
-    const double mine = quadform_body(nd, O, v, blockIdx.x);
-    if(threadIdx.x < nout) atomicAdd(&out[threadIdx.x], mine);
-}
-
-__global__ __launch_bounds__(256)
 void dot_kernel(int n, const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ out)
 {
     double acc = 0.0;
@@ -32,15 +20,6 @@ void dot_kernel(int n, const double* __restrict__ a, const double* __restrict__ 
     if((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
     __syncthreads();
     if(threadIdx.x == 0) atomicAdd(out, part[0]+part[1]+part[2]+part[3]);
-}
-
-// y = alpha a + beta b
-__global__ __launch_bounds__(256)
-void axpby_kernel(int n, double alpha, const double* __restrict__ a, double beta, const double* __restrict__ b,
-                  double* __restrict__ y)
-{
-    const int i = blockIdx.x*blockDim.x + threadIdx.x;
-    if(i < n) y[i] = alpha*a[i] + ((b != NULL) ? beta*b[i] : 0.0);
 }
 
 ////////////////////////////////////////////////////////////////////////////////
@@ -250,24 +229,10 @@ static int quadform_blocks(const NormalDims& nd)
 {
     return (nd.Nc + nd.NE + 4*QF_ROWS_PER_WAVE - 1)/(4*QF_ROWS_PER_WAVE);
 }
-hipError_t launch_quadform(const NormalDims& nd, const OpRef& R, const double* v, double* out,
-                           hipStream_t stream)
-{
-    hipLaunchKernelGGL(quadform_kernel, dim3(quadform_blocks(nd)), dim3(256), 0, stream,
-                       nd, R, v, 0, out, 0, 1);
-    return hipGetLastError();
-}
 hipError_t launch_dot(int n, const double* a, const double* b, double* out, hipStream_t stream)
 {
     int nb = (n + 255)/256; if(nb > 1024) nb = 1024; if(nb < 1) nb = 1;
     hipLaunchKernelGGL(dot_kernel, dim3(nb), dim3(256), 0, stream, n, a, b, out);
-    return hipGetLastError();
-}
-hipError_t launch_axpby(int n, double alpha, const double* a, double beta, const double* b, double* y,
-                        hipStream_t stream)
-{
-    if(n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(axpby_kernel, dim3((n+255)/256), dim3(256), 0, stream, n, alpha, a, beta, b, y);
     return hipGetLastError();
 }
 size_t outlier_partial_doubles() { return OUTLIER_BLOCKS; }
@@ -330,7 +295,6 @@ hipError_t launch_mask_state(const NormalDims& nd, const BlockRanges& br, bool i
 }
 
 // ---- the fused step
-static int quadform_blocks(const NormalDims& nd);
 const int* solver_ctl_skip_eval2(const SolverCtl* ctl) { return &((const SolverCtlFlags*)(ctl + 1))->skip_eval; }
 
 ChooseArgs step2_choose_args(const Step2Args& a)
@@ -350,22 +314,21 @@ hipError_t launch_step2_choose(const Step2Args& a, hipStream_t stream)
     return hipGetLastError();
 }
 
-// (launch_step2_assemble left work on the side stream: launch_step2_reduce, which always follows it, joins)
-static thread_local bool step2_side_pending = false;
-// the block normal equations of the point the flags name, and the elimination of its frame/point blocks
-hipError_t launch_step2_assemble(const Step2Args& a, bool initial, hipStream_t stream)
+bool step2_chol_in_lds(const NormalDims& nd) { return chol_fits_lds(nd.Nc); }
+
+// the block normal equations of the point the flags name, and the elimination of its frame/point blocks. *forked: work
+// was left on the side stream, which launch_step2_reduce() joins
+hipError_t launch_step2_assemble(const Step2Args& a, hipStream_t stream, bool* forked)
 {
-    step2_side_pending = false;
+    *forked = false;
     const DeviceProblem& P = *a.P;
     const NormalDims& nd = *a.nd;
     const BlockRanges& br = *a.br;
     SolverCtlFlags* fl = ctl_flags(a.ctl);
-    const int* sel_eval = initial ? &a.ctl->ib : &a.ctl->ia;
-    const bool by_rows = (P.lens_type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC);
+    const int* sel_eval = a.initial ? &a.ctl->ib : &a.ctl->ia;
     int nframes_fused = 0;
-    if(P.Nobs_board > 0 && !by_rows)
+    if(a.with_grams)
     {
-        const int row0 = 2*P.W*P.H*P.Nobs_board;
         nframes_fused = br.frame_hi - br.frame_lo;
         // (round 6) the planned rows of the evaluated point are the launch's last workgroups (a trial without an evaluation
         // skips them: elim_mode != 1). Their sums are added after the Grams' (launch_step2_reduce)
@@ -373,17 +336,14 @@ hipError_t launch_step2_assemble(const Step2Args& a, bool initial, hipStream_t s
         hipLaunchKernelGGL(assemble_factor_kernel, dim3(nframes_fused + a.plan->Nchunks*assemble_chunk_slices(P) + assemble_row_blocks(P, *a.plan) + ngen), dim3(256),
                            assemble_lds_bytes_with_gen(nd, *a.plan), stream, P, nd, br, a.ops, sel_eval, &a.ctl->ib, a.ctl, (const int*)NULL,
                            &fl->elim_mode, 0, 1, 0.0, *a.plan, a.gram, *a.F, nframes_fused, assemble_row0(P, *a.plan), P.Nmeas, a.Jp, a.Ji, ngen);
-        (void)row0;
     }
     else
     {
         // no Grams (splined models, problems without boards): the atomic row-by-row assembly of the evaluated point
         EvalBuffers B; memset(&B, 0, sizeof(B));
         B.R = OpRef{ a.ops, sel_eval, &fl->skip_asm }; B.Jp = (int32_t*)a.Jp; B.Ji = (int32_t*)a.Ji;
-        bool forked = false;
-        const hipError_t e = launch_assemble(P, nd, br, *a.plan, B, stream, a.side, a.ev_fork, a.ev_join, &forked);
+        const hipError_t e = launch_assemble(P, nd, br, *a.plan, B, stream, a.side, a.ev_fork, a.ev_join, forked);
         if(e != hipSuccess) return e;
-        step2_side_pending = forked;
     }
     // the blocks the fused kernel did not eliminate: all of them on the row-by-row
     // path; the point blocks otherwise (their rows are accumulated in the same launch)
@@ -401,53 +361,41 @@ hipError_t launch_step2_assemble(const Step2Args& a, bool initial, hipStream_t s
     return hipGetLastError();
 }
 
-// SYRK (+ finalize of A, g, |x|^2) | S, r and the tail of comm1. (Sharded: comm1 is all-reduced after this)
-// Does the end-of-trial logic (step2_finish) ride in the reduction's launch (round 5)? On a single GPU the tail it reads -
-// g_S, |x|^2, the block elimination's status - is complete when the reduction's last workgroup has written it, and that
-// workgroup can decide the trial there and then, beside the others: the factorization's first launch starts on its matrix
-// at once (and may be several workgroups: the dissection's). Sharded, the tail is summed over the ranks behind this launch.
-// (With the backward sweep - FactorBuffers::use_sweep - the end-of-trial logic and the verdict are launches of their own.)
-static bool step2_finish_rides(const Step2Args& a)
-{
-    return a.comm2 == NULL && !a.F->use_sweep;
-}
-hipError_t launch_step2_reduce(const Step2Args& a, hipStream_t stream, int initial)
+// SYRK (+ finalize of A, g, |x|^2) | S, r and the tail of comm1. (Sharded: comm1 is all-reduced after this.) Where
+// a.finish_rides, the end-of-trial logic rides in this launch; where a.S_packed, it leaves the packed copy of S
+hipError_t launch_step2_reduce(const Step2Args& a, hipStream_t stream, bool side_forked)
 {
     const DeviceProblem& P = *a.P;
     const NormalDims& nd = *a.nd;
     const BlockRanges& br = *a.br;
     const FactorBuffers& F = *a.F;
     SolverCtlFlags* fl = ctl_flags(a.ctl);
-    const bool with_grams = P.Nobs_board > 0 && P.lens_type != MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC;
     FinalizeRide ride; memset(&ride, 0, sizeof(ride));
-    if(with_grams && a.plan->Ndest > 0)
+    if(a.with_grams && a.plan->Ndest > 0)
     {
         ride.npos = gram_stride(P.Ndist); ride.ops = a.ops; ride.sel = &fl->elim_sel; ride.skip = &fl->skip_asm; ride.plan = *a.plan;
     }
     const unsigned char* live = NULL;
     const int nslots = launch_syrk(nd, br, &fl->skip_elim, F, ride.npos ? &ride : NULL, stream, &live);
-    if(with_grams)
+    if(a.with_grams)
     {
         // (after the ride: one adder per destination at a time)
         const hipError_t e = launch_gen_finalize(nd, *a.plan, OpRef{ a.ops, &fl->elim_sel, &fl->skip_asm }, stream);
         if(e != hipSuccess) return e;
     }
     // A, g of the camera block and |x|^2 may still be on their way on the side stream
-    if(step2_side_pending)
+    if(side_forked)
     {
         const hipError_t e = hipStreamWaitEvent(stream, a.ev_join, 0);
         if(e != hipSuccess) return e;
-        step2_side_pending = false;
     }
     const int nb = (nd.Nc + 15)/16, npairs = nb*(nb+1)/2;
     const int nred = ((npairs*256 + nb*16)*(live ? 1 : SRED_SPLIT) + 255)/256;
-    // (the dissection: its matrices' borders and pads by nfill more workgroups; where its launches follow, the end of the
-    //  trial step rides in this launch's last ordinary workgroup - launch_step2_factor() then leaves it out)
-    const bool rides = initial >= 0 && step2_finish_rides(a);
+    // (the dissection: its matrices' borders and pads by nfill more workgroups; the end of the trial step rides in this
+    //  launch's last ordinary workgroup)
     const bool nd_on = F.ndMA != NULL && F.cperm_cur != NULL;
-    const bool nd_launches = nd_on && F.nd_lim.rounds > 0 && rides;
     int nfill = 0;
-    if(nd_launches)
+    if(a.nd_launches)
     {
         // (a thread an entry of what the dissection's matrices hold beside the camera block's entries: step2_reduce_kernel)
         const long long NSp = F.nd_lim.ns_max, nxm = (long long)ND_PANEL*F.nd_lim.rounds, pads = ND_PANEL - 1;
@@ -457,37 +405,35 @@ hipError_t launch_step2_reduce(const Step2Args& a, hipStream_t stream, int initi
         nfill = std::max(nfill, ncopy);
     }
     Step2Dev sd; memset(&sd, 0, sizeof(sd));
-    if(rides) { sd.nd = nd; sd.ops = a.ops; sd.ctl = a.ctl; sd.fl = fl; sd.initial = initial ? 1 : 0; sd.comm1_tail = F.r + nd.Nc; }
+    if(a.finish_rides) { sd.nd = nd; sd.ops = a.ops; sd.ctl = a.ctl; sd.fl = fl; sd.initial = a.initial ? 1 : 0; sd.comm1_tail = F.r + nd.Nc; }
     hipLaunchKernelGGL(step2_reduce_kernel, dim3(nred + 1 + nfill), dim3(256), 0, stream,
                        nd, a.ops, a.ctl, fl, a.is_leader ? 1 : 0, nred, nslots, F.Spart, F.S, F.r, F.status, live, F.cperm_cur, F.iso, &a.ctl->error,
-                       nd_launches ? F.ndMA : (double*)NULL, nd_launches ? F.ndMB : (double*)NULL, nd_on ? F.ndp_cur : (int*)NULL, nfill,
-                       rides ? 1 : 0, sd,
+                       a.nd_launches ? F.ndMA : (double*)NULL, a.nd_launches ? F.ndMB : (double*)NULL, nd_on ? F.ndp_cur : (int*)NULL, nfill,
+                       a.finish_rides ? 1 : 0, sd,
                        // (a packed copy of S for the one-workgroup Cholesky's launch behind this one - launch_cholesky_lds_quadform())
-                       (rides && chol_fits_lds(nd.Nc)) ? factor_S_packed(F, nd.Nc) : (double*)NULL);
+                       a.S_packed ? factor_S_packed(F, nd.Nc) : (double*)NULL);
     return hipGetLastError();
 }
 int64_t step2_comm1_doubles(const NormalDims& nd) { return (int64_t)nd.Nc*nd.Nc + 2*nd.Nc + 2; }
 
 // finish + Cholesky | back-substitution + quadratic form | (sharded) this rank's summands of comm2
-hipError_t launch_step2_factor(const Step2Args& a, bool initial, hipStream_t stream)
+hipError_t launch_step2_factor(const Step2Args& a, hipStream_t stream)
 {
     const NormalDims& nd = *a.nd;
     const BlockRanges& br = *a.br;
     const FactorBuffers& F = *a.F;
     SolverCtlFlags* fl = ctl_flags(a.ctl);
     Step2Dev sd;
-    sd.nd = nd; sd.ops = a.ops; sd.ctl = a.ctl; sd.fl = fl; sd.initial = initial ? 1 : 0;
+    sd.nd = nd; sd.ops = a.ops; sd.ctl = a.ctl; sd.fl = fl; sd.initial = a.initial ? 1 : 0;
     sd.comm1_tail = F.r + nd.Nc;
-    bool qf_rode = false;
     {
         const int n = nd.Nc;
-        // (round 5, single GPU: the end-of-trial logic has run in the reduction's launch - step2_finish_rides())
-        const bool finish_done = step2_finish_rides(a);
         if(chol_fits_lds(n))
         {
-            // (round 6, single GPU: the quadratic form's workgroups in the factorization's launch - they never needed it)
-            if(finish_done) { launch_cholesky_lds_quadform(n, nd, F, sd, a.plan->qf_part, quadform_blocks(nd), stream); qf_rode = true; }
-            else            launch_cholesky_lds(1, n, (const int*)NULL, 0, F.S, F.r, F.status, sd, stream);
+            // (round 6, single GPU: the end-of-trial logic has run in the reduction's launch, which left the packed S; the
+            //  quadratic form's workgroups in the factorization's launch - they never needed it)
+            if(a.S_packed) launch_cholesky_lds_quadform(n, nd, F, sd, a.plan->qf_part, quadform_blocks(nd), stream);
+            else           launch_cholesky_lds(1, n, (const int*)NULL, 0, F.S, F.r, F.status, sd, stream);
         }
         else
         {
@@ -501,9 +447,8 @@ hipError_t launch_step2_factor(const Step2Args& a, bool initial, hipStream_t str
             const bool compact = F.cperm_cur != NULL;       // (what the reduction went by; never with the backward sweep: solver.cpp)
             if(compact) { cp.cperm = F.cperm_cur; cp.iso = F.iso; cp.dout = F.r; cp.Nc = n; }
             // (the dissection's launches, where the host has provided for them: learn_likely_size())
-            const bool nd_launches = compact && F.ndMA != NULL && F.nd_lim.rounds > 0 && finish_done;
             LcholNdLaunch nds; memset(&nds, 0, sizeof(nds));
-            if(nd_launches)
+            if(a.nd_launches)
             {
                 const int* h = F.ndp_cur;
                 nds.A = LcholChain{ F.ndMA, F.ndLinvA, h + NDH_NA, h + NDH_NS };
@@ -512,17 +457,17 @@ hipError_t launch_step2_factor(const Step2Args& a, bool initial, hipStream_t str
                 cp.ndh = h; cp.ndMA = F.ndMA; cp.ndMB = F.ndMB; cp.ndpart = F.ndPart;
             }
             launch_cholesky_large(n, &fl->skip_chol, F.S, F.Linv, F.status, stream, separate ? NULL : &sd, &fused,
-                                  compact ? (nd_launches ? F.ndp_cur + NDH_NSEFF : F.cperm_cur + 2*n) : (const int*)NULL,
+                                  compact ? (a.nd_launches ? F.ndp_cur + NDH_NSEFF : F.cperm_cur + 2*n) : (const int*)NULL,
                                   compact ? &cp : (const LcholCompact*)NULL,
-                                  compact ? (nd_launches ? F.nd_likely_panels : F.lchol_likely_panels) : 0,
-                                  compact ? (unsigned*)(F.cperm_cur + 2*n + 1) : (unsigned*)NULL, nd_launches ? &nds : (const LcholNdLaunch*)NULL,
-                                  finish_done, F.use_sweep != 0, F.diag_minmax);
+                                  compact ? (a.nd_launches ? F.nd_likely_panels : F.lchol_likely_panels) : 0,
+                                  compact ? (unsigned*)(F.cperm_cur + 2*n + 1) : (unsigned*)NULL, a.nd_launches ? &nds : (const LcholNdLaunch*)NULL,
+                                  a.finish_rides, F.use_sweep != 0, F.diag_minmax);
             if(separate) hipLaunchKernelGGL(step2_post_kernel, dim3(1), dim3(64), 0, stream, sd, F.status);
             else if(!fused) return hipErrorInvalidValue;
         }
     }
     const int nbs = (br.count() + 3)/4, nqf = quadform_blocks(nd);
-    hipLaunchKernelGGL(step2_backsub_quadform_kernel, dim3(nbs + 1 + (qf_rode ? 0 : nqf)), dim3(256), 0, stream,
+    hipLaunchKernelGGL(step2_backsub_quadform_kernel, dim3(nbs + 1 + (a.S_packed ? 0 : nqf)), dim3(256), 0, stream,
                        nd, br, a.ops, a.ctl, fl, F.Wt, F.LD, F.y, F.r, a.plan->dots_part, a.plan->qf_part, nbs, a.snap,
                        (nd.Nc > SYRK_STRIP_FROM) ? F.occ : (const unsigned*)NULL, occ_words(nd));
     if(a.comm2 != NULL)
