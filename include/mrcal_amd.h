@@ -421,6 +421,12 @@ const char* mrcal_amd_last_error(void);
 /* Number of visible HIP devices; <=0 if there is no usable GPU */
 int mrcal_amd_device_count(void);
 
+/* Device and pinned-host buffers the library holds in this process right now, over
+   all problems, factorizations and uncertainty contexts: back at its earlier value
+   once everything made since has been destroyed (the drop-in entry points tear
+   their problem down on a thread of their own, a moment after they return) */
+long mrcal_amd_device_buffers_live(void);
+
 typedef struct mrcal_amd_problem mrcal_amd_problem_t;
 
 /* Uploads a whole optimization problem (same arguments as

@@ -25,16 +25,6 @@
 
 using namespace mrcal_amd;
 
-#define HIP_TRY(expr, onfail)                                           \
-    do {                                                                \
-        hipError_t _e = (expr);                                         \
-        if(_e != hipSuccess)                                            \
-        {                                                               \
-            set_error("%s:%d: %s failed: %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-            onfail;                                                     \
-        }                                                               \
-    } while(0)
-
 struct mrcal_amd_factorization
 {
     NormalDims    nd;
@@ -52,29 +42,11 @@ struct mrcal_amd_factorization
     int           batch_capacity = 0;
     int           Nmeas = 0;
     hipStream_t   stream = NULL;
-    std::vector<void*> allocs;
+    DeviceBuffers mem;
 
-    template<class T> bool alloc(T** p, size_t n)
-    {
-        *p = NULL;
-        if(n == 0) n = 1;
-        if(hipMalloc((void**)p, n*sizeof(T)) != hipSuccess)
-        {
-            set_error("out of device memory allocating %zu bytes for a factorization", n*sizeof(T));
-            return false;
-        }
-        allocs.push_back((void*)*p);
-        return true;
-    }
-    void release(void* p)
-    {
-        if(!p) return;
-        for(size_t i = 0; i < allocs.size(); i++)
-            if(allocs[i] == p) { hipStreamSynchronize(stream); hipFree(p); allocs.erase(allocs.begin() + i); return; }
-    }
     ~mrcal_amd_factorization()
     {
-        for(void* p : allocs) hipFree(p);
+        mem.free_all();
         if(stream) hipStreamDestroy(stream);
     }
 };
@@ -96,27 +68,27 @@ static mrcal_amd_factorization* factorization_alloc(const NormalDims& nd_in, con
     bool ok = true;
     memset(&f->op, 0, sizeof(f->op));
     HIP_TRY(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking), ok = false);
-    ok = ok && f->alloc(&f->d_Jp, (size_t)Nmeas+1);
-    ok = ok && f->alloc(&f->d_Ji, (size_t)Nnz);
-    ok = ok && f->alloc(&f->op.Jv, (size_t)Nnz);
-    ok = ok && f->alloc(&f->op.x,  (size_t)Nmeas);
-    ok = ok && f->alloc(&f->op.A,  (size_t)nd.Nc*nd.Nc);
-    ok = ok && f->alloc(&f->op.Bt, (size_t)nd.NE*nd.Nc);
-    ok = ok && f->alloc(&f->op.D,  (size_t)nd.NEb*36);
-    ok = ok && f->alloc(&f->op.g,  (size_t)nd.Nstate);
-    ok = ok && f->alloc(&f->op.scalars, (size_t)NSCALARS);
-    ok = ok && f->alloc(&f->op.step_gn, (size_t)nd.Nstate);
-    ok = ok && f->alloc(&f->d_op, 1);
-    ok = ok && f->alloc(&f->F.Wt, (size_t)nd.NE*nd.Nc);
-    ok = ok && f->alloc(&f->F.LD, (size_t)nd.NEb*36);
-    ok = ok && f->alloc(&f->F.y,  (size_t)nd.NE);
-    ok = ok && f->alloc(&f->F.S,  (size_t)nd.Nc*nd.Nc + nd.Nc);
-    ok = ok && f->alloc(&f->F.Spart, schur_partial_doubles(nd));
-    ok = ok && f->alloc(&f->F.Linv,  cholesky_large_workspace_doubles(nd.Nc));
-    ok = ok && f->alloc(&f->F.status, 1);
-    ok = ok && f->alloc(&f->d_rhs, (size_t)nd.Nstate);
-    ok = ok && f->alloc(&f->d_sol, (size_t)nd.Nstate);
-    ok = ok && f->alloc(&f->d_mm, 2);
+    ok = ok && f->mem.alloc(&f->d_Jp, (size_t)Nmeas+1);
+    ok = ok && f->mem.alloc(&f->d_Ji, (size_t)Nnz);
+    ok = ok && f->mem.alloc(&f->op.Jv, (size_t)Nnz);
+    ok = ok && f->mem.alloc(&f->op.x,  (size_t)Nmeas);
+    ok = ok && f->mem.alloc(&f->op.A,  (size_t)nd.Nc*nd.Nc);
+    ok = ok && f->mem.alloc(&f->op.Bt, (size_t)nd.NE*nd.Nc);
+    ok = ok && f->mem.alloc(&f->op.D,  (size_t)nd.NEb*36);
+    ok = ok && f->mem.alloc(&f->op.g,  (size_t)nd.Nstate);
+    ok = ok && f->mem.alloc(&f->op.scalars, (size_t)NSCALARS);
+    ok = ok && f->mem.alloc(&f->op.step_gn, (size_t)nd.Nstate);
+    ok = ok && f->mem.alloc(&f->d_op, 1);
+    ok = ok && f->mem.alloc(&f->F.Wt, (size_t)nd.NE*nd.Nc);
+    ok = ok && f->mem.alloc(&f->F.LD, (size_t)nd.NEb*36);
+    ok = ok && f->mem.alloc(&f->F.y,  (size_t)nd.NE);
+    ok = ok && f->mem.alloc(&f->F.S,  (size_t)nd.Nc*nd.Nc + nd.Nc);
+    ok = ok && f->mem.alloc(&f->F.Spart, schur_partial_doubles(nd));
+    ok = ok && f->mem.alloc(&f->F.Linv,  cholesky_large_workspace_doubles(nd.Nc));
+    ok = ok && f->mem.alloc(&f->F.status, 1);
+    ok = ok && f->mem.alloc(&f->d_rhs, (size_t)nd.Nstate);
+    ok = ok && f->mem.alloc(&f->d_sol, (size_t)nd.Nstate);
+    ok = ok && f->mem.alloc(&f->d_mm, 2);
     if(!ok) { delete f; return NULL; }
     f->F.r = f->F.S + (size_t)nd.Nc*nd.Nc;
     return f;
@@ -216,12 +188,12 @@ mrcal_amd_factorization_create(int Nmeas, int Nstate,
     // bits whatever order the atomics land in.
     // The factorization optimizer_callback() returns does not come through here: mrcal_amd_factorization_create_from_problem()
     const OpRef R = { f->d_op, NULL, NULL };
+    DeviceBuffers tmp;
     double* scratch = NULL;
-    HIP_TRY(hipMalloc((void**)&scratch, assemble_rows_scratch_doubles(f->nd)*sizeof(double)), { delete f; return NULL; });
+    if(!tmp.alloc(&scratch, assemble_rows_scratch_doubles(f->nd))) { delete f; return NULL; }
     const hipError_t ea = launch_assemble_rows(f->nd, R, Nmeas, f->d_Jp, f->d_Ji, f->stream, scratch, Nnz);
     mrcal_amd_factorization* out = (ea == hipSuccess) ? factorization_finish(f) : NULL;      // (synchronizes the stream)
     if(ea != hipSuccess) { set_error("launch_assemble_rows: %s", hipGetErrorString(ea)); delete f; }
-    if(scratch != NULL) hipFree(scratch);
     return out;
 }
 
@@ -288,8 +260,10 @@ static int batch_prepare(mrcal_amd_factorization_t* f, int Nrhs, size_t* part_pe
     if(f->batch_capacity < BATCH)
     {
         double *rb = NULL, *sb = NULL, *sc = NULL;
-        if(!f->alloc(&rb, (size_t)BATCH*n) || !f->alloc(&sb, (size_t)BATCH*n) || !f->alloc(&sc, (size_t)BATCH*per_rhs)) return 0;
-        f->release(f->d_rhs_batch); f->release(f->d_sol_batch); f->release(f->d_batch_scratch);
+        if(!f->mem.alloc(&rb, (size_t)BATCH*n) || !f->mem.alloc(&sb, (size_t)BATCH*n) || !f->mem.alloc(&sc, (size_t)BATCH*per_rhs)) return 0;
+        // (the smaller ones may still be in use on the stream)
+        if(f->batch_capacity > 0) hipStreamSynchronize(f->stream);
+        f->mem.release(&f->d_rhs_batch); f->mem.release(&f->d_sol_batch); f->mem.release(&f->d_batch_scratch);
         f->d_rhs_batch = rb; f->d_sol_batch = sb; f->d_batch_scratch = sc; f->batch_capacity = BATCH;
     }
     return BATCH;
@@ -338,13 +312,13 @@ bool mrcal_amd_factorization_Jt_x(mrcal_amd_factorization_t* f, const double* x,
     last_error_string().clear();
     const size_t n = (size_t)f->nd.Nstate;
     HIP_TRY(hipMemcpyAsync(f->op.x, x, (size_t)f->Nmeas*sizeof(double), hipMemcpyHostToDevice, f->stream), return false);
+    DeviceBuffers tmp;
     double* scratch = NULL;
-    HIP_TRY(hipMalloc((void**)&scratch, csr_Jt_x_scratch_doubles(f->Nmeas, (int)n)*sizeof(double)), return false);
+    if(!tmp.alloc(&scratch, csr_Jt_x_scratch_doubles(f->Nmeas, (int)n))) return false;
     bool ok = true;
     HIP_TRY(launch_csr_Jt_x(f->Nmeas, (int)n, f->d_Jp, f->d_Ji, f->op.Jv, f->op.x, f->d_sol, scratch, f->stream), ok = false);
     if(ok) HIP_TRY(hipMemcpyAsync(y, f->d_sol, n*sizeof(double), hipMemcpyDeviceToHost, f->stream), ok = false);
     if(ok) HIP_TRY(hipStreamSynchronize(f->stream), ok = false);
-    hipFree(scratch);
     return ok;
 }
 
@@ -360,39 +334,19 @@ bool mrcal_amd_factorization_A_Jt_J_At(mrcal_amd_factorization_t* f, const doubl
         return false;
     }
     const size_t n = (size_t)f->nd.Nstate;
+    DeviceBuffers tmp;
     double *dA = NULL, *dout = NULL;
-    bool ok = true;
     const size_t nscratch = (size_t)64*((Nleading_rows_J + 255)/256);
-    HIP_TRY(hipMalloc((void**)&dA, (size_t)Nx*n*sizeof(double)), return false);
-    HIP_TRY(hipMalloc((void**)&dout, (64 + nscratch)*sizeof(double)), ok = false);
+    bool ok = tmp.alloc(&dA, (size_t)Nx*n) && tmp.alloc(&dout, 64 + nscratch);
     if(ok) HIP_TRY(hipMemcpyAsync(dA, A, (size_t)Nx*n*sizeof(double), hipMemcpyHostToDevice, f->stream), ok = false);
     if(ok) HIP_TRY(launch_csr_A_Jt_J_At(Nx, Nleading_rows_J, (int)n, f->d_Jp, f->d_Ji, f->op.Jv, dA, dout, dout + 64, f->stream), ok = false);
     if(ok) HIP_TRY(hipMemcpyAsync(out, dout, (size_t)Nx*Nx*sizeof(double), hipMemcpyDeviceToHost, f->stream), ok = false);
     if(ok) HIP_TRY(hipStreamSynchronize(f->stream), ok = false);
-    hipFree(dA); hipFree(dout);
     return ok;
 }
 
 // The same two for a CSR matrix that is on the host (the reference's signatures take the
 // p, i, x arrays: mrcal._mrcal_npsp._Jt_x, _A_Jt_J_At): upload, compute, free
-namespace {
-struct CsrOnDevice
-{
-    int32_t *Jp = NULL, *Ji = NULL; double *Jx = NULL; bool ok = false;
-    CsrOnDevice(int Nrows, const int32_t* p, const int32_t* i, const double* x)
-    {
-        const size_t nnz = (size_t)p[Nrows];
-        if(hipMalloc((void**)&Jp, ((size_t)Nrows+1)*sizeof(int32_t)) != hipSuccess) return;
-        if(hipMalloc((void**)&Ji, (nnz ? nnz : 1)*sizeof(int32_t)) != hipSuccess) return;
-        if(hipMalloc((void**)&Jx, (nnz ? nnz : 1)*sizeof(double)) != hipSuccess) return;
-        if(hipMemcpy(Jp, p, ((size_t)Nrows+1)*sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) return;
-        if(nnz && hipMemcpy(Ji, i, nnz*sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) return;
-        if(nnz && hipMemcpy(Jx, x, nnz*sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return;
-        ok = true;
-    }
-    ~CsrOnDevice() { hipFree(Jp); hipFree(Ji); hipFree(Jx); }
-};
-}
 // the caller's CSR is what the kernels index with: rowptr non-decreasing from 0, every column inside the matrix
 static bool csr_is_valid(int Nrows, int Ncols, const int32_t* Jp, const int32_t* Ji)
 {
@@ -411,17 +365,15 @@ bool mrcal_amd_csr_Jt_x(int Nrows, int Ncols, const int32_t* Jp, const int32_t* 
     last_error_string().clear();
     if(mrcal_amd_device_count() <= 0) { set_error("no HIP device is visible: libmrcal_amd has no CPU fallback"); return false; }
     if(!csr_is_valid(Nrows, Ncols, Jp, Ji)) return false;
-    CsrOnDevice J(Nrows, Jp, Ji, Jx);
-    if(!J.ok) { set_error("could not put J on the device"); return false; }
+    DeviceBuffers tmp;
+    CsrDev J;
     double *dx = NULL, *dy = NULL;
-    bool ok = true;
-    HIP_TRY(hipMalloc((void**)&dx, (size_t)(Nrows > 0 ? Nrows : 1)*sizeof(double)), return false);
-    HIP_TRY(hipMalloc((void**)&dy, ((size_t)(Ncols > 0 ? Ncols : 1) + csr_Jt_x_scratch_doubles(Nrows, Ncols))*sizeof(double)), ok = false);
-    if(ok) HIP_TRY(hipMemcpy(dx, x, (size_t)Nrows*sizeof(double), hipMemcpyHostToDevice), ok = false);
+    bool ok = upload_csr(tmp, &J, Nrows, Jp, Ji, Jx);
+    ok = ok && tmp.upload(&dx, x, (size_t)Nrows);
+    ok = ok && tmp.alloc(&dy, (size_t)(Ncols > 0 ? Ncols : 1) + csr_Jt_x_scratch_doubles(Nrows, Ncols));
     if(ok) HIP_TRY(hipDeviceSynchronize(), ok = false);
     if(ok) HIP_TRY(launch_csr_Jt_x(Nrows, Ncols, J.Jp, J.Ji, J.Jx, dx, dy, dy + (Ncols > 0 ? Ncols : 1), NULL), ok = false);
     if(ok) HIP_TRY(hipMemcpy(y, dy, (size_t)Ncols*sizeof(double), hipMemcpyDeviceToHost), ok = false);
-    hipFree(dx); hipFree(dy);
     return ok;
 }
 bool mrcal_amd_csr_A_Jt_J_At(int Nrows, int Ncols, const int32_t* Jp, const int32_t* Ji, const double* Jx,
@@ -436,18 +388,16 @@ bool mrcal_amd_csr_A_Jt_J_At(int Nrows, int Ncols, const int32_t* Jp, const int3
         return false;
     }
     if(!csr_is_valid(Nrows, Ncols, Jp, Ji)) return false;
-    CsrOnDevice J(Nrows, Jp, Ji, Jx);
-    if(!J.ok) { set_error("could not put J on the device"); return false; }
+    DeviceBuffers tmp;
+    CsrDev J;
     double *dA = NULL, *dout = NULL;
-    bool ok = true;
     const size_t nscratch = (size_t)64*((Nleading_rows_J + 255)/256);
-    HIP_TRY(hipMalloc((void**)&dA, (size_t)Nx*Ncols*sizeof(double)), return false);
-    HIP_TRY(hipMalloc((void**)&dout, (64 + nscratch)*sizeof(double)), ok = false);
-    if(ok) HIP_TRY(hipMemcpy(dA, A, (size_t)Nx*Ncols*sizeof(double), hipMemcpyHostToDevice), ok = false);
+    bool ok = upload_csr(tmp, &J, Nrows, Jp, Ji, Jx);
+    ok = ok && tmp.upload(&dA, A, (size_t)Nx*Ncols);
+    ok = ok && tmp.alloc(&dout, 64 + nscratch);
     if(ok) HIP_TRY(hipDeviceSynchronize(), ok = false);
     if(ok) HIP_TRY(launch_csr_A_Jt_J_At(Nx, Nleading_rows_J, Ncols, J.Jp, J.Ji, J.Jx, dA, dout, dout + 64, NULL), ok = false);
     if(ok) HIP_TRY(hipMemcpy(out, dout, (size_t)Nx*Nx*sizeof(double), hipMemcpyDeviceToHost), ok = false);
-    hipFree(dA); hipFree(dout);
     return ok;
 }
 

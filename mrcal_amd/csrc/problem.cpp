@@ -26,69 +26,10 @@
 
 using namespace mrcal_amd;
 
-#define HIP_TRY(expr, onfail)                                           \
-    do {                                                                \
-        hipError_t _e = (expr);                                         \
-        if(_e != hipSuccess)                                            \
-        {                                                               \
-            set_error("%s:%d: %s failed: %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-            onfail;                                                     \
-        }                                                               \
-    } while(0)
-
-namespace mrcal_amd {
-
-template<class T>
-static bool dev_alloc(T** p, size_t n)
-{
-    *p = NULL;
-    if(n == 0) n = 1;
-    HIP_TRY(hipMalloc((void**)p, n*sizeof(T)), return false);
-    return true;
-}
-template<class T>
-static bool dev_upload(T** p, const T* host, size_t n)
-{
-    if(!dev_alloc(p, n)) return false;
-    if(n > 0 && host != NULL)
-        HIP_TRY(hipMemcpy(*p, host, n*sizeof(T), hipMemcpyHostToDevice), return false);
-    return true;
-}
-
-} // namespace
-
 mrcal_amd_problem::~mrcal_amd_problem()
 {
-    hipFree(d_seed_intrinsics); hipFree(d_seed_rt_cam_ref); hipFree(d_seed_rt_ref_frame);
-    hipFree(d_seed_points); hipFree(d_board_meta); hipFree(d_board_pool);
-    hipFree(d_point_meta); hipFree(d_point_pool); hipFree(d_imagersizes);
-    hipFree(d_tri_meta); hipFree(d_tri_px); hipFree(d_tri_outlier);
-    hipFree(d_joint); hipFree(d_gram); hipFree(d_Jp); hipFree(d_Ji);
-    for(int i=0;i<2;i++)
-    {
-        hipFree(op[i].b); hipFree(op[i].x); hipFree(op[i].Jv); hipFree(op[i].spl_box);
-        hipFree(op[i].A); hipFree(op[i].Bt); hipFree(op[i].D); hipFree(op[i].g); hipFree(op[i].scalars);
-        hipFree(op[i].step_cauchy); hipFree(op[i].step_gn);
-    }
-    hipFree(d_ops);
-    hipFree(plan.frame_obs_begin); hipFree(plan.frame_obs); hipFree(plan.chunk_begin); hipFree(plan.pair_obs); hipFree(plan.pos_table);
-    hipFree(plan.chunk_pair); hipFree(plan.obs_pair); hipFree(plan.pair_table); hipFree(plan.frame_pos); hipFree(plan.obs_cols);
-    hipFree(plan.chunk_part); hipFree(plan.dest_id); hipFree(plan.dest_begin); hipFree(plan.dest_src);
-    hipFree(plan.pair_chunk_begin); hipFree(plan.row_part); hipFree(plan.qf_part); hipFree(plan.dots_part);
-    hipFree(plan.spl_hdr); hipFree(plan.spl_part); hipFree(plan.spl_hdr_extra); hipFree(plan.chunk_extra);
-    {
-        mrcal_amd::GenPlan& G = plan.gen;
-        hipFree(G.rows); hipFree(G.chunk_begin); hipFree(G.chunk_group); hipFree(G.group_k); hipFree(G.group_off); hipFree(G.spos);
-        hipFree(G.scol); hipFree(G.part); hipFree(G.dest_id); hipFree(G.dest_begin); hipFree(G.dest_src); hipFree(G.group_chunk_begin);
-        hipFree(G.eb_block); hipFree(G.eb_begin); hipFree(G.eb_rows); hipFree(G.eb_group); hipFree(G.eb_epos);
-    }
-    hipFree(F.Wt); hipFree(F.LD); hipFree(F.y); hipFree(F.S); hipFree(F.Spart); hipFree(F.Linv); hipFree(F.diag_minmax); hipFree(F.status); hipFree(F.occ); hipFree(F.Wtile);
-    hipFree(cperm_cur_alloc); hipFree(F.iso); hipFree(op[0].cperm); hipFree(op[1].cperm);
-    hipFree(op[0].ndp); hipFree(op[1].ndp); hipFree(F.ndp_cur); hipFree(F.ndMA); hipFree(F.ndMB); hipFree(F.ndLinvA); hipFree(F.ndLinvB); hipFree(F.ndPart); hipFree(F.nd_lim_dev);
-    hipFree(plan.repro.lvl[0]); hipFree(plan.repro.lvl[1]); hipFree(plan.repro.lvl[2]); hipFree(plan.repro.cmax); hipFree(plan.repro.any);
-    hipFree(d_step); hipFree(d_comm); hipFree(d_counts); hipFree(d_outlier_part); hipFree(d_ctl);
-    if(h_scalars)  hipHostFree(h_scalars);
-    if(h_ctl_ring) hipHostFree(h_ctl_ring);
+    // (the buffers before the streams, whatever the order of the members)
+    mem.free_all();
     for(hipEvent_t e : ctl_events) hipEventDestroy(e);
     for(hipEvent_t e : ev_pool) hipEventDestroy(e);
     if(ev_j0)  hipEventDestroy(ev_j0);
@@ -252,66 +193,66 @@ static bool build_gen_plan(mrcal_amd_problem* P)
     nonempty(chunk_group); nonempty(spos_all); nonempty(scol_all); nonempty(dest_id); nonempty(dest_src);
     nonempty(eb_block); nonempty(eb_rows); nonempty(eb_group); nonempty(eb_epos);
     bool ok = true;
-    ok = ok && dev_upload(&G.rows,        rows.data(),        rows.size());
-    ok = ok && dev_upload(&G.chunk_begin, chunk_begin.data(), chunk_begin.size());
-    ok = ok && dev_upload(&G.chunk_group, chunk_group.data(), chunk_group.size());
-    ok = ok && dev_upload(&G.group_k,     group_k.data(),     group_k.size());
-    ok = ok && dev_upload(&G.group_off,   group_off.data(),   group_off.size());
-    ok = ok && dev_upload(&G.spos,        spos_all.data(),    spos_all.size());
-    ok = ok && dev_upload(&G.scol,        scol_all.data(),    scol_all.size());
-    ok = ok && dev_upload(&G.dest_id,     dest_id.data(),     dest_id.size());
-    ok = ok && dev_upload(&G.dest_begin,  dest_begin.data(),  dest_begin.size());
-    ok = ok && dev_upload(&G.dest_src,    dest_src.data(),    dest_src.size());
-    ok = ok && dev_upload(&G.group_chunk_begin, group_chunk_begin.data(), group_chunk_begin.size());
-    ok = ok && dev_upload(&G.eb_block,    eb_block.data(),    eb_block.size());
-    ok = ok && dev_upload(&G.eb_begin,    eb_begin.data(),    eb_begin.size());
-    ok = ok && dev_upload(&G.eb_rows,     eb_rows.data(),     eb_rows.size());
-    ok = ok && dev_upload(&G.eb_group,    eb_group.data(),    eb_group.size());
-    ok = ok && dev_upload(&G.eb_epos,     eb_epos.data(),     eb_epos.size());
-    ok = ok && dev_alloc (&G.part, (size_t)(Nchunks > 0 ? Nchunks : 1)*stride);
+    ok = ok && P->mem.upload(&G.rows,        rows.data(),        rows.size());
+    ok = ok && P->mem.upload(&G.chunk_begin, chunk_begin.data(), chunk_begin.size());
+    ok = ok && P->mem.upload(&G.chunk_group, chunk_group.data(), chunk_group.size());
+    ok = ok && P->mem.upload(&G.group_k,     group_k.data(),     group_k.size());
+    ok = ok && P->mem.upload(&G.group_off,   group_off.data(),   group_off.size());
+    ok = ok && P->mem.upload(&G.spos,        spos_all.data(),    spos_all.size());
+    ok = ok && P->mem.upload(&G.scol,        scol_all.data(),    scol_all.size());
+    ok = ok && P->mem.upload(&G.dest_id,     dest_id.data(),     dest_id.size());
+    ok = ok && P->mem.upload(&G.dest_begin,  dest_begin.data(),  dest_begin.size());
+    ok = ok && P->mem.upload(&G.dest_src,    dest_src.data(),    dest_src.size());
+    ok = ok && P->mem.upload(&G.group_chunk_begin, group_chunk_begin.data(), group_chunk_begin.size());
+    ok = ok && P->mem.upload(&G.eb_block,    eb_block.data(),    eb_block.size());
+    ok = ok && P->mem.upload(&G.eb_begin,    eb_begin.data(),    eb_begin.size());
+    ok = ok && P->mem.upload(&G.eb_rows,     eb_rows.data(),     eb_rows.size());
+    ok = ok && P->mem.upload(&G.eb_group,    eb_group.data(),    eb_group.size());
+    ok = ok && P->mem.upload(&G.eb_epos,     eb_epos.data(),     eb_epos.size());
+    ok = ok && P->mem.alloc(&G.part, (size_t)(Nchunks > 0 ? Nchunks : 1)*stride);
     if(!ok) return false;
     G.Nrows = r1 - r0; G.Nchunks = Nchunks; G.Ngroups = Ngroups; G.stride = stride; G.kmax = kmax;
     G.Ndest = Ndest; G.Neblocks = Neb;
     return true;
 }
 
-bool problem_prepare_solver(mrcal_amd_problem* P)
+static bool allocate_solver_buffers(mrcal_amd_problem* P)
 {
-    if(P->solver_ready) return true;
     const Layout& L = P->L;
     NormalDims& nd = P->nd;
 
     // second operating point
     bool ok = true;
-    ok = ok && dev_alloc(&P->op[1].b,  (size_t)L.Nstate);
-    ok = ok && dev_alloc(&P->op[1].x,  (size_t)L.Nmeas);
-    ok = ok && dev_alloc(&P->op[1].Jv, (size_t)P->Nnz);
-    if(P->op[0].spl_box != NULL) ok = ok && dev_alloc(&P->op[1].spl_box, (size_t)4*P->D.Nobs_board);
+    ok = ok && P->mem.alloc(&P->op[1].b,  (size_t)L.Nstate);
+    ok = ok && P->mem.alloc(&P->op[1].x,  (size_t)L.Nmeas);
+    ok = ok && P->mem.alloc(&P->op[1].Jv, (size_t)P->Nnz);
+    if(P->op[0].spl_box != NULL) ok = ok && P->mem.alloc(&P->op[1].spl_box, (size_t)4*P->D.Nobs_board);
     if(L.lensmodel.type != MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC && (size_t)P->D.Nobs_board*gram_stride(L.Ndist) >= ((size_t)1 << 32))
     {
         // (reduce_pair_chunk() addresses the Grams with 32-bit element offsets; this is 34 GB of Grams)
         set_error("too many board observations: %d Grams of %d doubles", P->D.Nobs_board, gram_stride(L.Ndist));
         return false;
     }
-    ok = ok && dev_alloc(&P->d_gram,   (L.lensmodel.type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC) ? (size_t)1 : (size_t)P->D.Nobs_board*gram_stride(L.Ndist));
+    ok = ok && P->mem.alloc(&P->d_gram,   (L.lensmodel.type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC) ? (size_t)1 : (size_t)P->D.Nobs_board*gram_stride(L.Ndist));
     for(int i=0;i<2 && ok;i++)
     {
-        ok = ok && dev_alloc(&P->op[i].A,       (size_t)nd.Nc*nd.Nc);
-        ok = ok && dev_alloc(&P->op[i].Bt,      (size_t)nd.NE*nd.Nc);
-        ok = ok && dev_alloc(&P->op[i].D,       (size_t)nd.NEb*36);
-        ok = ok && dev_alloc(&P->op[i].g,       (size_t)nd.Nstate);
-        ok = ok && dev_alloc(&P->op[i].scalars, (size_t)NSCALARS);
-        ok = ok && dev_alloc(&P->op[i].step_cauchy, (size_t)nd.Nstate);
-        ok = ok && dev_alloc(&P->op[i].step_gn,     (size_t)nd.Nstate);
+        ok = ok && P->mem.alloc(&P->op[i].A,       (size_t)nd.Nc*nd.Nc);
+        // (rows of blocks nobody writes - frames without observations in this shard - must read as zero)
+        ok = ok && P->mem.alloc_zeroed(&P->op[i].Bt, (size_t)nd.NE*nd.Nc);
+        ok = ok && P->mem.alloc_zeroed(&P->op[i].D,  (size_t)nd.NEb*36);
+        ok = ok && P->mem.alloc_zeroed(&P->op[i].g,  (size_t)nd.Nstate);
+        ok = ok && P->mem.alloc(&P->op[i].scalars, (size_t)NSCALARS);
+        ok = ok && P->mem.alloc_zeroed(&P->op[i].step_cauchy, (size_t)nd.Nstate);
+        ok = ok && P->mem.alloc_zeroed(&P->op[i].step_gn,     (size_t)nd.Nstate);
     }
-    ok = ok && dev_alloc(&P->F.Spart, schur_partial_doubles(nd));
-    ok = ok && dev_alloc(&P->F.Linv,  cholesky_large_workspace_doubles(nd.Nc));
-    if(cholesky_large_workspace_doubles(nd.Nc) > 1) ok = ok && dev_alloc(&P->F.diag_minmax, 2);
+    ok = ok && P->mem.alloc(&P->F.Spart, schur_partial_doubles(nd));
+    ok = ok && P->mem.alloc(&P->F.Linv,  cholesky_large_workspace_doubles(nd.Nc));
+    if(cholesky_large_workspace_doubles(nd.Nc) > 1) ok = ok && P->mem.alloc(&P->F.diag_minmax, 2);
     // the tile occupancy of Wt: only where the couplings are sparse (the splined models) and the strip SYRK runs
     if(L.lensmodel.type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC && nd.Nc > 256 && nd.Nc <= 4096)
     {
-        ok = ok && dev_alloc(&P->F.occ, (size_t)(nd.NEb > 0 ? nd.NEb : 1)*occ_words(nd));
-        ok = ok && dev_alloc(&P->F.Wtile, (size_t)((nd.Nc + 15)/16)*16*(size_t)(nd.NE > 0 ? nd.NE : 1));
+        ok = ok && P->mem.alloc(&P->F.occ, (size_t)(nd.NEb > 0 ? nd.NEb : 1)*occ_words(nd));
+        ok = ok && P->mem.alloc(&P->F.Wtile, (size_t)((nd.Nc + 15)/16)*16*(size_t)(nd.NE > 0 ? nd.NE : 1));
     }
     // The splined models' camera block without the control points no board covers (round 5; assembly_splined.hip,
     // spl_compact_kernel / LcholCompact): where the big camera block's launch-per-panel Cholesky runs, every row that
@@ -328,16 +269,15 @@ bool problem_prepare_solver(mrcal_amd_problem* P)
         {
             for(int i=0;i<2 && ok;i++)
             {
-                ok = ok && dev_alloc(&P->op[i].cperm, (size_t)2*nd.Nc + 1);
                 // (until the first evaluation: the identity)
                 std::vector<int> id((size_t)2*nd.Nc + 1);
                 for(int c = 0; c < nd.Nc; c++) { id[c] = c; id[nd.Nc + c] = c; }
                 id[2*nd.Nc] = nd.Nc;
-                if(ok) HIP_TRY(hipMemcpy(P->op[i].cperm, id.data(), id.size()*sizeof(int), hipMemcpyHostToDevice), ok = false);
+                ok = ok && P->mem.upload(&P->op[i].cperm, id.data(), id.size());
             }
-            ok = ok && dev_alloc(&P->cperm_cur_alloc, (size_t)2*nd.Nc + 2);
-            ok = ok && dev_alloc(&P->F.iso, (size_t)4*(nd.Nc/2 + 1) + nd.Nc + 2);
-            P->F.cperm_cur = P->cperm_cur_alloc;
+            // (a communicator turns the compaction off by taking this pointer away: the buffer stays the problem's)
+            ok = ok && P->mem.alloc(&P->F.cperm_cur, (size_t)2*nd.Nc + 2);
+            ok = ok && P->mem.alloc(&P->F.iso, (size_t)4*(nd.Nc/2 + 1) + nd.Nc + 2);
             P->plan.spl_compact = 1;
             // ... and in a nested-dissection order where the boards leave a strip worth having (cholesky_large.hip,
             // lchol_nd_*): one camera's grid. MRCAL_AMD_NO_ND=1: off
@@ -348,18 +288,12 @@ bool problem_prepare_solver(mrcal_amd_problem* P)
                 const size_t W = LCH_ND_WMAX, wsz = (W/ND_PANEL)*ND_PANEL*ND_PANEL + W*W + W;
                 std::vector<int> h0(nd_plan_ints(nd.Nc), 0);
                 h0[NDH_NS] = nd.Nc; h0[NDH_NSEFF] = nd.Nc;
-                for(int i=0;i<2 && ok;i++)
-                {
-                    ok = ok && dev_alloc(&P->op[i].ndp, h0.size());
-                    if(ok) HIP_TRY(hipMemcpy(P->op[i].ndp, h0.data(), h0.size()*sizeof(int), hipMemcpyHostToDevice), ok = false);
-                }
-                ok = ok && dev_alloc(&P->F.ndp_cur, h0.size());
-                if(ok) HIP_TRY(hipMemcpy(P->F.ndp_cur, h0.data(), h0.size()*sizeof(int), hipMemcpyHostToDevice), ok = false);
-                ok = ok && dev_alloc(&P->F.ndMA, (Npos + 1)*Npos) && dev_alloc(&P->F.ndMB, (Npos + 1)*Npos);
-                ok = ok && dev_alloc(&P->F.ndLinvA, wsz) && dev_alloc(&P->F.ndLinvB, wsz);
-                ok = ok && dev_alloc(&P->F.ndPart, (size_t)((nd.Nc + 15)/16)*2*LCH_ND_WMAX);
-                ok = ok && dev_alloc(&P->F.nd_lim_dev, 2);
-                if(ok) HIP_TRY(hipMemset(P->F.nd_lim_dev, 0, 2*sizeof(int)), ok = false);
+                for(int i=0;i<2 && ok;i++) ok = ok && P->mem.upload(&P->op[i].ndp, h0.data(), h0.size());
+                ok = ok && P->mem.upload(&P->F.ndp_cur, h0.data(), h0.size());
+                ok = ok && P->mem.alloc(&P->F.ndMA, (Npos + 1)*Npos) && P->mem.alloc(&P->F.ndMB, (Npos + 1)*Npos);
+                ok = ok && P->mem.alloc(&P->F.ndLinvA, wsz) && P->mem.alloc(&P->F.ndLinvB, wsz);
+                ok = ok && P->mem.alloc(&P->F.ndPart, (size_t)((nd.Nc + 15)/16)*2*LCH_ND_WMAX);
+                ok = ok && P->mem.alloc_zeroed(&P->F.nd_lim_dev, 2);
                 P->F.nd_lim = NdLimits{0, 0}; P->F.nd_likely_panels = 0;
                 P->plan.nd_lim = P->F.nd_lim_dev;
             }
@@ -370,48 +304,34 @@ bool problem_prepare_solver(mrcal_amd_problem* P)
     {
         ReproStep& rs = P->plan.repro;
         rs.one = (size_t)nd.Nc*nd.Nc + (size_t)nd.NE*nd.Nc + (size_t)nd.NEb*36 + (size_t)nd.Nstate + 1;
-        for(int l = 0; l < 3 && ok; l++)
-        {
-            ok = ok && dev_alloc(&rs.lvl[l], rs.one);
-            if(ok) HIP_TRY(hipMemset(rs.lvl[l], 0, rs.one*sizeof(double)), ok = false);
-        }
-        ok = ok && dev_alloc(&rs.cmax, (size_t)nd.Nstate + 1);
-        ok = ok && dev_alloc(&rs.any, 1);
-        if(ok) HIP_TRY(hipMemset(rs.cmax, 0, ((size_t)nd.Nstate + 1)*sizeof(unsigned long long)), ok = false);
-        if(ok) HIP_TRY(hipMemset(rs.any, 0, sizeof(int)), ok = false);
-        if(!ok) rs.lvl[0] = NULL;
+        for(int l = 0; l < 3 && ok; l++) ok = ok && P->mem.alloc_zeroed(&rs.lvl[l], rs.one);
+        ok = ok && P->mem.alloc_zeroed(&rs.cmax, (size_t)nd.Nstate + 1);
+        ok = ok && P->mem.alloc_zeroed(&rs.any, 1);
     }
     {
         char* ctl = NULL;
-        ok = ok && dev_alloc(&ctl, solver_ctl_bytes());
+        ok = ok && P->mem.alloc(&ctl, solver_ctl_bytes());
         P->d_ctl = (SolverCtl*)ctl;
     }
-    ok = ok && dev_alloc(&P->F.Wt, (size_t)nd.NE*nd.Nc);
-    ok = ok && dev_alloc(&P->F.LD, (size_t)nd.NEb*36);
-    ok = ok && dev_alloc(&P->F.y,  (size_t)nd.NE);
+    // (rows of blocks this shard does not own are never written: they must read as 0)
+    ok = ok && P->mem.alloc_zeroed(&P->F.Wt, (size_t)nd.NE*nd.Nc);
+    ok = ok && P->mem.alloc(&P->F.LD, (size_t)nd.NEb*36);
+    ok = ok && P->mem.alloc_zeroed(&P->F.y,  (size_t)nd.NE);
     // S and r contiguous: one all-reduce moves both
     // [S | r | g_S | |x|^2 | status]: comm1 of the sharded step (step2_comm1_doubles())
     // (round 6: + a packed copy of the lower triangle behind them, for the one-workgroup Cholesky: factor_S_packed())
-    ok = ok && dev_alloc(&P->F.S,  (size_t)nd.Nc*nd.Nc + 2*nd.Nc + 2 + 64 + ((((size_t)nd.Nc*(nd.Nc + 1)) >> 1) + nd.Nc + 2));
+    ok = ok && P->mem.alloc(&P->F.S,  (size_t)nd.Nc*nd.Nc + 2*nd.Nc + 2 + 64 + ((((size_t)nd.Nc*(nd.Nc + 1)) >> 1) + nd.Nc + 2));
     P->F.r = ok ? P->F.S + (size_t)nd.Nc*nd.Nc : NULL;
-    ok = ok && dev_alloc(&P->F.status, 1);
-    ok = ok && dev_alloc(&P->d_step,   (size_t)nd.Nstate);
-    ok = ok && dev_alloc(&P->d_comm,   (size_t)nd.Nstate + 64);
-    ok = ok && dev_alloc(&P->d_counts, 4);
-    ok = ok && dev_alloc(&P->d_outlier_part, outlier_partial_doubles());
+    ok = ok && P->mem.alloc(&P->F.status, 1);
+    ok = ok && P->mem.alloc(&P->d_step,   (size_t)nd.Nstate);
+    ok = ok && P->mem.alloc(&P->d_comm,   (size_t)nd.Nstate + 64);
+    ok = ok && P->mem.alloc(&P->d_counts, 4);
+    ok = ok && P->mem.alloc(&P->d_outlier_part, outlier_partial_doubles());
     if(!ok) return false;
     // only the lower triangle of S is ever written; the rest rides along in the
     // all-reduce of [S | r] and should be numbers
     HIP_TRY(hipMemset(P->F.S, 0, ((size_t)nd.Nc*nd.Nc + 2*nd.Nc + 2)*sizeof(double)), return false);
-    // rows of blocks this shard does not own are never written: they must read as 0
-    HIP_TRY(hipMemset(P->F.Wt, 0, (size_t)(nd.NE*nd.Nc > 0 ? nd.NE*nd.Nc : 1)*sizeof(double)), return false);
-    HIP_TRY(hipMemset(P->F.y,  0, (size_t)(nd.NE > 0 ? nd.NE : 1)*sizeof(double)), return false);
-    for(int i=0;i<2;i++)
-    {
-        HIP_TRY(hipMemset(P->op[i].step_gn,     0, (size_t)nd.Nstate*sizeof(double)), return false);
-        HIP_TRY(hipMemset(P->op[i].step_cauchy, 0, (size_t)nd.Nstate*sizeof(double)), return false);
-    }
-    HIP_TRY(hipHostMalloc((void**)&P->h_scalars, 64*sizeof(double)), return false);
+    if(!P->mem.alloc_pinned(&P->h_scalars, 64)) return false;
     if(!problem_sync_ops(P)) return false;
 
     // assembly work lists. Observations of one frame are contiguous; the
@@ -468,10 +388,10 @@ bool problem_prepare_solver(mrcal_amd_problem* P)
     }
     chunk_begin.push_back(Nobs);
     P->plan.Nchunks = (int)chunk_begin.size() - 1;
-    ok = ok && dev_upload(&P->plan.frame_obs_begin, frame_begin.data(), frame_begin.size());
-    if(elimx) ok = ok && dev_upload(&P->plan.frame_obs, eblock_obs.data(), eblock_obs.size());
-    ok = ok && dev_upload(&P->plan.chunk_begin,     chunk_begin.data(), chunk_begin.size());
-    ok = ok && dev_upload(&P->plan.pair_obs,        order.data(),       order.size());
+    ok = ok && P->mem.upload(&P->plan.frame_obs_begin, frame_begin.data(), frame_begin.size());
+    if(elimx) ok = ok && P->mem.upload(&P->plan.frame_obs, eblock_obs.data(), eblock_obs.size());
+    ok = ok && P->mem.upload(&P->plan.chunk_begin,     chunk_begin.data(), chunk_begin.size());
+    ok = ok && P->mem.upload(&P->plan.pair_obs,        order.data(),       order.size());
     {
         // the (intrinsics, extrinsics) pairs, in the order of `order`
         std::vector<int> obs_pair(Nobs > 0 ? Nobs : 1, 0), pair_rep;
@@ -530,8 +450,8 @@ bool problem_prepare_solver(mrcal_amd_problem* P)
                 if(k == PAIROP_D || k == PAIROP_BT || k == PAIROP_GF) tab[pos] |= 0x20000;
             }
         }
-        ok = ok && dev_upload(&P->plan.pos_table,  tab.data(),        tab.size());
-        ok = ok && dev_upload(&P->plan.pair_table, ptab.data(),       ptab.size());
+        ok = ok && P->mem.upload(&P->plan.pos_table,  tab.data(),        tab.size());
+        ok = ok && P->mem.upload(&P->plan.pair_table, ptab.data(),       ptab.size());
         {
             // the frame part, per position and per observation (AssemblyPlan::frame_pos). Derived from the table
             // above and checked against it: every pair's operation at every position must come back out
@@ -590,11 +510,11 @@ bool problem_prepare_solver(mrcal_amd_problem* P)
             if(!consistent && uses_grams) { set_error("internal: the Gram positions of the frame part depend on the camera pair"); return false; }
             std::vector<int> obs_cols(2*(Nobs > 0 ? Nobs : 1), -1);
             for(int o = 0; o < Nobs; o++) { obs_cols[2*o] = pair_cols[2*obs_pair[o]]; obs_cols[2*o+1] = pair_cols[2*obs_pair[o]+1]; }
-            ok = ok && dev_upload(&P->plan.frame_pos, fpos.data(),     fpos.size());
-            ok = ok && dev_upload(&P->plan.obs_cols,  obs_cols.data(), obs_cols.size());
+            ok = ok && P->mem.upload(&P->plan.frame_pos, fpos.data(),     fpos.size());
+            ok = ok && P->mem.upload(&P->plan.obs_cols,  obs_cols.data(), obs_cols.size());
         }
-        ok = ok && dev_upload(&P->plan.obs_pair,   obs_pair.data(),   obs_pair.size());
-        ok = ok && dev_upload(&P->plan.chunk_pair, chunk_pair.data(), chunk_pair.size());
+        ok = ok && P->mem.upload(&P->plan.obs_pair,   obs_pair.data(),   obs_pair.size());
+        ok = ok && P->mem.upload(&P->plan.chunk_pair, chunk_pair.data(), chunk_pair.size());
 
         // The fixed-order reduction of the camera-block part (solver_kernels.hpp):
         // for every destination - entry of A, of g (S part), |x|^2 - the (pair,
@@ -642,55 +562,61 @@ bool problem_prepare_solver(mrcal_amd_problem* P)
         P->plan.Ndest = (int)dest_id.size();
         if(dest_id.empty())  dest_id.push_back(0);
         if(dest_src.empty()) dest_src.push_back(0);
-        ok = ok && dev_upload(&P->plan.dest_id,          dest_id.data(),          dest_id.size());
-        ok = ok && dev_upload(&P->plan.dest_begin,       dest_begin.data(),       dest_begin.size());
-        ok = ok && dev_upload(&P->plan.dest_src,         dest_src.data(),         dest_src.size());
-        ok = ok && dev_upload(&P->plan.pair_chunk_begin, pair_chunk_begin.data(), pair_chunk_begin.size());
+        ok = ok && P->mem.upload(&P->plan.dest_id,          dest_id.data(),          dest_id.size());
+        ok = ok && P->mem.upload(&P->plan.dest_begin,       dest_begin.data(),       dest_begin.size());
+        ok = ok && P->mem.upload(&P->plan.dest_src,         dest_src.data(),         dest_src.size());
+        ok = ok && P->mem.upload(&P->plan.pair_chunk_begin, pair_chunk_begin.data(), pair_chunk_begin.size());
         if(with_grams || Nobs == 0)
-            ok = ok && dev_alloc(&P->plan.chunk_part, with_grams ? (size_t)(P->plan.Nchunks > 0 ? P->plan.Nchunks : 1)*npos : (size_t)1);
+            ok = ok && P->mem.alloc(&P->plan.chunk_part, with_grams ? (size_t)(P->plan.Nchunks > 0 ? P->plan.Nchunks : 1)*npos : (size_t)1);
         else
         {
             // splined models: the staged Grams of assemble_splined_kernel (two passes per observation), the knot
             // boxes, and the parts of the rows of the camera block that are not knots (+ the x row)
             const int nknotrows = P->D.Nintr_state > 0 ? P->D.Ncameras_intrinsics*(P->D.Nintr_state - P->D.Ncore_state) : 0;
-            ok = ok && dev_alloc(&P->plan.chunk_part,    (size_t)2*Nobs*SPL_TRI);
-            ok = ok && dev_alloc(&P->plan.spl_hdr,       (size_t)Nobs);
-            ok = ok && dev_alloc(&P->plan.spl_part,   (size_t)(nd.Nc + 1 - nknotrows)*SPLG_E*(nd.Nc + 1));
+            ok = ok && P->mem.alloc(&P->plan.chunk_part,    (size_t)2*Nobs*SPL_TRI);
+            ok = ok && P->mem.alloc(&P->plan.spl_hdr,       (size_t)Nobs);
+            ok = ok && P->mem.alloc(&P->plan.spl_part,   (size_t)(nd.Nc + 1 - nknotrows)*SPLG_E*(nd.Nc + 1));
         }
         ok = ok && build_gen_plan(P);
         {
             // (with the plan above, the row-by-row workgroups of the assembly take the regularization rows only)
             const int row0 = (P->plan.gen.Nrows > 0) ? L.i_meas_regularization : 2*P->D.W*P->D.H*Nobs;
             P->plan.row_part_n = (Nobs > 0 && L.Nmeas > row0) ? (L.Nmeas - row0 + 255)/256 : 0;
-            ok = ok && dev_alloc(&P->plan.row_part, (size_t)(P->plan.row_part_n > 0 ? P->plan.row_part_n : 1));
+            ok = ok && P->mem.alloc(&P->plan.row_part, (size_t)(P->plan.row_part_n > 0 ? P->plan.row_part_n : 1));
             P->plan.qf_part_n = (nd.Nc + nd.NE + 4*QF_ROWS_PER_WAVE - 1)/(4*QF_ROWS_PER_WAVE);
-            ok = ok && dev_alloc(&P->plan.qf_part, (size_t)4*(P->plan.qf_part_n > 0 ? P->plan.qf_part_n : 1));
-            ok = ok && dev_alloc(&P->plan.dots_part, (size_t)2*(nd.NEb > 0 ? nd.NEb : 1));
+            ok = ok && P->mem.alloc(&P->plan.qf_part, (size_t)4*(P->plan.qf_part_n > 0 ? P->plan.qf_part_n : 1));
+            ok = ok && P->mem.alloc(&P->plan.dots_part, (size_t)2*(nd.NEb > 0 ? nd.NEb : 1));
         }
     }
     // (the second, third and fourth sub-boxes of the splined models' close-ups, which mostly nobody touches: last)
     if(P->plan.spl_hdr != NULL)
     {
         const size_t Nobs = (size_t)(P->D.Nobs_board > 0 ? P->D.Nobs_board : 1);
-        ok = ok && dev_alloc(&P->plan.chunk_extra,   (size_t)2*Nobs*(SPL_MAXSUB - 1)*SPL_TRI);
-        ok = ok && dev_alloc(&P->plan.spl_hdr_extra, Nobs*(SPL_MAXSUB - 1));
+        ok = ok && P->mem.alloc(&P->plan.chunk_extra,   (size_t)2*Nobs*(SPL_MAXSUB - 1)*SPL_TRI);
+        ok = ok && P->mem.alloc(&P->plan.spl_hdr_extra, Nobs*(SPL_MAXSUB - 1));
     }
-    if(!ok) return false;
-    // rows of blocks nobody writes (frames without observations in this shard) must read as zero
-    for(int i=0;i<2;i++)
-    {
-        HIP_TRY(hipMemset(P->op[i].Bt, 0, (size_t)(nd.NE*nd.Nc > 0 ? nd.NE*nd.Nc : 1)*sizeof(double)), return false);
-        HIP_TRY(hipMemset(P->op[i].D,  0, (size_t)(nd.NEb > 0 ? nd.NEb*36 : 1)*sizeof(double)), return false);
-        HIP_TRY(hipMemset(P->op[i].g,  0, (size_t)(nd.Nstate > 0 ? nd.Nstate : 1)*sizeof(double)), return false);
-    }
+    return ok;
+}
 
-    P->solver_ready = true;
-    return true;
+// A preparation that failed stays failed: what it had allocated by then is the problem's until the problem goes, and
+// the next call reports the same error instead of allocating everything a second time
+bool problem_prepare_solver(mrcal_amd_problem* P)
+{
+    if(P->solver_ready) return true;
+    if(P->prepare_error.empty())
+    {
+        P->solver_ready = allocate_solver_buffers(P);
+        if(P->solver_ready) return true;
+        P->prepare_error = last_error_string().empty() ? "the solver's buffers could not be allocated" : last_error_string();
+        return false;
+    }
+    set_error("%s", P->prepare_error.c_str());
+    return false;
 }
 
 bool problem_sync_ops(mrcal_amd_problem* P)
 {
-    if(P->d_ops == NULL && !dev_alloc(&P->d_ops, 2)) return false;
+    if(P->d_ops == NULL && !P->mem.alloc(&P->d_ops, 2)) return false;
     OpDev h[2] = { P->op[0], P->op[1] };
     HIP_TRY(hipMemcpy(P->d_ops, h, sizeof(h), hipMemcpyHostToDevice), return false);
     return true;
@@ -776,7 +702,7 @@ bool problem_evaluate_op(mrcal_amd_problem* P, int i, bool with_jacobian, bool w
 
 namespace { int& elimination_policy() { static int policy = 0; return policy; } }
 
-// (round 6) The drop-in entry points make a problem, use it once and tear it down: some forty hipFree() calls, each of
+// (round 6) The drop-in entry points make a problem, use it once and tear it down: a hipFree call per buffer, each of
 // which waits for the device - 4 ms at the metric's size, a tenth of an mrcal_optimize() call. A problem that nobody can
 // reach any more is torn down by a thread of its own instead, while the caller already has its results; at most two
 // are in line at a time (a caller in a loop does not pile up gigabytes: the third it tears down itself, as before)
@@ -853,6 +779,11 @@ int mrcal_amd_set_elimination(int policy)
 const char* mrcal_amd_last_error(void)
 {
     return last_error_string().c_str();
+}
+
+long mrcal_amd_device_buffers_live(void)
+{
+    return DeviceBuffers::live();
 }
 
 int mrcal_amd_device_count(void)
@@ -1130,15 +1061,15 @@ mrcal_amd_problem_create_sharded(const double*                 intrinsics,
     HIP_TRY(hipEventCreate(&P->ev_j0), ok = false);
     HIP_TRY(hipEventCreate(&P->ev_j1), ok = false);
 
-    ok = ok && dev_upload(&P->d_seed_intrinsics,   intrinsics,                  (size_t)Ncameras_intrinsics*L.Nintrinsics);
-    ok = ok && dev_upload(&P->d_seed_rt_cam_ref,   (const double*)rt_cam_ref,   (size_t)Ncameras_extrinsics*6);
-    ok = ok && dev_upload(&P->d_seed_rt_ref_frame, (const double*)rt_ref_frame, (size_t)Nframes*6);
-    ok = ok && dev_upload(&P->d_seed_points,       (const double*)points,       (size_t)Npoints*3);
-    ok = ok && dev_upload(&P->d_board_meta,        bmeta.data(),                (size_t)Nboard_local);
-    ok = ok && dev_upload(&P->d_board_pool,        (const double*)pool_src,     (size_t)Nboard_local*NPTS*3);
-    ok = ok && dev_upload(&P->d_point_meta,        pmeta.data(),                (size_t)Npoint_local);
-    ok = ok && dev_upload(&P->d_point_pool,        (const double*)point_pool_local.data(), (size_t)Npoint_local*3);
-    ok = ok && dev_upload(&P->d_imagersizes,       imagersizes,                 (size_t)Ncameras_intrinsics*2);
+    ok = ok && P->mem.upload(&P->d_seed_intrinsics,   intrinsics,                  (size_t)Ncameras_intrinsics*L.Nintrinsics);
+    ok = ok && P->mem.upload(&P->d_seed_rt_cam_ref,   (const double*)rt_cam_ref,   (size_t)Ncameras_extrinsics*6);
+    ok = ok && P->mem.upload(&P->d_seed_rt_ref_frame, (const double*)rt_ref_frame, (size_t)Nframes*6);
+    ok = ok && P->mem.upload(&P->d_seed_points,       (const double*)points,       (size_t)Npoints*3);
+    ok = ok && P->mem.upload(&P->d_board_meta,        bmeta.data(),                (size_t)Nboard_local);
+    ok = ok && P->mem.upload(&P->d_board_pool,        (const double*)pool_src,     (size_t)Nboard_local*NPTS*3);
+    ok = ok && P->mem.upload(&P->d_point_meta,        pmeta.data(),                (size_t)Npoint_local);
+    ok = ok && P->mem.upload(&P->d_point_pool,        (const double*)point_pool_local.data(), (size_t)Npoint_local*3);
+    ok = ok && P->mem.upload(&P->d_imagersizes,       imagersizes,                 (size_t)Ncameras_intrinsics*2);
     {
         const int Nt = Ntri_local;
         P->tri_obs0 = tri_o0;
@@ -1150,19 +1081,19 @@ mrcal_amd_problem_create_sharded(const double*                 intrinsics,
             for(int j=0;j<3;j++) P->tri_px_host[3*i+j] = tri_local[i].px.xyz[j];
             P->tri_outlier_host[i] = tri_local[i].outlier ? 1 : 0;
         }
-        ok = ok && dev_upload(&P->d_tri_meta,    tmeta.data(),                tmeta.size());
-        ok = ok && dev_upload(&P->d_tri_px,      P->tri_px_host.data(),       (size_t)3*Nt);
-        ok = ok && dev_upload(&P->d_tri_outlier, P->tri_outlier_host.data(),  (size_t)Nt);
+        ok = ok && P->mem.upload(&P->d_tri_meta,    tmeta.data(),                tmeta.size());
+        ok = ok && P->mem.upload(&P->d_tri_px,      P->tri_px_host.data(),       (size_t)3*Nt);
+        ok = ok && P->mem.upload(&P->d_tri_outlier, P->tri_outlier_host.data(),  (size_t)Nt);
     }
-    ok = ok && dev_alloc (&P->op[0].b,  (size_t)L.Nstate);
+    ok = ok && P->mem.alloc(&P->op[0].b,  (size_t)L.Nstate);
     // + the unpacked intrinsics and warp (DeviceProblem::unpacked)
-    ok = ok && dev_alloc (&P->d_joint,  (size_t)Nboard_local*JOINT_STRIDE + (size_t)Ncameras_intrinsics*L.Nintrinsics + 2);
-    ok = ok && dev_alloc (&P->op[0].x,  (size_t)L.Nmeas);
-    ok = ok && dev_alloc (&P->op[0].Jv, (size_t)innz);
+    ok = ok && P->mem.alloc(&P->d_joint,  (size_t)Nboard_local*JOINT_STRIDE + (size_t)Ncameras_intrinsics*L.Nintrinsics + 2);
+    ok = ok && P->mem.alloc(&P->op[0].x,  (size_t)L.Nmeas);
+    ok = ok && P->mem.alloc(&P->op[0].Jv, (size_t)innz);
     if(L.lensmodel.type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC && Nboard_local > 0)
-        ok = ok && dev_alloc(&P->op[0].spl_box, (size_t)4*Nboard_local);
-    ok = ok && dev_alloc (&P->d_Jp,     (size_t)L.Nmeas+1);
-    ok = ok && dev_alloc (&P->d_Ji,     (size_t)innz);
+        ok = ok && P->mem.alloc(&P->op[0].spl_box, (size_t)4*Nboard_local);
+    ok = ok && P->mem.alloc(&P->d_Jp,     (size_t)L.Nmeas+1);
+    ok = ok && P->mem.alloc(&P->d_Ji,     (size_t)innz);
     if(!ok) { delete P; return NULL; }
     if(!problem_sync_ops(P)) { delete P; return NULL; }
 
@@ -1495,9 +1426,9 @@ int mrcal_amd_problem_debug_timestamps(mrcal_amd_problem_t* p, bool with_gram, l
 {
     if(with_gram && !problem_prepare_solver(p)) return -1;
     const size_t n = (size_t)p->D.Nobs_board*10;
+    DeviceBuffers mem;
     long long* d = NULL;
-    if(hipMalloc((void**)&d, n*sizeof(long long)) != hipSuccess) return -1;
-    hipMemset(d, 0, n*sizeof(long long));
+    if(!mem.alloc_zeroed(&d, n)) return -1;
     const EvalBuffers B = p->eval_buffers(p->icur, with_gram);
     for(int i=0;i<3;i++)
     {
@@ -1507,7 +1438,6 @@ int mrcal_amd_problem_debug_timestamps(mrcal_amd_problem_t* p, bool with_gram, l
     }
     p->D.debug_ts = NULL;
     hipMemcpy(out, d, n*sizeof(long long), hipMemcpyDeviceToHost);
-    hipFree(d);
     return p->D.Nobs_board;
 }
 #endif
@@ -1664,19 +1594,18 @@ bool mrcal_project(mrcal_point2_t* q, mrcal_point3_t* dq_dp, double* dq_dintrins
     if(lensmodel->type == MRCAL_LENSMODEL_CAHVORE)
         cfg.cahvore_linearity = lensmodel->LENSMODEL_CAHVORE__config.linearity;
 
+    DeviceBuffers mem;
     double *d_p = NULL, *d_i = NULL, *d_q = NULL, *d_g = NULL, *d_gi = NULL;
     bool ok = true;
-    ok = ok && dev_upload(&d_p, (const double*)p, (size_t)3*N);
-    ok = ok && dev_upload(&d_i, intrinsics, (size_t)Ni);
-    ok = ok && dev_alloc(&d_q, (size_t)2*N);
-    if(dq_dp)          ok = ok && dev_alloc(&d_g,  (size_t)6*N);
-    if(dq_dintrinsics) ok = ok && dev_alloc(&d_gi, (size_t)2*N*Ni);
-    if(ok && d_gi) HIP_TRY(hipMemset(d_gi, 0, (size_t)2*N*Ni*sizeof(double)), ok = false);
+    ok = ok && mem.upload(&d_p, (const double*)p, (size_t)3*N);
+    ok = ok && mem.upload(&d_i, intrinsics, (size_t)Ni);
+    ok = ok && mem.alloc(&d_q, (size_t)2*N);
+    if(dq_dp)          ok = ok && mem.alloc(&d_g,  (size_t)6*N);
+    if(dq_dintrinsics) ok = ok && mem.alloc_zeroed(&d_gi, (size_t)2*N*Ni);
     if(ok) HIP_TRY(launch_project_points((int)lensmodel->type, cfg, N, Ni, d_p, d_i, d_q, d_g, d_gi, NULL), ok = false);
     if(ok) HIP_TRY(hipMemcpy(q, d_q, (size_t)2*N*sizeof(double), hipMemcpyDeviceToHost), ok = false);
     if(ok && dq_dp)          HIP_TRY(hipMemcpy(dq_dp, d_g, (size_t)6*N*sizeof(double), hipMemcpyDeviceToHost), ok = false);
     if(ok && dq_dintrinsics) HIP_TRY(hipMemcpy(dq_dintrinsics, d_gi, (size_t)2*N*Ni*sizeof(double), hipMemcpyDeviceToHost), ok = false);
-    hipFree(d_p); hipFree(d_i); hipFree(d_q); hipFree(d_g); hipFree(d_gi);
     return ok;
 }
 

@@ -2,10 +2,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
+#include <string>
 #include "layout.hpp"
 #include "problem.hpp"
 #include "kernels.hpp"
 #include "solver_kernels.hpp"
+#include "device_memory.hpp"
 
 // One operating point of the dog-leg iteration: the state, the cost function
 // there (x, J) and its normal equations. The solver flips between two of these
@@ -38,6 +40,9 @@ struct mrcal_amd_problem
     std::vector<int>         board_sel;  // global index of each local board observation
     std::vector<double>      b_host;     // the seed, packed
 
+    // owns every device and pinned buffer the pointers below (and those of op[], plan, F) point at: a new one is
+    // one mem.alloc() / alloc_zeroed() / upload() where it is needed, and nothing else
+    mrcal_amd::DeviceBuffers mem;
     hipStream_t stream = NULL;
     hipEvent_t  ev_j0  = NULL, ev_j1 = NULL;
     // a second stream for work of a step that nothing on the first one waits for at once (the gather of the
@@ -60,7 +65,6 @@ struct mrcal_amd_problem
     int         ev_pool_used = 0;
     int         ev_pool_seen = 0, ev_pool_stride = 1;      // launches since _begin(); every stride-th one is timed
     bool        ev_pool_enabled = false;
-    int*                cperm_cur_alloc = NULL;    // what F.cperm_cur points at while the compaction is on (a communicator turns it off)
 
     // inputs
     double* d_seed_intrinsics   = NULL;
@@ -93,6 +97,7 @@ struct mrcal_amd_problem
 
     // solver
     bool                       solver_ready = false;
+    std::string                prepare_error;     // not empty: problem_prepare_solver() failed with this, and fails with it again
     mrcal_amd::AssemblyPlan    plan = {};
     mrcal_amd::FactorBuffers   F    = {};
     double*                    d_step   = NULL;   // [Nstate]
@@ -135,7 +140,7 @@ struct mrcal_amd_problem
 };
 
 namespace mrcal_amd {
-// allocates the second operating point and all solver scratch; idempotent
+// allocates the second operating point and all solver scratch, once: true again after it succeeded, the same error again after it failed
 bool problem_prepare_solver(mrcal_amd_problem* P);
 // x, J (and the normal equations if with_normal) at op[i].b
 bool problem_evaluate_op(mrcal_amd_problem* P, int i, bool with_jacobian, bool with_normal);

@@ -40,16 +40,6 @@
 
 using namespace mrcal_amd;
 
-#define HIP_TRY(expr, onfail)                                           \
-    do {                                                                \
-        hipError_t _e = (expr);                                         \
-        if(_e != hipSuccess)                                            \
-        {                                                               \
-            set_error("%s:%d: %s failed: %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-            onfail;                                                     \
-        }                                                               \
-    } while(0)
-
 namespace mrcal_amd {
 // factorization.cpp (internal)
 hipStream_t factorization_stream(mrcal_amd_factorization_t* f);
@@ -354,9 +344,10 @@ struct mrcal_amd_uncertainty
     double*            d_out  = NULL;   // [capacity][4]
     int                capacity = 0;
     hipStream_t        stream = NULL;
+    DeviceBuffers      mem;
     ~mrcal_amd_uncertainty()
     {
-        hipFree(d_C); hipFree(d_intr); hipFree(d_pose); hipFree(d_p); hipFree(d_out);
+        mem.free_all();
         if(stream) hipStreamDestroy(stream);
     }
 };
@@ -523,20 +514,21 @@ mrcal_amd_uncertainty_create(mrcal_amd_problem_t* P, int icam_intrinsics, int me
     }
 
     hipStream_t st = factorization_stream(f);
+    DeviceBuffers tmp;      // what only this function needs
     double *d_K = NULL, *d_rhs = NULL, *d_X = NULL, *d_KX = NULL, *d_JX = NULL, *d_scale = NULL, *d_sig = NULL;
     int* d_col = NULL;
     HIP_TRY(hipStreamCreateWithFlags(&u->stream, hipStreamNonBlocking), ok = false);
-    if(ok) HIP_TRY(hipMalloc((void**)&d_K,     (size_t)6*Nstate*sizeof(double)), ok = false);
-    if(ok) HIP_TRY(hipMalloc((void**)&d_rhs,   (size_t)k*Nstate*sizeof(double)), ok = false);
-    if(ok) HIP_TRY(hipMalloc((void**)&d_X,     (size_t)k*Nstate*sizeof(double)), ok = false);
-    if(ok) HIP_TRY(hipMalloc((void**)&d_KX,    (size_t)6*k*sizeof(double)), ok = false);
-    if(ok) HIP_TRY(hipMalloc((void**)&d_JX,    (size_t)std::max(Nreg, 1)*k*sizeof(double)), ok = false);
-    if(ok) HIP_TRY(hipMalloc((void**)&d_scale, (size_t)k*sizeof(double)), ok = false);
-    if(ok) HIP_TRY(hipMalloc((void**)&d_col,   (size_t)k*sizeof(int)), ok = false);
-    if(ok) HIP_TRY(hipMalloc((void**)&d_sig,   2*sizeof(double)), ok = false);
-    if(ok) HIP_TRY(hipMalloc((void**)&u->d_C,    (size_t)k*k*sizeof(double)), ok = false);
-    if(ok) HIP_TRY(hipMalloc((void**)&u->d_intr, (size_t)L.Nintrinsics*sizeof(double)), ok = false);
-    if(ok) HIP_TRY(hipMalloc((void**)&u->d_pose, sizeof(pose)), ok = false);
+    ok = ok && tmp.alloc(&d_K,     (size_t)6*Nstate);
+    ok = ok && tmp.alloc(&d_rhs,   (size_t)k*Nstate);
+    ok = ok && tmp.alloc(&d_X,     (size_t)k*Nstate);
+    ok = ok && tmp.alloc(&d_KX,    (size_t)6*k);
+    ok = ok && tmp.alloc(&d_JX,    (size_t)std::max(Nreg, 1)*k);
+    ok = ok && tmp.alloc(&d_scale, (size_t)k);
+    ok = ok && tmp.alloc(&d_col,   (size_t)k);
+    ok = ok && tmp.alloc(&d_sig,   2);
+    ok = ok && u->mem.alloc(&u->d_C,    (size_t)k*k);
+    ok = ok && u->mem.alloc(&u->d_intr, (size_t)L.Nintrinsics);
+    ok = ok && u->mem.alloc(&u->d_pose, sizeof(pose)/sizeof(double));
     if(ok) HIP_TRY(hipMemcpyAsync(d_K, K.data(), (size_t)6*Nstate*sizeof(double), hipMemcpyHostToDevice, st), ok = false);
     if(ok) HIP_TRY(hipMemcpyAsync(d_scale, scale.data(), (size_t)k*sizeof(double), hipMemcpyHostToDevice, st), ok = false);
     if(ok) HIP_TRY(hipMemcpyAsync(d_col, col.data(), (size_t)k*sizeof(int), hipMemcpyHostToDevice, st), ok = false);
@@ -578,7 +570,7 @@ mrcal_amd_uncertainty_create(mrcal_amd_problem_t* P, int icam_intrinsics, int me
         if(ok) HIP_TRY(hipMemcpyAsync(sig, d_sig, sizeof(sig), hipMemcpyDeviceToHost, st), ok = false);
     }
     if(ok) HIP_TRY(hipStreamSynchronize(st), ok = false);
-    hipFree(d_K); hipFree(d_rhs); hipFree(d_X); hipFree(d_KX); hipFree(d_JX); hipFree(d_scale); hipFree(d_col); hipFree(d_sig);
+    tmp.free_all();
     mrcal_amd_factorization_destroy(f);
     if(!ok) { delete u; return NULL; }
 
@@ -617,10 +609,9 @@ bool mrcal_amd_uncertainty_evaluate(mrcal_amd_uncertainty_t* u, const double* p_
     if(N <= 0) return true;
     if(u->capacity < N)
     {
-        hipFree(u->d_p); hipFree(u->d_out);
-        u->d_p = u->d_out = NULL; u->capacity = 0;
-        HIP_TRY(hipMalloc((void**)&u->d_p,   (size_t)N*3*sizeof(double)), return false);
-        HIP_TRY(hipMalloc((void**)&u->d_out, (size_t)N*4*sizeof(double)), return false);
+        u->mem.release(&u->d_p); u->mem.release(&u->d_out);
+        u->capacity = 0;
+        if(!u->mem.alloc(&u->d_p, (size_t)N*3) || !u->mem.alloc(&u->d_out, (size_t)N*4)) return false;
         u->capacity = N;
     }
     PUArgs a = u->args;

@@ -29,16 +29,6 @@
 
 using namespace mrcal_amd;
 
-#define HIP_TRY(expr, onfail)                                           \
-    do {                                                                \
-        hipError_t _e = (expr);                                         \
-        if(_e != hipSuccess)                                            \
-        {                                                               \
-            set_error("%s:%d: %s failed: %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-            onfail;                                                     \
-        }                                                               \
-    } while(0)
-
 namespace {
 
 struct DoglegParameters
@@ -67,9 +57,9 @@ enum { CTL_RING = 8 };
 
 bool ctl_prepare(mrcal_amd_problem* P)
 {
-    if(P->h_ctl_ring != NULL) return true;
-    HIP_TRY(hipHostMalloc((void**)&P->h_ctl_ring, CTL_RING*sizeof(SolverCtl)), return false);
-    for(int i=0;i<CTL_RING;i++)
+    // (a call that failed half way is taken up where it stopped)
+    if(P->h_ctl_ring == NULL && !P->mem.alloc_pinned(&P->h_ctl_ring, CTL_RING)) return false;
+    while((int)P->ctl_events.size() < CTL_RING)
     {
         hipEvent_t e;
         HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming), return false);

@@ -38,16 +38,6 @@
 
 using namespace mrcal_amd;
 
-#define HIP_TRY(expr, onfail)                                           \
-    do {                                                                \
-        hipError_t _e = (expr);                                         \
-        if(_e != hipSuccess)                                            \
-        {                                                               \
-            set_error("%s:%d: %s failed: %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-            onfail;                                                     \
-        }                                                               \
-    } while(0)
-
 namespace {
 
 // where the blocks of the state are, and which camera is asked for
@@ -518,8 +508,9 @@ bool drt_cross_reprojection_device(double* Kpackede,  int Ke_s0, int Ke_s1,
     std::vector<DrtRec> rec((size_t)(Nrec > 0 ? Nrec : 1));
     if(Nrec > 0)
     {
+        DeviceBuffers tmp;
         DrtRec* d_rec = NULL;
-        HIP_TRY(hipMalloc((void**)&d_rec, (size_t)Nrec*sizeof(DrtRec)), return false);
+        if(!tmp.alloc(&d_rec, (size_t)Nrec)) return false;
         bool ok = true;
         if(Nb > 0)
         {
@@ -533,7 +524,6 @@ bool drt_cross_reprojection_device(double* Kpackede,  int Ke_s0, int Ke_s1,
         }
         if(ok) HIP_TRY(hipMemcpyAsync(rec.data(), d_rec, (size_t)Nrec*sizeof(DrtRec), hipMemcpyDeviceToHost, stream), ok = false);
         if(ok) HIP_TRY(hipStreamSynchronize(stream), ok = false);
-        (void)hipFree(d_rec);
         if(!ok) return false;
     }
 
@@ -706,20 +696,14 @@ bool _mrcal_drt_cross_reprojection__dbpacked(double* Kpackede,  int Kpackede_str
         for(int64_t p = 0; p < nnz; p++) bad |= (unsigned)((unsigned)Ji[p] >= (unsigned)L.Nstate);
         if(bad) { set_error("malformed Jt: a state index is outside [0,%d)", L.Nstate); return false; }
     }
-    int32_t *d_Jp = NULL, *d_Ji = NULL; double* d_Jx = NULL;
-    bool ok = true;
-    HIP_TRY(hipMalloc((void**)&d_Jp, (size_t)(Nmeas_obs + 1)*sizeof(int32_t)), return false);
-    HIP_TRY(hipMalloc((void**)&d_Ji, (size_t)(nnz > 0 ? nnz : 1)*sizeof(int32_t)), ok = false);
-    if(ok) HIP_TRY(hipMalloc((void**)&d_Jx, (size_t)(nnz > 0 ? nnz : 1)*sizeof(double)), ok = false);
-    if(ok) HIP_TRY(hipMemcpy(d_Jp, Jp, (size_t)(Nmeas_obs + 1)*sizeof(int32_t), hipMemcpyHostToDevice), ok = false);
-    if(ok && nnz) HIP_TRY(hipMemcpy(d_Ji, Ji, (size_t)nnz*sizeof(int32_t), hipMemcpyHostToDevice), ok = false);
-    if(ok && nnz) HIP_TRY(hipMemcpy(d_Jx, Jx, (size_t)nnz*sizeof(double), hipMemcpyHostToDevice), ok = false);
+    DeviceBuffers tmp;
+    CsrDev dJ;
+    bool ok = upload_csr(tmp, &dJ, Nmeas_obs, Jp, Ji, Jx);
     if(ok)
         ok = drt_cross_reprojection_device(Kpackede, Kpackede_stride0, Kpackede_stride1, Kpackedf, Kpackedf_stride0, Kpackedf_stride1,
                                            Kpackedp, Kpackedp_stride0, Kpackedp_stride1, Kpackedcw, Kpackedcw_stride0, Kpackedcw_stride1,
-                                           icam_intrinsics, b_packed, d_Jp, d_Ji, d_Jx,
+                                           icam_intrinsics, b_packed, dJ.Jp, dJ.Ji, dJ.Jx,
                                            Ji, Nmeas_obs > 0 ? (Jp[1] - Jp[0]) : 0, L, NULL);
-    (void)hipFree(d_Jp); (void)hipFree(d_Ji); (void)hipFree(d_Jx);
     return ok;
 }
 

@@ -23,6 +23,7 @@
 #include "kernels.hpp"
 #include "host_state.hpp"
 #include "lens_models.hpp"
+#include "device_memory.hpp"
 #include "../../include/mrcal_amd.h"
 
 using namespace mrcal_amd;
@@ -242,27 +243,19 @@ bool mrcal_amd_unproject(mrcal_point3_t* v, double* dv_dq, double* dv_dintrinsic
     const bool closed = t == MRCAL_LENSMODEL_PINHOLE || t == MRCAL_LENSMODEL_STEREOGRAPHIC ||
                         t == MRCAL_LENSMODEL_LONLAT  || t == MRCAL_LENSMODEL_LATLON;
     const bool grads  = dv_dq != NULL;
+    DeviceBuffers tmp;
     double *d_q = NULL, *d_i = NULL, *d_v = NULL, *d_gq = NULL, *d_gi = NULL, *s_q = NULL, *s_gv = NULL, *s_gi = NULL;
-    bool ok = true;
-#define TRY(expr) do { if(ok && (expr) != hipSuccess) { set_error("mrcal_amd_unproject(): %s failed", #expr); ok = false; } } while(0)
-    TRY(hipMalloc((void**)&d_q, (size_t)2*N*sizeof(double)));
-    TRY(hipMalloc((void**)&d_i, (size_t)Ni*sizeof(double)));
-    TRY(hipMalloc((void**)&d_v, (size_t)3*N*sizeof(double)));
-    if(grads)                  TRY(hipMalloc((void**)&d_gq, (size_t)6*N*sizeof(double)));
-    if(dv_dintrinsics != NULL) TRY(hipMalloc((void**)&d_gi, (size_t)3*N*Ni*sizeof(double)));
+    bool ok = tmp.upload(&d_q, (const double*)q, (size_t)2*N) && tmp.upload(&d_i, intrinsics, (size_t)Ni) && tmp.alloc(&d_v, (size_t)3*N);
+    if(grads)                  ok = ok && tmp.alloc(&d_gq, (size_t)6*N);
+    if(dv_dintrinsics != NULL) ok = ok && tmp.alloc(&d_gi, (size_t)3*N*Ni);
     if(grads && !closed)
     {
-        TRY(hipMalloc((void**)&s_q,  (size_t)2*N*sizeof(double)));
-        TRY(hipMalloc((void**)&s_gv, (size_t)6*N*sizeof(double)));
-        if(dv_dintrinsics != NULL) TRY(hipMalloc((void**)&s_gi, (size_t)2*N*Ni*sizeof(double)));
+        ok = ok && tmp.alloc(&s_q,  (size_t)2*N) && tmp.alloc(&s_gv, (size_t)6*N);
+        if(dv_dintrinsics != NULL) ok = ok && tmp.alloc(&s_gi, (size_t)2*N*Ni);
     }
-    TRY(hipMemcpy(d_q, q, (size_t)2*N*sizeof(double), hipMemcpyHostToDevice));
-    TRY(hipMemcpy(d_i, intrinsics, (size_t)Ni*sizeof(double), hipMemcpyHostToDevice));
-    TRY(launch_unproject_points((int)t, cfg, N, Ni, d_q, d_i, d_v, d_gq, d_gi, s_q, s_gv, s_gi, normalize, NULL));
-    TRY(hipMemcpy(v, d_v, (size_t)3*N*sizeof(double), hipMemcpyDeviceToHost));
-    if(grads)                  TRY(hipMemcpy(dv_dq, d_gq, (size_t)6*N*sizeof(double), hipMemcpyDeviceToHost));
-    if(dv_dintrinsics != NULL) TRY(hipMemcpy(dv_dintrinsics, d_gi, (size_t)3*N*Ni*sizeof(double), hipMemcpyDeviceToHost));
-#undef TRY
-    hipFree(d_q); hipFree(d_i); hipFree(d_v); hipFree(d_gq); hipFree(d_gi); hipFree(s_q); hipFree(s_gv); hipFree(s_gi);
+    if(ok) HIP_TRY(launch_unproject_points((int)t, cfg, N, Ni, d_q, d_i, d_v, d_gq, d_gi, s_q, s_gv, s_gi, normalize, NULL), ok = false);
+    if(ok) HIP_TRY(hipMemcpy(v, d_v, (size_t)3*N*sizeof(double), hipMemcpyDeviceToHost), ok = false);
+    if(ok && grads)                  HIP_TRY(hipMemcpy(dv_dq, d_gq, (size_t)6*N*sizeof(double), hipMemcpyDeviceToHost), ok = false);
+    if(ok && dv_dintrinsics != NULL) HIP_TRY(hipMemcpy(dv_dintrinsics, d_gi, (size_t)3*N*Ni*sizeof(double), hipMemcpyDeviceToHost), ok = false);
     return ok;
 }

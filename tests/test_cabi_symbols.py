@@ -44,3 +44,7 @@ def test_no_gpu_means_loud_failure(amd):
                                indices_frame_camintrinsics_camextrinsics = np.array(((0,0,-1),), dtype=np.int32),
                                calibration_object_spacing = 0.1,
                                do_optimize_calobject_warp = False)
+    # the half-made problem was deleted on the spot: nothing of it is held
+    live = amd._lib.lib.mrcal_amd_device_buffers_live
+    live.restype, live.argtypes = ctypes.c_long, []
+    assert live() == 0
