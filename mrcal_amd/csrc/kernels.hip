@@ -31,6 +31,7 @@
 #include "problem.hpp"
 #include "device_math.hpp"
 #include "lens_models.hpp"
+#include "lens_dispatch.hpp"
 #include "triangulation.hpp"
 #include "kernels.hpp"
 #include "dogleg_choose.hpp"
@@ -1593,19 +1594,6 @@ static bool board_allopt(const DeviceProblem& P, int ndist)
     return ((16 + ndist) & 1) == 0 && P.Ncore_state && (ndist == 0 || P.Ndist_state) && P.do_optimize_extrinsics &&
            P.do_optimize_frames && P.has_warp_state && P.has_warp_seed && !ABLATE(P, ~0);
 }
-static int lens_ndist(int lens_type)
-{
-    switch(lens_type)
-    {
-    case MRCAL_LENSMODEL_OPENCV4:  return 4;
-    case MRCAL_LENSMODEL_OPENCV5:  return 5;
-    case MRCAL_LENSMODEL_OPENCV8:  return 8;
-    case MRCAL_LENSMODEL_OPENCV12: return 12;
-    case MRCAL_LENSMODEL_CAHVOR:   return 5;
-    case MRCAL_LENSMODEL_CAHVORE:  return 8;
-    default:                       return 0;
-    }
-}
 // the triangulated pairs ride in the board kernel's launch (board_tri_kernel) when both are there and the Jacobian and
 // the Grams are asked for
 bool board_launch_takes_triangulated(const DeviceProblem& P)
@@ -1696,46 +1684,18 @@ bool prologue_takes_choose(const DeviceProblem& P)
     // (every evaluation of a problem with boards starts with the prologue launch, the splined models' too)
     return P.Nobs_board > 0;
 }
-bool lens_supported(int lens_type)
-{
-    switch(lens_type)
-    {
-    case MRCAL_LENSMODEL_PINHOLE:
-    case MRCAL_LENSMODEL_STEREOGRAPHIC:
-    case MRCAL_LENSMODEL_LONLAT:
-    case MRCAL_LENSMODEL_LATLON:
-    case MRCAL_LENSMODEL_OPENCV4:
-    case MRCAL_LENSMODEL_OPENCV5:
-    case MRCAL_LENSMODEL_OPENCV8:
-    case MRCAL_LENSMODEL_OPENCV12:
-    case MRCAL_LENSMODEL_CAHVOR:
-    case MRCAL_LENSMODEL_CAHVORE:
-    case MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC:
-        return true;
-    default:
-        return false;
-    }
-}
-
 hipError_t launch_evaluate(const DeviceProblem& P, const EvalBuffers& B, bool with_jacobian,
                            int lds_bytes, hipStream_t stream,
                            hipEvent_t ev_j0, hipEvent_t ev_j1, int parts)
 {
-    switch(P.lens_type)
+    if(!for_parametric_lens(P.lens_type, [&](auto k)
+       {
+           using K = decltype(k);
+           launch_eval_t<K::PROJ,K::NDIST>(P,B,with_jacobian,lds_bytes,stream,ev_j0,ev_j1,parts);
+       }))
     {
-    case MRCAL_LENSMODEL_PINHOLE:       launch_eval_t<PROJ_OPENCV,        0 >(P,B,with_jacobian,lds_bytes,stream,ev_j0,ev_j1,parts); break;
-    case MRCAL_LENSMODEL_STEREOGRAPHIC: launch_eval_t<PROJ_STEREOGRAPHIC, 0 >(P,B,with_jacobian,lds_bytes,stream,ev_j0,ev_j1,parts); break;
-    case MRCAL_LENSMODEL_LONLAT:        launch_eval_t<PROJ_LONLAT,        0 >(P,B,with_jacobian,lds_bytes,stream,ev_j0,ev_j1,parts); break;
-    case MRCAL_LENSMODEL_LATLON:        launch_eval_t<PROJ_LATLON,        0 >(P,B,with_jacobian,lds_bytes,stream,ev_j0,ev_j1,parts); break;
-    case MRCAL_LENSMODEL_OPENCV4:       launch_eval_t<PROJ_OPENCV,        4 >(P,B,with_jacobian,lds_bytes,stream,ev_j0,ev_j1,parts); break;
-    case MRCAL_LENSMODEL_OPENCV5:       launch_eval_t<PROJ_OPENCV,        5 >(P,B,with_jacobian,lds_bytes,stream,ev_j0,ev_j1,parts); break;
-    case MRCAL_LENSMODEL_OPENCV8:       launch_eval_t<PROJ_OPENCV,        8 >(P,B,with_jacobian,lds_bytes,stream,ev_j0,ev_j1,parts); break;
-    case MRCAL_LENSMODEL_OPENCV12:      launch_eval_t<PROJ_OPENCV,        12>(P,B,with_jacobian,lds_bytes,stream,ev_j0,ev_j1,parts); break;
-    case MRCAL_LENSMODEL_CAHVOR:        launch_eval_t<PROJ_CAHVOR,        5 >(P,B,with_jacobian,lds_bytes,stream,ev_j0,ev_j1,parts); break;
-    case MRCAL_LENSMODEL_CAHVORE:       launch_eval_t<PROJ_CAHVORE,       8 >(P,B,with_jacobian,lds_bytes,stream,ev_j0,ev_j1,parts); break;
-    case MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC: launch_eval_splined(P,B,with_jacobian,stream,ev_j0,ev_j1,parts); break;
-    default:
-        return hipErrorInvalidValue;
+        if(P.lens_type != MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC) return hipErrorInvalidValue;
+        launch_eval_splined(P,B,with_jacobian,stream,ev_j0,ev_j1,parts);
     }
     return hipGetLastError();
 }

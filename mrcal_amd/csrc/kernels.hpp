@@ -102,8 +102,6 @@ bool prologue_takes_choose(const DeviceProblem& P);
 // the triangulated pairs ride in the board kernel's launch (kernels.hip board_tri_kernel) when the Jacobian and the Grams are asked for
 bool board_launch_takes_triangulated(const DeviceProblem& P);
 
-bool lens_supported(int lens_type);
-
 // x (and J values if with_jacobian) at B.b. ev_j0/ev_j1, if given, bracket the
 // board Jacobian kernel on the stream
 // parts: which of the evaluation's kernels to queue (the solver splits an

@@ -14,6 +14,7 @@
 #include "host_state.hpp"
 #include "problem.hpp"
 #include "kernels.hpp"
+#include "lens_dispatch.hpp"
 #include "problem_object.hpp"
 #include "host_copy.hpp"
 #include <thread>
@@ -763,6 +764,32 @@ public:
     }
 };
 void problem_destroy_later(mrcal_amd_problem* P) { ProblemReaper::get().later(P); }
+
+bool dropin_inputs_ok(mrcal_problem_selections_t problem_selections,
+                      const mrcal_observation_point_triangulated_t* observations_point_triangulated,
+                      int Nobservations_point_triangulated,
+                      int Nobservations_board, const mrcal_calobject_warp_t* calobject_warp,
+                      bool warp_seed_first)
+{
+    const bool bad_triangulated =
+        observations_point_triangulated != NULL && Nobservations_point_triangulated &&
+        !(!problem_selections.do_optimize_intrinsics_core &&
+          !problem_selections.do_optimize_intrinsics_distortions &&
+          problem_selections.do_optimize_extrinsics);
+    const bool bad_warp_seed =
+        Nobservations_board > 0 && problem_selections.do_optimize_calobject_warp && calobject_warp == NULL;
+    if(bad_warp_seed && (warp_seed_first || !bad_triangulated))
+    {
+        set_error("ERROR: We're optimizing the calibration object warp, so a buffer with a seed MUST be passed in.");
+        return false;
+    }
+    if(bad_triangulated)
+    {
+        set_error("ERROR: We have triangulated points. At this time this is only allowed if we're NOT optimizing intrinsics AND if we ARE optimizing extrinsics.");
+        return false;
+    }
+    return true;
+}
 } // namespace mrcal_amd
 
 extern "C" {
@@ -1180,17 +1207,7 @@ mrcal_amd_problem_create_sharded(const double*                 intrinsics,
     D.inv_Wm1 = 1.0/(double)(D.W - 1);      // (W = 1 or H = 1 with a warp: the reference divides by zero just the same)
     D.inv_Hm1 = 1.0/(double)(D.H - 1);
     if(calobject_warp) { D.seed_warp[0] = calobject_warp->x2; D.seed_warp[1] = calobject_warp->y2; }
-    if(lensmodel->type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC)
-    {
-        D.cfg.spline_order = lensmodel->LENSMODEL_SPLINED_STEREOGRAPHIC__config.order;
-        D.cfg.spline_Nx    = lensmodel->LENSMODEL_SPLINED_STEREOGRAPHIC__config.Nx;
-        D.cfg.spline_Ny    = lensmodel->LENSMODEL_SPLINED_STEREOGRAPHIC__config.Ny;
-        D.cfg.spline_segments_per_u =
-            spline_segments_per_u(D.cfg.spline_order, D.cfg.spline_Nx,
-                                  (double)lensmodel->LENSMODEL_SPLINED_STEREOGRAPHIC__config.fov_x_deg);
-    }
-    if(lensmodel->type == MRCAL_LENSMODEL_CAHVORE)
-        D.cfg.cahvore_linearity = lensmodel->LENSMODEL_CAHVORE__config.linearity;
+    D.cfg = lens_config_of(*lensmodel);
     D.do_apply_regularization = sel.do_apply_regularization && is_shard_leader;
     D.has_unity_cam01         = L.has_unity_cam01;
     D.i_meas_regularization   = L.i_meas_regularization;
@@ -1484,19 +1501,9 @@ bool mrcal_optimizer_callback(double* b_packed, int buffer_size_b_packed,
     (void)problem_constants; (void)verbose;
     last_error_string().clear();
 
-    if(observations_point_triangulated != NULL && Nobservations_point_triangulated &&
-       !(!problem_selections.do_optimize_intrinsics_core &&
-         !problem_selections.do_optimize_intrinsics_distortions &&
-         problem_selections.do_optimize_extrinsics))
-    {
-        set_error("ERROR: We have triangulated points. At this time this is only allowed if we're NOT optimizing intrinsics AND if we ARE optimizing extrinsics.");
+    if(!dropin_inputs_ok(problem_selections, observations_point_triangulated, Nobservations_point_triangulated,
+                         Nobservations_board, calobject_warp, /* warp_seed_first = */ false))
         return false;
-    }
-    if(Nobservations_board > 0 && problem_selections.do_optimize_calobject_warp && calobject_warp == NULL)
-    {
-        set_error("ERROR: We're optimizing the calibration object warp, so a buffer with a seed MUST be passed in.");
-        return false;
-    }
     const mrcal_problem_selections_t sel =
         effective_selections(problem_selections, *lensmodel, Nobservations_board);
     if(!sel.do_optimize_intrinsics_core && !sel.do_optimize_intrinsics_distortions &&
@@ -1581,18 +1588,7 @@ bool mrcal_project(mrcal_point2_t* q, mrcal_point3_t* dq_dp, double* dq_dintrins
     }
     if(N <= 0) return true;
     const int Ni = lensmodel_num_params(*lensmodel);
-    LensConfig cfg; memset(&cfg, 0, sizeof(cfg));
-    if(lensmodel->type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC)
-    {
-        cfg.spline_order = lensmodel->LENSMODEL_SPLINED_STEREOGRAPHIC__config.order;
-        cfg.spline_Nx    = lensmodel->LENSMODEL_SPLINED_STEREOGRAPHIC__config.Nx;
-        cfg.spline_Ny    = lensmodel->LENSMODEL_SPLINED_STEREOGRAPHIC__config.Ny;
-        cfg.spline_segments_per_u =
-            spline_segments_per_u(cfg.spline_order, cfg.spline_Nx,
-                                  (double)lensmodel->LENSMODEL_SPLINED_STEREOGRAPHIC__config.fov_x_deg);
-    }
-    if(lensmodel->type == MRCAL_LENSMODEL_CAHVORE)
-        cfg.cahvore_linearity = lensmodel->LENSMODEL_CAHVORE__config.linearity;
+    const LensConfig cfg = lens_config_of(*lensmodel);
 
     DeviceBuffers mem;
     double *d_p = NULL, *d_i = NULL, *d_q = NULL, *d_g = NULL, *d_gi = NULL;

@@ -303,4 +303,14 @@ struct DeviceProblem
     const double*       unpacked;
 };
 
+// The input checks mrcal_optimize() and mrcal_optimizer_callback() share (mrcal.c:6049-6060, 6250-6270), with the
+// reference's messages (set_error): triangulated points only with the intrinsics locked and the extrinsics optimized; a
+// warp that is optimized needs a seed. warp_seed_first: which of the two is reported when both fail - the reference's
+// mrcal_optimize() looks at the warp seed first, its callback at the triangulated points
+bool dropin_inputs_ok(mrcal_problem_selections_t problem_selections,
+                      const mrcal_observation_point_triangulated_t* observations_point_triangulated,
+                      int Nobservations_point_triangulated,
+                      int Nobservations_board, const mrcal_calobject_warp_t* calobject_warp,
+                      bool warp_seed_first);
+
 } // namespace mrcal_amd

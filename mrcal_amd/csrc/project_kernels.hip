@@ -7,6 +7,7 @@
 #include "problem.hpp"
 #include "device_math.hpp"
 #include "lens_models.hpp"
+#include "lens_dispatch.hpp"
 #include "kernels.hpp"
 
 namespace mrcal_amd {
@@ -80,25 +81,15 @@ hipError_t launch_project_points(int lens_type, const LensConfig& cfg, int N, in
 {
     if(N <= 0) return hipSuccess;
     const dim3 grid((N + 63)/64), block(64);
-#define MRCAL_AMD_PROJECT(PROJ, ND) hipLaunchKernelGGL((project_points_kernel<PROJ,ND>), grid, block, 0, stream, cfg, N, Nintrinsics, p, intr, q, dq_dp, dq_di)
-    switch(lens_type)
+    if(!for_parametric_lens(lens_type, [&](auto k)
+       {
+           using K = decltype(k);
+           hipLaunchKernelGGL((project_points_kernel<K::PROJ,K::NDIST>), grid, block, 0, stream, cfg, N, Nintrinsics, p, intr, q, dq_dp, dq_di);
+       }))
     {
-    case MRCAL_LENSMODEL_PINHOLE:       MRCAL_AMD_PROJECT(PROJ_OPENCV,        0 ); break;
-    case MRCAL_LENSMODEL_STEREOGRAPHIC: MRCAL_AMD_PROJECT(PROJ_STEREOGRAPHIC, 0 ); break;
-    case MRCAL_LENSMODEL_LONLAT:        MRCAL_AMD_PROJECT(PROJ_LONLAT,        0 ); break;
-    case MRCAL_LENSMODEL_LATLON:        MRCAL_AMD_PROJECT(PROJ_LATLON,        0 ); break;
-    case MRCAL_LENSMODEL_OPENCV4:       MRCAL_AMD_PROJECT(PROJ_OPENCV,        4 ); break;
-    case MRCAL_LENSMODEL_OPENCV5:       MRCAL_AMD_PROJECT(PROJ_OPENCV,        5 ); break;
-    case MRCAL_LENSMODEL_OPENCV8:       MRCAL_AMD_PROJECT(PROJ_OPENCV,        8 ); break;
-    case MRCAL_LENSMODEL_OPENCV12:      MRCAL_AMD_PROJECT(PROJ_OPENCV,        12); break;
-    case MRCAL_LENSMODEL_CAHVOR:        MRCAL_AMD_PROJECT(PROJ_CAHVOR,        5 ); break;
-    case MRCAL_LENSMODEL_CAHVORE:       MRCAL_AMD_PROJECT(PROJ_CAHVORE,       8 ); break;
-    case MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC:
+        if(lens_type != MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC) return hipErrorInvalidValue;
         hipLaunchKernelGGL(project_points_splined_kernel, grid, block, 0, stream, cfg, N, Nintrinsics, p, intr, q, dq_dp, dq_di);
-        break;
-    default: return hipErrorInvalidValue;
     }
-#undef MRCAL_AMD_PROJECT
     return hipGetLastError();
 }
 
@@ -309,29 +300,23 @@ hipError_t launch_unproject_points(int lens_type, const LensConfig& cfg, int N, 
 {
     if(N <= 0) return hipSuccess;
     const dim3 grid((N + 63)/64), block(64);
-    const bool closed = lens_type == MRCAL_LENSMODEL_PINHOLE || lens_type == MRCAL_LENSMODEL_STEREOGRAPHIC ||
-                        lens_type == MRCAL_LENSMODEL_LONLAT  || lens_type == MRCAL_LENSMODEL_LATLON;
-    if(closed)
+    if(lens_has_closed_form_inverse(lens_type))
         hipLaunchKernelGGL(unproject_closed_form_kernel, grid, block, 0, stream, lens_type, N, q, intr, v, dv_dq, dv_di);
     else
     {
         // can_project_behind_camera (mrcal.c:255-288): none of the parametric models that come this way can: a solution with z < 0 is flipped, mrcal.c:3274
         const int behind_ok = 0;       // (the splined model, which can, has its own kernel below)
-#define MRCAL_AMD_UNPROJECT(PROJ, ND) hipLaunchKernelGGL((unproject_points_kernel<PROJ,ND>), grid, block, 0, stream, cfg, N, q, intr, behind_ok, v)
-        switch(lens_type)
+        if(!for_parametric_lens(lens_type, [&](auto k)
+           {
+               using K = decltype(k);
+               // (the closed-form models took the branch above: nothing is compiled for them here, and none arrives)
+               if constexpr (!K::has_closed_form_inverse)
+                   hipLaunchKernelGGL((unproject_points_kernel<K::PROJ,K::NDIST>), grid, block, 0, stream, cfg, N, q, intr, behind_ok, v);
+           }))
         {
-        case MRCAL_LENSMODEL_OPENCV4:  MRCAL_AMD_UNPROJECT(PROJ_OPENCV,  4 ); break;
-        case MRCAL_LENSMODEL_OPENCV5:  MRCAL_AMD_UNPROJECT(PROJ_OPENCV,  5 ); break;
-        case MRCAL_LENSMODEL_OPENCV8:  MRCAL_AMD_UNPROJECT(PROJ_OPENCV,  8 ); break;
-        case MRCAL_LENSMODEL_OPENCV12: MRCAL_AMD_UNPROJECT(PROJ_OPENCV,  12); break;
-        case MRCAL_LENSMODEL_CAHVOR:   MRCAL_AMD_UNPROJECT(PROJ_CAHVOR,  5 ); break;
-        case MRCAL_LENSMODEL_CAHVORE:  MRCAL_AMD_UNPROJECT(PROJ_CAHVORE, 8 ); break;
-        case MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC:
+            if(lens_type != MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC) return hipErrorInvalidValue;
             hipLaunchKernelGGL(unproject_points_splined_kernel, grid, block, 0, stream, cfg, N, q, intr, v);
-            break;
-        default: return hipErrorInvalidValue;
         }
-#undef MRCAL_AMD_UNPROJECT
         if(dv_dq != NULL)
         {
             // the gradients of project() at the stereographic representative of v

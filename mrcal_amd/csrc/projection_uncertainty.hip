@@ -35,6 +35,7 @@
 #include "host_state.hpp"
 #include "problem_object.hpp"
 #include "lens_models.hpp"
+#include "lens_dispatch.hpp"
 #include "device_math.hpp"
 #include "../../include/mrcal_amd.h"
 
@@ -432,17 +433,7 @@ mrcal_amd_uncertainty_create(mrcal_amd_problem_t* P, int icam_intrinsics, int me
     memset(&u->args, 0, sizeof(u->args));
     PUArgs& a = u->args;
     a.rrp = rrp ? 1 : 0;
-    if(L.lensmodel.type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC)
-    {
-        a.cfg.spline_order = L.lensmodel.LENSMODEL_SPLINED_STEREOGRAPHIC__config.order;
-        a.cfg.spline_Nx    = L.lensmodel.LENSMODEL_SPLINED_STEREOGRAPHIC__config.Nx;
-        a.cfg.spline_Ny    = L.lensmodel.LENSMODEL_SPLINED_STEREOGRAPHIC__config.Ny;
-        a.cfg.spline_segments_per_u =
-            spline_segments_per_u(a.cfg.spline_order, a.cfg.spline_Nx,
-                                  (double)L.lensmodel.LENSMODEL_SPLINED_STEREOGRAPHIC__config.fov_x_deg);
-    }
-    if(L.lensmodel.type == MRCAL_LENSMODEL_CAHVORE)
-        a.cfg.cahvore_linearity = L.lensmodel.LENSMODEL_CAHVORE__config.linearity;
+    a.cfg = lens_config_of(L.lensmodel);
     a.Nint = L.Nintr_state;
     a.arg0 = L.Ncore - L.Ncore_state;
     if(L.lensmodel.type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC)
@@ -618,24 +609,20 @@ bool mrcal_amd_uncertainty_evaluate(mrcal_amd_uncertainty_t* u, const double* p_
     a.N = N; a.atinfinity = atinfinity ? 1 : 0; a.what = what;
     const size_t nout = (size_t)N*(what == MRCAL_AMD_UNCERTAINTY_COVARIANCE ? 4 : 1);
     HIP_TRY(hipMemcpyAsync(u->d_p, p_cam, (size_t)N*3*sizeof(double), hipMemcpyHostToDevice, u->stream), return false);
-    hipError_t e;
-#define PU_LAUNCH(PROJ, ND) e = launch_points<PROJ,ND>(a, u->d_C, u->d_intr, u->d_pose, u->d_p, u->d_out, u->stream)
-    switch(u->lensmodel.type)
+    hipError_t e = hipSuccess;
+    if(!for_parametric_lens(u->lensmodel.type, [&](auto k)
+       {
+           using K = decltype(k);
+           e = launch_points<K::PROJ,K::NDIST>(a, u->d_C, u->d_intr, u->d_pose, u->d_p, u->d_out, u->stream);
+       }))
     {
-    case MRCAL_LENSMODEL_PINHOLE:       PU_LAUNCH(PROJ_OPENCV,        0 ); break;
-    case MRCAL_LENSMODEL_STEREOGRAPHIC: PU_LAUNCH(PROJ_STEREOGRAPHIC, 0 ); break;
-    case MRCAL_LENSMODEL_LONLAT:        PU_LAUNCH(PROJ_LONLAT,        0 ); break;
-    case MRCAL_LENSMODEL_LATLON:        PU_LAUNCH(PROJ_LATLON,        0 ); break;
-    case MRCAL_LENSMODEL_OPENCV4:       PU_LAUNCH(PROJ_OPENCV,        4 ); break;
-    case MRCAL_LENSMODEL_OPENCV5:       PU_LAUNCH(PROJ_OPENCV,        5 ); break;
-    case MRCAL_LENSMODEL_OPENCV8:       PU_LAUNCH(PROJ_OPENCV,        8 ); break;
-    case MRCAL_LENSMODEL_OPENCV12:      PU_LAUNCH(PROJ_OPENCV,        12); break;
-    case MRCAL_LENSMODEL_CAHVOR:        PU_LAUNCH(PROJ_CAHVOR,        5 ); break;
-    case MRCAL_LENSMODEL_CAHVORE:       PU_LAUNCH(PROJ_CAHVORE,       8 ); break;
-    case MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC: PU_LAUNCH(PROJ_SPLINED, 0); break;
-    default: set_error("lens model %d is not supported", (int)u->lensmodel.type); return false;
+        if(u->lensmodel.type != MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC)
+        {
+            set_error("lens model %d is not supported", (int)u->lensmodel.type);
+            return false;
+        }
+        e = launch_points<PROJ_SPLINED,0>(a, u->d_C, u->d_intr, u->d_pose, u->d_p, u->d_out, u->stream);
     }
-#undef PU_LAUNCH
     HIP_TRY(e, return false);
     HIP_TRY(hipMemcpyAsync(out, u->d_out, nout*sizeof(double), hipMemcpyDeviceToHost, u->stream), return false);
     HIP_TRY(hipStreamSynchronize(u->stream), return false);

@@ -990,19 +990,9 @@ mrcal_optimize( double* b_packed, int buffer_size_b_packed,
     (void)problem_constants;
     last_error_string().clear();
     const mrcal_stats_t failed = { -1.0, 0, 0 };
-    if(Nobservations_board > 0 && problem_selections.do_optimize_calobject_warp && calobject_warp == NULL)
-    {
-        set_error("ERROR: We're optimizing the calibration object warp, so a buffer with a seed MUST be passed in.");
+    if(!dropin_inputs_ok(problem_selections, observations_point_triangulated, Nobservations_point_triangulated,
+                         Nobservations_board, calobject_warp, /* warp_seed_first = */ true))
         return failed;
-    }
-    if(observations_point_triangulated != NULL && Nobservations_point_triangulated &&
-       !(!problem_selections.do_optimize_intrinsics_core &&
-         !problem_selections.do_optimize_intrinsics_distortions &&
-         problem_selections.do_optimize_extrinsics))
-    {
-        set_error("ERROR: We have triangulated points. At this time this is only allowed if we're NOT optimizing intrinsics AND if we ARE optimizing extrinsics.");
-        return failed;
-    }
     const mrcal_problem_selections_t sel =
         effective_selections(problem_selections, *lensmodel, Nobservations_board);
     if(!sel.do_optimize_intrinsics_core && !sel.do_optimize_intrinsics_distortions &&

@@ -23,6 +23,7 @@
 #include "kernels.hpp"
 #include "host_state.hpp"
 #include "lens_models.hpp"
+#include "lens_dispatch.hpp"
 #include "device_memory.hpp"
 #include "../../include/mrcal_amd.h"
 
@@ -30,31 +31,27 @@ using namespace mrcal_amd;
 
 namespace {
 
-template<int PROJ, int NDIST>
-bool project_grad(double* q, double (*dq_dp)[3], const double* v, const double* intr, const LensConfig& cfg)
-{
-    double gk[2][NDIST > 0 ? NDIST : 1];
-    return project_lens<PROJ,NDIST,true>(q, dq_dp, gk, v, intr, cfg);
-}
+// (the models with a closed-form inverse never come this way: false for them, as for an unknown type)
 bool project_any(const mrcal_lensmodel_t& m, const LensConfig& cfg,
                  double* q, double (*dq_dp)[3], const double* v, const double* intr)
 {
-    switch(m.type)
+    bool ok = false;
+    if(!for_parametric_lens(m.type, [&](auto k)
+       {
+           using K = decltype(k);
+           if constexpr (!K::has_closed_form_inverse)
+           {
+               double gk[2][K::NDIST];
+               ok = project_lens<K::PROJ,K::NDIST,true>(q, dq_dp, gk, v, intr, cfg);
+           }
+       }))
     {
-    case MRCAL_LENSMODEL_OPENCV4:  return project_grad<PROJ_OPENCV,4 >(q, dq_dp, v, intr, cfg);
-    case MRCAL_LENSMODEL_OPENCV5:  return project_grad<PROJ_OPENCV,5 >(q, dq_dp, v, intr, cfg);
-    case MRCAL_LENSMODEL_OPENCV8:  return project_grad<PROJ_OPENCV,8 >(q, dq_dp, v, intr, cfg);
-    case MRCAL_LENSMODEL_OPENCV12: return project_grad<PROJ_OPENCV,12>(q, dq_dp, v, intr, cfg);
-    case MRCAL_LENSMODEL_CAHVOR:   return project_grad<PROJ_CAHVOR,5 >(q, dq_dp, v, intr, cfg);
-    case MRCAL_LENSMODEL_CAHVORE:  return project_grad<PROJ_CAHVORE,8>(q, dq_dp, v, intr, cfg);
-    case MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC:
-    {
+        if(m.type != MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC) return false;
         double dfxy[2], cx[4], cy[4]; int ivar0;
         project_splined<true>(q, dq_dp, dfxy, &ivar0, cx, cy, v, intr, cfg);
-        return true;
+        ok = true;
     }
-    default: return false;
-    }
+    return ok;
 }
 bool projects_behind_camera(mrcal_lensmodel_type_t t)
 {
@@ -74,8 +71,7 @@ bool mrcal_unproject(mrcal_point3_t* out, const mrcal_point2_t* q, int N,
     const double fx = intrinsics[0], fy = intrinsics[1], cx = intrinsics[2], cy = intrinsics[3];
     const mrcal_lensmodel_type_t t = lensmodel->type;
 
-    if(t == MRCAL_LENSMODEL_PINHOLE || t == MRCAL_LENSMODEL_STEREOGRAPHIC ||
-       t == MRCAL_LENSMODEL_LONLAT  || t == MRCAL_LENSMODEL_LATLON)
+    if(lens_has_closed_form_inverse(t))
     {
         for(int i=0;i<N;i++)
         {
@@ -96,19 +92,9 @@ bool mrcal_unproject(mrcal_point3_t* out, const mrcal_point2_t* q, int N,
         return true;
     }
 
-    LensConfig cfg; memset(&cfg, 0, sizeof(cfg));
-    if(t == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC)
+    const LensConfig cfg = lens_config_of(*lensmodel);
+    if(t == MRCAL_LENSMODEL_CAHVORE)
     {
-        cfg.spline_order = lensmodel->LENSMODEL_SPLINED_STEREOGRAPHIC__config.order;
-        cfg.spline_Nx    = lensmodel->LENSMODEL_SPLINED_STEREOGRAPHIC__config.Nx;
-        cfg.spline_Ny    = lensmodel->LENSMODEL_SPLINED_STEREOGRAPHIC__config.Ny;
-        cfg.spline_segments_per_u =
-            spline_segments_per_u(cfg.spline_order, cfg.spline_Nx,
-                                  (double)lensmodel->LENSMODEL_SPLINED_STEREOGRAPHIC__config.fov_x_deg);
-    }
-    else if(t == MRCAL_LENSMODEL_CAHVORE)
-    {
-        cfg.cahvore_linearity = lensmodel->LENSMODEL_CAHVORE__config.linearity;
         for(int i=9;i<12;i++)
             if(intrinsics[i] != 0.)
             {
@@ -116,7 +102,7 @@ bool mrcal_unproject(mrcal_point3_t* out, const mrcal_point2_t* q, int N,
                 return false;
             }
     }
-    else if(!(lensmodel_is_opencv(t) || t == MRCAL_LENSMODEL_CAHVOR))
+    else if(!lens_supported(t))
     {
         set_error("mrcal_unproject(): unknown lens model %d", (int)t);
         return false;
@@ -220,19 +206,9 @@ bool mrcal_amd_unproject(mrcal_point3_t* v, double* dv_dq, double* dv_dintrinsic
     const mrcal_lensmodel_type_t t = lensmodel->type;
     if(!lens_supported((int)t)) { set_error("mrcal_amd_unproject(): lens model %d is not supported", (int)t); return false; }
     const int Ni = lensmodel_num_params(*lensmodel);
-    LensConfig cfg; memset(&cfg, 0, sizeof(cfg));
-    if(t == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC)
+    const LensConfig cfg = lens_config_of(*lensmodel);
+    if(t == MRCAL_LENSMODEL_CAHVORE)
     {
-        cfg.spline_order = lensmodel->LENSMODEL_SPLINED_STEREOGRAPHIC__config.order;
-        cfg.spline_Nx    = lensmodel->LENSMODEL_SPLINED_STEREOGRAPHIC__config.Nx;
-        cfg.spline_Ny    = lensmodel->LENSMODEL_SPLINED_STEREOGRAPHIC__config.Ny;
-        cfg.spline_segments_per_u =
-            spline_segments_per_u(cfg.spline_order, cfg.spline_Nx,
-                                  (double)lensmodel->LENSMODEL_SPLINED_STEREOGRAPHIC__config.fov_x_deg);
-    }
-    else if(t == MRCAL_LENSMODEL_CAHVORE)
-    {
-        cfg.cahvore_linearity = lensmodel->LENSMODEL_CAHVORE__config.linearity;
         for(int i=9;i<12;i++)
             if(intrinsics[i] != 0.)
             {
@@ -240,8 +216,7 @@ bool mrcal_amd_unproject(mrcal_point3_t* v, double* dv_dq, double* dv_dintrinsic
                 return false;
             }
     }
-    const bool closed = t == MRCAL_LENSMODEL_PINHOLE || t == MRCAL_LENSMODEL_STEREOGRAPHIC ||
-                        t == MRCAL_LENSMODEL_LONLAT  || t == MRCAL_LENSMODEL_LATLON;
+    const bool closed = lens_has_closed_form_inverse(t);
     const bool grads  = dv_dq != NULL;
     DeviceBuffers tmp;
     double *d_q = NULL, *d_i = NULL, *d_v = NULL, *d_gq = NULL, *d_gi = NULL, *s_q = NULL, *s_gv = NULL, *s_gi = NULL;

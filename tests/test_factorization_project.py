@@ -125,6 +125,7 @@ MODELS = [
     ("LENSMODEL_LONLAT",        (1200., 1150, 500., 333.)),
     ("LENSMODEL_LATLON",        (1200., 1150, 500., 333.)),
     ("LENSMODEL_OPENCV4",  (1512., 1112, 500., 333., -0.012, 0.035, -0.001, 0.002)),
+    ("LENSMODEL_OPENCV5",  (1512., 1112, 500., 333., -0.012, 0.035, -0.001, 0.002, 0.019)),
     ("LENSMODEL_OPENCV8",  (1512., 1112, 500., 333., -0.012, 0.035, -0.001, 0.002, 0.019, 0.014, -0.056, 0.050)),
     ("LENSMODEL_OPENCV12", (1512., 1112, 500., 333., -0.012, 0.035, -0.001, 0.002, 0.019, 0.014, -0.056, 0.050,
                             0.003, -0.002, 0.001, 0.004)),
@@ -172,6 +173,31 @@ def test_project_splined_matches_reference(amd, ref_api):
     assert relative_error(q, qr).max() < 1e-6
     assert relative_error(g, gr).max() < 1e-6
     assert relative_error(gi, gir).max() < 1e-6
+
+
+def test_unknown_lens_type_is_refused(amd):
+    """a type value outside mrcal_lensmodel_type_t: the error return and its message from mrcal_amd_problem_create(),
+    mrcal_project() and mrcal_amd_unproject(), before anything is queued on the device"""
+    from mrcal_amd.resident import Problem
+    api, clib = amd._api, amd._api.clib
+    oi, _ = make_calibration_problem(api, Ncameras=1, Nframes=3, lensmodel="LENSMODEL_OPENCV4",
+                                     object_width_n=4, object_height_n=3, seed=1)
+    ingested = api._ingest(oi, callback=False)
+    ingested.lensmodel.type = 99
+    with pytest.raises(RuntimeError, match=r"lens model \S+ \(99\) is not implemented on the GPU yet"):
+        Problem(_ingested=ingested)
+
+    m = Lensmodel(); m.type = 99
+    intr = np.array((1512., 1112, 500., 333.))
+    p, q, v = np.array(((0.1, 0.2, 1.0),)), np.zeros((1,2)), np.zeros((1,3))
+    clib.mrcal_project.restype  = C.c_bool
+    clib.mrcal_project.argtypes = [C.c_void_p]*4 + [C.c_int, C.POINTER(Lensmodel), C.c_void_p]
+    assert not clib.mrcal_project(q.ctypes.data, None, None, p.ctypes.data, 1, C.byref(m), intr.ctypes.data)
+    assert api._last_error() == " mrcal_project(): lens model 99 is not supported"
+    clib.mrcal_amd_unproject.restype  = C.c_bool
+    clib.mrcal_amd_unproject.argtypes = [C.c_void_p]*4 + [C.c_int, C.POINTER(Lensmodel), C.c_void_p, C.c_bool]
+    assert not clib.mrcal_amd_unproject(v.ctypes.data, None, None, q.ctypes.data, 1, C.byref(m), intr.ctypes.data, False)
+    assert api._last_error() == " mrcal_amd_unproject(): lens model 99 is not supported"
 
 
 def _factor_dense(F, N):

@@ -42,10 +42,23 @@ UNPROJECT_MODELS = [
     ("LENSMODEL_OPENCV8",  (1512., 1112, 500., 333., -0.012, 0.035, -0.001, 0.002, 0.019, 0.014, -0.056, 0.050)),
     ("LENSMODEL_CAHVOR",   (4842.918, 4842.771, 1970.528, 1085.302, -0.001, 0.002, -0.637, -0.002, 0.016)),
     ("LENSMODEL_CAHVORE_linearity=0.40", (4842.918, 4842.771, 1970.528, 1085.302, -0.001, 0.002, -0.637, -0.002, 0.016, 0., 0., 0.)),
+    ("LENSMODEL_OPENCV5",  (1512., 1112, 500., 333., -0.012, 0.035, -0.001, 0.002, 0.019)),
+    ("LENSMODEL_OPENCV12", (1512., 1112, 500., 333., -0.012, 0.035, -0.001, 0.002, 0.019, 0.014, -0.056, 0.050,
+                            0.003, -0.002, 0.001, 0.004)),
 ]
 
 
-@pytest.mark.parametrize("lensmodel,intrinsics", UNPROJECT_MODELS, ids=[m[0] for m in UNPROJECT_MODELS])
+SPLINED_MODEL = "LENSMODEL_SPLINED_STEREOGRAPHIC_order=3_Nx=11_Ny=8_fov_x_deg=120"
+
+
+def _unproject_cases():
+    cases = list(UNPROJECT_MODELS)
+    rng = np.random.RandomState(12)
+    cases.append((SPLINED_MODEL, tuple(np.r_[1100., 1100., 500., 333., rng.uniform(-0.02, 0.02, 2*11*8)])))
+    return cases
+
+
+@pytest.mark.parametrize("lensmodel,intrinsics", _unproject_cases(), ids=[m[0] for m in _unproject_cases()])
 def test_unproject_matches_reference(amd, ref_api, lensmodel, intrinsics):
     """host code: runs without a GPU"""
     rng = np.random.RandomState(2)
@@ -62,6 +75,17 @@ def test_unproject_matches_reference(amd, ref_api, lensmodel, intrinsics):
         out.append(v / np.linalg.norm(v, axis=1, keepdims=True))   # "may have any length"
     assert np.isfinite(out[0]).all()
     assert np.abs(out[0] - out[1]).max() < 1e-8
+
+
+def test_unproject_refuses_an_unknown_lens_type(amd):
+    """a type value outside mrcal_lensmodel_type_t: the error return and its message. Host code: runs without a GPU"""
+    lib = amd._lib.lib
+    lib.mrcal_unproject.restype  = C.c_bool
+    lib.mrcal_unproject.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Lensmodel), C.c_void_p]
+    m = Lensmodel(); m.type = 99
+    intr, q, v = np.array((1512., 1112, 500., 333.)), np.array(((600., 400.),)), np.zeros((1,3))
+    assert not lib.mrcal_unproject(v.ctypes.data, q.ctypes.data, 1, C.byref(m), intr.ctypes.data)
+    assert amd._api._last_error() == " mrcal_unproject(): unknown lens model 99"
 
 
 def test_unproject_of_many_points_is_the_unprojection_of_each(amd):
@@ -83,16 +107,6 @@ def test_unproject_of_many_points_is_the_unprojection_of_each(amd):
         n = min(200, q.shape[0] - i0)
         assert lib.mrcal_unproject(w[i0:].ctypes.data, q[i0:].ctypes.data, n, C.byref(m), intr.ctypes.data)
     assert np.isfinite(v).all() and np.array_equal(v, w)
-
-
-SPLINED_MODEL = "LENSMODEL_SPLINED_STEREOGRAPHIC_order=3_Nx=11_Ny=8_fov_x_deg=120"
-
-
-def _unproject_cases():
-    cases = list(UNPROJECT_MODELS)
-    rng = np.random.RandomState(12)
-    cases.append((SPLINED_MODEL, tuple(np.r_[1100., 1100., 500., 333., rng.uniform(-0.02, 0.02, 2*11*8)])))
-    return cases
 
 
 @pytest.mark.gpu
