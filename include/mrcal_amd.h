@@ -762,6 +762,8 @@ bool mrcal_amd_problem_get_board_pool(mrcal_amd_problem_t* problem, mrcal_point3
    Nstate_shared_leading: intrinsics and extrinsics; plus the last Nwarp) and
    which are the mutually independent 6x6 frame / 3x3 point blocks in between.
    Pass (Nstate,0,0,0) for a matrix without that structure (dense; small only).
+   The shared block must hold at least one variable: Nstate_shared_leading + Nwarp == 0
+   is refused (NULL, with a message).
    Returns NULL if JtJ is not positive definite (the reference returns None) */
 typedef struct mrcal_amd_factorization mrcal_amd_factorization_t;
 mrcal_amd_factorization_t*

@@ -27,6 +27,7 @@ __host__ __device__ inline size_t chol_lds_bytes(int n)
     const int npanels = (n + CHOL_PB - 1)/CHOL_PB;
     return ((size_t)chol_tri_doubles(n) + (size_t)npanels*CHOL_PB*CHOL_XLD + 3*64)*sizeof(double);
 }
+// (n <= 180: 159 424 bytes there, and 181 would take 160 880)
 static inline bool chol_fits_lds(int n) { return n <= 200 && chol_lds_bytes(n) <= 160*1024 - 4096; }
 
 // The 16x16 diagonal block of a Cholesky panel, one wave, in registers. Lanes 0..15

@@ -1,4 +1,4 @@
-// The camera block's dense Cholesky by one workgroup in LDS (camera blocks to 178 variables)
+// The camera block's dense Cholesky by one workgroup in LDS (camera blocks to 180 variables)
 // (round 6: one of the translation units solver_kernels.hip was cut into; solver_device.hpp has what they share)
 #include "solver_device.hpp"
 #include "chol_diag16.hpp"
@@ -26,7 +26,8 @@ namespace mrcal_amd {
 // backwards, the block's own solve being the product d_p = X w.
 //
 // Storage: packed lower triangle in LDS, (n+1)(n+2)/2 doubles, + the X blocks:
-// n <= 178 (chol_fits_lds). Larger camera blocks use launch_cholesky_large() below
+// n <= 180 (chol_fits_lds: 159 424 bytes at n = 180 of the 159 744 it allows). Larger camera blocks use
+// launch_cholesky_large() below
 
 // FINISH: 0 a factorization and solve and nothing else | 1 the end of the trial step in front, the verdict behind (sharded:
 // the end-of-trial logic needs the tail summed over the ranks, which is complete only now) | 2 the verdict behind alone:

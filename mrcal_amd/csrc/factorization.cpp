@@ -158,6 +158,14 @@ mrcal_amd_factorization_create(int Nmeas, int Nstate,
                   Nstate_shared_leading, Nframe_blocks, Npoint_blocks, Nwarp, Nstate);
         return NULL;
     }
+    if(Nstate_shared_leading + Nwarp == 0)
+    {
+        // (the Schur complement's reduction - launch_factor_local() - and the solves' - launch_fsolve_sys_batch() - size their
+        //  grids by the camera block: none of it, no workgroups, and a launch of none is an error of its own)
+        set_error("the partition leaves no variable outside the eliminated blocks (%d frame blocks, %d point blocks): "
+                  "a factorization without a camera block is not served", Nframe_blocks, Npoint_blocks);
+        return NULL;
+    }
     const int64_t Nnz = rowptr[Nmeas];
     NormalDims nd;
     memset(&nd, 0, sizeof(nd));

@@ -110,7 +110,9 @@ void fsolve_dense_kernel(int n, const double* __restrict__ S, double* __restrict
         __syncthreads();
     }
 }
-// The same with the factor in LDS (n <= 178, the sizes schur_cholesky_solve_kernel keeps there): the whole
+// The same with the factor in LDS (n <= 178: its loads and the three slots a lane hold 192 rows, the launch below takes
+// it to 178. schur_cholesky_solve_kernel factors in LDS to n = 180 - chol_fits_lds() -: factors of 179 and 180
+// variables are solved against by fsolve_dense_blocked_kernel, tests/test_factorization_sizes.py): the whole
 // workgroup loads the packed triangle, then ONE wave runs the two sweeps with r in registers (lane l holds
 // entries l, l+64, l+128) - a step is a cross-lane read of the pivot entry and one multiply-add per slot, its
 // multipliers (a column of L going forward, a row going back) requested a step ahead. The global-memory

@@ -301,7 +301,9 @@ def test_normal_equations_match_JtJ(amd, case):
 # panel-by-panel Cholesky in HBM, three full 64-column panels and a partial one)
 # and 780 variables (splined: 13 panels)
 # ... and the panel edges of the LDS kernel (panels of 16): camera blocks of exactly 16 and 32
-# variables, one past (18), one short of three panels (46), the biggest that still fits the LDS (170 of <= 178)
+# variables, one past (18), one short of three panels (46), a big one that still fits the LDS (170),
+# and 178 = 14 x 13 - 4 (OPENCV4, 13 cameras): the largest the kept factor's LDS triangular solve takes, of the <= 180 the
+# LDS Cholesky factors (every size between: tests/test_factorization_sizes.py)
 @pytest.mark.parametrize("lensmodel,Ncam,Nf,W,H", (("LENSMODEL_OPENCV4", 2, 8, 8, 7),
                                                    ("LENSMODEL_PINHOLE", 2, 8, 8, 7),
                                                    ("LENSMODEL_OPENCV8", 2, 8, 8, 7),
@@ -309,6 +311,7 @@ def test_normal_equations_match_JtJ(amd, case):
                                                    ("LENSMODEL_PINHOLE", 5, 8, 8, 7),
                                                    ("LENSMODEL_OPENCV12", 8, 6, 10, 10),
                                                    ("LENSMODEL_OPENCV8", 12, 6, 10, 10),
+                                                   ("LENSMODEL_OPENCV4", 13, 4, 8, 7),
                                                    # whole panels of the launch-per-panel Cholesky: 192 = 3 x 64, 256 = 4 x 64
                                                    ("LENSMODEL_OPENCV4", 14, 6, 8, 7),
                                                    ("LENSMODEL_PINHOLE", 26, 5, 8, 7),
