@@ -838,6 +838,50 @@ bool   mrcal_amd_uncertainty_evaluate(mrcal_amd_uncertainty_t* u, const double* 
 double mrcal_amd_uncertainty_observed_pixel_uncertainty(const mrcal_amd_uncertainty_t* u);
 void   mrcal_amd_uncertainty_destroy(mrcal_amd_uncertainty_t* u);
 
+/* ---- projection differences: mrcal.projection_diff() ----------------------
+   Reference: mrcal/model_analysis.py:27-395 (implied_Rt10__from_unprojections), :1520-1928 (projection_diff).
+   The implied transformation: the rt10 (r at infinity; t is then 0) that minimises
+       F = 1/2 sum C^2 rho(x_i^2/C^2),  x_i = 2 (1 - v1_i . p/|p|) w_i,  p = R(r) p0_i + t
+   (C = (5 deg)^2, rho = scipy's 'huber': the reference's cost) over the points with |q0 - focus_center| <
+   focus_radius, by damped Gauss-Newton from rt = 0 in ONE launch of one workgroup (csrc/projection_diff.hip): the
+   same bits on every call. Non-finite weights count as 0, a non-finite component of p0 or v1 zeroes its point's
+   weight, and so does a p0 or a v1 that is the zero vector (a failed unprojection, normalized: a constant in the
+   reference's cost, or 0/0 at the start). q0 (N,2), p0 (M,N,3), v1 (N,3) unit vectors, weights (M,N) or NULL: host pointers.
+   status: 0 converged; 1 the bound on cost evaluations (400) was reached; 3 no descent step was found (both leave the
+   best rt seen, and are not errors); 2 fewer than 3 points in the focus region: false, "Focus region contained too
+   few points". cost, Nevaluations, Nused, status may be NULL */
+#define MRCAL_AMD_IMPLIED_RT10_CONVERGED      0
+#define MRCAL_AMD_IMPLIED_RT10_BOUND          1
+#define MRCAL_AMD_IMPLIED_RT10_TOO_FEW_POINTS 2
+#define MRCAL_AMD_IMPLIED_RT10_STALLED        3
+bool mrcal_amd_implied_rt10(double* rt10 /*6*/, double* cost, int* Nevaluations, int* Nused, int* status,
+                            const double* q0 /*N,2*/, const double* p0 /*M,N,3*/, const double* v1 /*N,3*/,
+                            const double* weights /*M,N or NULL*/, int M, int N, bool atinfinity,
+                            const double focus_center[2], double focus_radius);
+/* The resident form. _create(): the pixels q0 (N,2) unprojected through every one of the Nmodels >= 2 models
+   (intrinsics[i]: that model's parameters; a CAHVORE model must have E = 0), the unit vectors kept on the device.
+   _evaluate(), for Ndistances distances (at infinity: one distance of 1), model 0 against each of the others:
+     fit: the implied transformations, all Nmodels-1 in one launch, from p0 = v[0] d over all the distances;
+          uncertainties (Nmodels contexts, or NULL: equal weights) give the weights 1/(u_0 u_i)^2 of the
+          worst-direction standard deviations at v[i] d. Rt10 (Nmodels-1,4,3) comes back as the device used it, with
+          rt10 (Nmodels-1,6), cost, Nevaluations, Nused, status (Nmodels-1 each; any may be NULL)
+     otherwise Rt10 is the caller's
+     diff (Nmodels-1,Ndistances,N,2; may be NULL) = project_i(Rt10_i (v[0] d)) - q0, difflen (Ndistances,N) its
+     length: the root-mean-square over the models when there are more than two.
+   The vectors, the weights and the pixels stay on the device between the stages. _time_fit(on): bracket the fit's launch with events from now on; returns the last one's ms (< 0: none) */
+typedef struct mrcal_amd_projection_diff mrcal_amd_projection_diff_t;
+mrcal_amd_projection_diff_t*
+mrcal_amd_projection_diff_create(int Nmodels, const mrcal_lensmodel_t* lensmodels, const double* const* intrinsics,
+                                 const double* q0, int N);
+bool   mrcal_amd_projection_diff_evaluate(mrcal_amd_projection_diff_t* pd,
+                                          const double* distances, int Ndistances, bool atinfinity,
+                                          mrcal_amd_uncertainty_t* const* uncertainties,
+                                          bool fit, const double focus_center[2], double focus_radius,
+                                          double* Rt10, double* rt10, double* cost, int* Nevaluations, int* Nused, int* status,
+                                          double* difflen, double* diff);
+double mrcal_amd_projection_diff_time_fit(mrcal_amd_projection_diff_t* pd, bool on);
+void   mrcal_amd_projection_diff_destroy(mrcal_amd_projection_diff_t* pd);
+
 #ifdef __cplusplus
 }
 #endif

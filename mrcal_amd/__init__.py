@@ -71,7 +71,9 @@ project                               = _api.project
 unproject                             = _api.unproject
 
 from ._factorization import CHOLMOD_factorization, _Jt_x, _A_Jt_J_At, _A_Jt_J_At__2
-from .model_analysis import projection_uncertainty, ProjectionUncertainty, worst_direction_stdev
+from .model_analysis import (projection_uncertainty, ProjectionUncertainty, worst_direction_stdev,
+                             implied_Rt10__from_unprojections, projection_diff)
+from .utils import sample_imager, sample_imager_unproject
 
 # the callers either side of the path: the on-disk format of
 # a calibration, host-side pose arithmetic, the seeding. As in the reference, the class

@@ -353,6 +353,46 @@ struct mrcal_amd_uncertainty
     }
 };
 
+static bool what_is_known(int what)
+{
+    if(what == MRCAL_AMD_UNCERTAINTY_COVARIANCE || what == MRCAL_AMD_UNCERTAINTY_WORSTDIRECTION_STDEV ||
+       what == MRCAL_AMD_UNCERTAINTY_RMS_STDEV)
+        return true;
+    set_error("unknown 'what': %d", what);
+    return false;
+}
+
+namespace mrcal_amd {
+// evaluate() on device pointers: p_cam [N][3] in, out [N][4] (covariance) or [N], queued on the caller's stream and not
+// waited for. For projection_diff.hip, whose points and weights never leave the device. (C and the camera's
+// intrinsics were complete when _create() returned: any stream may read them)
+bool uncertainty_evaluate_device(mrcal_amd_uncertainty_t* u, const double* d_p_cam, int N, bool atinfinity, int what,
+                                 double* d_out, hipStream_t stream)
+{
+    if(u == NULL) { set_error("no uncertainty context"); return false; }
+    if(!what_is_known(what)) return false;
+    if(N <= 0) return true;
+    PUArgs a = u->args;
+    a.N = N; a.atinfinity = atinfinity ? 1 : 0; a.what = what;
+    hipError_t e = hipSuccess;
+    if(!for_parametric_lens(u->lensmodel.type, [&](auto k)
+       {
+           using K = decltype(k);
+           e = launch_points<K::PROJ,K::NDIST>(a, u->d_C, u->d_intr, u->d_pose, d_p_cam, d_out, stream);
+       }))
+    {
+        if(u->lensmodel.type != MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC)
+        {
+            set_error("lens model %d is not supported", (int)u->lensmodel.type);
+            return false;
+        }
+        e = launch_points<PROJ_SPLINED,0>(a, u->d_C, u->d_intr, u->d_pose, d_p_cam, d_out, stream);
+    }
+    HIP_TRY(e, return false);
+    return true;
+}
+}
+
 extern "C" {
 
 mrcal_amd_uncertainty_t*
@@ -591,12 +631,7 @@ bool mrcal_amd_uncertainty_evaluate(mrcal_amd_uncertainty_t* u, const double* p_
 {
     last_error_string().clear();
     if(u == NULL) { set_error("no uncertainty context"); return false; }
-    if(what != MRCAL_AMD_UNCERTAINTY_COVARIANCE && what != MRCAL_AMD_UNCERTAINTY_WORSTDIRECTION_STDEV &&
-       what != MRCAL_AMD_UNCERTAINTY_RMS_STDEV)
-    {
-        set_error("unknown 'what': %d", what);
-        return false;
-    }
+    if(!what_is_known(what)) return false;
     if(N <= 0) return true;
     if(u->capacity < N)
     {
@@ -605,25 +640,9 @@ bool mrcal_amd_uncertainty_evaluate(mrcal_amd_uncertainty_t* u, const double* p_
         if(!u->mem.alloc(&u->d_p, (size_t)N*3) || !u->mem.alloc(&u->d_out, (size_t)N*4)) return false;
         u->capacity = N;
     }
-    PUArgs a = u->args;
-    a.N = N; a.atinfinity = atinfinity ? 1 : 0; a.what = what;
     const size_t nout = (size_t)N*(what == MRCAL_AMD_UNCERTAINTY_COVARIANCE ? 4 : 1);
     HIP_TRY(hipMemcpyAsync(u->d_p, p_cam, (size_t)N*3*sizeof(double), hipMemcpyHostToDevice, u->stream), return false);
-    hipError_t e = hipSuccess;
-    if(!for_parametric_lens(u->lensmodel.type, [&](auto k)
-       {
-           using K = decltype(k);
-           e = launch_points<K::PROJ,K::NDIST>(a, u->d_C, u->d_intr, u->d_pose, u->d_p, u->d_out, u->stream);
-       }))
-    {
-        if(u->lensmodel.type != MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC)
-        {
-            set_error("lens model %d is not supported", (int)u->lensmodel.type);
-            return false;
-        }
-        e = launch_points<PROJ_SPLINED,0>(a, u->d_C, u->d_intr, u->d_pose, u->d_p, u->d_out, u->stream);
-    }
-    HIP_TRY(e, return false);
+    if(!uncertainty_evaluate_device(u, u->d_p, N, atinfinity, what, u->d_out, u->stream)) return false;
     HIP_TRY(hipMemcpyAsync(out, u->d_out, nout*sizeof(double), hipMemcpyDeviceToHost, u->stream), return false);
     HIP_TRY(hipStreamSynchronize(u->stream), return false);
     return true;

@@ -1,4 +1,10 @@
-"""Projection uncertainty: mrcal.projection_uncertainty() (mrcal/model_analysis.py:1192-1517) with the propagation on
+"""Model analysis: the projection uncertainty and the projection differences between models.
+
+Projection differences: mrcal.projection_diff() (mrcal/model_analysis.py:1520-1928) and the fit in its middle,
+implied_Rt10__from_unprojections() (:27-395), on the device (include/mrcal_amd.h, mrcal_amd_implied_rt10,
+mrcal_amd_projection_diff_*; csrc/projection_diff.hip). See the end of this file.
+
+Projection uncertainty: mrcal.projection_uncertainty() (mrcal/model_analysis.py:1192-1517) with the propagation on
 the device (include/mrcal_amd.h, mrcal_amd_uncertainty_*; csrc/projection_uncertainty.hip).
 
     u = mrcal.ProjectionUncertainty(model)                 # C (k x k) computed once, on the GPU
@@ -11,6 +17,7 @@ The methods are the cross-reprojection ones, "cross-reprojection-ccp" (the defau
 """
 import ctypes as C
 import re
+import sys
 import numpy as np
 
 from ._cabi import _ptr
@@ -163,3 +170,273 @@ def projection_uncertainty(p_cam, model, *, method='cross-reprojection-ccp', ati
     _check_what(what)
     with ProjectionUncertainty(model, method=method, observed_pixel_uncertainty=observed_pixel_uncertainty) as u:
         return u.evaluate(p_cam, atinfinity=atinfinity, what=what)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# projection differences
+
+def _declare_diff(L):
+    if getattr(L, "_mrcal_amd_projection_diff_declared", False):
+        return
+    vp = C.c_void_p
+    L.mrcal_amd_implied_rt10.restype  = C.c_bool
+    L.mrcal_amd_implied_rt10.argtypes = [vp]*9 + [C.c_int, C.c_int, C.c_bool, vp, C.c_double]
+    L.mrcal_amd_projection_diff_create.restype  = vp
+    L.mrcal_amd_projection_diff_create.argtypes = [C.c_int, vp, vp, vp, C.c_int]
+    L.mrcal_amd_projection_diff_evaluate.restype  = C.c_bool
+    L.mrcal_amd_projection_diff_evaluate.argtypes = [vp, vp, C.c_int, C.c_bool, vp, C.c_bool, vp, C.c_double] + [vp]*8
+    L.mrcal_amd_projection_diff_time_fit.restype  = C.c_double
+    L.mrcal_amd_projection_diff_time_fit.argtypes = [vp, C.c_bool]
+    L.mrcal_amd_projection_diff_destroy.restype  = None
+    L.mrcal_amd_projection_diff_destroy.argtypes = [vp]
+    L._mrcal_amd_projection_diff_declared = True
+
+
+def _Rt_from_fit(rt, atinfinity):
+    """(..., 4,3) from the fitted (..., 6): at infinity the fit is a rotation, and row 3 is 0"""
+    from .poseutils import R_from_r
+    rt = np.asarray(rt, dtype=float)
+    Rt = np.zeros(rt.shape[:-1] + (4, 3))
+    Rt[..., :3, :] = R_from_r(rt[..., :3])
+    if not atinfinity:
+        Rt[..., 3, :] = rt[..., 3:]
+    return Rt
+
+
+def _implied_rt10(q0, p0, v1, weights, atinfinity, focus_center, focus_radius):
+    """The fit and what it reports: (rt (6,), dict(cost, Nevaluations, Nused, status))"""
+    q0 = np.asarray(q0, dtype=float)
+    p0 = np.asarray(p0, dtype=float)
+    v1 = np.asarray(v1, dtype=float)
+    if q0.ndim < 2 or q0.shape[-1] != 2:
+        raise Exception(f"q0 must have shape (Nh,Nw,2), got {q0.shape}")
+    grid = q0.shape[:-1]
+    if v1.shape != grid + (3,):
+        raise Exception(f"v1 must have shape {grid + (3,)}, got {v1.shape}")
+    if p0.shape[-1:] != (3,) or p0.shape[-1-len(grid):-1] != grid:
+        raise Exception(f"p0 must have shape (...,{','.join(str(n) for n in grid)},3), got {p0.shape}")
+    N = int(np.prod(grid))
+    q0 = np.ascontiguousarray(q0.reshape(N, 2))
+    v1 = np.ascontiguousarray(v1.reshape(N, 3))
+    p0 = np.ascontiguousarray(p0.reshape(-1, N, 3))
+    M = p0.shape[0]
+    if weights is not None:
+        weights = np.asarray(weights, dtype=float)
+        if weights.size != M*N or weights.shape[-len(grid):] != grid:
+            raise Exception(f"weights must have the shape of p0 less its last dimension, got {weights.shape}")
+        weights = np.ascontiguousarray(weights.reshape(M, N))
+    fc = np.ascontiguousarray(np.asarray(focus_center, dtype=float).reshape(2))
+
+    from . import _lib, _api
+    L = _lib.lib
+    _declare_diff(L)
+    rt = np.zeros(6)
+    cost = C.c_double(0.0)
+    Nevaluations, Nused, status = C.c_int(0), C.c_int(0), C.c_int(-1)
+    ok = L.mrcal_amd_implied_rt10(_ptr(rt), C.byref(cost), C.byref(Nevaluations), C.byref(Nused), C.byref(status),
+                                  _ptr(q0), _ptr(p0), _ptr(v1), _ptr(weights), M, N, bool(atinfinity), _ptr(fc),
+                                  float(focus_radius))
+    if not ok:
+        if status.value == 2:
+            raise Exception("Focus region contained too few points")
+        raise Exception("implied_Rt10__from_unprojections() failed:" + _api._last_error())
+    return rt, dict(cost=cost.value, Nevaluations=Nevaluations.value, Nused=Nused.value, status=status.value)
+
+
+def implied_Rt10__from_unprojections(q0, p0, v1, *, weights=None, atinfinity=True, focus_center=(0, 0), focus_radius=1.0e8):
+    """mrcal.implied_Rt10__from_unprojections() (mrcal/model_analysis.py:27-395): the Rt (4,3) from camera 0 to camera 1
+    that best lines up the unprojections p0 (...,Nh,Nw,3) of camera 0 with the unit vectors v1 (Nh,Nw,3) of camera 1 at
+    the pixels q0 (Nh,Nw,2) inside the focus region, weighted by weights (...,Nh,Nw). Every leading dimension of p0
+    takes part in the one fit. atinfinity: a rotation only (row 3 is 0), p0 are unit vectors. The reference's cost
+    (Huber at (5 deg)^2), minimised on the GPU in one launch from rt = 0: the same bits on every call, and exactly the
+    identity for a model against itself (csrc/projection_diff.hip)"""
+    rt, _ = _implied_rt10(q0, p0, v1, weights, atinfinity, focus_center, focus_radius)
+    return _Rt_from_fit(rt, atinfinity)
+
+
+def _is_noncentral(lensmodel):
+    # (mrcal_lensmodel_metadata(): of the models here only CAHVORE is)
+    return re.match("LENSMODEL_CAHVORE_", lensmodel) is not None
+
+
+class _DiffContext:
+    """The gridded unprojections of two or more models, resident (mrcal_amd_projection_diff_*)"""
+    def __init__(self, lensmodels, intrinsics_data, q0):
+        from . import _lib, _api
+        self._L, self._api = _lib.lib, _api
+        _declare_diff(self._L)
+        self.handle = None
+        self.Nmodels = len(lensmodels)
+        self.grid = q0.shape[:-1]
+        self.N = int(np.prod(self.grid))
+        ms = [_lib.lensmodel(name) for name in lensmodels]
+        arr = (type(ms[0])*self.Nmodels)(*ms)
+        intr = [np.ascontiguousarray(i, dtype=np.float64) for i in intrinsics_data]
+        for name, m, i in zip(lensmodels, ms, intr):
+            Ni = self._L.mrcal_lensmodel_num_params(C.byref(m))
+            if i.shape != (Ni,):
+                raise Exception(f"{name} takes {Ni} intrinsics, got an array of shape {i.shape}")
+        ptrs = (C.c_void_p*self.Nmodels)(*[i.ctypes.data for i in intr])
+        q = np.ascontiguousarray(q0.reshape(self.N, 2), dtype=np.float64)
+        self.handle = self._L.mrcal_amd_projection_diff_create(self.Nmodels, arr, ptrs, _ptr(q), self.N)
+        if not self.handle:
+            raise Exception("projection_diff() failed:" + _api._last_error())
+
+    def evaluate(self, distance, atinfinity, uncertainties, Rt10, focus_center, focus_radius):
+        """(difflen (Nd,Nh,Nw), diff (Nfits,Nd,Nh,Nw,2), Rt10 (Nfits,4,3), report). Rt10 None: the fit"""
+        Nfits, Nd = self.Nmodels - 1, len(distance)
+        d = np.ascontiguousarray(distance, dtype=np.float64)
+        fit = Rt10 is None
+        Rt = np.zeros((Nfits, 4, 3)) if fit else np.ascontiguousarray(Rt10, dtype=np.float64).reshape(Nfits, 4, 3).copy()
+        rt = np.zeros((Nfits, 6))
+        cost = np.zeros(Nfits)
+        Nevaluations, Nused, status = (np.full(Nfits, -1, dtype=np.int32) for _ in range(3))
+        difflen = np.empty((Nd,) + self.grid)
+        diff    = np.empty((Nfits, Nd) + self.grid + (2,))
+        us = None
+        if fit and uncertainties is not None:
+            us = (C.c_void_p*self.Nmodels)(*[u.handle for u in uncertainties])
+        fc = np.ascontiguousarray(np.asarray(focus_center, dtype=float).reshape(2))
+        ok = self._L.mrcal_amd_projection_diff_evaluate(self.handle, _ptr(d), Nd, bool(atinfinity), us, fit, _ptr(fc),
+                                                        float(focus_radius), _ptr(Rt), _ptr(rt), _ptr(cost),
+                                                        _ptr(Nevaluations), _ptr(Nused), _ptr(status), _ptr(difflen), _ptr(diff))
+        if not ok:
+            if fit and (status == 2).any():
+                raise Exception("Focus region contained too few points")
+            raise Exception("projection_diff() failed:" + self._api._last_error())
+        if fit:
+            # (the same conversion as implied_Rt10__from_unprojections(): the same bits; the device's own R differs from
+            #  it by rounding)
+            Rt = _Rt_from_fit(rt, atinfinity)
+        return difflen, diff, Rt, dict(rt=rt, cost=cost, Nevaluations=Nevaluations, Nused=Nused, status=status)
+
+    def time_fit(self, on=True):
+        return self._L.mrcal_amd_projection_diff_time_fit(self.handle, bool(on))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._L.mrcal_amd_projection_diff_destroy(self.handle)
+            self.handle = None
+    def __del__(self):
+        try:    self.close()
+        except Exception: pass
+    def __enter__(self): return self
+    def __exit__(self, *a): self.close()
+
+
+def projection_diff(models, *, implied_Rt10=None, gridn_width=60, gridn_height=None, intrinsics_only=False, distance=None,
+                    use_uncertainties=True, focus_center=None, focus_radius=-1.):
+    """mrcal.projection_diff() (mrcal/model_analysis.py:1520-1928): the difference in projection between models, on a
+    grid of the imager. Returns (difflen, diff, q0, Rt10):
+      difflen (gridn_height,gridn_width), with a leading len(distance) if distance is iterable: |diff|; with more than
+              two models sqrt(mean_i |q_i - q0|^2) over models 1..
+      diff    difflen's shape + (2,): q1 - q0, or None with more than two models
+      q0      (gridn_height,gridn_width,2): the grid
+      Rt10    (4,3), or (len(models)-1,4,3) with more than two models: the transformation used - implied_Rt10 as given;
+              the identity if intrinsics_only; the models' own extrinsics if focus_radius == 0; otherwise the fit of
+              implied_Rt10__from_unprojections() over all the distances, weighted by 1/(u0 u1)^2 of the models'
+              worst-direction projection uncertainties if use_uncertainties (with a WARNING on stderr, and without
+              weights, if those cannot be computed).
+    distance None: infinity. focus_center None: the imager's centre. focus_radius < 0: the whole imager with
+    uncertainties, min(W,H)/6 without. The grid's unprojections, the weights and the pixels stay on the GPU between
+    the stages (csrc/projection_diff.hip)"""
+    return _projection_diff(models, None, None, implied_Rt10=implied_Rt10, gridn_width=gridn_width, gridn_height=gridn_height,
+                            intrinsics_only=intrinsics_only, distance=distance, use_uncertainties=use_uncertainties,
+                            focus_center=focus_center, focus_radius=focus_radius)
+
+
+def _projection_diff(models, _uncertainties, _report, *, implied_Rt10=None, gridn_width=60, gridn_height=None,
+                     intrinsics_only=False, distance=None, use_uncertainties=True, focus_center=None, focus_radius=-1.):
+    """projection_diff(), and for the tools: _uncertainties, ProjectionUncertainty contexts (one a model) to use instead of
+    making them; _report, a dict that receives what the fit reported (rt, cost, Nevaluations, Nused, status)"""
+    from .poseutils import identity_Rt, compose_Rt
+    from .utils import sample_imager
+
+    if len(models) < 2:
+        raise Exception("At least 2 models are required to compute the diff")
+    if len(models) > 2 and implied_Rt10 is not None:
+        raise Exception("A given implied_Rt10 is currently supported ONLY if exactly 2 models are being compared")
+
+    distance_is_iterable = True
+    try:    len(distance)
+    except Exception: distance_is_iterable = False
+    if distance is None:
+        atinfinity = True
+        distance   = np.ones((1,), dtype=float)
+    else:
+        atinfinity = False
+        distance   = np.atleast_1d(np.array(distance, dtype=float)).ravel()
+
+    imagersizes = np.array([model.imagersize() for model in models])
+    if np.linalg.norm(np.std(imagersizes, axis=-2)) != 0:
+        raise Exception("The diff function needs all the imager dimensions to match. Instead got {}".format(imagersizes))
+    W, H = (int(x) for x in imagersizes[0])
+
+    lensmodels      = [model.intrinsics()[0] for model in models]
+    intrinsics_data = [np.array(model.intrinsics()[1], dtype=float) for model in models]
+    for i in range(len(models)):
+        if _is_noncentral(lensmodels[i]) and not np.sum(intrinsics_data[i][-3:]**2) < 1e-12:
+            if not atinfinity:
+                raise Exception(f"Model {i} is noncentral, so I can only evaluate the diff at infinity")
+            if use_uncertainties:
+                raise Exception("I have a noncentral model. No usable uncertainties for those yet")
+            # (the reference's special case: CAHVORE is compared with its E set to 0)
+            intrinsics_data[i][-3:] = 0
+
+    want_fit     = implied_Rt10 is None and not intrinsics_only and focus_radius != 0
+    want_weights = use_uncertainties and want_fit
+    if implied_Rt10 is not None:
+        implied_Rt10 = np.asarray(implied_Rt10, dtype=float)
+        if implied_Rt10.shape != (4, 3):
+            raise Exception(f"implied_Rt10 must have shape (4,3), got {implied_Rt10.shape}")
+
+    # everything the host can refuse has been refused: the device from here on
+    uncertainties, made_here = None, []
+    if want_weights:
+        try:
+            if _uncertainties is not None:
+                uncertainties = list(_uncertainties)
+                if len(uncertainties) != len(models):
+                    raise Exception(f"{len(uncertainties)} uncertainty contexts for {len(models)} models")
+            else:
+                for model in models:
+                    made_here.append(ProjectionUncertainty(model))
+                uncertainties = made_here
+        except Exception as e:
+            print("WARNING: projection_diff() was asked to use uncertainties, but they aren't available/couldn't be "
+                  f"computed. Falling back on the region-based-only logic. Caught exception: {e}", file=sys.stderr)
+            for u in made_here: u.close()
+            uncertainties, made_here = None, []
+
+    try:
+        if focus_center is None:
+            focus_center = ((W - 1.)/2., (H - 1.)/2.)
+        if focus_radius < 0:
+            focus_radius = float(max(W, H)*100.) if uncertainties is not None else float(min(W, H)/6.)
+
+        Nfits = len(models) - 1
+        if implied_Rt10 is not None:
+            Rt10 = implied_Rt10[None]
+        elif intrinsics_only:
+            Rt10 = np.tile(identity_Rt(), (Nfits, 1, 1))
+        elif focus_radius == 0:
+            Rt10 = np.array([compose_Rt(models[i].Rt_cam_ref(), models[0].Rt_ref_cam()) for i in range(1, len(models))])
+        else:
+            Rt10 = None
+
+        q0 = sample_imager(gridn_width, gridn_height, W, H)
+        with _DiffContext(lensmodels, intrinsics_data, q0) as ctx:
+            difflen, diff, Rt10, report = ctx.evaluate(distance, atinfinity, uncertainties, Rt10, focus_center, focus_radius)
+        if _report is not None:
+            _report.update(report)
+    finally:
+        for u in made_here: u.close()
+
+    if len(models) == 2:
+        diff, Rt10 = diff[0], Rt10[0]
+    else:
+        diff = None
+    if not distance_is_iterable:
+        difflen = difflen[0]
+        if diff is not None: diff = diff[0]
+    return difflen, diff, q0, Rt10
