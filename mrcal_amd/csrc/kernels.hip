@@ -1048,15 +1048,22 @@ void board_observation(const DeviceProblem& P,
             __builtin_amdgcn_wave_barrier();
             {
                 double* __restrict__ t0 = tile + (size_t)(2*(lane & 31) + (lane >> 5))*KS;
+                // h is wave-uniform: a scalar branch around two copies of the stores, each reading its own slot's
+                // registers. (Left to itself the compiler merges the two arms into ONE set of stores behind 2*NCOLS4
+                // selects on an all-ones or all-zeros mask, which sit between a pass's arithmetic and the half's first
+                // MFMA: 2.4 us of the kernel's 76, LEDGER "After round 6: the board kernel's row shuffling". An arm
+                // that ends in an asm statement is not merged with its sibling)
                 if(h == 0)
                 {
 #pragma unroll
                     for(int c=0;c<NCOLS4;c++) t0[c] = row[0][c];
+                    asm volatile("" ::: "memory");
                 }
                 else
                 {
 #pragma unroll
                     for(int c=0;c<NCOLS4;c++) t0[c] = row[1][c];
+                    asm volatile("" ::: "memory");
                 }
             }
             __builtin_amdgcn_wave_barrier();
