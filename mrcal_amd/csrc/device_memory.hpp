@@ -94,6 +94,11 @@ public:
             HIP_TRY(hipMemcpy(*p, host, n*sizeof(T), hipMemcpyHostToDevice), return false);
         return true;
     }
+    // ... holding a list of the host's (an empty list: one element that is zero)
+    template<class T> bool upload(T** p, const std::vector<T>& v)
+    {
+        return v.empty() ? alloc_zeroed(p, 1) : upload(p, v.data(), v.size());
+    }
     // n elements of pinned host memory
     template<class T> bool alloc_pinned(T** p, size_t n) { return take(p, n, true); }
 

@@ -8,8 +8,6 @@
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
-#include <map>
-#include <algorithm>
 #include "layout.hpp"
 #include "host_state.hpp"
 #include "problem.hpp"
@@ -17,8 +15,8 @@
 #include "lens_dispatch.hpp"
 #include "problem_object.hpp"
 #include "host_copy.hpp"
+#include "solver_plan.hpp"
 #include <thread>
-#include <unordered_map>
 #include <mutex>
 #include <condition_variable>
 #include <deque>
@@ -43,198 +41,26 @@ mrcal_amd_problem::~mrcal_amd_problem()
 
 namespace mrcal_amd {
 
-// The fixed-order plan for the rows outside the Grams that share destinations: discrete points, triangulated
-// pairs (GenPlan, solver_kernels.hpp). From the CSR structure itself, which does not change between evaluations
-// (except the splined models' patch columns: no plan then, those rows keep the atomics)
-static bool build_gen_plan(mrcal_amd_problem* P)
+// ---- problem_prepare_solver(): what the solver holds beyond the evaluation's buffers, one step after the other ----
+
+// the second operating point, and both points' normal equations
+static bool alloc_normal_equations(mrcal_amd_problem* P)
 {
-    GenPlan& G = P->plan.gen;
-    memset(&G, 0, sizeof(G));
     const Layout& L = P->L;
     const NormalDims& nd = P->nd;
-    const int r0 = L.i_meas_points, r1 = L.i_meas_regularization;
-    G.row_first = r0; G.row_end = r1;
-    if(r1 <= r0) return true;
-    if(L.lensmodel.type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC && L.Nmeas_points > 0 && L.Ndist_state > 0) return true;
-    std::vector<int32_t> Jp((size_t)(r1 - r0) + 1);
-    HIP_TRY(hipMemcpy(Jp.data(), P->d_Jp + r0, Jp.size()*sizeof(int32_t), hipMemcpyDeviceToHost), return false);
-    const int32_t p0 = Jp[0], p1 = Jp[r1 - r0];
-    std::vector<int32_t> Ji((size_t)(p1 - p0 > 0 ? p1 - p0 : 1));
-    if(p1 > p0) HIP_TRY(hipMemcpy(Ji.data(), P->d_Ji + p0, (size_t)(p1 - p0)*sizeof(int32_t), hipMemcpyDeviceToHost), return false);
-
-    struct RowInfo { int group, eblk, epos; };
-    std::vector<RowInfo> info((size_t)(r1 - r0));
-    // a row's signature [k | spos.. | scol..] -> its group, the groups numbered as they first appear. (Round 6: the
-    // signature on the stack and a hash in front of the comparison; three vectors and an ordered map of vectors a row
-    // were 10 ms of BASELINE configuration 4's 67 000 rows - as long as its five dog-leg steps and their launches together)
-    std::unordered_map<uint64_t, std::vector<int>> groups;
-    std::vector<std::vector<int>> group_sig;
-    int kmax = 0;
-    for(int r = r0; r < r1; r++)
-    {
-        const int a = Jp[r - r0] - p0, b = Jp[r - r0 + 1] - p0;
-        int sig[2*GEN_KMAX + 1], scol[GEN_KMAX];
-        int k = 0;
-        int eblk = -1, epos = -1, ecount = 0;
-        for(int p = a; p < b; p++)
-        {
-            const int c = Ji[p];
-            if(c < 0 || c >= nd.Nstate) return true;                 // (flagged at run time by the row-by-row path)
-            const int se = state_to_SE(nd, c);
-            if(se >= 0)
-            {
-                if(k >= GEN_KMAX) return true;
-                sig[1 + k] = p - a; scol[k] = se; k++;
-            }
-            else
-            {
-                const int e = -se - 1;
-                const int blk = (e < 6*nd.Nfb) ? e/6 : nd.Nfb + (e - 6*nd.Nfb)/3;
-                const int e0  = (blk < nd.Nfb) ? 6*blk : 6*nd.Nfb + 3*(blk - nd.Nfb);
-                const int de  = (blk < nd.Nfb) ? 6 : 3;
-                // the block's columns must be all there, side by side, in order
-                if(ecount == 0) { if(e != e0) return true; eblk = blk; epos = p - a; }
-                else if(blk != eblk || e != e0 + ecount) return true;
-                ecount++;
-                if(ecount > de) return true;
-            }
-        }
-        if(eblk >= 0 && ecount != ((eblk < nd.Nfb) ? 6 : 3)) return true;
-        if(k > kmax) kmax = k;
-        sig[0] = k;
-        for(int i = 0; i < k; i++) sig[1 + k + i] = scol[i];
-        const int nsig = 2*k + 1;
-        uint64_t h = 1469598103934665603ull;
-        for(int i = 0; i < nsig; i++) { h ^= (uint64_t)(uint32_t)sig[i]; h *= 1099511628211ull; }
-        std::vector<int>& cand = groups[h];
-        int g = -1;
-        for(int gc : cand)
-            if((int)group_sig[gc].size() == nsig && !memcmp(group_sig[gc].data(), sig, nsig*sizeof(int))) { g = gc; break; }
-        if(g < 0) { g = (int)group_sig.size(); cand.push_back(g); group_sig.emplace_back(sig, sig + nsig); }
-        info[r - r0] = RowInfo{ g, eblk, epos };
-    }
-    const int Ngroups = (int)group_sig.size();
-    const int stride  = (kmax*(kmax+1))/2 + kmax + 1;
-    if(stride > 1023 || Ngroups >= (1 << 20)) return true;
-    // (gen_eblock keeps a block's rows of Bt in LDS: 6 Nc doubles, within the 64 KB a launch gets without asking)
-    {
-        bool any_eblock = false;
-        for(const RowInfo& ri : info) any_eblock = any_eblock || ri.eblk >= 0;
-        if(any_eblock && ((size_t)6*nd.Nc + 42)*sizeof(double) > 64*1024) return true;
-    }
-
-    // rows by (group, row); chunks
-    // (by counting: the groups are few)
-    std::vector<int> rows((size_t)(r1 - r0));
-    {
-        std::vector<int> at(Ngroups + 1, 0);
-        for(const RowInfo& ri : info) at[ri.group + 1]++;
-        for(int g = 0; g < Ngroups; g++) at[g + 1] += at[g];
-        for(int i = 0; i < r1 - r0; i++) rows[at[info[i].group]++] = r0 + i;
-    }
-    std::vector<int> chunk_begin, chunk_group, group_chunk_begin(Ngroups + 1, 0);
-    for(size_t i = 0; i < rows.size();)
-    {
-        const int g = info[rows[i] - r0].group;
-        size_t j = i;
-        while(j < rows.size() && j - i < GEN_CHUNK && info[rows[j] - r0].group == g) j++;
-        chunk_begin.push_back((int)i); chunk_group.push_back(g);
-        group_chunk_begin[g + 1]++;
-        i = j;
-    }
-    chunk_begin.push_back((int)rows.size());
-    for(int g = 0; g < Ngroups; g++) group_chunk_begin[g+1] += group_chunk_begin[g];
-    std::vector<int> group_k(Ngroups), group_off(Ngroups), spos_all, scol_all;
-    for(int g = 0; g < Ngroups; g++)
-    {
-        const std::vector<int>& sig = group_sig[g];
-        const int k = sig[0];
-        group_k[g] = k; group_off[g] = (int)spos_all.size();
-        spos_all.insert(spos_all.end(), sig.begin() + 1, sig.begin() + 1 + k);
-        scol_all.insert(scol_all.end(), sig.begin() + 1 + k, sig.end());
-    }
-    // destinations: entries of A (both orientations, as the row-by-row path adds them), of g (S part), |x|^2
-    const int nA = nd.Nc*nd.Nc;
-    std::map<int, std::vector<int>> src;
-    for(int g = 0; g < Ngroups; g++)
-    {
-        const int k = group_k[g];
-        const int* sc = scol_all.data() + group_off[g];
-        int pos = 0;
-        for(int p = 0; p < k; p++)
-            for(int q = p; q < k; q++, pos++)
-            {
-                const int code = (g << 10) | pos;
-                src[sc[p]*nd.Nc + sc[q]].push_back(code);
-                if(q != p) src[sc[q]*nd.Nc + sc[p]].push_back(code);
-            }
-        for(int p = 0; p < k; p++, pos++) src[nA + sc[p]].push_back((g << 10) | pos);
-        src[nA + nd.Nc].push_back((g << 10) | pos);
-    }
-    std::vector<int> dest_id, dest_begin(1, 0), dest_src;
-    for(auto& kv : src)
-    {
-        dest_id.push_back(kv.first);
-        dest_src.insert(dest_src.end(), kv.second.begin(), kv.second.end());
-        dest_begin.push_back((int)dest_src.size());
-    }
-    // the eliminated blocks: their rows, in row order
-    std::map<int, std::vector<int>> by_block;
-    for(int r = r0; r < r1; r++)
-        if(info[r - r0].eblk >= 0) by_block[info[r - r0].eblk].push_back(r);
-    std::vector<int> eb_block, eb_begin(1, 0), eb_rows, eb_group, eb_epos;
-    for(auto& kv : by_block)
-    {
-        eb_block.push_back(kv.first);
-        for(int r : kv.second) { eb_rows.push_back(r); eb_group.push_back(info[r - r0].group); eb_epos.push_back(info[r - r0].epos); }
-        eb_begin.push_back((int)eb_rows.size());
-    }
-    auto nonempty = [](std::vector<int>& v) { if(v.empty()) v.push_back(0); };
-    const int Nchunks = (int)chunk_group.size(), Neb = (int)eb_block.size(), Ndest = (int)dest_id.size();
-    nonempty(chunk_group); nonempty(spos_all); nonempty(scol_all); nonempty(dest_id); nonempty(dest_src);
-    nonempty(eb_block); nonempty(eb_rows); nonempty(eb_group); nonempty(eb_epos);
-    bool ok = true;
-    ok = ok && P->mem.upload(&G.rows,        rows.data(),        rows.size());
-    ok = ok && P->mem.upload(&G.chunk_begin, chunk_begin.data(), chunk_begin.size());
-    ok = ok && P->mem.upload(&G.chunk_group, chunk_group.data(), chunk_group.size());
-    ok = ok && P->mem.upload(&G.group_k,     group_k.data(),     group_k.size());
-    ok = ok && P->mem.upload(&G.group_off,   group_off.data(),   group_off.size());
-    ok = ok && P->mem.upload(&G.spos,        spos_all.data(),    spos_all.size());
-    ok = ok && P->mem.upload(&G.scol,        scol_all.data(),    scol_all.size());
-    ok = ok && P->mem.upload(&G.dest_id,     dest_id.data(),     dest_id.size());
-    ok = ok && P->mem.upload(&G.dest_begin,  dest_begin.data(),  dest_begin.size());
-    ok = ok && P->mem.upload(&G.dest_src,    dest_src.data(),    dest_src.size());
-    ok = ok && P->mem.upload(&G.group_chunk_begin, group_chunk_begin.data(), group_chunk_begin.size());
-    ok = ok && P->mem.upload(&G.eb_block,    eb_block.data(),    eb_block.size());
-    ok = ok && P->mem.upload(&G.eb_begin,    eb_begin.data(),    eb_begin.size());
-    ok = ok && P->mem.upload(&G.eb_rows,     eb_rows.data(),     eb_rows.size());
-    ok = ok && P->mem.upload(&G.eb_group,    eb_group.data(),    eb_group.size());
-    ok = ok && P->mem.upload(&G.eb_epos,     eb_epos.data(),     eb_epos.size());
-    ok = ok && P->mem.alloc(&G.part, (size_t)(Nchunks > 0 ? Nchunks : 1)*stride);
-    if(!ok) return false;
-    G.Nrows = r1 - r0; G.Nchunks = Nchunks; G.Ngroups = Ngroups; G.stride = stride; G.kmax = kmax;
-    G.Ndest = Ndest; G.Neblocks = Neb;
-    return true;
-}
-
-static bool allocate_solver_buffers(mrcal_amd_problem* P)
-{
-    const Layout& L = P->L;
-    NormalDims& nd = P->nd;
-
-    // second operating point
+    const bool splined = L.lensmodel.type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC;
     bool ok = true;
     ok = ok && P->mem.alloc(&P->op[1].b,  (size_t)L.Nstate);
     ok = ok && P->mem.alloc(&P->op[1].x,  (size_t)L.Nmeas);
     ok = ok && P->mem.alloc(&P->op[1].Jv, (size_t)P->Nnz);
     if(P->op[0].spl_box != NULL) ok = ok && P->mem.alloc(&P->op[1].spl_box, (size_t)4*P->D.Nobs_board);
-    if(L.lensmodel.type != MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC && (size_t)P->D.Nobs_board*gram_stride(L.Ndist) >= ((size_t)1 << 32))
+    if(!splined && (size_t)P->D.Nobs_board*gram_stride(L.Ndist) >= ((size_t)1 << 32))
     {
         // (reduce_pair_chunk() addresses the Grams with 32-bit element offsets; this is 34 GB of Grams)
         set_error("too many board observations: %d Grams of %d doubles", P->D.Nobs_board, gram_stride(L.Ndist));
         return false;
     }
-    ok = ok && P->mem.alloc(&P->d_gram,   (L.lensmodel.type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC) ? (size_t)1 : (size_t)P->D.Nobs_board*gram_stride(L.Ndist));
+    ok = ok && P->mem.alloc(&P->d_gram, splined ? (size_t)1 : (size_t)P->D.Nobs_board*gram_stride(L.Ndist));
     for(int i=0;i<2 && ok;i++)
     {
         ok = ok && P->mem.alloc(&P->op[i].A,       (size_t)nd.Nc*nd.Nc);
@@ -246,74 +72,24 @@ static bool allocate_solver_buffers(mrcal_amd_problem* P)
         ok = ok && P->mem.alloc_zeroed(&P->op[i].step_cauchy, (size_t)nd.Nstate);
         ok = ok && P->mem.alloc_zeroed(&P->op[i].step_gn,     (size_t)nd.Nstate);
     }
+    return ok;
+}
+
+// the factorization's scratch (FactorBuffers), the step and the dog-leg control block
+static bool alloc_factor_scratch(mrcal_amd_problem* P)
+{
+    const NormalDims& nd = P->nd;
+    bool ok = true;
     ok = ok && P->mem.alloc(&P->F.Spart, schur_partial_doubles(nd));
     ok = ok && P->mem.alloc(&P->F.Linv,  cholesky_large_workspace_doubles(nd.Nc));
     if(cholesky_large_workspace_doubles(nd.Nc) > 1) ok = ok && P->mem.alloc(&P->F.diag_minmax, 2);
     // the tile occupancy of Wt: only where the couplings are sparse (the splined models) and the strip SYRK runs
-    if(L.lensmodel.type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC && nd.Nc > 256 && nd.Nc <= 4096)
+    if(P->L.lensmodel.type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC && nd.Nc > 256 && nd.Nc <= 4096)
     {
-        ok = ok && P->mem.alloc(&P->F.occ, (size_t)(nd.NEb > 0 ? nd.NEb : 1)*occ_words(nd));
-        ok = ok && P->mem.alloc(&P->F.Wtile, (size_t)((nd.Nc + 15)/16)*16*(size_t)(nd.NE > 0 ? nd.NE : 1));
+        ok = ok && P->mem.alloc(&P->F.occ, (size_t)nd.NEb*occ_words(nd));
+        ok = ok && P->mem.alloc(&P->F.Wtile, (size_t)((nd.Nc + 15)/16)*16*(size_t)nd.NE);
     }
-    // The splined models' camera block without the control points no board covers (round 5; assembly_splined.hip,
-    // spl_compact_kernel / LcholCompact): where the big camera block's launch-per-panel Cholesky runs, every row that
-    // touches a control point is a board's (no discrete points: they have no boxes) and all rows are here (not a shard:
-    // the ranks of a sharded solve sum their camera blocks entry by entry). MRCAL_AMD_NO_SPL_COMPACT=1: off
-    {
-        // (nor with the backward sweep, which knows nothing of a size the device decides)
-        P->F.use_sweep = test_hooks().lchol_sweep ? 1 : 0;
-        static const bool env_off = (getenv("MRCAL_AMD_NO_SPL_COMPACT") != NULL);
-        const bool off = env_off || P->F.use_sweep;
-        const bool whole = (int)P->board_sel.size() == L.dims.Nobservations_board && P->comm == NULL;
-        if(!off && whole && L.lensmodel.type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC && cholesky_large_workspace_doubles(nd.Nc) > 1 && nd.Nc <= 4096 &&
-           P->D.Nobs_board > 0 && P->D.Nobs_point == 0 && P->D.Ndist_state > 0 && !nd.elim_extrinsics)
-        {
-            for(int i=0;i<2 && ok;i++)
-            {
-                // (until the first evaluation: the identity)
-                std::vector<int> id((size_t)2*nd.Nc + 1);
-                for(int c = 0; c < nd.Nc; c++) { id[c] = c; id[nd.Nc + c] = c; }
-                id[2*nd.Nc] = nd.Nc;
-                ok = ok && P->mem.upload(&P->op[i].cperm, id.data(), id.size());
-            }
-            // (a communicator turns the compaction off by taking this pointer away: the buffer stays the problem's)
-            ok = ok && P->mem.alloc(&P->F.cperm_cur, (size_t)2*nd.Nc + 2);
-            ok = ok && P->mem.alloc(&P->F.iso, (size_t)4*(nd.Nc/2 + 1) + nd.Nc + 2);
-            P->plan.spl_compact = 1;
-            // ... and in a nested-dissection order where the boards leave a strip worth having (cholesky_large.hip,
-            // lchol_nd_*): one camera's grid. MRCAL_AMD_NO_ND=1: off
-            static const bool nd_off = (getenv("MRCAL_AMD_NO_ND") != NULL);
-            if(!nd_off && P->D.Ncameras_intrinsics == 1)
-            {
-                const size_t Npos = (size_t)nd.Nc + 2*ND_PANEL;
-                const size_t W = LCH_ND_WMAX, wsz = (W/ND_PANEL)*ND_PANEL*ND_PANEL + W*W + W;
-                std::vector<int> h0(nd_plan_ints(nd.Nc), 0);
-                h0[NDH_NS] = nd.Nc; h0[NDH_NSEFF] = nd.Nc;
-                for(int i=0;i<2 && ok;i++) ok = ok && P->mem.upload(&P->op[i].ndp, h0.data(), h0.size());
-                ok = ok && P->mem.upload(&P->F.ndp_cur, h0.data(), h0.size());
-                ok = ok && P->mem.alloc(&P->F.ndMA, (Npos + 1)*Npos) && P->mem.alloc(&P->F.ndMB, (Npos + 1)*Npos);
-                ok = ok && P->mem.alloc(&P->F.ndLinvA, wsz) && P->mem.alloc(&P->F.ndLinvB, wsz);
-                ok = ok && P->mem.alloc(&P->F.ndPart, (size_t)((nd.Nc + 15)/16)*2*LCH_ND_WMAX);
-                ok = ok && P->mem.alloc_zeroed(&P->F.nd_lim_dev, 2);
-                P->F.nd_lim = NdLimits{0, 0}; P->F.nd_likely_panels = 0;
-                P->plan.nd_lim = P->F.nd_lim_dev;
-            }
-        }
-    }
-    // the rows of a splined problem that no plan covers: their three levels of pre-rounded sums (ReproStep), zero at rest
-    if(ok && splined_needs_repro_rows(P->D))
-    {
-        ReproStep& rs = P->plan.repro;
-        rs.one = (size_t)nd.Nc*nd.Nc + (size_t)nd.NE*nd.Nc + (size_t)nd.NEb*36 + (size_t)nd.Nstate + 1;
-        for(int l = 0; l < 3 && ok; l++) ok = ok && P->mem.alloc_zeroed(&rs.lvl[l], rs.one);
-        ok = ok && P->mem.alloc_zeroed(&rs.cmax, (size_t)nd.Nstate + 1);
-        ok = ok && P->mem.alloc_zeroed(&rs.any, 1);
-    }
-    {
-        char* ctl = NULL;
-        ok = ok && P->mem.alloc(&ctl, solver_ctl_bytes());
-        P->d_ctl = (SolverCtl*)ctl;
-    }
+    ok = ok && P->mem.alloc((char**)&P->d_ctl, solver_ctl_bytes());
     // (rows of blocks this shard does not own are never written: they must read as 0)
     ok = ok && P->mem.alloc_zeroed(&P->F.Wt, (size_t)nd.NE*nd.Nc);
     ok = ok && P->mem.alloc(&P->F.LD, (size_t)nd.NEb*36);
@@ -332,271 +108,159 @@ static bool allocate_solver_buffers(mrcal_amd_problem* P)
     // only the lower triangle of S is ever written; the rest rides along in the
     // all-reduce of [S | r] and should be numbers
     HIP_TRY(hipMemset(P->F.S, 0, ((size_t)nd.Nc*nd.Nc + 2*nd.Nc + 2)*sizeof(double)), return false);
-    if(!P->mem.alloc_pinned(&P->h_scalars, 64)) return false;
-    if(!problem_sync_ops(P)) return false;
+    return P->mem.alloc_pinned(&P->h_scalars, 64);
+}
 
-    // assembly work lists. Observations of one frame are contiguous; the
-    // observations of one (intrinsics,extrinsics) pair are gathered in chunks
+// The splined models' camera block without the control points no board covers (round 5; assembly_splined.hip,
+// spl_compact_kernel / LcholCompact): where the big camera block's launch-per-panel Cholesky runs, every row that
+// touches a control point is a board's (no discrete points: they have no boxes) and all rows are here (not a shard:
+// the ranks of a sharded solve sum their camera blocks entry by entry). MRCAL_AMD_NO_SPL_COMPACT=1: off
+static bool alloc_splined_compaction(mrcal_amd_problem* P)
+{
+    const Layout& L = P->L;
+    const NormalDims& nd = P->nd;
+    // (nor with the backward sweep, which knows nothing of a size the device decides)
+    P->F.use_sweep = test_hooks().lchol_sweep ? 1 : 0;
+    static const bool env_off = (getenv("MRCAL_AMD_NO_SPL_COMPACT") != NULL);
+    const bool off = env_off || P->F.use_sweep;
+    const bool whole = (int)P->board_sel.size() == L.dims.Nobservations_board && P->comm == NULL;
+    if(off || !whole || L.lensmodel.type != MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC || cholesky_large_workspace_doubles(nd.Nc) <= 1 || nd.Nc > 4096 ||
+       P->D.Nobs_board <= 0 || P->D.Nobs_point != 0 || P->D.Ndist_state <= 0 || nd.elim_extrinsics)
+        return true;
+    // (until the first evaluation: the identity)
+    std::vector<int> id((size_t)2*nd.Nc + 1);
+    for(int c = 0; c < nd.Nc; c++) { id[c] = c; id[nd.Nc + c] = c; }
+    id[2*nd.Nc] = nd.Nc;
+    bool ok = P->mem.upload(&P->op[0].cperm, id) && P->mem.upload(&P->op[1].cperm, id);
+    // (a communicator turns the compaction off by taking this pointer away: the buffer stays the problem's)
+    ok = ok && P->mem.alloc(&P->F.cperm_cur, (size_t)2*nd.Nc + 2);
+    ok = ok && P->mem.alloc(&P->F.iso, (size_t)4*(nd.Nc/2 + 1) + nd.Nc + 2);
+    P->plan.spl_compact = 1;
+    // ... and in a nested-dissection order where the boards leave a strip worth having (cholesky_large.hip,
+    // lchol_nd_*): one camera's grid. MRCAL_AMD_NO_ND=1: off
+    static const bool nd_off = (getenv("MRCAL_AMD_NO_ND") != NULL);
+    if(!nd_off && P->D.Ncameras_intrinsics == 1)
+    {
+        const size_t Npos = (size_t)nd.Nc + 2*ND_PANEL;
+        const size_t W = LCH_ND_WMAX, wsz = (W/ND_PANEL)*ND_PANEL*ND_PANEL + W*W + W;
+        std::vector<int> h0(nd_plan_ints(nd.Nc), 0);
+        h0[NDH_NS] = nd.Nc; h0[NDH_NSEFF] = nd.Nc;
+        ok = ok && P->mem.upload(&P->op[0].ndp, h0) && P->mem.upload(&P->op[1].ndp, h0) && P->mem.upload(&P->F.ndp_cur, h0);
+        ok = ok && P->mem.alloc(&P->F.ndMA, (Npos + 1)*Npos) && P->mem.alloc(&P->F.ndMB, (Npos + 1)*Npos);
+        ok = ok && P->mem.alloc(&P->F.ndLinvA, wsz) && P->mem.alloc(&P->F.ndLinvB, wsz);
+        ok = ok && P->mem.alloc(&P->F.ndPart, (size_t)((nd.Nc + 15)/16)*2*LCH_ND_WMAX);
+        ok = ok && P->mem.alloc_zeroed(&P->F.nd_lim_dev, 2);
+        P->F.nd_lim = NdLimits{0, 0}; P->F.nd_likely_panels = 0;
+        P->plan.nd_lim = P->F.nd_lim_dev;
+    }
+    return ok;
+}
+
+// the rows of a splined problem that no plan covers: their three levels of pre-rounded sums (ReproStep), zero at rest
+static bool alloc_repro_levels(mrcal_amd_problem* P)
+{
+    if(!splined_needs_repro_rows(P->D)) return true;
+    const NormalDims& nd = P->nd;
+    ReproStep& rs = P->plan.repro;
+    rs.one = (size_t)nd.Nc*nd.Nc + (size_t)nd.NE*nd.Nc + (size_t)nd.NEb*36 + (size_t)nd.Nstate + 1;
+    bool ok = true;
+    for(int l = 0; l < 3 && ok; l++) ok = ok && P->mem.alloc_zeroed(&rs.lvl[l], rs.one);
+    return ok && P->mem.alloc_zeroed(&rs.cmax, (size_t)nd.Nstate + 1) && P->mem.alloc_zeroed(&rs.any, 1);
+}
+
+// the lists the board observations' Grams are summed by (plan_board_grams()), and the partial sums' own buffers
+static bool upload_board_gram_plan(mrcal_amd_problem* P)
+{
+    const NormalDims& nd = P->nd;
+    DeviceBuffers& mem = P->mem;
+    AssemblyPlan& A = P->plan;
     const int Nobs = P->D.Nobs_board;
     std::vector<BoardObsMeta> meta(Nobs);
     if(Nobs > 0)
         HIP_TRY(hipMemcpy(meta.data(), P->d_board_meta, (size_t)Nobs*sizeof(BoardObsMeta), hipMemcpyDeviceToHost), return false);
-    // the eliminated pose of an observation (its frame; with elim_extrinsics its camera, which may be the
-    // reference: none then), and the one that stays in the camera block
-    const bool elimx = nd.elim_extrinsics != 0;
-    auto eblock_of = [&](const BoardObsMeta& m) -> int { return elimx ? m.icam_extrinsics : m.iframe; };
-    // (what a Gram position means is common to the observations with the same camera-block columns AND the same
-    //  columns present: the key of a "pair" carries whether there is an eliminated pose - a camera at the
-    //  reference has none)
-    auto spose_of  = [&](const BoardObsMeta& m) -> int { return 2*(elimx ? m.iframe : m.icam_extrinsics) + ((eblock_of(m) >= 0) ? 1 : 0); };
-    const int Neblocks_board = elimx ? P->D.Ncameras_extrinsics : L.dims.Nframes;
-    std::vector<int> frame_begin(Neblocks_board+1, 0);
-    for(int o=0;o<Nobs;o++) if(eblock_of(meta[o]) >= 0) frame_begin[eblock_of(meta[o])+1]++;
-    for(int f=0;f<Neblocks_board;f++) frame_begin[f+1] += frame_begin[f];
-    // sanity: contiguity
-    for(int o=1;o<Nobs;o++)
-        if(meta[o].iframe < meta[o-1].iframe)
-        {
-            set_error("board observations must be sorted by frame");
-            return false;
-        }
-    // (the observations of a frame are contiguous, those of a camera need not be: a list then)
-    std::vector<int> eblock_obs;
-    if(elimx)
-    {
-        std::vector<int> fill(frame_begin.begin(), frame_begin.end() - 1);
-        eblock_obs.assign(Nobs > 0 ? Nobs : 1, 0);
-        for(int o=0;o<Nobs;o++) if(eblock_of(meta[o]) >= 0) eblock_obs[fill[eblock_of(meta[o])]++] = o;
-    }
+    BoardGramPlan bp;
+    if(!plan_board_grams(P->D, nd, meta.data(), nd.elim_extrinsics ? P->D.Ncameras_extrinsics : P->L.dims.Nframes, &bp)) return false;
+    A.Nchunks = bp.Nchunks; A.Npairs = bp.Npairs; A.Ndest = (int)bp.dest.id.size();
+    bool ok = mem.upload(&A.frame_obs_begin, bp.frame_obs_begin) &&
+              (!nd.elim_extrinsics || mem.upload(&A.frame_obs, bp.frame_obs)) &&
+              mem.upload(&A.chunk_begin, bp.chunk_begin) && mem.upload(&A.pair_obs,   bp.pair_obs)   &&
+              mem.upload(&A.pos_table,   bp.pos_table)   && mem.upload(&A.pair_table, bp.pair_table) &&
+              mem.upload(&A.frame_pos,   bp.frame_pos)   && mem.upload(&A.obs_cols,   bp.obs_cols)   &&
+              mem.upload(&A.obs_pair,    bp.obs_pair)    && mem.upload(&A.chunk_pair, bp.chunk_pair) &&
+              mem.upload(&A.dest_id,     bp.dest.id)     && mem.upload(&A.dest_begin, bp.dest.begin) &&
+              mem.upload(&A.dest_src,    bp.dest.src)    && mem.upload(&A.pair_chunk_begin, bp.pair_chunk_begin);
+    if(P->D.lens_type != MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC)
+        return ok && mem.alloc(&A.chunk_part, (size_t)A.Nchunks*bp.pos_table.size());
+    if(Nobs == 0) return ok && mem.alloc(&A.chunk_part, 1);
+    // splined models: the staged Grams of assemble_splined_kernel (two passes per observation), the knot
+    // boxes, and the parts of the rows of the camera block that are not knots (+ the x row)
+    const int nknotrows = P->D.Nintr_state > 0 ? P->D.Ncameras_intrinsics*(P->D.Nintr_state - P->D.Ncore_state) : 0;
+    return ok && mem.alloc(&A.chunk_part, (size_t)2*Nobs*SPL_TRI) && mem.alloc(&A.spl_hdr, (size_t)Nobs) &&
+           mem.alloc(&A.spl_part, (size_t)(nd.Nc + 1 - nknotrows)*SPLG_E*(nd.Nc + 1));
+}
 
-    std::vector<int> order(Nobs);
-    for(int o=0;o<Nobs;o++) order[o] = o;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b)
-                     {
-                         if(meta[a].icam_intrinsics != meta[b].icam_intrinsics) return meta[a].icam_intrinsics < meta[b].icam_intrinsics;
-                         return spose_of(meta[a]) < spose_of(meta[b]);
-                     });
-    const int CHUNK = REDUCE_CHUNK;
-    std::vector<int> chunk_begin;
-    for(int i=0;i<Nobs;)
-    {
-        int j = i;
-        while(j < Nobs && j - i < CHUNK &&
-              meta[order[j]].icam_intrinsics == meta[order[i]].icam_intrinsics &&
-              spose_of(meta[order[j]]) == spose_of(meta[order[i]])) j++;
-        chunk_begin.push_back(i);
-        i = j;
-    }
-    chunk_begin.push_back(Nobs);
-    P->plan.Nchunks = (int)chunk_begin.size() - 1;
-    ok = ok && P->mem.upload(&P->plan.frame_obs_begin, frame_begin.data(), frame_begin.size());
-    if(elimx) ok = ok && P->mem.upload(&P->plan.frame_obs, eblock_obs.data(), eblock_obs.size());
-    ok = ok && P->mem.upload(&P->plan.chunk_begin,     chunk_begin.data(), chunk_begin.size());
-    ok = ok && P->mem.upload(&P->plan.pair_obs,        order.data(),       order.size());
-    {
-        // the (intrinsics, extrinsics) pairs, in the order of `order`
-        std::vector<int> obs_pair(Nobs > 0 ? Nobs : 1, 0), pair_rep;
-        for(int k=0;k<Nobs;k++)
-        {
-            const int o = order[k];
-            if(k == 0 || meta[o].icam_intrinsics != meta[order[k-1]].icam_intrinsics ||
-                         spose_of(meta[o]) != spose_of(meta[order[k-1]]))
-                pair_rep.push_back(o);
-            obs_pair[o] = (int)pair_rep.size() - 1;
-        }
-        std::vector<int> chunk_pair(P->plan.Nchunks > 0 ? P->plan.Nchunks : 1, 0);
-        for(int c=0;c<P->plan.Nchunks;c++) chunk_pair[c] = obs_pair[order[chunk_begin[c]]];
-        P->plan.Npairs = (int)pair_rep.size();
+// The fixed-order plan of the point and pair rows (plan_gen_rows()), from the CSR structure itself, which does not
+// change between evaluations (except the splined models' patch columns: no plan then, those rows keep the atomics)
+static bool upload_gen_rows_plan(mrcal_amd_problem* P)
+{
+    GenPlan& G = P->plan.gen;
+    memset(&G, 0, sizeof(G));
+    const Layout& L = P->L;
+    DeviceBuffers& mem = P->mem;
+    const int r0 = L.i_meas_points, r1 = L.i_meas_regularization;
+    G.row_first = r0; G.row_end = r1;
+    if(r1 <= r0) return true;
+    if(L.lensmodel.type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC && L.Nmeas_points > 0 && L.Ndist_state > 0) return true;
+    std::vector<int32_t> Jp((size_t)(r1 - r0) + 1);
+    HIP_TRY(hipMemcpy(Jp.data(), P->d_Jp + r0, Jp.size()*sizeof(int32_t), hipMemcpyDeviceToHost), return false);
+    const int32_t p0 = Jp[0], p1 = Jp[r1 - r0];
+    std::vector<int32_t> Ji((size_t)(p1 - p0));
+    if(p1 > p0) HIP_TRY(hipMemcpy(Ji.data(), P->d_Ji + p0, Ji.size()*sizeof(int32_t), hipMemcpyDeviceToHost), return false);
+    const GenRowsPlan gp = plan_gen_rows(P->nd, r0, r1, Jp.data(), Ji.data());
+    if(gp.Nrows == 0) return true;
+    if(!(mem.upload(&G.rows,        gp.rows)        && mem.upload(&G.chunk_begin, gp.chunk_begin) &&
+         mem.upload(&G.chunk_group, gp.chunk_group) && mem.upload(&G.group_k,     gp.group_k)     &&
+         mem.upload(&G.group_off,   gp.group_off)   && mem.upload(&G.spos,        gp.spos)        &&
+         mem.upload(&G.scol,        gp.scol)        && mem.upload(&G.dest_id,     gp.dest.id)     &&
+         mem.upload(&G.dest_begin,  gp.dest.begin)  && mem.upload(&G.dest_src,    gp.dest.src)    &&
+         mem.upload(&G.group_chunk_begin, gp.group_chunk_begin) &&
+         mem.upload(&G.eb_block,    gp.eb_block)    && mem.upload(&G.eb_begin,    gp.eb_begin)    &&
+         mem.upload(&G.eb_rows,     gp.eb_rows)     && mem.upload(&G.eb_group,    gp.eb_group)    &&
+         mem.upload(&G.eb_epos,     gp.eb_epos)     && mem.alloc(&G.part, (size_t)gp.Nchunks*gp.stride)))
+        return false;
+    G.Nrows = gp.Nrows; G.Nchunks = gp.Nchunks; G.Ngroups = gp.Ngroups; G.stride = gp.stride; G.kmax = gp.kmax;
+    G.Ndest = (int)gp.dest.id.size(); G.Neblocks = (int)gp.eb_block.size();
+    return true;
+}
 
-        const int nblk = tile_nblk(L.Ndist), npos = gram_stride(L.Ndist);
-        std::vector<int>    tab(npos, 0);
-        std::vector<PairOp> ptab((size_t)(pair_rep.empty() ? 1 : pair_rep.size())*npos, PairOp{PAIROP_NONE, 0});
-        for(int pos = 0; pos < npos; pos++)
-        {
-            int i, j; bool diag;
-            if(!gram_pos_to_entry(nblk, pos, &i, &j, &diag)) continue;
-            tab[pos] = (int)(0x80000000u | (diag ? 0x10000u : 0u) | ((unsigned)i << 8) | (unsigned)j);
-            for(size_t ip = 0; ip < pair_rep.size(); ip++)
-            {
-                const BoardObsMeta& m = meta[pair_rep[ip]];
-                const TileColInfo ci = board_tile_col_info(P->D, m, i), cj = board_tile_col_info(P->D, m, j);
-                PairOp op = { PAIROP_NONE, 0 };
-                const bool fi = ci.kind == COL_FRAME, fj = cj.kind == COL_FRAME;
-                const bool si = ci.kind == COL_S,     sj = cj.kind == COL_S;
-                const bool xi = ci.kind == COL_X,     xj = cj.kind == COL_X;
-                if(fi && fj)
-                    op = PairOp{ PAIROP_D | (diag ? 0 : PAIROP_MIRROR), ci.idx | (cj.idx << 16) };
-                else if(fi)
-                {
-                    // (frame, S) or (frame, x). In a diagonal block the mirrored
-                    // position carries the same product: it is taken there only
-                    if(!diag && sj)      op = PairOp{ PAIROP_BT, ci.idx | (state_to_SE(nd, cj.idx) << 16) };
-                    else if(!diag && xj) op = PairOp{ PAIROP_GF, ci.idx };
-                }
-                else if(fj)
-                {
-                    if(si)      op = PairOp{ PAIROP_BT, cj.idx | (state_to_SE(nd, ci.idx) << 16) };
-                    else if(xi) op = PairOp{ PAIROP_GF, cj.idx };
-                }
-                else if((si || xi) && (sj || xj) && !(diag && xi && sj))
-                {
-                    if(xi && xj)   op = PairOp{ PAIROP_NORM, 0 };
-                    else if(xj)    op = PairOp{ PAIROP_G, ci.idx };
-                    else if(xi)    op = PairOp{ PAIROP_G, cj.idx };
-                    else           op = PairOp{ PAIROP_A | (diag ? 0 : PAIROP_MIRROR),
-                                                state_to_SE(nd, ci.idx) | (state_to_SE(nd, cj.idx) << 16) };
-                }
-                ptab[ip*npos + pos] = op;
-                const int k = op.op & 0xff;
-                if(k == PAIROP_D || k == PAIROP_BT || k == PAIROP_GF) tab[pos] |= 0x20000;
-            }
-        }
-        ok = ok && P->mem.upload(&P->plan.pos_table,  tab.data(),        tab.size());
-        ok = ok && P->mem.upload(&P->plan.pair_table, ptab.data(),       ptab.size());
-        {
-            // the frame part, per position and per observation (AssemblyPlan::frame_pos). Derived from the table
-            // above and checked against it: every pair's operation at every position must come back out
-            const int nintr = (P->D.Nintr_state > 0) ? P->D.Ncameras_intrinsics*P->D.Nintr_state : 0;
-            std::vector<int> fpos(npos, FRAMEPOS_NONE);
-            std::vector<int> pair_cols(2*(pair_rep.empty() ? 1 : pair_rep.size()), -1);
-            auto classify = [&](const PairOp& op, int* kind, int* a, int* k, int* base) -> void
-            {
-                *kind = FRAMEPOS_NONE; *a = 0; *k = 0; *base = -1;
-                const int b = op.aux >> 16;
-                switch(op.op & 0xff)
-                {
-                case PAIROP_D:  *kind = (op.op & PAIROP_MIRROR) ? FRAMEPOS_D_MIRROR : FRAMEPOS_D; *a = op.aux & 0xffff; *k = b; break;
-                case PAIROP_GF: *kind = FRAMEPOS_GF; *a = op.aux & 0xffff; break;
-                case PAIROP_BT:
-                    *a = op.aux & 0xffff;
-                    if(b < nintr)        { *kind = FRAMEPOS_BT_INTRINSICS; *base = (b/P->D.Nintr_state)*P->D.Nintr_state; *k = b - *base; }
-                    else if(b < nd.Nc - nd.Nwarp) { *kind = FRAMEPOS_BT_EXTRINSICS; *base = nintr + ((b - nintr)/6)*6;     *k = b - *base; }
-                    else                 { *kind = FRAMEPOS_BT_WARP; *k = b; }
-                    break;
-                default: break;
-                }
-            };
-            bool consistent = true;
-            for(size_t ip = 0; ip < pair_rep.size(); ip++)
-                for(int pos = 0; pos < npos; pos++)
-                {
-                    int kind, a, k, base;
-                    classify(ptab[ip*npos + pos], &kind, &a, &k, &base);
-                    if(kind == FRAMEPOS_NONE) continue;
-                    const int code = kind | (a << 3) | (k << 6);
-                    if(fpos[pos] == FRAMEPOS_NONE) fpos[pos] = code;
-                    else if(fpos[pos] != code) consistent = false;
-                    if(kind == FRAMEPOS_BT_INTRINSICS || kind == FRAMEPOS_BT_EXTRINSICS)
-                    {
-                        int& c = pair_cols[2*ip + (kind == FRAMEPOS_BT_EXTRINSICS ? 1 : 0)];
-                        if(c < 0) c = base; else if(c != base) consistent = false;
-                    }
-                }
-            // ... and back: a pair without a block (the camera at the reference has no extrinsics) has nothing
-            // at that block's positions, and every other position reads the same through both tables
-            for(size_t ip = 0; ip < pair_rep.size() && consistent; ip++)
-                for(int pos = 0; pos < npos; pos++)
-                {
-                    // (observations without an eliminated pose - a camera at the reference, with elim_extrinsics -
-                    //  are in no block's list: what the frame part's tables say about them is never looked at)
-                    if(eblock_of(meta[pair_rep[ip]]) < 0) break;
-                    int kind, a, k, base;
-                    classify(ptab[ip*npos + pos], &kind, &a, &k, &base);
-                    const int fk = fpos[pos] & 7;
-                    const bool absent = (fk == FRAMEPOS_BT_INTRINSICS && pair_cols[2*ip] < 0) || (fk == FRAMEPOS_BT_EXTRINSICS && pair_cols[2*ip+1] < 0);
-                    if(kind == FRAMEPOS_NONE ? !(fk == FRAMEPOS_NONE || absent) : absent) consistent = false;
-                }
-            // (the splined models assemble from staged rows, not from Grams: no use for these tables)
-            const bool uses_grams = P->D.lens_type != MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC;
-            if(!consistent && uses_grams) { set_error("internal: the Gram positions of the frame part depend on the camera pair"); return false; }
-            std::vector<int> obs_cols(2*(Nobs > 0 ? Nobs : 1), -1);
-            for(int o = 0; o < Nobs; o++) { obs_cols[2*o] = pair_cols[2*obs_pair[o]]; obs_cols[2*o+1] = pair_cols[2*obs_pair[o]+1]; }
-            ok = ok && P->mem.upload(&P->plan.frame_pos, fpos.data(),     fpos.size());
-            ok = ok && P->mem.upload(&P->plan.obs_cols,  obs_cols.data(), obs_cols.size());
-        }
-        ok = ok && P->mem.upload(&P->plan.obs_pair,   obs_pair.data(),   obs_pair.size());
-        ok = ok && P->mem.upload(&P->plan.chunk_pair, chunk_pair.data(), chunk_pair.size());
+// the per-workgroup partial sums of the step's reductions
+static bool alloc_step_partials(mrcal_amd_problem* P)
+{
+    const NormalDims& nd = P->nd;
+    AssemblyPlan& A = P->plan;
+    const int Nobs = P->D.Nobs_board;
+    // (with the plan above, the row-by-row workgroups of the assembly take the regularization rows only)
+    const int row0 = (A.gen.Nrows > 0) ? P->L.i_meas_regularization : 2*P->D.W*P->D.H*Nobs;
+    A.row_part_n = (Nobs > 0 && P->L.Nmeas > row0) ? (P->L.Nmeas - row0 + 255)/256 : 0;
+    A.qf_part_n  = (nd.Nc + nd.NE + 4*QF_ROWS_PER_WAVE - 1)/(4*QF_ROWS_PER_WAVE);
+    return P->mem.alloc(&A.row_part, (size_t)A.row_part_n) && P->mem.alloc(&A.qf_part, (size_t)4*A.qf_part_n) &&
+           P->mem.alloc(&A.dots_part, (size_t)2*nd.NEb);
+}
 
-        // The fixed-order reduction of the camera-block part (solver_kernels.hpp):
-        // for every destination - entry of A, of g (S part), |x|^2 - the (pair,
-        // position) sources that add to it, in (pair, position) order
-        // (the splined models have no Grams: nothing is reduced this way)
-        const bool with_grams = (L.lensmodel.type != MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC);
-        const int Npairs = with_grams ? (int)pair_rep.size() : 0;
-        if(with_grams && npos > 1024)
-        {
-            set_error("internal error: %d Gram positions per observation", npos);
-            return false;
-        }
-        std::vector<int> pair_chunk_begin(Npairs + 1, 0);
-        for(int c=0;c<P->plan.Nchunks && Npairs > 0;c++) pair_chunk_begin[chunk_pair[c] + 1]++;
-        for(int ip=0;ip<Npairs;ip++) pair_chunk_begin[ip+1] += pair_chunk_begin[ip];
-        const int nA = nd.Nc*nd.Nc, Ndest_all = nA + nd.Nc + 1;
-        std::vector<std::vector<int>> src(Npairs > 0 ? Ndest_all : 0);
-        for(int ip = 0; ip < Npairs; ip++)
-            for(int pos = 0; pos < npos; pos++)
-            {
-                const PairOp op = ptab[(size_t)ip*npos + pos];
-                const int k = op.op & 0xff, code = (ip << 10) | pos;
-                if(k == PAIROP_NORM) src[nA + nd.Nc].push_back(code);
-                else if(k == PAIROP_G)
-                {
-                    const int sc = state_to_SE(nd, op.aux);     // a camera-block variable: S index >= 0
-                    if(sc >= 0) src[nA + sc].push_back(code);
-                }
-                else if(k == PAIROP_A)
-                {
-                    const int a = op.aux & 0xffff, b = op.aux >> 16;
-                    src[a*nd.Nc + b].push_back(code);
-                    if(op.op & PAIROP_MIRROR) src[b*nd.Nc + a].push_back(code);
-                }
-            }
-        std::vector<int> dest_id, dest_begin(1, 0), dest_src;
-        for(int d = 0; d < (int)src.size(); d++)
-        {
-            // |x|^2 is always a destination when there are rows outside the Grams (their partials are added there)
-            if(src[d].empty() && d != nA + nd.Nc) continue;
-            dest_id.push_back(d);
-            dest_src.insert(dest_src.end(), src[d].begin(), src[d].end());
-            dest_begin.push_back((int)dest_src.size());
-        }
-        P->plan.Ndest = (int)dest_id.size();
-        if(dest_id.empty())  dest_id.push_back(0);
-        if(dest_src.empty()) dest_src.push_back(0);
-        ok = ok && P->mem.upload(&P->plan.dest_id,          dest_id.data(),          dest_id.size());
-        ok = ok && P->mem.upload(&P->plan.dest_begin,       dest_begin.data(),       dest_begin.size());
-        ok = ok && P->mem.upload(&P->plan.dest_src,         dest_src.data(),         dest_src.size());
-        ok = ok && P->mem.upload(&P->plan.pair_chunk_begin, pair_chunk_begin.data(), pair_chunk_begin.size());
-        if(with_grams || Nobs == 0)
-            ok = ok && P->mem.alloc(&P->plan.chunk_part, with_grams ? (size_t)(P->plan.Nchunks > 0 ? P->plan.Nchunks : 1)*npos : (size_t)1);
-        else
-        {
-            // splined models: the staged Grams of assemble_splined_kernel (two passes per observation), the knot
-            // boxes, and the parts of the rows of the camera block that are not knots (+ the x row)
-            const int nknotrows = P->D.Nintr_state > 0 ? P->D.Ncameras_intrinsics*(P->D.Nintr_state - P->D.Ncore_state) : 0;
-            ok = ok && P->mem.alloc(&P->plan.chunk_part,    (size_t)2*Nobs*SPL_TRI);
-            ok = ok && P->mem.alloc(&P->plan.spl_hdr,       (size_t)Nobs);
-            ok = ok && P->mem.alloc(&P->plan.spl_part,   (size_t)(nd.Nc + 1 - nknotrows)*SPLG_E*(nd.Nc + 1));
-        }
-        ok = ok && build_gen_plan(P);
-        {
-            // (with the plan above, the row-by-row workgroups of the assembly take the regularization rows only)
-            const int row0 = (P->plan.gen.Nrows > 0) ? L.i_meas_regularization : 2*P->D.W*P->D.H*Nobs;
-            P->plan.row_part_n = (Nobs > 0 && L.Nmeas > row0) ? (L.Nmeas - row0 + 255)/256 : 0;
-            ok = ok && P->mem.alloc(&P->plan.row_part, (size_t)(P->plan.row_part_n > 0 ? P->plan.row_part_n : 1));
-            P->plan.qf_part_n = (nd.Nc + nd.NE + 4*QF_ROWS_PER_WAVE - 1)/(4*QF_ROWS_PER_WAVE);
-            ok = ok && P->mem.alloc(&P->plan.qf_part, (size_t)4*(P->plan.qf_part_n > 0 ? P->plan.qf_part_n : 1));
-            ok = ok && P->mem.alloc(&P->plan.dots_part, (size_t)2*(nd.NEb > 0 ? nd.NEb : 1));
-        }
-    }
-    // (the second, third and fourth sub-boxes of the splined models' close-ups, which mostly nobody touches: last)
-    if(P->plan.spl_hdr != NULL)
-    {
-        const size_t Nobs = (size_t)(P->D.Nobs_board > 0 ? P->D.Nobs_board : 1);
-        ok = ok && P->mem.alloc(&P->plan.chunk_extra,   (size_t)2*Nobs*(SPL_MAXSUB - 1)*SPL_TRI);
-        ok = ok && P->mem.alloc(&P->plan.spl_hdr_extra, Nobs*(SPL_MAXSUB - 1));
-    }
-    return ok;
+// (the second, third and fourth sub-boxes of the splined models' close-ups, which mostly nobody touches: last)
+static bool alloc_splined_closeups(mrcal_amd_problem* P)
+{
+    if(P->plan.spl_hdr == NULL) return true;
+    const size_t Nobs = (size_t)P->D.Nobs_board;
+    return P->mem.alloc(&P->plan.chunk_extra,   (size_t)2*Nobs*(SPL_MAXSUB - 1)*SPL_TRI) &&
+           P->mem.alloc(&P->plan.spl_hdr_extra, Nobs*(SPL_MAXSUB - 1));
+}
+
+static bool allocate_solver_buffers(mrcal_amd_problem* P)
+{
+    return alloc_normal_equations(P) && alloc_factor_scratch(P) && alloc_splined_compaction(P) && alloc_repro_levels(P) &&
+           problem_sync_ops(P) &&
+           upload_board_gram_plan(P) && upload_gen_rows_plan(P) && alloc_step_partials(P) && alloc_splined_closeups(P);
 }
 
 // A preparation that failed stays failed: what it had allocated by then is the problem's until the problem goes, and
