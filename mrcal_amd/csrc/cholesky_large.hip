@@ -1164,16 +1164,19 @@ extern "C" void mrcal_amd_debug_lchol_plan(int n, int l, int with_inverse, int o
 namespace mrcal_amd {
 // the workspace behind FactorBuffers::Linv: [npanels][64][64] inverse diagonal blocks | Yb [npad][npad] | zc [npad]
 static inline size_t lchol_npad(int n) { return (size_t)((n + LCH_NB - 1)/LCH_NB)*LCH_NB; }
-// sd (optional): the trial step this factorization belongs to - its end-of-trial logic rides in the first launch and
-// the verdict in the last (no step2_finish_kernel / step2_post_kernel around the call). *fused says whether that happened
-// (not with the backward sweep of MRCAL_AMD_LCHOL_SWEEP, whose last launch is another).
-// n_dev (optional, round 5): the size of the matrix as the DEVICE knows it, <= n (LcholCompact: the camera block without
-// its isolated variables, whose number follows the boards). The launches and their grids are those of n; a launch past
-// the device's last panel finds nothing to do
-// nds (round 5): the dissection's chains in front (lchol_nd_*): M is then the separator's matrix, the first launches are
+// launch_cholesky_large(), by the route (camblock_route.hpp):
+// sd (optional): the trial step this factorization belongs to - its end-of-trial logic rides in the first launch (unless
+// route.finish_rides: it has run already, in the reduction's launch, and the first launch goes by `skip`) and the verdict
+// in the last (no step2_finish_kernel / step2_post_kernel around the call). Not with the backward sweep, whose last
+// launch is another: the caller launches those two.
+// route.compact (round 5): the size of the matrix as the DEVICE knows it, <= n (LcholCompact: the camera block without
+// its isolated variables, whose number follows the boards), behind the permutation; lchol_tail_kernel's barrier behind
+// that. The launches and their grids are those of n; a launch past the device's last panel finds nothing to do.
+// Launches 0 .. route.l_last go one by one, the rest (route.with_tail) in lchol_tail_kernel
+// route.nd_launches (round 5): the dissection's chains in front (lchol_nd_*): M is then the separator's matrix, whose size
+// is the plan's; the first launches are
 // lchol_nd_first_kernel, R of lchol_nd_pair_kernel and lchol_nd_junction_kernel (in lchol_diag_kernel's place), the last
-// lchol_nd_apply_kernel; the end-of-trial logic has run already (it rides in the reduction: step2_reduce_kernel), the
-// verdict rides in lchol_apply_inverse_kernel as ever
+// lchol_nd_apply_kernel; the verdict rides in lchol_apply_inverse_kernel as ever
 // lchol_tail_kernel's workgroups wait for each other (lchol_grid_barrier): every one of them must be RESIDENT at once.
 // LCH_TAIL_WGS of them (any number gives the same bits: they share the blocks of a panel round-robin), but never more than
 // the device holds of this kernel - a partitioned or CU-masked GPU with fewer than 96 free CUs would otherwise leave the
@@ -1193,24 +1196,21 @@ static int lchol_tail_grid()
     }();
     return grid;
 }
-hipError_t launch_cholesky_large(int n, const int* skip, double* M, double* Linv, int* status, hipStream_t stream,
-                                 const Step2Dev* sd, bool* fused, const int* n_dev, const LcholCompact* compact,
-                                 int likely_panels /* with n_dev: launches 0 .. likely_panels one by one, the rest in lchol_tail_kernel; 0: all one by one */,
-                                 unsigned* tail_counter, const LcholNdLaunch* nds,
-                                 bool finish_done /* with sd: the end-of-trial logic has run already (the first launch goes by `skip`); the verdict still rides in the last */,
-                                 bool sweep /* the solve by the backward sweep in groups of panels (rounds 2-3; backward stable) instead of through
-                                                       L^-1 built on the side (lchol_inverse_block): FactorBuffers::use_sweep */,
-                                 LcholDiagSpread diag_minmax)
+hipError_t launch_cholesky_large(const LcholLaunch& c, hipStream_t stream)
 {
-    const int npanels = (n + LCH_NB - 1)/LCH_NB;
-    if(sweep && (n_dev != NULL || compact != NULL)) return hipErrorInvalidValue;
+    const CamBlockRoute& route = c.route;
+    const int  n = c.n, npanels = (n + LCH_NB - 1)/LCH_NB;
+    const int* skip = c.skip; double* M = c.M; double* Linv = c.Linv; int* status = c.status;
+    const bool sweep = route.sweep, fuse = (c.sd != NULL && !sweep);
+    const LcholCompact*  compact = route.compact ? &c.compact : NULL;
+    const LcholNdLaunch* nds     = route.nd_launches ? &c.nds : NULL;
+    const int* n_dev        = compact ? (nds ? nds->ndh + NDH_NSEFF : compact->cperm + 2*n) : NULL;
+    unsigned*  tail_counter = compact ? (unsigned*)(compact->cperm + 2*n + 1) : NULL;
+    const LcholDiagSpread diag_minmax = c.diag_minmax;
     Step2Dev sd0; memset(&sd0, 0, sizeof(sd0));
     LcholCompact cp0; memset(&cp0, 0, sizeof(cp0));
-    const bool fuse = (sd != NULL && !sweep);
-    if(fused != NULL) *fused = fuse;
     if(nds != NULL)
     {
-        if(sweep || !fuse || !finish_done || n_dev == NULL || compact == NULL) return hipErrorInvalidValue;
         const int R = nds->lim.rounds, Nprov = LCH_NB*R + nds->lim.ns_max;
         hipLaunchKernelGGL(lchol_nd_first_kernel, dim3(2), dim3(LCH_THREADS), 0, stream, nds->A, nds->B, nds->ndh, skip, status);
         for(int l = 0; l < R; l++)
@@ -1229,10 +1229,10 @@ hipError_t launch_cholesky_large(int n, const int* skip, double* M, double* Linv
     }
     else
     hipLaunchKernelGGL(lchol_diag_kernel, dim3(1), dim3(LCH_THREADS), 0, stream, n_dev, n, skip, M, 0, Linv, status,
-                       (fuse && !finish_done) ? 1 : 0, fuse ? *sd : sd0, compact ? compact->iso : (const double*)NULL, compact ? compact->Nc : 0,
-                       (n_dev != NULL) ? tail_counter : (unsigned*)NULL);
-    const bool with_tail = n_dev != NULL && tail_counter != NULL && likely_panels > 0 && likely_panels < npanels && !sweep;
-    const int  l_last = with_tail ? likely_panels : npanels;
+                       (fuse && !route.finish_rides) ? 1 : 0, fuse ? *c.sd : sd0, compact ? compact->iso : (const double*)NULL, compact ? compact->Nc : 0,
+                       tail_counter);
+    const bool with_tail = route.with_tail;
+    const int  l_last = route.l_last;
     for(int l = 0; l <= l_last; l++)
     {
         const LcholPlan q = lchol_plan(n, l, !sweep);
@@ -1250,7 +1250,7 @@ hipError_t launch_cholesky_large(int n, const int* skip, double* M, double* Linv
     {
         const int niso_blocks = (compact != NULL) ? (n/2 + 1 + 255)/256 : 0;
         hipLaunchKernelGGL(lchol_apply_inverse_kernel, dim3((n + LCH_AI_COLS - 1)/LCH_AI_COLS + niso_blocks), dim3(256), 0, stream,
-                           n_dev, n, skip, M, (const double*)Linv, fuse ? 1 : 0, fuse ? *sd : sd0, status, compact ? *compact : cp0, diag_minmax);
+                           n_dev, n, skip, M, (const double*)Linv, fuse ? 1 : 0, fuse ? *c.sd : sd0, status, compact ? *compact : cp0, diag_minmax);
         if(nds != NULL)
         {
             const int ncb = LCH_NB*nds->lim.rounds/LCH_AI_COLS;

@@ -114,15 +114,14 @@ static bool alloc_factor_scratch(mrcal_amd_problem* P)
 // The splined models' camera block without the control points no board covers (round 5; assembly_splined.hip,
 // spl_compact_kernel / LcholCompact): where the big camera block's launch-per-panel Cholesky runs, every row that
 // touches a control point is a board's (no discrete points: they have no boxes) and all rows are here (not a shard:
-// the ranks of a sharded solve sum their camera blocks entry by entry). MRCAL_AMD_NO_SPL_COMPACT=1: off
-static bool alloc_splined_compaction(mrcal_amd_problem* P)
+// the ranks of a sharded solve sum their camera blocks entry by entry; nor with the backward sweep, which knows nothing
+// of a size the device decides). MRCAL_AMD_NO_SPL_COMPACT=1: off. Only allocates: what is in use is the mode's to say
+static bool alloc_splined_compaction(mrcal_amd_problem* P, bool sweep)
 {
     const Layout& L = P->L;
     const NormalDims& nd = P->nd;
-    // (nor with the backward sweep, which knows nothing of a size the device decides)
-    P->F.use_sweep = test_hooks().lchol_sweep ? 1 : 0;
     static const bool env_off = (getenv("MRCAL_AMD_NO_SPL_COMPACT") != NULL);
-    const bool off = env_off || P->F.use_sweep;
+    const bool off = env_off || sweep;
     const bool whole = (int)P->board_sel.size() == L.dims.Nobservations_board && P->comm == NULL;
     if(off || !whole || L.lensmodel.type != MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC || cholesky_large_workspace_doubles(nd.Nc) <= 1 || nd.Nc > 4096 ||
        P->D.Nobs_board <= 0 || P->D.Nobs_point != 0 || P->D.Ndist_state <= 0 || nd.elim_extrinsics)
@@ -132,10 +131,8 @@ static bool alloc_splined_compaction(mrcal_amd_problem* P)
     for(int c = 0; c < nd.Nc; c++) { id[c] = c; id[nd.Nc + c] = c; }
     id[2*nd.Nc] = nd.Nc;
     bool ok = P->mem.upload(&P->op[0].cperm, id) && P->mem.upload(&P->op[1].cperm, id);
-    // (a communicator turns the compaction off by taking this pointer away: the buffer stays the problem's)
     ok = ok && P->mem.alloc(&P->F.cperm_cur, (size_t)2*nd.Nc + 2);
     ok = ok && P->mem.alloc(&P->F.iso, (size_t)4*(nd.Nc/2 + 1) + nd.Nc + 2);
-    P->plan.spl_compact = 1;
     // ... and in a nested-dissection order where the boards leave a strip worth having (cholesky_large.hip,
     // lchol_nd_*): one camera's grid. MRCAL_AMD_NO_ND=1: off
     static const bool nd_off = (getenv("MRCAL_AMD_NO_ND") != NULL);
@@ -151,7 +148,6 @@ static bool alloc_splined_compaction(mrcal_amd_problem* P)
         ok = ok && P->mem.alloc(&P->F.ndPart, (size_t)((nd.Nc + 15)/16)*2*LCH_ND_WMAX);
         ok = ok && P->mem.alloc_zeroed(&P->F.nd_lim_dev, 2);
         P->F.nd_lim = NdLimits{0, 0}; P->F.nd_likely_panels = 0;
-        P->plan.nd_lim = P->F.nd_lim_dev;
     }
     return ok;
 }
@@ -256,9 +252,23 @@ static bool alloc_splined_closeups(mrcal_amd_problem* P)
            P->mem.alloc(&P->plan.spl_hdr_extra, Nobs*(SPL_MAXSUB - 1));
 }
 
+// The one place that says what of the camera block's compaction is in use, on the host (FactorBuffers::mode, which
+// camblock_route() goes by) and for the evaluation's kernels (AssemblyPlan, passed by value)
+void problem_set_camblock_mode(mrcal_amd_problem* P, const CamBlockMode& mode)
+{
+    P->F.mode = mode;
+    P->plan.spl_compact = mode.compact ? 1 : 0;
+    P->plan.nd_lim      = mode.dissect ? P->F.nd_lim_dev : NULL;
+}
+
 static bool allocate_solver_buffers(mrcal_amd_problem* P)
 {
-    return alloc_normal_equations(P) && alloc_factor_scratch(P) && alloc_splined_compaction(P) && alloc_repro_levels(P) &&
+    // (the tests' hook: the backward sweep from the start)
+    const bool sweep = test_hooks().lchol_sweep != 0;
+    if(!(alloc_normal_equations(P) && alloc_factor_scratch(P) && alloc_splined_compaction(P, sweep))) return false;
+    // what was allocated is in use, until a communicator, the fallback to the sweep or error 3 say otherwise (solver.cpp)
+    problem_set_camblock_mode(P, CamBlockMode{ P->F.cperm_cur != NULL, P->F.ndMA != NULL, sweep });
+    return alloc_repro_levels(P) &&
            problem_sync_ops(P) &&
            upload_board_gram_plan(P) && upload_gen_rows_plan(P) && alloc_step_partials(P) && alloc_splined_closeups(P);
 }

@@ -152,6 +152,8 @@ bool problem_ensure_jacobian(mrcal_amd_problem* P);
 bool problem_evaluate_ref(mrcal_amd_problem* P, const mrcal_amd::OpRef& R, bool with_jacobian, bool with_normal,
                           int parts = mrcal_amd::EVAL_PART_ALL, hipStream_t stream = NULL /* default: the problem's */,
                           const mrcal_amd::ChooseArgs* choose = NULL /* the prologue launch also chooses the trial point */);
+// sets FactorBuffers::mode and what of AssemblyPlan follows from it
+void problem_set_camblock_mode(mrcal_amd_problem* P, const mrcal_amd::CamBlockMode& mode);
 // uploads op[0..1] to d_ops
 bool problem_sync_ops(mrcal_amd_problem* P);
 }

@@ -97,9 +97,9 @@ bool ctl_reset(mrcal_amd_problem* P, const DoglegParameters& prm, bool check_ter
 }
 
 // The arguments of the fused step's launchers and the step's layout: decided here, once per queued step
-Step2Args step2_args(mrcal_amd_problem* P, bool initial)
+bool step2_args(mrcal_amd_problem* P, bool initial, Step2Args* out)
 {
-    Step2Args a;
+    Step2Args& a = *out;
     a.P = &P->D; a.nd = &P->nd; a.br = &P->br; a.plan = &P->plan;
     a.ops = P->d_ops; a.ctl = P->d_ctl; a.F = &P->F; a.gram = P->d_gram;
     a.Jp = P->d_Jp; a.Ji = P->d_Ji; a.step = P->d_step; a.is_leader = P->is_leader;
@@ -108,18 +108,10 @@ Step2Args step2_args(mrcal_amd_problem* P, bool initial)
     a.side = P->side_stream; a.ev_fork = P->ev_fork; a.ev_join = P->ev_join;
     a.initial    = initial;
     a.with_grams = problem_has_grams(P->D);
-    // Does the end-of-trial logic (step2_finish) ride in the reduction's launch (round 5)? On a single GPU the tail it
-    // reads - g_S, |x|^2, the block elimination's status - is complete when the reduction's last workgroup has written it,
-    // and that workgroup can decide the trial there and then, beside the others: the factorization's first launch starts
-    // on its matrix at once (and may be several workgroups: the dissection's). Sharded, the tail is summed over the ranks
-    // behind that launch. (With the backward sweep - FactorBuffers::use_sweep - the end-of-trial logic and the verdict are
-    // launches of their own.)
-    a.finish_rides = a.comm2 == NULL && !P->F.use_sweep;
-    // (where the host has provided for the dissection's launches - learn_likely_size() -, the reduction fills the
-    //  dissection's matrices with more workgroups, and the factorization goes through those launches)
-    a.nd_launches  = a.finish_rides && P->F.ndMA != NULL && P->F.cperm_cur != NULL && P->F.nd_lim.rounds > 0;
-    a.S_packed     = a.finish_rides && step2_chol_in_lds(P->nd);
-    return a;
+    if(camblock_route(&a.route, P->nd.Nc, a.comm2 != NULL, P->F.mode, P->F.nd_lim, P->F.lchol_likely_panels, P->F.nd_likely_panels)) return true;
+    set_error("internal error: no route for a camera block that is %s%s%s%s", P->F.mode.compact ? "compacted " : "", P->F.mode.dissect ? "dissected " : "",
+              P->F.mode.sweep ? "solved by the backward sweep " : "", a.comm2 != NULL ? "sharded" : "");
+    return false;
 }
 
 // The two sums over the ranks of a sharded trial step (include/mrcal_amd.h):
@@ -139,7 +131,7 @@ bool enqueue_evaluation(mrcal_amd_problem* P, const Step2Args& a)
 {
     const int parts = EVAL_PART_PROLOGUE | EVAL_PART_ZERO | EVAL_PART_BOARD | EVAL_PART_REST;
     if(a.initial) return problem_evaluate_ref(P, OpRef{ P->d_ops, &a.ctl->ib, NULL }, true, true, parts);
-    const OpRef Rto = { P->d_ops, &a.ctl->ia, solver_ctl_skip_eval2(a.ctl) };
+    const OpRef Rto = { P->d_ops, &a.ctl->ia, solver_ctl_skip_eval(a.ctl) };
     if(prologue_takes_choose(P->D))
     {
         const ChooseArgs ca = step2_choose_args(a);
@@ -165,14 +157,6 @@ bool enqueue_factorization(mrcal_amd_problem* P, const Step2Args& a, int segment
     return true;
 }
 
-// x, J, the normal equations, g, |x|^2, the Cauchy step and (unless the Cauchy
-// step already leaves the trust region) the Gauss-Newton step at the starting point
-bool enqueue_initial_point(mrcal_amd_problem* P)
-{
-    const Step2Args a = step2_args(P, true);
-    return enqueue_evaluation(P, a) && enqueue_factorization(P, a, -1);
-}
-
 // SolverCtl::error, in words
 static const char* solver_error_text(int error)
 {
@@ -181,12 +165,13 @@ static const char* solver_error_text(int error)
            error == 3 ? "internal error: a control point taken for uncovered by every board is coupled to other variables (spl_compact_kernel)" :
                         "could not make JtJ positive definite";
 }
-// One trial step of the dog-leg, entirely queued: every decision is taken on
-// the device (step.hip, "the fused step")
-bool enqueue_trial_step(mrcal_amd_problem* P)
+// One step, entirely queued: every decision is taken on the device (step.hip, "the fused step").
+// initial: x, J, the normal equations, g, |x|^2, the Cauchy step and (unless the Cauchy step already leaves the trust
+// region) the Gauss-Newton step at the starting point; else one trial step of the dog-leg
+bool enqueue_step(mrcal_amd_problem* P, bool initial)
 {
-    const Step2Args a = step2_args(P, false);
-    return enqueue_evaluation(P, a) && enqueue_factorization(P, a, -1);
+    Step2Args a;
+    return step2_args(P, initial, &a) && enqueue_evaluation(P, a) && enqueue_factorization(P, a, -1);
 }
 
 bool read_ctl(mrcal_amd_problem* P, SolverCtl* c)
@@ -208,7 +193,7 @@ void absorb_ctl(mrcal_amd_problem* P, const SolverCtl& c)
 // The splined models' camera block factored whole from here on: neither compacted (LcholCompact) nor dissected
 void compaction_off(mrcal_amd_problem* P)
 {
-    P->F.cperm_cur = NULL; P->plan.spl_compact = 0; P->plan.nd_lim = NULL; P->F.nd_lim.rounds = 0;
+    problem_set_camblock_mode(P, CamBlockMode{ false, false, P->F.mode.sweep });
 }
 
 // The splined models' compacted camera block (LcholCompact): how many of its factorization's launches the host
@@ -217,7 +202,7 @@ void compaction_off(mrcal_amd_problem* P)
 // does not depend on it
 static bool learn_likely_size(mrcal_amd_problem* P)
 {
-    if(P->F.cperm_cur == NULL) return true;
+    if(!P->F.mode.compact) return true;
     int n1 = 0;
     HIP_TRY(hipMemcpyAsync(&n1, P->op[P->icur].cperm + 2*P->nd.Nc, sizeof(int), hipMemcpyDeviceToHost, P->stream), return false);
     HIP_TRY(hipStreamSynchronize(P->stream), return false);
@@ -232,7 +217,7 @@ static bool learn_likely_size(mrcal_amd_problem* P)
     // of later points are used where they fit (else the point goes the ordinary way through the same launches). Where
     // that differs from what the last solve had, the device's copy of the limits is replaced (a solve from the seed and
     // the solve after an outlier pass may well differ: the boxes move with the state)
-    if(P->F.ndMA != NULL && P->op[P->icur].ndp != NULL)
+    if(P->F.mode.dissect)
     {
         int h[NDH_WORDS];
         HIP_TRY(hipMemcpyAsync(h, P->op[P->icur].ndp, sizeof(h), hipMemcpyDeviceToHost, P->stream), return false);
@@ -267,7 +252,7 @@ static bool learn_likely_size(mrcal_amd_problem* P)
 bool run_dogleg(mrcal_amd_problem* P, const DoglegParameters& prm)
 {
     if(!ctl_reset(P, prm, true)) return false;
-    if(!enqueue_initial_point(P)) return false;
+    if(!enqueue_step(P, true)) return false;
     if(!learn_likely_size(P)) return false;
 
     const int LAG = 3;      // how many steps the host may run ahead of what it has seen
@@ -282,7 +267,7 @@ bool run_dogleg(mrcal_amd_problem* P, const DoglegParameters& prm)
         const int slot = nqueued % CTL_RING;
         // the step's last kernel leaves the snapshot in the pinned ring itself
         P->snap_target = &P->h_ctl_ring[slot];
-        const bool queued = enqueue_trial_step(P);
+        const bool queued = enqueue_step(P, false);
         P->snap_target = NULL;
         if(!queued) return false;
         HIP_TRY(hipEventRecord(P->ctl_events[slot], P->stream), return false);
@@ -362,7 +347,7 @@ bool run_dogleg(mrcal_amd_problem* P, const DoglegParameters& prm)
         {
             P->lchol_diag_ratio = lo/hi;
             const int lg = test_hooks().lchol_fallback_log10 ? test_hooks().lchol_fallback_log10 : -10;
-            if(P->lchol_diag_ratio < pow(10.0, (double)lg) && !P->F.use_sweep && P->comm == NULL) P->sweep_fallback_wanted = true;
+            if(P->lchol_diag_ratio < pow(10.0, (double)lg) && !P->F.mode.sweep && P->comm == NULL) P->sweep_fallback_wanted = true;
         }
     }
     return true;
@@ -601,6 +586,10 @@ void report_regularization(mrcal_amd_problem* P, const mrcal_problem_selections_
         fprintf(stderr, "mrcal_amd: reg err ratio (unity_cam01): %.3g\n", xreg[i]*xreg[i]/norm2_error);
 }
 
+// (round 6) the evaluations queued while one of these lives leave the Jacobian stream out if the problem was told so
+struct JfreeScope { mrcal_amd_problem* P; JfreeScope(mrcal_amd_problem* p) : P(p) { P->jfree_now = !P->solve_stores_jacobian; }
+                    ~JfreeScope() { P->jfree_now = false; } };
+
 } // namespace
 
 namespace { int& optimize_jacobian_stream_policy() { static int policy = 0; return policy; } }
@@ -633,7 +622,7 @@ int mrcal_amd_set_test_hook(const char* name, int value)
 
 // min / max of the diagonal of the big camera block's Cholesky factors over the last dog-leg pass (1: no such factorization)
 double mrcal_amd_problem_lchol_diag_ratio(mrcal_amd_problem_t* P) { return P->lchol_diag_ratio; }
-int    mrcal_amd_problem_uses_sweep(mrcal_amd_problem_t* P) { return P->F.use_sweep; }
+int    mrcal_amd_problem_uses_sweep(mrcal_amd_problem_t* P) { return P->F.mode.sweep ? 1 : 0; }
 
 // Resident tier: the full solve on a resident problem. Returns rms error, <0
 // on failure
@@ -648,9 +637,7 @@ double mrcal_amd_problem_solve(mrcal_amd_problem_t* P, int max_iterations,
     const auto t0 = std::chrono::steady_clock::now();
     P->stats = mrcal_amd_solver_stats();
     int Noutliers = 0, Noutliers_tri = 0;
-    // (round 6: the evaluations queued from here on leave the Jacobian stream out if the problem was told so)
-    struct JfreeScope { mrcal_amd_problem* P; JfreeScope(mrcal_amd_problem* p) : P(p) { P->jfree_now = !P->solve_stores_jacobian; }
-                        ~JfreeScope() { P->jfree_now = false; } } jfree_scope(P);
+    JfreeScope jfree_scope(P);
     for(;;)
     {
         // the reference makes a new libdogleg context for every pass
@@ -665,7 +652,7 @@ double mrcal_amd_problem_solve(mrcal_amd_problem_t* P, int max_iterations,
             // is wrong for this problem - a kind of row it does not know - and the answer is the ordinary reduction of
             // the whole camblock, not a failed solve: both off for good, the pass again from the point it reached (every
             // accepted point lowered the true cost). Loudly
-            if(P->last_ctl_error == 3 && P->plan.spl_compact)
+            if(P->last_ctl_error == 3 && P->F.mode.compact)
             {
                 fprintf(stderr, "mrcal_amd: WARNING: %s. Solving this problem without the compaction of its camera block\n", solver_error_text(3));
                 compaction_off(P);
@@ -684,8 +671,7 @@ double mrcal_amd_problem_solve(mrcal_amd_problem_t* P, int max_iterations,
             //  goes through the sweep)
             fprintf(stderr, "mrcal_amd: WARNING: the diagonal of the camera block's Cholesky factor spans %.1e: this problem's steps go through "
                             "the backward sweep from here on instead of the explicit inverse (slower, backward stable)\n", 1.0/P->lchol_diag_ratio);
-            P->F.use_sweep = 1;
-            compaction_off(P);
+            problem_set_camblock_mode(P, CamBlockMode{ false, false, true });
         }
         if(!P->L.sel.do_apply_outlier_rejection) break;
         bool found;
@@ -715,16 +701,15 @@ int mrcal_amd_problem_run_steps(mrcal_amd_problem_t* P, int Nsteps, double* trus
     if(!problem_prepare_solver(P)) return -1;
     DoglegParameters prm;
     if(trustregion_inout && *trustregion_inout > 0.0) prm.trustregion0 = *trustregion_inout;
-    struct JfreeScope { mrcal_amd_problem* P; JfreeScope(mrcal_amd_problem* p) : P(p) { P->jfree_now = !P->solve_stores_jacobian; }
-                        ~JfreeScope() { P->jfree_now = false; } } jfree_scope(P);
+    JfreeScope jfree_scope(P);
     if(!P->ctl_initialized || !(trustregion_inout && *trustregion_inout > 0.0))
     {
         if(!ctl_reset(P, prm, false)) return -1;
-        if(!enqueue_initial_point(P)) return -1;
+        if(!enqueue_step(P, true)) return -1;
         if(!learn_likely_size(P)) return -1;
     }
     for(int n = 0; n < Nsteps; n++)
-        if(!enqueue_trial_step(P)) return -1;
+        if(!enqueue_step(P, false)) return -1;
     SolverCtl c;
     if(!read_ctl(P, &c)) return -1;
     if(c.error) { set_error("%s", solver_error_text(c.error)); return -1; }
@@ -791,7 +776,7 @@ bool mrcal_amd_problem_gauss_newton_step(mrcal_amd_problem_t* P, double* step)
 
 ////////////////////////////////////////////////////////////////////////////////
 // multi-GPU (include/mrcal_amd.h). The sharded step IS the single-GPU step with
-// two all-reduces in it (enqueue_trial_step); what is here is the attachment of
+// two all-reduces in it (enqueue_step); what is here is the attachment of
 // the communicator, the final gather of the state, and the same step cut at the
 // collectives for a driver that brings its own (the protocol tests)
 ////////////////////////////////////////////////////////////////////////////////
@@ -812,7 +797,7 @@ bool mrcal_amd_problem_dissection(mrcal_amd_problem_t* P, int* out /* [9] */)
 {
     for(int i = 0; i < 9; i++) out[i] = 0;
     if(P->F.ndMA == NULL || P->op[P->icur].ndp == NULL) return true;
-    out[0] = P->F.nd_lim.rounds; out[1] = P->F.nd_lim.ns_max;
+    out[0] = P->F.mode.dissect ? P->F.nd_lim.rounds : 0; out[1] = P->F.nd_lim.ns_max;
     int h[NDH_WORDS];
     HIP_TRY(hipMemcpyAsync(h, P->op[P->icur].ndp, sizeof(h), hipMemcpyDeviceToHost, P->stream), return false);
     HIP_TRY(hipStreamSynchronize(P->stream), return false);
@@ -884,7 +869,8 @@ bool mrcal_amd_problem_sharded_enqueue(mrcal_amd_problem_t* P, int initial, int 
     //  copy of S in the reduction's launch, on this shard's terms alone, before the caller's sums)
     if(!P->ctl_initialized || !P->sharded_external) { set_error("mrcal_amd_problem_sharded_reset() first"); return false; }
     if(segment != 0 && segment != 1) { set_error("mrcal_amd_problem_sharded_enqueue(): segment %d", segment); return false; }
-    const Step2Args a = step2_args(P, initial != 0);
+    Step2Args a;
+    if(!step2_args(P, initial != 0, &a)) return false;
     if(segment == 0 && !enqueue_evaluation(P, a)) return false;
     return enqueue_factorization(P, a, segment);
 }

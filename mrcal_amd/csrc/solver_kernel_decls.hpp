@@ -77,14 +77,18 @@ struct LcholChain
 
 struct LcholNdLaunch { LcholChain A, B; const int* ndh; NdLimits lim; };
 
-hipError_t launch_cholesky_large(int n, const int* skip, double* M, double* Linv, int* status, hipStream_t stream,
-                                 const Step2Dev* sd = NULL, bool* fused = NULL, const int* n_dev = NULL, const LcholCompact* compact = NULL,
-                                 int likely_panels = 0 /* with n_dev: launches 0 .. likely_panels one by one, the rest in lchol_tail_kernel; 0: all one by one */,
-                                 unsigned* tail_counter = NULL, const LcholNdLaunch* nds = NULL,
-                                 bool finish_done = false /* with sd: the end-of-trial logic has run already (the first launch goes by `skip`); the verdict still rides in the last */,
-                                 bool sweep = false /* the solve by the backward sweep in groups of panels (rounds 2-3; backward stable) instead of through
-                                                       L^-1 built on the side (lchol_inverse_block): FactorBuffers::use_sweep */,
-                                 LcholDiagSpread diag_minmax = NULL);
+// One factorization (and solve) by the launch-per-panel Cholesky, the route decided (camblock_route(); never in_lds)
+struct LcholLaunch
+{
+    int n; double* M; double* Linv; int* status;   // the matrix with its rhs row, FactorBuffers::Linv's workspace
+    const int* skip;
+    const Step2Dev* sd;        // the trial step this belongs to (NULL: none; not looked at with the backward sweep)
+    CamBlockRoute route;
+    LcholCompact  compact;     // with route.compact
+    LcholNdLaunch nds;         // with route.nd_launches
+    LcholDiagSpread diag_minmax;
+};
+hipError_t launch_cholesky_large(const LcholLaunch& c, hipStream_t stream);
 // ---- between assembly.hip / schur.hip and the trial step's launchers (step.hip)
 // a pair chunk is reduced by one workgroup per 256 Gram positions
 __host__ __device__ __forceinline__ int assemble_chunk_slices(const DeviceProblem& P) { return (gram_stride(P.Ndist) + 255) >> 8; }

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include "problem.hpp"
 #include "kernels.hpp"
+#include "camblock_route.hpp"
 
 namespace mrcal_amd {
 
@@ -97,8 +98,6 @@ enum { NDH_ACTIVE = 0,           // this point's camera block goes by the dissec
        NDH_WORDS };
 __host__ __device__ inline size_t nd_plan_ints(int Nc) { return (size_t)NDH_WORDS + (size_t)Nc + (size_t)Nc + 2*ND_PANEL; }
 hipError_t launch_nd_plans_off(const struct OpDev* ops, int Nc, hipStream_t stream);
-// what the host provided launches for: [0] rounds (panels a side; 0: none - the plans are made and not used) | [1] the largest separator
-struct NdLimits { int rounds, ns_max; };
 
 // factorization scratch, one set
 struct FactorBuffers
@@ -113,11 +112,11 @@ struct FactorBuffers
     int*    status;   // [1] nonzero: not positive definite
     unsigned* occ;    // [NEb][occ_words(nd)] bit per 16-column tile of the camera block: does the block's Wt hold a nonzero there?
                       // Written by eblock_factor_kernel, read by the sparse SYRK (the splined models). NULL: not tracked
-    int     lchol_likely_panels; // with cperm_cur: the factorization's launches the host provides one by one (the rest: lchol_tail_kernel); 0: all
+    int     lchol_likely_panels; // compacted: the factorization's launches the host provides one by one (the rest: lchol_tail_kernel); 0: all
     int*    cperm_cur; // [2 Nc + 2] (the last word: lchol_tail_kernel's barrier) the permutation (OpDev::cperm) of the point whose camera block was reduced last: what the
-                      // factorization and the solve behind that reduction go by. NULL: no compaction
+                      // factorization and the solve behind that reduction go by. NULL: not allocated (whether it is USED: mode)
     double* iso;      // with cperm_cur: [4 (Nc/2 + 1)] the 2 x 2 blocks of the isolated pairs (s00, s10, s11, -) | [Nc] their rhs
-    // the dissection (NULL / 0: none): the two sides' matrices and workspaces, the plan of the point reduced last (a copy
+    // the dissection (NULL / 0: not allocated): the two sides' matrices and workspaces, the plan of the point reduced last (a copy
     // of its OpDev::ndp), the limits as the host set them (and their device copy, which the plans are made against)
     double* ndMA; double* ndMB; double* ndLinvA; double* ndLinvB;
     double* ndPart;   // [ceil(Nc/16)][2 LCH_ND_WMAX] L_SX^T d_S in shares of 16 entries of d_S (LcholCompact::ndpart)
@@ -125,15 +124,15 @@ struct FactorBuffers
     int*    nd_lim_dev;
     NdLimits nd_lim;
     int     nd_likely_panels;   // the separator's panels at the solve's first point (as lchol_likely_panels)
-    int     use_sweep; // the large Cholesky's solve by the backward sweep in groups of panels (backward stable; slower: no explicit
-                      // L^-1, no compaction, the end-of-trial logic in launches of its own) instead of d = -Y^T z. Set by the
-                      // automatic fallback (solver.cpp: a factor whose diagonal spans more than 1e10) or by a test hook
+    CamBlockMode mode; // which of this is in use at present (camblock_route.hpp): set by problem_set_camblock_mode() alone. Host
+                      // logic; no larger than the int it stands for, so that the kernels taking FactorBuffers by value take what they took
     unsigned long long* diag_minmax; // [2] the smallest / largest diagonal entry of the big camera block's Cholesky factor since the solve's
                       // start (bit patterns of positive doubles; set to +inf, 0 by ctl_reset()): what the fallback to the sweep goes by. NULL: no large Cholesky
     double* Wtile;    // with occ: a second copy of the tiles of Wt that hold something, tile column by tile column -
                       // [ceil(Nc/16)][NE][16] - for the sparse SYRK: a block's rows of a tile are 768 contiguous bytes
                       // (in Wt itself they are six pieces 9.6 KB apart, and a workgroup's few blocks that count are all over 46 MB)
 };
+static_assert(sizeof(CamBlockMode) <= sizeof(int), "FactorBuffers::mode stands where an int stood");
 inline int occ_words(const NormalDims& nd) { return (((nd.Nc + 15) >> 4) + 31) >> 5; }
 
 // Hooks for the tests (mrcal_amd_set_test_hook(), include/mrcal_amd.h): force paths a solve takes by itself only when a
@@ -142,7 +141,7 @@ struct TestHooks
 {
     int lchol_likely_panels;   // launches of the large Cholesky provided one by one; the rest go through lchol_tail_kernel
     int nd_rounds;             // rounds of the dissection provided for, whatever the plan needs
-    int lchol_sweep;           // the large Cholesky's solve by the backward sweep (FactorBuffers::use_sweep) from the start
+    int lchol_sweep;           // the large Cholesky's solve by the backward sweep (CamBlockMode::sweep) from the start
     int lchol_fallback_log10;  // the automatic fallback's threshold on min / max of the factor's diagonal as a power of ten (default -10)
 };
 TestHooks& test_hooks();
@@ -241,6 +240,7 @@ struct AssemblyPlan
 {
     GenPlan gen;
     ReproStep repro;
+    // (these two follow FactorBuffers::mode: problem_set_camblock_mode() sets them and nothing else does)
     int  spl_compact;      // splined models: the evaluation's assembly also makes OpDev::cperm (spl_compact_kernel)
     const int* nd_lim;     // ... and OpDev::ndp, against these limits (FactorBuffers::nd_lim_dev); NULL: no dissection
     int* frame_obs_begin;  // [blocks+1] the board observations of each 6x6 eliminated block (a frame: contiguous) ...
@@ -420,7 +420,7 @@ size_t assemble_rows_scratch_doubles(const NormalDims& nd);
 hipError_t launch_assemble_rows(const NormalDims& nd, const OpRef& R, int Nmeas,
                                 const int32_t* Jp, const int32_t* Ji, hipStream_t stream, double* scratch, long long Nnz);
 
-// ---- The device-controlled dog-leg trial step (solver.cpp enqueue_trial_step()). Per trial, in this order:
+// ---- The device-controlled dog-leg trial step (solver.cpp enqueue_step()). Per trial, in this order:
 //   choose            the dog-leg step from the current point, b_trial; the first trial from a new point also
 //                     derives its Cauchy step                                          (launch_step2_choose)
 //   [prologue, board] x, J, Grams at the trial point                                   (launch_evaluate)
@@ -445,11 +445,8 @@ struct Step2Args
     // The step's layout, decided once (solver.cpp step2_args()); the launchers only read it
     bool initial;            // the evaluation of the starting point (no choose, no accept)
     bool with_grams;         // the board rows come with per-observation Grams (problem_has_grams()): the fused assembly
-    bool finish_rides;       // the end-of-trial logic rides in the reduction's launch
-    bool nd_launches;        // the dissection's launches follow the reduction (FactorBuffers::nd_lim)
-    bool S_packed;           // the reduction leaves a packed copy of S (factor_S_packed()) that the one-workgroup Cholesky reads
+    CamBlockRoute route;     // how the camera block is reduced and factored (camblock_route())
 };
-bool       step2_chol_in_lds(const NormalDims& nd);     // the camera block's Cholesky is the one-workgroup LDS one
 hipError_t launch_step2_choose(const Step2Args& a, hipStream_t stream);
 // the same as arguments, for an evaluation whose prologue launch carries the choice (EvalBuffers::choose)
 struct ChooseArgs;
@@ -462,7 +459,6 @@ hipError_t launch_step2_reduce(const Step2Args& a, hipStream_t stream, bool side
 hipError_t launch_step2_factor(const Step2Args& a, hipStream_t stream);
 int64_t    step2_comm1_doubles(const NormalDims& nd);
 hipError_t launch_mask_state(const NormalDims& nd, const BlockRanges& br, bool is_leader, double* b, hipStream_t stream);
-const int* solver_ctl_skip_eval2(const SolverCtl* ctl);
 // the board rows come with per-observation Grams: every lens model but the splined one (whose assembly goes row by row)
 inline bool problem_has_grams(const DeviceProblem& P)
 {

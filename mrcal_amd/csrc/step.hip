@@ -216,7 +216,12 @@ hipError_t launch_solve_backsub(const NormalDims& nd, const BlockRanges& br,
             launch_cholesky_lds(0, n, R.skip, keep_factor ? 1 : 0, F.S, F.r, F.status, none, stream);
         }
         else if(F.Linv != NULL)
-            launch_cholesky_large(n, R.skip, F.S, F.Linv, F.status, stream, NULL, NULL, NULL, NULL, 0, NULL, NULL, false, F.use_sweep != 0, F.diag_minmax);
+        {
+            // (the plain route: the whole matrix, nothing of a trial step around it)
+            LcholLaunch c = { n, F.S, F.Linv, F.status, R.skip, NULL, {}, {}, {}, F.diag_minmax };
+            camblock_route(&c.route, n, false, CamBlockMode{ false, false, F.mode.sweep }, NdLimits{ 0, 0 }, 0, 0);
+            launch_cholesky_large(c, stream);
+        }
         else
             launch_cholesky_global(n, R.skip, F.S, F.r, F.status, stream);
     }
@@ -295,8 +300,6 @@ hipError_t launch_mask_state(const NormalDims& nd, const BlockRanges& br, bool i
 }
 
 // ---- the fused step
-const int* solver_ctl_skip_eval2(const SolverCtl* ctl) { return &((const SolverCtlFlags*)(ctl + 1))->skip_eval; }
-
 ChooseArgs step2_choose_args(const Step2Args& a)
 {
     ChooseArgs c;
@@ -313,8 +316,6 @@ hipError_t launch_step2_choose(const Step2Args& a, hipStream_t stream)
     hipLaunchKernelGGL(step2_choose_kernel, dim3((nd.Nstate + PRO_T - 1)/PRO_T), dim3(PRO_T), 0, stream, step2_choose_args(a));
     return hipGetLastError();
 }
-
-bool step2_chol_in_lds(const NormalDims& nd) { return chol_fits_lds(nd.Nc); }
 
 // the block normal equations of the point the flags name, and the elimination of its frame/point blocks. *forked: work
 // was left on the side stream, which launch_step2_reduce() joins
@@ -362,13 +363,14 @@ hipError_t launch_step2_assemble(const Step2Args& a, hipStream_t stream, bool* f
 }
 
 // SYRK (+ finalize of A, g, |x|^2) | S, r and the tail of comm1. (Sharded: comm1 is all-reduced after this.) Where
-// a.finish_rides, the end-of-trial logic rides in this launch; where a.S_packed, it leaves the packed copy of S
+// a.route.finish_rides, the end-of-trial logic rides in this launch; where a.route.S_packed, it leaves the packed copy of S
 hipError_t launch_step2_reduce(const Step2Args& a, hipStream_t stream, bool side_forked)
 {
     const DeviceProblem& P = *a.P;
     const NormalDims& nd = *a.nd;
     const BlockRanges& br = *a.br;
     const FactorBuffers& F = *a.F;
+    const CamBlockRoute& route = a.route;
     SolverCtlFlags* fl = ctl_flags(a.ctl);
     FinalizeRide ride; memset(&ride, 0, sizeof(ride));
     if(a.with_grams && a.plan->Ndest > 0)
@@ -393,9 +395,8 @@ hipError_t launch_step2_reduce(const Step2Args& a, hipStream_t stream, bool side
     const int nred = ((npairs*256 + nb*16)*(live ? 1 : SRED_SPLIT) + 255)/256;
     // (the dissection: its matrices' borders and pads by nfill more workgroups; the end of the trial step rides in this
     //  launch's last ordinary workgroup)
-    const bool nd_on = F.ndMA != NULL && F.cperm_cur != NULL;
     int nfill = 0;
-    if(a.nd_launches)
+    if(route.nd_launches)
     {
         // (a thread an entry of what the dissection's matrices hold beside the camera block's entries: step2_reduce_kernel)
         const long long NSp = F.nd_lim.ns_max, nxm = (long long)ND_PANEL*F.nd_lim.rounds, pads = ND_PANEL - 1;
@@ -405,13 +406,13 @@ hipError_t launch_step2_reduce(const Step2Args& a, hipStream_t stream, bool side
         nfill = std::max(nfill, ncopy);
     }
     Step2Dev sd; memset(&sd, 0, sizeof(sd));
-    if(a.finish_rides) { sd.nd = nd; sd.ops = a.ops; sd.ctl = a.ctl; sd.fl = fl; sd.initial = a.initial ? 1 : 0; sd.comm1_tail = F.r + nd.Nc; }
+    if(route.finish_rides) { sd.nd = nd; sd.ops = a.ops; sd.ctl = a.ctl; sd.fl = fl; sd.initial = a.initial ? 1 : 0; sd.comm1_tail = F.r + nd.Nc; }
     hipLaunchKernelGGL(step2_reduce_kernel, dim3(nred + 1 + nfill), dim3(256), 0, stream,
-                       nd, a.ops, a.ctl, fl, a.is_leader ? 1 : 0, nred, nslots, F.Spart, F.S, F.r, F.status, live, F.cperm_cur, F.iso, &a.ctl->error,
-                       a.nd_launches ? F.ndMA : (double*)NULL, a.nd_launches ? F.ndMB : (double*)NULL, nd_on ? F.ndp_cur : (int*)NULL, nfill,
-                       a.finish_rides ? 1 : 0, sd,
+                       nd, a.ops, a.ctl, fl, a.is_leader ? 1 : 0, nred, nslots, F.Spart, F.S, F.r, F.status, live, route.compact ? F.cperm_cur : (int*)NULL, F.iso, &a.ctl->error,
+                       route.nd_launches ? F.ndMA : (double*)NULL, route.nd_launches ? F.ndMB : (double*)NULL, route.nd_plans ? F.ndp_cur : (int*)NULL, nfill,
+                       route.finish_rides ? 1 : 0, sd,
                        // (a packed copy of S for the one-workgroup Cholesky's launch behind this one - launch_cholesky_lds_quadform())
-                       a.S_packed ? factor_S_packed(F, nd.Nc) : (double*)NULL);
+                       route.S_packed ? factor_S_packed(F, nd.Nc) : (double*)NULL);
     return hipGetLastError();
 }
 int64_t step2_comm1_doubles(const NormalDims& nd) { return (int64_t)nd.Nc*nd.Nc + 2*nd.Nc + 2; }
@@ -422,52 +423,41 @@ hipError_t launch_step2_factor(const Step2Args& a, hipStream_t stream)
     const NormalDims& nd = *a.nd;
     const BlockRanges& br = *a.br;
     const FactorBuffers& F = *a.F;
+    const CamBlockRoute& route = a.route;
     SolverCtlFlags* fl = ctl_flags(a.ctl);
     Step2Dev sd;
     sd.nd = nd; sd.ops = a.ops; sd.ctl = a.ctl; sd.fl = fl; sd.initial = a.initial ? 1 : 0;
     sd.comm1_tail = F.r + nd.Nc;
+    const int n = nd.Nc;
+    if(route.in_lds)
     {
-        const int n = nd.Nc;
-        if(chol_fits_lds(n))
+        // (round 6, single GPU: the end-of-trial logic has run in the reduction's launch, which left the packed S; the
+        //  quadratic form's workgroups in the factorization's launch - they never needed it)
+        if(route.S_packed) launch_cholesky_lds_quadform(n, nd, F, sd, a.plan->qf_part, quadform_blocks(nd), stream);
+        else               launch_cholesky_lds(1, n, (const int*)NULL, 0, F.S, F.r, F.status, sd, stream);
+    }
+    else
+    {
+        // (round 5: finish and post ride in the factorization's first and last launch; with the backward sweep the
+        //  factorization's last launch is another: launches of their own then)
+        if(route.sweep) hipLaunchKernelGGL(step2_finish_kernel, dim3(1), dim3(1024), 0, stream, sd, F.status);
+        LcholLaunch c = { n, F.S, F.Linv, F.status, &fl->skip_chol, &sd, route, {}, {}, F.diag_minmax };
+        // (the splined models: the camera block as the reduction left it - without the control points no board covers)
+        if(route.compact) { c.compact.cperm = F.cperm_cur; c.compact.iso = F.iso; c.compact.dout = F.r; c.compact.Nc = n; }
+        // (the dissection's launches, where the host has provided for them: learn_likely_size())
+        if(route.nd_launches)
         {
-            // (round 6, single GPU: the end-of-trial logic has run in the reduction's launch, which left the packed S; the
-            //  quadratic form's workgroups in the factorization's launch - they never needed it)
-            if(a.S_packed) launch_cholesky_lds_quadform(n, nd, F, sd, a.plan->qf_part, quadform_blocks(nd), stream);
-            else           launch_cholesky_lds(1, n, (const int*)NULL, 0, F.S, F.r, F.status, sd, stream);
+            const int* h = F.ndp_cur;
+            c.nds.A = LcholChain{ F.ndMA, F.ndLinvA, h + NDH_NA, h + NDH_NS };
+            c.nds.B = LcholChain{ F.ndMB, F.ndLinvB, h + NDH_NB, h + NDH_NS };
+            c.nds.ndh = h; c.nds.lim = F.nd_lim;
+            c.compact.ndh = h; c.compact.ndMA = F.ndMA; c.compact.ndMB = F.ndMB; c.compact.ndpart = F.ndPart;
         }
-        else
-        {
-            // (round 5: finish and post ride in the factorization's first and last launch; with the backward sweep the
-            //  factorization's last launch is another: launches of their own then)
-            const bool separate = F.use_sweep != 0;
-            bool fused = false;
-            if(separate) hipLaunchKernelGGL(step2_finish_kernel, dim3(1), dim3(1024), 0, stream, sd, F.status);
-            // (the splined models: the camera block as the reduction left it - without the control points no board covers)
-            LcholCompact cp; memset(&cp, 0, sizeof(cp));
-            const bool compact = F.cperm_cur != NULL;       // (what the reduction went by; never with the backward sweep: solver.cpp)
-            if(compact) { cp.cperm = F.cperm_cur; cp.iso = F.iso; cp.dout = F.r; cp.Nc = n; }
-            // (the dissection's launches, where the host has provided for them: learn_likely_size())
-            LcholNdLaunch nds; memset(&nds, 0, sizeof(nds));
-            if(a.nd_launches)
-            {
-                const int* h = F.ndp_cur;
-                nds.A = LcholChain{ F.ndMA, F.ndLinvA, h + NDH_NA, h + NDH_NS };
-                nds.B = LcholChain{ F.ndMB, F.ndLinvB, h + NDH_NB, h + NDH_NS };
-                nds.ndh = h; nds.lim = F.nd_lim;
-                cp.ndh = h; cp.ndMA = F.ndMA; cp.ndMB = F.ndMB; cp.ndpart = F.ndPart;
-            }
-            launch_cholesky_large(n, &fl->skip_chol, F.S, F.Linv, F.status, stream, separate ? NULL : &sd, &fused,
-                                  compact ? (a.nd_launches ? F.ndp_cur + NDH_NSEFF : F.cperm_cur + 2*n) : (const int*)NULL,
-                                  compact ? &cp : (const LcholCompact*)NULL,
-                                  compact ? (a.nd_launches ? F.nd_likely_panels : F.lchol_likely_panels) : 0,
-                                  compact ? (unsigned*)(F.cperm_cur + 2*n + 1) : (unsigned*)NULL, a.nd_launches ? &nds : (const LcholNdLaunch*)NULL,
-                                  a.finish_rides, F.use_sweep != 0, F.diag_minmax);
-            if(separate) hipLaunchKernelGGL(step2_post_kernel, dim3(1), dim3(64), 0, stream, sd, F.status);
-            else if(!fused) return hipErrorInvalidValue;
-        }
+        launch_cholesky_large(c, stream);
+        if(route.sweep) hipLaunchKernelGGL(step2_post_kernel, dim3(1), dim3(64), 0, stream, sd, F.status);
     }
     const int nbs = (br.count() + 3)/4, nqf = quadform_blocks(nd);
-    hipLaunchKernelGGL(step2_backsub_quadform_kernel, dim3(nbs + 1 + (a.S_packed ? 0 : nqf)), dim3(256), 0, stream,
+    hipLaunchKernelGGL(step2_backsub_quadform_kernel, dim3(nbs + 1 + (route.S_packed ? 0 : nqf)), dim3(256), 0, stream,
                        nd, br, a.ops, a.ctl, fl, F.Wt, F.LD, F.y, F.r, a.plan->dots_part, a.plan->qf_part, nbs, a.snap,
                        (nd.Nc > SYRK_STRIP_FROM) ? F.occ : (const unsigned*)NULL, occ_words(nd));
     if(a.comm2 != NULL)

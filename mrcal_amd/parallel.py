@@ -8,7 +8,7 @@ all shards share is the small dense camera block (all intrinsics + extrinsics +
 the board warp: Nc = 140 variables at 8 cameras).
 
 The sharded trial step IS the single-GPU device-controlled step
-(csrc/solver.cpp enqueue_trial_step) with TWO sums over the ranks in it:
+(csrc/solver.cpp enqueue_step) with TWO sums over the ranks in it:
 
   [choose the step | evaluate x, J, Grams at the trial point for MY frames |
    block normal equations, my frames eliminated on the spot | my summand of the
