@@ -19,16 +19,8 @@ static Layout layout_from_args(int Ncameras_intrinsics, int Ncameras_extrinsics,
                                mrcal_problem_selections_t sel,
                                const mrcal_lensmodel_t* lensmodel)
 {
-    Dims d;
-    d.Ncameras_intrinsics = Ncameras_intrinsics;
-    d.Ncameras_extrinsics = Ncameras_extrinsics;
-    d.Nframes             = Nframes;
-    d.Npoints             = Npoints;
-    d.Npoints_fixed       = Npoints_fixed;
-    d.Nobservations_board = Nobservations_board;
-    d.Nobservations_point = Nobservations_point;
-    d.object_width_n      = width_n;
-    d.object_height_n     = height_n;
+    const Dims d = make_dims(Ncameras_intrinsics, Ncameras_extrinsics, Nframes, Npoints, Npoints_fixed,
+                             Nobservations_board, Nobservations_point, width_n, height_n);
     return make_layout(d, sel, *lensmodel, obs_tri, Nobs_tri);
 }
 

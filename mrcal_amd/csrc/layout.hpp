@@ -67,6 +67,12 @@ struct Dims
     int Nobservations_board, Nobservations_point;
     int object_width_n, object_height_n;
 };
+inline Dims make_dims(int Ncameras_intrinsics, int Ncameras_extrinsics, int Nframes, int Npoints, int Npoints_fixed,
+                      int Nobservations_board, int Nobservations_point, int object_width_n, int object_height_n)
+{
+    return Dims{ Ncameras_intrinsics, Ncameras_extrinsics, Nframes, Npoints, Npoints_fixed,
+                 Nobservations_board, Nobservations_point, object_width_n, object_height_n };
+}
 
 // All the derived counts. "state" sizes are in state variables, "meas" sizes
 // in measurement rows
@@ -224,6 +230,26 @@ inline int nnz_per_point_row(const Layout& L, int icam_extrinsics, int i_point)
         ((L.sel.do_optimize_frames && i_point < L.dims.Npoints - L.dims.Npoints_fixed) ? 3 : 0);
 }
 
+// first state index of a camera's intrinsics and of its extrinsics, as an observation's rows see them; -1: not in
+// the state (or, the extrinsics: the camera sits at the reference)
+struct CameraStateIndex { int intrinsics, extrinsics; };
+inline CameraStateIndex camera_state_index(const Layout& L, const mrcal_camera_index_t& icam)
+{
+    return CameraStateIndex{
+        (L.Nintr_state > 0) ? L.i_state_intrinsics + icam.intrinsics*L.Nintr_state : -1,
+        (L.Nstate_extrinsics > 0 && icam.extrinsics >= 0) ? L.i_state_extrinsics + 6*icam.extrinsics : -1 };
+}
+
+// nonzeros of the regularization rows: one column per row, except that each splined-model knot row mixes the knot's
+// two values (mrcal.c:847-869); 3 in the unity_cam01 row. (A shard that is not the leader has no such rows:
+// Nreg_percamera == 0, no unity_cam01)
+inline int64_t num_j_nonzero_regularization(const Layout& L)
+{
+    const bool knot_rows = L.lensmodel.type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC && L.Nreg_percamera > 0;
+    return (int64_t)L.dims.Ncameras_intrinsics*(L.Nreg_percamera + (knot_rows ? L.Ndist_state : 0)) +
+           (L.has_unity_cam01 ? 3 : 0);
+}
+
 inline int64_t num_j_nonzero(const Layout& L,
                              const mrcal_observation_board_t* obs_board,
                              const mrcal_observation_point_t* obs_point,
@@ -257,17 +283,7 @@ inline int64_t num_j_nonzero(const Layout& L,
         }
     }
 
-    // regularization: one column per row, except that each splined-model knot
-    // row mixes the knot's two values
-    if(L.lensmodel.type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC)
-    {
-        if(L.sel.do_apply_regularization)
-            N += (int64_t)d.Ncameras_intrinsics *
-                 (2*L.Ndist_state + (L.sel.do_optimize_intrinsics_core ? 2 : 0));
-    }
-    else
-        N += (int64_t)d.Ncameras_intrinsics * L.Nreg_percamera;
-    if(L.has_unity_cam01) N += 3;
+    N += num_j_nonzero_regularization(L);
     return N;
 }
 

@@ -16,6 +16,8 @@
 #include "problem_object.hpp"
 #include "host_copy.hpp"
 #include "solver_plan.hpp"
+#include "problem_plan.hpp"
+#include <utility>
 #include <thread>
 #include <mutex>
 #include <condition_variable>
@@ -375,7 +377,173 @@ bool problem_evaluate_op(mrcal_amd_problem* P, int i, bool with_jacobian, bool w
 
 } // namespace mrcal_amd
 
-namespace { int& elimination_policy() { static int policy = 0; return policy; } }
+namespace {
+int& elimination_policy() { static int policy = 0; return policy; }
+// Which pose blocks the next problem eliminates where it can choose (plan_problem()): 0 auto, 1 frames, 2 extrinsics.
+// mrcal_amd_set_elimination() wins; without a call the environment variable MRCAL_AMD_ELIMINATE=frames|extrinsics
+// says (for a process that cannot make one)
+int effective_elimination()
+{
+    if(elimination_policy() != 0) return elimination_policy();
+    const char* env = getenv("MRCAL_AMD_ELIMINATE");
+    if(env && !strcmp(env, "frames"))     return 1;
+    if(env && !strcmp(env, "extrinsics")) return 2;
+    return 0;
+}
+}
+
+// ---- problem_create(): the plan (problem_plan.cpp) says what; here it is allocated, uploaded and launched ----
+namespace mrcal_amd {
+
+static bool create_streams(mrcal_amd_problem* P)
+{
+    bool ok = true;
+    HIP_TRY(hipStreamCreateWithFlags(&P->stream, hipStreamNonBlocking), ok = false);
+    HIP_TRY(hipStreamCreateWithFlags(&P->side_stream, hipStreamNonBlocking), ok = false);
+    HIP_TRY(hipEventCreateWithFlags(&P->ev_fork, hipEventDisableTiming), ok = false);
+    HIP_TRY(hipEventCreateWithFlags(&P->ev_join, hipEventDisableTiming), ok = false);
+    HIP_TRY(hipEventCreate(&P->ev_j0), ok = false);
+    HIP_TRY(hipEventCreate(&P->ev_j1), ok = false);
+    return ok;
+}
+
+// the seeds, the observations' records and their pools: of a shard's pools the rows it owns, gathered here
+static bool upload_inputs(mrcal_amd_problem* P, const ProblemInputs& in, const ProblemPlan& plan, bool sharded)
+{
+    const Layout& L = P->L;
+    const int Nboard_local = P->D.Nobs_board, Npoint_local = P->D.Nobs_point, NPTS = P->D.W*P->D.H;
+    std::vector<mrcal_point3_t> pool_local;
+    const mrcal_point3_t* pool_src = in.observations_board_pool;
+    if(sharded)
+    {
+        pool_local.resize((size_t)Nboard_local*NPTS);
+        for(int j=0; j<Nboard_local; j++)
+            memcpy(&pool_local[(size_t)j*NPTS], &in.observations_board_pool[(size_t)P->board_sel[j]*NPTS],
+                   NPTS*sizeof(mrcal_point3_t));
+        pool_src = pool_local.data();
+    }
+    std::vector<mrcal_point3_t> point_pool_local((size_t)(Npoint_local > 0 ? Npoint_local : 1));
+    for(int j=0; j<Npoint_local; j++) point_pool_local[j] = in.observations_point_pool[plan.point_sel[j]];
+    // the triangulated observations' vectors and outlier marks: host copies too, for the outlier logic
+    const int Nt = plan.tri_o1 - plan.tri_o0;
+    P->tri_px_host.resize((size_t)3*Nt + 1);
+    P->tri_outlier_host.resize((size_t)Nt + 1);
+    for(int i=0;i<Nt;i++)
+    {
+        const mrcal_observation_point_triangulated_t& o = in.observations_point_triangulated[plan.tri_o0 + i];
+        for(int j=0;j<3;j++) P->tri_px_host[3*i+j] = o.px.xyz[j];
+        P->tri_outlier_host[i] = o.outlier ? 1 : 0;
+    }
+
+    DeviceBuffers& mem = P->mem;
+    return mem.upload(&P->d_seed_intrinsics,   in.intrinsics,                  (size_t)in.Ncameras_intrinsics*L.Nintrinsics) &&
+           mem.upload(&P->d_seed_rt_cam_ref,   (const double*)in.rt_cam_ref,   (size_t)in.Ncameras_extrinsics*6) &&
+           mem.upload(&P->d_seed_rt_ref_frame, (const double*)in.rt_ref_frame, (size_t)in.Nframes*6) &&
+           mem.upload(&P->d_seed_points,       (const double*)in.points,       (size_t)in.Npoints*3) &&
+           mem.upload(&P->d_board_meta,        plan.bmeta.data(),              (size_t)Nboard_local) &&
+           mem.upload(&P->d_board_pool,        (const double*)pool_src,        (size_t)Nboard_local*NPTS*3) &&
+           mem.upload(&P->d_point_meta,        plan.pmeta.data(),              (size_t)Npoint_local) &&
+           mem.upload(&P->d_point_pool,        (const double*)point_pool_local.data(), (size_t)Npoint_local*3) &&
+           mem.upload(&P->d_imagersizes,       in.imagersizes,                 (size_t)in.Ncameras_intrinsics*2) &&
+           mem.upload(&P->d_tri_meta,          P->tri_meta_host.data(),        P->tri_meta_host.size()) &&
+           mem.upload(&P->d_tri_px,            P->tri_px_host.data(),          (size_t)3*Nt) &&
+           mem.upload(&P->d_tri_outlier,       P->tri_outlier_host.data(),     (size_t)Nt);
+}
+
+// what an evaluation writes: the first operating point, the joint pose records, the CSR structure
+static bool alloc_evaluation_buffers(mrcal_amd_problem* P)
+{
+    const Layout& L = P->L;
+    const int Nboard_local = P->D.Nobs_board;
+    DeviceBuffers& mem = P->mem;
+    bool ok = mem.alloc(&P->op[0].b,  (size_t)L.Nstate) &&
+              // + the unpacked intrinsics and warp (DeviceProblem::unpacked)
+              mem.alloc(&P->d_joint,  (size_t)Nboard_local*JOINT_STRIDE + (size_t)P->D.Ncameras_intrinsics*L.Nintrinsics + 2) &&
+              mem.alloc(&P->op[0].x,  (size_t)L.Nmeas) &&
+              mem.alloc(&P->op[0].Jv, (size_t)P->Nnz);
+    if(L.lensmodel.type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC && Nboard_local > 0)
+        ok = ok && mem.alloc(&P->op[0].spl_box, (size_t)4*Nboard_local);
+    return ok && mem.alloc(&P->d_Jp, (size_t)L.Nmeas+1) && mem.alloc(&P->d_Ji, (size_t)P->Nnz) && problem_sync_ops(P);
+}
+
+static void set_device_pointers(mrcal_amd_problem* P)
+{
+    DeviceProblem& D = P->D;
+    D.seed_intrinsics   = P->d_seed_intrinsics;
+    D.seed_rt_cam_ref   = P->d_seed_rt_cam_ref;
+    D.seed_rt_ref_frame = P->d_seed_rt_ref_frame;
+    D.seed_points       = P->d_seed_points;
+    D.board_meta        = P->d_board_meta;
+    D.board_pool        = P->d_board_pool;
+    D.point_meta        = P->d_point_meta;
+    D.point_pool        = P->d_point_pool;
+    D.imagersizes       = P->d_imagersizes;
+    D.tri_meta          = P->d_tri_meta;
+    D.tri_px            = P->d_tri_px;
+    D.tri_outlier       = P->d_tri_outlier;
+    D.unpacked          = P->d_joint + (size_t)D.Nobs_board*JOINT_STRIDE;
+}
+
+// the seed state, packed, and the iteration-invariant CSR structure
+static bool upload_seed_and_structure(mrcal_amd_problem* P, const ProblemInputs& in)
+{
+    const Layout& L = P->L;
+    P->b_host.assign(L.Nstate > 0 ? L.Nstate : 1, 0.0);
+    pack_state_from_arrays(P->b_host.data(), L, in.intrinsics, in.rt_cam_ref, in.rt_ref_frame, in.points, in.calobject_warp);
+    HIP_TRY(hipMemcpyAsync(P->op[0].b, P->b_host.data(), (size_t)L.Nstate*sizeof(double),
+                           hipMemcpyHostToDevice, P->stream), return false);
+    HIP_TRY(launch_structure(P->D, P->eval_buffers(0,false), P->stream), return false);
+    if(L.Nmeas_regularization <= 0)
+    {
+        const int32_t last = (int32_t)P->Nnz;
+        HIP_TRY(hipMemcpyAsync(&P->d_Jp[L.Nmeas], &last, sizeof(last), hipMemcpyHostToDevice, P->stream), return false);
+    }
+    HIP_TRY(hipStreamSynchronize(P->stream), return false);
+    return true;
+}
+
+mrcal_amd_problem* problem_create(const ProblemInputs& in, const ShardRanges& shard)
+{
+    last_error_string().clear();
+    if(mrcal_amd_device_count() <= 0)
+    {
+        set_error("no HIP device is visible: libmrcal_amd has no CPU fallback");
+        return NULL;
+    }
+    if(!lens_supported(in.lensmodel->type))
+    {
+        char name[128] = "?";
+        mrcal_lensmodel_name(name, sizeof(name), in.lensmodel);
+        set_error("lens model %s (%d) is not implemented on the GPU yet", name, (int)in.lensmodel->type);
+        return NULL;
+    }
+    ProblemPlan plan;
+    std::string refusal;
+    if(!plan_problem(&plan, &refusal, in, shard, effective_elimination()))
+    {
+        set_error("%s", refusal.c_str());
+        return NULL;
+    }
+
+    mrcal_amd_problem* P = new mrcal_amd_problem();
+    P->L = plan.L;  P->D = plan.D;  P->nd = plan.nd;  P->br = plan.br;  P->is_leader = plan.is_leader;
+    P->Nnz = plan.Nnz;  P->board_alg_bytes = plan.board_alg_bytes;  P->lds_bytes = plan.lds_bytes;
+    P->board_sel     = std::move(plan.board_sel);
+    P->tri_meta_host = std::move(plan.tmeta);
+    P->tri_obs0      = plan.tri_o0;
+
+    bool ok = create_streams(P) && upload_inputs(P, in, plan, /* sharded = */ shard.end_frame >= 0) &&
+              alloc_evaluation_buffers(P);
+    if(ok)
+    {
+        set_device_pointers(P);
+        ok = upload_seed_and_structure(P, in);
+    }
+    if(!ok) { delete P; return NULL; }
+    return P;
+}
+
+} // namespace mrcal_amd
 
 // (round 6) The drop-in entry points make a problem, use it once and tear it down: a hipFree call per buffer, each of
 // which waits for the device - 4 ms at the metric's size, a tenth of an mrcal_optimize() call. A problem that nobody can
@@ -521,409 +689,15 @@ mrcal_amd_problem_create_sharded(const double*                 intrinsics,
                          int shard_begin_tripoint, int shard_end_tripoint,
                          bool is_shard_leader)
 {
-    last_error_string().clear();
-
-    if(mrcal_amd_device_count() <= 0)
-    {
-        set_error("no HIP device is visible: libmrcal_amd has no CPU fallback");
-        return NULL;
-    }
-    if(!lens_supported(lensmodel->type))
-    {
-        char name[128] = "?";
-        mrcal_lensmodel_name(name, sizeof(name), lensmodel);
-        set_error("lens model %s (%d) is not implemented on the GPU yet", name, (int)lensmodel->type);
-        return NULL;
-    }
-    if(observations_point_triangulated == NULL || Nobservations_point_triangulated <= 0)
-    {
-        observations_point_triangulated = NULL;
-        Nobservations_point_triangulated = 0;
-    }
-    if(Nobservations_board > 0 &&
-       (calibration_object_width_n <= 0 || calibration_object_height_n <= 0))
-    {
-        set_error("board observations given, but the board has no corners");
-        return NULL;
-    }
-
-    if(Nobservations_board <= 0) { Nobservations_board = 0; calibration_object_width_n = calibration_object_height_n = 0; }
-    if(Nobservations_point <= 0)   Nobservations_point = 0;
-
-    const mrcal_problem_selections_t sel =
-        effective_selections(problem_selections, *lensmodel, Nobservations_board);
-
-    mrcal_amd_problem* P = new mrcal_amd_problem();
-
-    // The STATE layout is global: every shard sees the whole state vector
-    Dims dg;
-    dg.Ncameras_intrinsics = Ncameras_intrinsics;
-    dg.Ncameras_extrinsics = Ncameras_extrinsics;
-    dg.Nframes             = Nframes;
-    dg.Npoints             = Npoints;
-    dg.Npoints_fixed       = Npoints_fixed;
-    dg.Nobservations_board = Nobservations_board;
-    dg.Nobservations_point = Nobservations_point;
-    dg.object_width_n      = calibration_object_width_n;
-    dg.object_height_n     = calibration_object_height_n;
-    const Layout Lg = make_layout(dg, sel, *lensmodel, observations_point_triangulated, Nobservations_point_triangulated);
-
-    // The MEASUREMENT layout is local to the shard
-    // shard_end_frame < 0: the whole problem. Anything else is a shard, even an
-    // empty frame range (a points-only problem under the multi-GPU driver gives
-    // every rank the range (0,0)): only the leader then owns the points, the
-    // triangulated pairs and the regularization rows
-    const bool sharded = shard_end_frame >= 0;
-    if(!sharded) is_shard_leader = true;
-    std::vector<int> board_sel;
-    board_sel.reserve(Nobservations_board);
-    for(int i=0; i<Nobservations_board; i++)
-    {
-        const int f = observations_board[i].iframe;
-        if(!sharded || (f >= shard_begin_frame && f < shard_end_frame))
-            board_sel.push_back(i);
-    }
-    const int Nboard_local = (int)board_sel.size();
-    // discrete points: the shard owns the points [shard_begin_point, shard_end_point) (their 3x3 blocks of JtJ,
-    // their rows of x and J) wherever their observations sit in the caller's array (the API does
-    // not promise point-sorted observations). shard_end_point < 0: all of them on the leader, none elsewhere
-    if(!sharded || shard_end_point < 0) { shard_begin_point = 0; shard_end_point = (!sharded || is_shard_leader) ? Npoints : 0; }
-    std::vector<int> point_sel;
-    for(int i=0; i<Nobservations_point; i++)
-    {
-        const int ip = observations_point[i].i_point;
-        if(ip >= shard_begin_point && ip < shard_end_point) point_sel.push_back(i);
-    }
-    const int Npoint_local = (int)point_sel.size();
-    // triangulated points: a point's observations are consecutive (last_in_set ends the set) and its pairs are its
-    // own, so the shard takes the point SETS [shard_begin_tripoint, shard_end_tripoint): one contiguous range of
-    // observations [tri_o0, tri_o1). < 0: all with the leader
-    int tri_o0 = 0, tri_o1 = 0;
-    {
-        if(!sharded || shard_end_tripoint < 0) { shard_begin_tripoint = 0; shard_end_tripoint = (!sharded || is_shard_leader) ? 0x7fffffff : 0; }
-        int iset = 0;
-        bool in_range = false;
-        for(int i=0; i<Nobservations_point_triangulated; i++)
-        {
-            const bool mine = iset >= shard_begin_tripoint && iset < shard_end_tripoint;
-            if(mine && !in_range) { tri_o0 = i; in_range = true; }
-            if(mine) tri_o1 = i + 1;
-            if(observations_point_triangulated[i].last_in_set) iset++;
-        }
-        if(!in_range) tri_o0 = tri_o1 = 0;
-    }
-    const int Ntri_local = tri_o1 - tri_o0;
-    const mrcal_observation_point_triangulated_t* tri_local = (Ntri_local > 0) ? observations_point_triangulated + tri_o0 : NULL;
-
-    Layout L = Lg;
-    L.dims.Nobservations_board = Nboard_local;   // NOTE: has_warp etc. stay global
-    L.dims.Nobservations_point = Npoint_local;
-    L.Nmeas_boards         = Nboard_local * calibration_object_width_n*calibration_object_height_n * 2;
-    L.Nmeas_points         = Npoint_local * 2;
-    L.Nmeas_triangulated   = num_measurements_triangulated_initial(tri_local, Ntri_local, -1);
-    if(!is_shard_leader) { L.Nmeas_regularization = 0; L.has_unity_cam01 = false; L.Nreg_percamera = 0; }
-    L.i_meas_boards         = 0;
-    L.i_meas_points         = L.Nmeas_boards;
-    L.i_meas_triangulated   = L.i_meas_points + L.Nmeas_points;
-    L.i_meas_regularization = L.i_meas_triangulated + L.Nmeas_triangulated;
-    L.Nmeas                 = L.i_meas_regularization + L.Nmeas_regularization;
-    P->L = L;
-
-    const int NPTS = calibration_object_width_n*calibration_object_height_n;
-
-    // per-observation metadata + CSR offsets
-    std::vector<BoardObsMeta> bmeta(Nboard_local);
-    int64_t innz = 0;
-    int     imeas = 0;
-    int     kmax  = 0;
-    for(int j=0; j<Nboard_local; j++)
-    {
-        const mrcal_observation_board_t& o = observations_board[board_sel[j]];
-        BoardObsMeta& m = bmeta[j];
-        memset(&m, 0, sizeof(m));
-        m.icam_intrinsics    = o.icam.intrinsics;
-        m.icam_extrinsics    = o.icam.extrinsics;
-        m.iframe             = o.iframe;
-        m.nnz_per_row        = nnz_per_board_row(L, o.icam.extrinsics);
-        m.i_state_intrinsics = (L.Nintr_state > 0) ? L.i_state_intrinsics + o.icam.intrinsics*L.Nintr_state : -1;
-        m.i_state_extrinsics = (L.Nstate_extrinsics > 0 && o.icam.extrinsics >= 0) ? L.i_state_extrinsics + 6*o.icam.extrinsics : -1;
-        m.i_state_frame      = (L.Nstate_frames > 0) ? L.i_state_frames + 6*o.iframe : -1;
-        m.i_meas0            = imeas;
-        m.i_nnz0             = innz;
-        imeas += 2*NPTS;
-        innz  += (int64_t)2*NPTS*m.nnz_per_row;
-        if(m.nnz_per_row > kmax) kmax = m.nnz_per_row;
-    }
-    // per board observation 24 P (read qx,qy,w) + 16 P (write x) + 16 P k (write J values)
-    P->board_alg_bytes = (int64_t)Nboard_local*NPTS*(24 + 16) + innz*8;
-    std::vector<PointObsMeta> pmeta(Npoint_local);
-    for(int j=0; j<Npoint_local; j++)
-    {
-        const mrcal_observation_point_t& o = observations_point[point_sel[j]];
-        PointObsMeta& m = pmeta[j];
-        memset(&m, 0, sizeof(m));
-        const bool variable = sel.do_optimize_frames && o.i_point < Npoints - Npoints_fixed;
-        m.icam_intrinsics    = o.icam.intrinsics;
-        m.icam_extrinsics    = o.icam.extrinsics;
-        m.i_point            = o.i_point;
-        m.nnz_per_row        = nnz_per_point_row(L, o.icam.extrinsics, o.i_point);
-        m.i_state_intrinsics = (L.Nintr_state > 0) ? L.i_state_intrinsics + o.icam.intrinsics*L.Nintr_state : -1;
-        m.i_state_extrinsics = (L.Nstate_extrinsics > 0 && o.icam.extrinsics >= 0) ? L.i_state_extrinsics + 6*o.icam.extrinsics : -1;
-        m.i_state_point      = variable ? L.i_state_points + 3*o.i_point : -1;
-        m.i_meas0            = imeas;
-        m.i_nnz0             = innz;
-        imeas += 2;
-        innz  += 2*m.nnz_per_row;
-    }
-    // triangulated points: one row per pair (i0 < i1) of observations of a point
-    std::vector<TriPairMeta> tmeta;
-    if(L.Nmeas_triangulated > 0)
-    {
-        const mrcal_observation_point_triangulated_t* ot = tri_local;      // (indices local to the shard's range)
-        for(int i0 = 0; i0 < Ntri_local; i0++)
-        {
-            if(ot[i0].last_in_set) continue;
-            for(int i1 = i0+1; i1 < Ntri_local; i1++)
-            {
-                TriPairMeta m;
-                memset(&m, 0, sizeof(m));
-                m.i0 = i0; m.i1 = i1;
-                m.icam_extrinsics0 = ot[i0].icam.extrinsics;
-                m.icam_extrinsics1 = ot[i1].icam.extrinsics;
-                m.i_state_extrinsics0 = (L.Nstate_extrinsics > 0 && m.icam_extrinsics0 >= 0) ? L.i_state_extrinsics + 6*m.icam_extrinsics0 : -1;
-                m.i_state_extrinsics1 = (L.Nstate_extrinsics > 0 && m.icam_extrinsics1 >= 0) ? L.i_state_extrinsics + 6*m.icam_extrinsics1 : -1;
-                m.i_meas = imeas;
-                m.i_nnz0 = innz;
-                imeas += 1;
-                innz  += (m.i_state_extrinsics0 >= 0 ? 6 : 0) + (m.i_state_extrinsics1 >= 0 ? 6 : 0);
-                tmeta.push_back(m);
-                if(ot[i1].last_in_set) break;
-            }
-        }
-        if((int)tmeta.size() != L.Nmeas_triangulated)
-        {
-            set_error("internal error: %d triangulated pairs, the layout says %d", (int)tmeta.size(), L.Nmeas_triangulated);
-            delete P;
-            return NULL;
-        }
-    }
-    const int64_t innz_reg = innz;
-    if(L.Nmeas_regularization > 0)
-    {
-        // one nonzero per row, except the splined models' knot rows, which have 2 (mrcal.c:847-869)
-        if(lensmodel->type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC)
-            innz += (int64_t)Ncameras_intrinsics*(L.Nreg_percamera + (sel.do_apply_regularization ? L.Ndist_state : 0));
-        else
-            innz += (int64_t)Ncameras_intrinsics*L.Nreg_percamera;
-        innz += (L.has_unity_cam01 ? 3 : 0);
-    }
-    P->Nnz = innz;
-    if(innz > 0x7fffffffLL)
-    {
-        // the reference's CSR uses int32 offsets (cholmod itype int); so do we
-        set_error("Jacobian has %lld nonzeros: more than int32 CSR offsets can address. Shard the problem", (long long)innz);
-        delete P;
-        return NULL;
-    }
-    // tile columns: k, +2 for the full core, +1 for the residual column (see board_kernel)
-    // LDS of the board kernel: the 64-row tile + the observation's pixels and
-    // weights (the splined models' kernels use none)
-    const bool splined = (lensmodel->type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC);
-    // the tile + the staged observation (in whole 64-element chunks) + the joint pose record
-    P->lds_bytes = splined ? 0 : (64*tile_stride(L.Ndist) + ((3*NPTS + 63) & ~63) + JOINT_REC + 4) * (int)sizeof(double);
-    if(P->lds_bytes > 160*1024)
-    {
-        set_error("the board has %d corners and the lens model %d distortion parameters: the LDS tile would not fit", NPTS, L.Ndist);
-        delete P;
-        return NULL;
-    }
-    (void)kmax;
-
-    // board pool of the local observations
-    std::vector<mrcal_point3_t> pool_local;
-    const mrcal_point3_t* pool_src = observations_board_pool;
-    if(sharded)
-    {
-        pool_local.resize((size_t)Nboard_local*NPTS);
-        for(int j=0; j<Nboard_local; j++)
-            memcpy(&pool_local[(size_t)j*NPTS], &observations_board_pool[(size_t)board_sel[j]*NPTS],
-                   NPTS*sizeof(mrcal_point3_t));
-        pool_src = pool_local.data();
-    }
-    P->board_sel = board_sel;
-    std::vector<mrcal_point3_t> point_pool_local((size_t)(Npoint_local > 0 ? Npoint_local : 1));
-    for(int j=0; j<Npoint_local; j++) point_pool_local[j] = observations_point_pool[point_sel[j]];
-
-    bool ok = true;
-    HIP_TRY(hipStreamCreateWithFlags(&P->stream, hipStreamNonBlocking), ok = false);
-    HIP_TRY(hipStreamCreateWithFlags(&P->side_stream, hipStreamNonBlocking), ok = false);
-    HIP_TRY(hipEventCreateWithFlags(&P->ev_fork, hipEventDisableTiming), ok = false);
-    HIP_TRY(hipEventCreateWithFlags(&P->ev_join, hipEventDisableTiming), ok = false);
-    HIP_TRY(hipEventCreate(&P->ev_j0), ok = false);
-    HIP_TRY(hipEventCreate(&P->ev_j1), ok = false);
-
-    ok = ok && P->mem.upload(&P->d_seed_intrinsics,   intrinsics,                  (size_t)Ncameras_intrinsics*L.Nintrinsics);
-    ok = ok && P->mem.upload(&P->d_seed_rt_cam_ref,   (const double*)rt_cam_ref,   (size_t)Ncameras_extrinsics*6);
-    ok = ok && P->mem.upload(&P->d_seed_rt_ref_frame, (const double*)rt_ref_frame, (size_t)Nframes*6);
-    ok = ok && P->mem.upload(&P->d_seed_points,       (const double*)points,       (size_t)Npoints*3);
-    ok = ok && P->mem.upload(&P->d_board_meta,        bmeta.data(),                (size_t)Nboard_local);
-    ok = ok && P->mem.upload(&P->d_board_pool,        (const double*)pool_src,     (size_t)Nboard_local*NPTS*3);
-    ok = ok && P->mem.upload(&P->d_point_meta,        pmeta.data(),                (size_t)Npoint_local);
-    ok = ok && P->mem.upload(&P->d_point_pool,        (const double*)point_pool_local.data(), (size_t)Npoint_local*3);
-    ok = ok && P->mem.upload(&P->d_imagersizes,       imagersizes,                 (size_t)Ncameras_intrinsics*2);
-    {
-        const int Nt = Ntri_local;
-        P->tri_obs0 = tri_o0;
-        P->tri_meta_host = tmeta;
-        P->tri_px_host.resize((size_t)3*Nt + 1);
-        P->tri_outlier_host.resize((size_t)Nt + 1);
-        for(int i=0;i<Nt;i++)
-        {
-            for(int j=0;j<3;j++) P->tri_px_host[3*i+j] = tri_local[i].px.xyz[j];
-            P->tri_outlier_host[i] = tri_local[i].outlier ? 1 : 0;
-        }
-        ok = ok && P->mem.upload(&P->d_tri_meta,    tmeta.data(),                tmeta.size());
-        ok = ok && P->mem.upload(&P->d_tri_px,      P->tri_px_host.data(),       (size_t)3*Nt);
-        ok = ok && P->mem.upload(&P->d_tri_outlier, P->tri_outlier_host.data(),  (size_t)Nt);
-    }
-    ok = ok && P->mem.alloc(&P->op[0].b,  (size_t)L.Nstate);
-    // + the unpacked intrinsics and warp (DeviceProblem::unpacked)
-    ok = ok && P->mem.alloc(&P->d_joint,  (size_t)Nboard_local*JOINT_STRIDE + (size_t)Ncameras_intrinsics*L.Nintrinsics + 2);
-    ok = ok && P->mem.alloc(&P->op[0].x,  (size_t)L.Nmeas);
-    ok = ok && P->mem.alloc(&P->op[0].Jv, (size_t)innz);
-    if(L.lensmodel.type == MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC && Nboard_local > 0)
-        ok = ok && P->mem.alloc(&P->op[0].spl_box, (size_t)4*Nboard_local);
-    ok = ok && P->mem.alloc(&P->d_Jp,     (size_t)L.Nmeas+1);
-    ok = ok && P->mem.alloc(&P->d_Ji,     (size_t)innz);
-    if(!ok) { delete P; return NULL; }
-    if(!problem_sync_ops(P)) { delete P; return NULL; }
-
-    {
-        NormalDims& nd = P->nd;
-        nd.Nstate       = L.Nstate;
-        nd.Nwarp        = L.Nstate_warp;
-        nd.i_state_warp = L.i_state_warp;
-        // Which pose blocks are eliminated (NormalDims, solver_kernels.hpp): the frames and points, unless the
-        // extrinsics are the numerous ones - a moving camera against a stationary board, many rt_cam_ref and
-        // few frames (test_calibration_helpers.py:422-493 builds such problems) - and every row touches at most
-        // one of them, and only board rows touch them: a camera's block is then written whole by the workgroup
-        // that sums its observations' Grams, as a frame's is (no triangulated pairs, no discrete points, no
-        // unity_cam01 row). The splined models' assembly and the sharding know frames only.
-        // mrcal_amd_set_elimination() overrides the choice where both are possible; without a call the environment
-        // variable MRCAL_AMD_ELIMINATE=frames|extrinsics does (for a process that cannot make one)
-        bool elimx = !sharded && lensmodel->type != MRCAL_LENSMODEL_SPLINED_STEREOGRAPHIC && Ntri_local == 0 &&
-                     Npoint_local == 0 && !sel.do_apply_regularization_unity_cam01 && L.Nstate_extrinsics > 0;
-        if(elimx)
-        {
-            const char* env = getenv("MRCAL_AMD_ELIMINATE");
-            if(elimination_policy() == 1)              elimx = false;
-            else if(elimination_policy() == 2)         elimx = true;
-            else if(env && !strcmp(env, "frames"))     elimx = false;
-            else if(env && !strcmp(env, "extrinsics")) elimx = true;
-            else elimx = Ncameras_extrinsics >= 4 && L.Nstate_frames + L.Nstate_points < L.Nstate_extrinsics;
-        }
-        if(!elimx)
-        {
-            nd.Nc  = L.Nstate_intrinsics + L.Nstate_extrinsics + nd.Nwarp;
-            nd.NE  = L.Nstate_frames + L.Nstate_points;
-            nd.Nfb = L.Nstate_frames/6;
-            nd.Npb = L.Nstate_points/3;
-            normal_dims_set_partition(nd, L.Nstate_intrinsics + L.Nstate_extrinsics);
-        }
-        else
-        {
-            nd.NE  = L.Nstate_extrinsics;
-            nd.Nc  = L.Nstate - nd.NE;
-            nd.Nfb = L.Nstate_extrinsics/6;
-            nd.Npb = 0;
-            nd.S_split = L.Nstate_intrinsics; nd.S_shift = nd.NE; nd.E_state0 = L.Nstate_intrinsics;
-            nd.elim_extrinsics = 1;
-        }
-        nd.NEb          = nd.Nfb + nd.Npb;
-        P->is_leader    = is_shard_leader;
-        P->br.frame_lo  = 0;  P->br.frame_hi = nd.Nfb;
-        if(sharded && nd.Nfb > 0)
-        {
-            P->br.frame_lo = shard_begin_frame < 0 ? 0 : shard_begin_frame;
-            P->br.frame_hi = (shard_end_frame < 0 || shard_end_frame > Nframes) ? Nframes : shard_end_frame;
-        }
-        // the point blocks (the variable points only) of the shard's point range
-        {
-            auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
-            P->br.point_lo = nd.Nfb + clampi(shard_begin_point, 0, nd.Npb);
-            P->br.point_hi = nd.Nfb + clampi(shard_end_point,   0, nd.Npb);
-            if(P->br.point_hi < P->br.point_lo) P->br.point_hi = P->br.point_lo;
-        }
-    }
-
-    DeviceProblem& D = P->D;
-    memset(&D, 0, sizeof(D));
-    D.lens_type   = (int)lensmodel->type;
-    D.Nintrinsics = L.Nintrinsics;   D.Ncore = L.Ncore;        D.Ncore_state = L.Ncore_state;
-    D.Ndist       = L.Ndist;         D.Ndist_state = L.Ndist_state; D.Nintr_state = L.Nintr_state;
-    D.Ndist_row   = L.Nintr_per_row - (L.Ncore_state ? 2 : 0);
-    D.i_state_intrinsics = L.i_state_intrinsics < 0 ? 0 : L.i_state_intrinsics;
-    D.i_state_extrinsics = L.i_state_extrinsics;
-    D.i_state_frames     = L.i_state_frames;
-    D.i_state_points     = L.i_state_points;
-    D.i_state_warp       = L.i_state_warp;
-    D.Nstate = L.Nstate;  D.Nmeas = L.Nmeas;
-    D.do_optimize_extrinsics = L.Nstate_extrinsics > 0;
-    D.do_optimize_frames     = sel.do_optimize_frames;
-    D.elim_extrinsics        = P->nd.elim_extrinsics;
-    D.has_warp_state         = L.has_warp;
-    D.has_warp_seed          = (calobject_warp != NULL);
-    D.Ncameras_intrinsics = Ncameras_intrinsics; D.Ncameras_extrinsics = Ncameras_extrinsics;
-    D.Nframes = Nframes; D.Npoints = Npoints; D.Npoints_fixed = Npoints_fixed;
-    D.Nobs_board = Nboard_local; D.Nobs_point = Npoint_local;
-    D.W = calibration_object_width_n; D.H = calibration_object_height_n;
-    D.spacing = calibration_object_spacing;
-    D.inv_Wm1 = 1.0/(double)(D.W - 1);      // (W = 1 or H = 1 with a warp: the reference divides by zero just the same)
-    D.inv_Hm1 = 1.0/(double)(D.H - 1);
-    if(calobject_warp) { D.seed_warp[0] = calobject_warp->x2; D.seed_warp[1] = calobject_warp->y2; }
-    D.cfg = lens_config_of(*lensmodel);
-    D.do_apply_regularization = sel.do_apply_regularization && is_shard_leader;
-    D.has_unity_cam01         = L.has_unity_cam01;
-    D.i_meas_regularization   = L.i_meas_regularization;
-    D.i_nnz_regularization    = innz_reg;
-    D.imager_width_cam0       = (Ncameras_intrinsics > 0) ? (double)imagersizes[0] : 1.0;
-    D.seed_intrinsics   = P->d_seed_intrinsics;
-    D.seed_rt_cam_ref   = P->d_seed_rt_cam_ref;
-    D.seed_rt_ref_frame = P->d_seed_rt_ref_frame;
-    D.seed_points       = P->d_seed_points;
-    D.board_meta        = P->d_board_meta;
-    D.board_pool        = P->d_board_pool;
-    D.point_meta        = P->d_point_meta;
-    D.point_pool        = P->d_point_pool;
-    D.imagersizes       = P->d_imagersizes;
-    D.Npairs_tri        = (int)P->tri_meta_host.size();
-    D.tri_meta          = P->d_tri_meta;
-    D.tri_px            = P->d_tri_px;
-    D.tri_outlier       = P->d_tri_outlier;
-    D.unpacked          = P->d_joint + (size_t)Nboard_local*JOINT_STRIDE;
-    // (round 6) where the triangulated pairs ride in the board kernel's launch (board_tri_kernel) the launch the
-    // benchmark times carries their bytes too: per pair two observation vectors and the record read, x and the
-    // (up to) 12 partials written
-    if(board_launch_takes_triangulated(D))
-        for(const TriPairMeta& m : P->tri_meta_host)
-            P->board_alg_bytes += 2*24 + (int64_t)sizeof(TriPairMeta) + 8 + 8*((m.i_state_extrinsics0 >= 0 ? 6 : 0) + (m.i_state_extrinsics1 >= 0 ? 6 : 0));
-
-    // the seed state
-    P->b_host.assign(L.Nstate > 0 ? L.Nstate : 1, 0.0);
-    pack_state_from_arrays(P->b_host.data(), L, intrinsics, rt_cam_ref, rt_ref_frame, points, calobject_warp);
-    HIP_TRY(hipMemcpyAsync(P->op[0].b, P->b_host.data(), (size_t)L.Nstate*sizeof(double),
-                           hipMemcpyHostToDevice, P->stream), { delete P; return NULL; });
-
-    // iteration-invariant CSR structure
-    HIP_TRY(launch_structure(D, P->eval_buffers(0,false), P->stream), { delete P; return NULL; });
-    if(L.Nmeas_regularization <= 0)
-    {
-        const int32_t last = (int32_t)innz;
-        HIP_TRY(hipMemcpyAsync(&P->d_Jp[L.Nmeas], &last, sizeof(last), hipMemcpyHostToDevice, P->stream),
-                { delete P; return NULL; });
-    }
-    HIP_TRY(hipStreamSynchronize(P->stream), { delete P; return NULL; });
-    return P;
+    const ProblemInputs in = { intrinsics, rt_cam_ref, rt_ref_frame, points, calobject_warp,
+                               Ncameras_intrinsics, Ncameras_extrinsics, Nframes, Npoints, Npoints_fixed,
+                               observations_board, observations_point, Nobservations_board, Nobservations_point,
+                               observations_point_triangulated, Nobservations_point_triangulated,
+                               observations_board_pool, observations_point_pool, lensmodel, imagersizes,
+                               problem_selections, calibration_object_spacing,
+                               calibration_object_width_n, calibration_object_height_n };
+    return problem_create(in, ShardRanges{ shard_begin_frame, shard_end_frame, shard_begin_point, shard_end_point,
+                                           shard_begin_tripoint, shard_end_tripoint, is_shard_leader });
 }
 
 mrcal_amd_problem_t*
@@ -951,15 +725,15 @@ mrcal_amd_problem_create(const double*                 intrinsics,
                          int shard_begin_frame, int shard_end_frame,
                          bool is_shard_leader)
 {
+    const ProblemInputs in = { intrinsics, rt_cam_ref, rt_ref_frame, points, calobject_warp,
+                               Ncameras_intrinsics, Ncameras_extrinsics, Nframes, Npoints, Npoints_fixed,
+                               observations_board, observations_point, Nobservations_board, Nobservations_point,
+                               observations_point_triangulated, Nobservations_point_triangulated,
+                               observations_board_pool, observations_point_pool, lensmodel, imagersizes,
+                               problem_selections, calibration_object_spacing,
+                               calibration_object_width_n, calibration_object_height_n };
     // the shard leader owns every discrete and triangulated point
-    return mrcal_amd_problem_create_sharded(intrinsics, rt_cam_ref, rt_ref_frame, points, calobject_warp,
-                                            Ncameras_intrinsics, Ncameras_extrinsics, Nframes, Npoints, Npoints_fixed,
-                                            observations_board, observations_point, Nobservations_board, Nobservations_point,
-                                            observations_point_triangulated, Nobservations_point_triangulated,
-                                            observations_board_pool, observations_point_pool, lensmodel, imagersizes,
-                                            problem_selections, calibration_object_spacing,
-                                            calibration_object_width_n, calibration_object_height_n,
-                                            shard_begin_frame, shard_end_frame, 0, -1, 0, -1, is_shard_leader);
+    return problem_create(in, ShardRanges{ shard_begin_frame, shard_end_frame, 0, -1, 0, -1, is_shard_leader });
 }
 
 void mrcal_amd_problem_destroy(mrcal_amd_problem_t* problem)
@@ -1210,18 +984,14 @@ bool mrcal_optimizer_callback(double* b_packed, int buffer_size_b_packed,
         return false;
     }
 
-    mrcal_amd_problem_t* P =
-        mrcal_amd_problem_create(intrinsics, rt_cam_ref, rt_ref_frame, points, calobject_warp,
-                                 Ncameras_intrinsics, Ncameras_extrinsics, Nframes,
-                                 Npoints, Npoints_fixed,
-                                 observations_board, observations_point,
-                                 Nobservations_board, Nobservations_point,
-                                 observations_point_triangulated, Nobservations_point_triangulated,
-                                 observations_board_pool, observations_point_pool,
-                                 lensmodel, imagersizes, sel,
-                                 calibration_object_spacing,
-                                 calibration_object_width_n, calibration_object_height_n,
-                                 0, -1, true);
+    const ProblemInputs in = { intrinsics, rt_cam_ref, rt_ref_frame, points, calobject_warp,
+                               Ncameras_intrinsics, Ncameras_extrinsics, Nframes, Npoints, Npoints_fixed,
+                               observations_board, observations_point, Nobservations_board, Nobservations_point,
+                               observations_point_triangulated, Nobservations_point_triangulated,
+                               observations_board_pool, observations_point_pool, lensmodel, imagersizes,
+                               sel, calibration_object_spacing,
+                               calibration_object_width_n, calibration_object_height_n };
+    mrcal_amd_problem_t* P = problem_create(in, ShardRanges{ 0, -1, 0, -1, 0, -1, true });
     if(P == NULL) return false;
 
     bool ok = false;

@@ -8,6 +8,7 @@
 #include "kernels.hpp"
 #include "solver_kernels.hpp"
 #include "device_memory.hpp"
+#include "problem_plan.hpp"
 
 // One operating point of the dog-leg iteration: the state, the cost function
 // there (x, J) and its normal equations. The solver flips between two of these
@@ -140,6 +141,9 @@ struct mrcal_amd_problem
 };
 
 namespace mrcal_amd {
+// what the two creators and the two drop-in entry points make their problem with: plan_problem(), then the device
+// half. NULL: set_error() says why
+mrcal_amd_problem* problem_create(const ProblemInputs& in, const ShardRanges& shard);
 // allocates the second operating point and all solver scratch, once: true again after it succeeded, the same error again after it failed
 bool problem_prepare_solver(mrcal_amd_problem* P);
 // x, J (and the normal equations if with_normal) at op[i].b

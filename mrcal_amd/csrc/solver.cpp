@@ -986,18 +986,14 @@ mrcal_optimize( double* b_packed, int buffer_size_b_packed,
        !sel.do_optimize_calobject_warp)
         fprintf(stderr, "mrcal_amd: Warning: Not optimizing any of our variables\n");
 
-    mrcal_amd_problem_t* P =
-        mrcal_amd_problem_create(intrinsics, rt_cam_ref, rt_ref_frame, points, calobject_warp,
-                                 Ncameras_intrinsics, Ncameras_extrinsics, Nframes,
-                                 Npoints, Npoints_fixed,
-                                 observations_board, observations_point,
-                                 Nobservations_board, Nobservations_point,
-                                 observations_point_triangulated, Nobservations_point_triangulated,
-                                 observations_board_pool, observations_point_pool,
-                                 lensmodel, imagersizes, sel,
-                                 calibration_object_spacing,
-                                 calibration_object_width_n, calibration_object_height_n,
-                                 0, -1, true);
+    const ProblemInputs in = { intrinsics, rt_cam_ref, rt_ref_frame, points, calobject_warp,
+                               Ncameras_intrinsics, Ncameras_extrinsics, Nframes, Npoints, Npoints_fixed,
+                               observations_board, observations_point, Nobservations_board, Nobservations_point,
+                               observations_point_triangulated, Nobservations_point_triangulated,
+                               observations_board_pool, observations_point_pool, lensmodel, imagersizes,
+                               sel, calibration_object_spacing,
+                               calibration_object_width_n, calibration_object_height_n };
+    mrcal_amd_problem_t* P = problem_create(in, ShardRanges{ 0, -1, 0, -1, 0, -1, true });
     if(P == NULL) return failed;
 
     mrcal_stats_t stats = failed;
