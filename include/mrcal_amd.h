@@ -882,6 +882,76 @@ bool   mrcal_amd_projection_diff_evaluate(mrcal_amd_projection_diff_t* pd,
 double mrcal_amd_projection_diff_time_fit(mrcal_amd_projection_diff_t* pd, bool on);
 void   mrcal_amd_projection_diff_destroy(mrcal_amd_projection_diff_t* pd);
 
+/* ---- triangulation: mrcal.triangulate_*() ----------------------------------
+   Reference: triangulation.h / triangulation.cc (mrcal_triangulate_geometric, _lindstrom, _leecivera_l1, _linf,
+   _mid2, _wmid2), broadcast by mrcal/triangulation.py. The batch forms ON THE GPU, one lane per pair
+   (csrc/triangulation.hip over csrc/triangulation_math.hpp): host arrays in and out.
+     v0, v1 (N,3): the two observation vectors, not necessarily normalized, BOTH in camera-0 coordinates;
+     t01 (N,3):    the origin of camera 1 in camera-0 coordinates;
+     p (N,3):      the point in camera-0 coordinates; (0,0,0) where the rays are parallel or divergent;
+     dp_dv0, dp_dv1, dp_dt01 (N,3,3): the gradients; each may be NULL. All zero where p is (0,0,0).
+   _lindstrom() differs as the reference's does: v0_local, v1_local are in their OWN cameras' coordinates, the pose
+   is the whole Rt01 (N,4,3), and its gradient dp_dRt01 is (N,3,4,3).
+   p has the same bits with and without gradients, and on every call */
+bool mrcal_amd_triangulate_geometric      (int N, const double* v0, const double* v1, const double* t01,
+                                           double* p, double* dp_dv0, double* dp_dv1, double* dp_dt01);
+bool mrcal_amd_triangulate_lindstrom      (int N, const double* v0_local, const double* v1_local, const double* Rt01,
+                                           double* p, double* dp_dv0, double* dp_dv1, double* dp_dRt01);
+bool mrcal_amd_triangulate_leecivera_l1   (int N, const double* v0, const double* v1, const double* t01,
+                                           double* p, double* dp_dv0, double* dp_dv1, double* dp_dt01);
+bool mrcal_amd_triangulate_leecivera_linf (int N, const double* v0, const double* v1, const double* t01,
+                                           double* p, double* dp_dv0, double* dp_dv1, double* dp_dt01);
+bool mrcal_amd_triangulate_leecivera_mid2 (int N, const double* v0, const double* v1, const double* t01,
+                                           double* p, double* dp_dv0, double* dp_dv1, double* dp_dt01);
+bool mrcal_amd_triangulate_leecivera_wmid2(int N, const double* v0, const double* v1, const double* t01,
+                                           double* p, double* dp_dv0, double* dp_dv1, double* dp_dt01);
+
+/* ---- mrcal.triangulate(): pixel pairs -> points, with the noise propagated ----
+   Reference: mrcal/triangulation.py:1090-2018 (triangulate(), _triangulation_uncertainty_internal(),
+   _compute_Var_q_triangulation()), mrcal/model_analysis.py:560-870 (_propagate_calibration_uncertainty()).
+   The resident form. _create(): a table of cameras, each with its lens model, intrinsics and rt_cam_ref; with a
+   problem (the calibration all the cameras came out of, at its solved state) also icam_intrinsics and
+   icam_extrinsics (< 0: the camera at the reference) in it, and then every camera has the problem's lens model. The
+   factorization of J*^T J*, the regularization rows of J, the frames and the estimate of the observed pixel
+   uncertainty are made here, once; the problem may be changed or destroyed afterwards. problem == NULL: a context
+   that cannot propagate calibration-time noise. A CAHVORE camera must have E = 0.
+   _evaluate(): q (N,2,2) pixels, icam (N,2) the two cameras of each pair in the table, method one of
+   MRCAL_AMD_TRIANGULATE_*; all host arrays.
+     p (N,3):                 the points in the coordinates of each pair's first camera; (0,0,0) for divergent rays
+     q_observation_stdev > 0: Var_p_observation (N,3,3) = dp/dq Var_q dp/dq^T, Var_q the 4x4 with
+                              q_observation_stdev^2 on the diagonal and (q_observation_stdev
+                              q_observation_stdev_correlation)^2 between q0x,q1x and between q0y,q1y. 0: not computed
+     q_calibration_stdev:     0: not computed. > 0: the calibration-time pixel noise; < 0: the estimate is used.
+                              Var_p_calibration (3N,3N), with the cross terms between the pairs:
+                              sigma^2 F (J*^T J*)^-1 J*[obs]^T J*[obs] (J*^T J*)^-1 F^T, F = dp/db_packed, with
+                              stabilize_coords in the coordinates of the first camera's housing
+   MRCAL_AMD_TRIANGULATE_LINDSTROM only without noise. Nothing uses floating-point atomics: the same bits on every
+   call. NULL / false on failure (mrcal_amd_last_error(): the reference's messages) */
+#define MRCAL_AMD_TRIANGULATE_GEOMETRIC       0
+#define MRCAL_AMD_TRIANGULATE_LINDSTROM       1
+#define MRCAL_AMD_TRIANGULATE_LEECIVERA_L1    2
+#define MRCAL_AMD_TRIANGULATE_LEECIVERA_LINF  3
+#define MRCAL_AMD_TRIANGULATE_LEECIVERA_MID2  4
+#define MRCAL_AMD_TRIANGULATE_LEECIVERA_WMID2 5
+typedef struct
+{
+    mrcal_lensmodel_t lensmodel;
+    const double*     intrinsics;       /* the lens model's number of parameters */
+    double            rt_cam_ref[6];
+    int               icam_intrinsics;  /* in the problem; not read without one */
+    int               icam_extrinsics;  /* in the problem; < 0: at the reference */
+} mrcal_amd_triangulation_camera_t;
+typedef struct mrcal_amd_triangulation mrcal_amd_triangulation_t;
+mrcal_amd_triangulation_t*
+mrcal_amd_triangulation_create(mrcal_amd_problem_t* problem, int Ncameras, const mrcal_amd_triangulation_camera_t* cameras);
+bool   mrcal_amd_triangulation_evaluate(mrcal_amd_triangulation_t* t, int N, const double* q, const int* icam, int method,
+                                        double q_calibration_stdev, double q_observation_stdev,
+                                        double q_observation_stdev_correlation, bool stabilize_coords,
+                                        double* p, double* Var_p_observation, double* Var_p_calibration);
+/* the estimate of the calibration-time pixel noise; < 0: there is none (no problem, or no observations in it) */
+double mrcal_amd_triangulation_observed_pixel_uncertainty(const mrcal_amd_triangulation_t* t);
+void   mrcal_amd_triangulation_destroy(mrcal_amd_triangulation_t* t);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,9 @@ unproject                             = _api.unproject
 from ._factorization import CHOLMOD_factorization, _Jt_x, _A_Jt_J_At, _A_Jt_J_At__2
 from .model_analysis import (projection_uncertainty, ProjectionUncertainty, worst_direction_stdev,
                              implied_Rt10__from_unprojections, projection_diff)
+from .triangulation import (triangulate_geometric, triangulate_lindstrom, triangulate_leecivera_l1,
+                            triangulate_leecivera_linf, triangulate_leecivera_mid2, triangulate_leecivera_wmid2,
+                            triangulate, Triangulation)
 from .utils import sample_imager, sample_imager_unproject
 
 # the callers either side of the path: the on-disk format of
@@ -92,6 +95,14 @@ def gpu_available():
     f = _lib.lib.mrcal_amd_device_count
     f.restype = ctypes.c_int
     return f() > 0
+
+
+def device_buffers_live():
+    """how many device (and pinned host) buffers the library's objects hold at this moment"""
+    import ctypes
+    f = _lib.lib.mrcal_amd_device_buffers_live
+    f.restype, f.argtypes = ctypes.c_long, []
+    return f()
 
 
 def set_optimize_jacobian_stream(stream):

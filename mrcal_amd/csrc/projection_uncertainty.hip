@@ -332,6 +332,34 @@ hipError_t launch_points(const PUArgs& a, const double* C, const double* intr, c
 
 } // namespace
 
+namespace mrcal_amd {
+// The estimate of the observed pixel uncertainty (model_analysis.py:491-557), for this file and triangulation.hip.
+// Queues on st: the sums over the board and point measurements of x at the problem's current operating point
+// (d_sig[2], a device buffer of the caller's), and their copy to sig[2], which is complete once st has been waited for
+bool queue_observed_pixel_sums(mrcal_amd_problem* P, double* d_sig, double* sig, hipStream_t st)
+{
+    const Layout& L = P->L;
+    hipLaunchKernelGGL(pu_sigma_kernel, dim3(1), dim3(256), 0, st,
+                       L.dims.Nobservations_board*L.dims.object_width_n*L.dims.object_height_n, P->d_board_pool, L.i_meas_boards,
+                       L.dims.Nobservations_point, P->d_point_pool, L.i_meas_points, P->op[P->icur].x, d_sig);
+    HIP_TRY(hipGetLastError(), return false);
+    HIP_TRY(hipMemcpyAsync(sig, d_sig, 2*sizeof(double), hipMemcpyDeviceToHost, st), return false);
+    return true;
+}
+// ... and the estimate from them: RMS / sqrt(1 - Nstate/Nmeasurements)
+bool observed_pixel_uncertainty_from_sums(double* sigma, const double* sig, int Nstate)
+{
+    if(sig[1] == 0.0)
+    {
+        set_error("observed_pixel_uncertainty cannot be computed because we don't have any board or point observations");
+        return false;
+    }
+    const double f_ = sqrt(1.0 - (double)Nstate/sig[1]);
+    *sigma = sqrt(sig[0]/sig[1]) / f_;
+    return true;
+}
+}
+
 struct mrcal_amd_uncertainty
 {
     int                method = 0;
@@ -593,13 +621,7 @@ mrcal_amd_uncertainty_create(mrcal_amd_problem_t* P, int icam_intrinsics, int me
     }
     double sig[2] = { 0.0, 0.0 };
     if(ok && !(observed_pixel_uncertainty > 0.0))
-    {
-        hipLaunchKernelGGL(pu_sigma_kernel, dim3(1), dim3(256), 0, st,
-                           L.dims.Nobservations_board*L.dims.object_width_n*L.dims.object_height_n, P->d_board_pool, L.i_meas_boards,
-                           L.dims.Nobservations_point, P->d_point_pool, L.i_meas_points, P->op[P->icur].x, d_sig);
-        HIP_TRY(hipGetLastError(), ok = false);
-        if(ok) HIP_TRY(hipMemcpyAsync(sig, d_sig, sizeof(sig), hipMemcpyDeviceToHost, st), ok = false);
-    }
+        ok = queue_observed_pixel_sums(P, d_sig, sig, st);
     if(ok) HIP_TRY(hipStreamSynchronize(st), ok = false);
     tmp.free_all();
     mrcal_amd_factorization_destroy(f);
@@ -609,14 +631,7 @@ mrcal_amd_uncertainty_create(mrcal_amd_problem_t* P, int icam_intrinsics, int me
         u->sigma = observed_pixel_uncertainty;
     else
     {
-        if(sig[1] == 0.0)
-        {
-            set_error("observed_pixel_uncertainty cannot be computed because we don't have any board or point observations");
-            delete u; return NULL;
-        }
-        // model_analysis.py:491-557: RMS / sqrt(1 - Nstate/Nmeasurements)
-        const double f_ = sqrt(1.0 - (double)Nstate/sig[1]);
-        u->sigma = sqrt(sig[0]/sig[1]) / f_;
+        if(!observed_pixel_uncertainty_from_sums(&u->sigma, sig, Nstate)) { delete u; return NULL; }
     }
     a.sigma = u->sigma;
     return u;
