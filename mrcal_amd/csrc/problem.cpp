@@ -375,6 +375,26 @@ bool problem_evaluate_op(mrcal_amd_problem* P, int i, bool with_jacobian, bool w
     return true;
 }
 
+bool problem_state_arrays(mrcal_amd_problem* P, ProblemStateArrays* s)
+{
+    const Layout& L = P->L;
+    std::vector<double> b((size_t)std::max(L.Nstate, 1));
+    s->intrinsics.assign((size_t)L.dims.Ncameras_intrinsics*L.Nintrinsics, 0.0);
+    s->rt_cam_ref.assign((size_t)std::max(L.dims.Ncameras_extrinsics, 1), mrcal_pose_t());
+    s->rt_ref_frame.assign((size_t)std::max(L.dims.Nframes, 1), mrcal_pose_t());
+    // (unpacked into and not handed out: nobody has asked for them yet)
+    std::vector<mrcal_point3_t> points((size_t)std::max(L.dims.Npoints, 1));
+    mrcal_calobject_warp_t warp;
+    if(!mrcal_amd_problem_get_b_packed(P, b.data())) return false;
+    HIP_TRY(hipMemcpy(s->intrinsics.data(), P->d_seed_intrinsics, s->intrinsics.size()*sizeof(double), hipMemcpyDeviceToHost), return false);
+    if(L.dims.Ncameras_extrinsics > 0)
+        HIP_TRY(hipMemcpy(s->rt_cam_ref.data(), P->d_seed_rt_cam_ref, (size_t)L.dims.Ncameras_extrinsics*sizeof(mrcal_pose_t), hipMemcpyDeviceToHost), return false);
+    if(L.dims.Nframes > 0)
+        HIP_TRY(hipMemcpy(s->rt_ref_frame.data(), P->d_seed_rt_ref_frame, (size_t)L.dims.Nframes*sizeof(mrcal_pose_t), hipMemcpyDeviceToHost), return false);
+    unpack_state_to_arrays(b.data(), L, s->intrinsics.data(), s->rt_cam_ref.data(), s->rt_ref_frame.data(), points.data(), &warp);
+    return true;
+}
+
 } // namespace mrcal_amd
 
 namespace {

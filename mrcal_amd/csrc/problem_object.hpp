@@ -160,4 +160,13 @@ bool problem_evaluate_ref(mrcal_amd_problem* P, const mrcal_amd::OpRef& R, bool 
 void problem_set_camblock_mode(mrcal_amd_problem* P, const mrcal_amd::CamBlockMode& mode);
 // uploads op[0..1] to d_ops
 bool problem_sync_ops(mrcal_amd_problem* P);
+// the problem's state at op[icur].b as arrays: the seeds with the state unpacked over them (what is not being
+// optimized stays at its seed)
+struct ProblemStateArrays
+{
+    std::vector<double>       intrinsics;       // [Ncameras_intrinsics][Nintrinsics]
+    std::vector<mrcal_pose_t> rt_cam_ref;       // [Ncameras_extrinsics]
+    std::vector<mrcal_pose_t> rt_ref_frame;     // [Nframes]
+};
+bool problem_state_arrays(mrcal_amd_problem* P, ProblemStateArrays* s);
 }

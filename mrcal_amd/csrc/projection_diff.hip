@@ -37,15 +37,10 @@
 #include "lens_dispatch.hpp"
 #include "device_math.hpp"
 #include "device_memory.hpp"
+#include "noise_propagation.hpp"
 #include "../../include/mrcal_amd.h"
 
 using namespace mrcal_amd;
-
-namespace mrcal_amd {
-// projection_uncertainty.hip (internal): evaluate() on device pointers, queued on the caller's stream
-bool uncertainty_evaluate_device(mrcal_amd_uncertainty_t* u, const double* d_p_cam, int N, bool atinfinity, int what,
-                                 double* d_out, hipStream_t stream);
-}
 
 namespace {
 

@@ -18,14 +18,12 @@
 // reference. The propagation, with F (3N x Nstate):
 //   X = (J*^T J*)^-1 F^T                                            (the resident factorization)
 //   Var_p_calibration = sigma^2 ( sym(F X) - (J*[reg] X)^T (J*[reg] X) )
-// (projection_uncertainty.hip's identity: only the regularization rows of J are read)
-//   tri_FX_kernel    a wavefront an entry of F X, lane l sums s = l, l+64, ... in order, then a fixed butterfly
-//   tri_JX_kernel    J*[reg] X: a lane per (row, column), the row's entries in CSR order
-//   tri_var_kernel   a lane an entry: symmetrized, the regularization rows summed in row order
+// which are noise_propagation.hpp's steps with F dense: F X is its row-dot kernel over all of F.
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <vector>
 #include <algorithm>
+#include <memory>
 #include "triangulation_math.hpp"
 #include "layout.hpp"
 #include "kernels.hpp"
@@ -33,17 +31,11 @@
 #include "problem_object.hpp"
 #include "device_memory.hpp"
 #include "host_state.hpp"
+#include "analysis_plan.hpp"
+#include "noise_propagation.hpp"
 #include "../../include/mrcal_amd.h"
 
 using namespace mrcal_amd;
-
-namespace mrcal_amd {
-// factorization.cpp, projection_uncertainty.hip (internal)
-hipStream_t factorization_stream(mrcal_amd_factorization_t* f);
-bool factorization_solve_device(mrcal_amd_factorization_t* f, int sys, const double* d_bt, int Nrhs, double* d_xt);
-bool queue_observed_pixel_sums(mrcal_amd_problem* P, double* d_sig, double* sig, hipStream_t st);
-bool observed_pixel_uncertainty_from_sums(double* sigma, const double* sig, int Nstate);
-}
 
 namespace {
 
@@ -428,47 +420,6 @@ tri_pairs_kernel(TriPairsArgs a, const TriCamDev* __restrict__ cams, const int* 
     }
 }
 
-// FX[a][b] = sum_s F[a][s] X[b][s]: a wavefront per (a,b)
-__global__ __launch_bounds__(256)
-void tri_FX_kernel(int n, int Nstate, const double* __restrict__ F, const double* __restrict__ X, double* __restrict__ FX)
-{
-    const int64_t w = (int64_t)blockIdx.x*(blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if(w >= (int64_t)n*n) return;
-    const int ra = (int)(w / n), rb = (int)(w % n);
-    const double* __restrict__ Fa = F + (size_t)ra*Nstate;
-    const double* __restrict__ Xb = X + (size_t)rb*Nstate;
-    double s = 0.0;
-    for(int i = lane; i < Nstate; i += 64) s += Fa[i]*Xb[i];
-    for(int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
-    if(lane == 0) FX[w] = s;
-}
-// JX[r][a] = sum over the entries of regularization row r of J[r][c] X[a][c], in CSR order. Jp: the rows' own
-// row pointers, whose entries start at e0 of the problem's CSR (Ji, Jx hold them from 0)
-__global__ __launch_bounds__(256)
-void tri_JX_kernel(int Nreg, int n, int Nstate, const int32_t* __restrict__ Jp, int32_t e0, const int32_t* __restrict__ Ji,
-                   const double* __restrict__ Jx, const double* __restrict__ X, double* __restrict__ JX)
-{
-    const int64_t i = (int64_t)blockIdx.x*blockDim.x + threadIdx.x;
-    if(i >= (int64_t)Nreg*n) return;
-    const int r = (int)(i / n), c = (int)(i % n);
-    const double* __restrict__ Xc = X + (size_t)c*Nstate;
-    double s = 0.0;
-    for(int32_t e = Jp[r] - e0; e < Jp[r + 1] - e0; e++) s += Jx[e]*Xc[Ji[e]];
-    JX[i] = s;
-}
-// Var[a][b] = sigma^2 ( (FX[a][b] + FX[b][a])/2 - sum_r JX[r][a] JX[r][b] )
-__global__ __launch_bounds__(256)
-void tri_var_kernel(int n, int Nreg, double sigma, const double* __restrict__ FX, const double* __restrict__ JX, double* __restrict__ Var)
-{
-    const int64_t i = (int64_t)blockIdx.x*blockDim.x + threadIdx.x;
-    if(i >= (int64_t)n*n) return;
-    const int ra = (int)(i / n), rb = (int)(i % n);
-    double s = 0.0;
-    for(int r = 0; r < Nreg; r++) s += JX[(size_t)r*n + ra]*JX[(size_t)r*n + rb];
-    Var[i] = (0.5*(FX[(size_t)ra*n + rb] + FX[(size_t)rb*n + ra]) - s)*sigma*sigma;
-}
-
 template<int METHOD>
 hipError_t launch_tri_pairs(bool with_var, bool with_F, const TriPairsArgs& a, const TriCamDev* cams, const int* pair_cam,
                             const int* pair_row, const double* v, const double* dv_dq, const double* dv_di,
@@ -528,27 +479,99 @@ struct mrcal_amd_triangulation
         int                 Ni = 0;
         double*             d_intr = NULL;
     };
-    std::vector<Camera>        cams;
-    bool                       have_problem = false;
-    Layout                     L;                   // of the problem
-    double                     sigma_estimate = -1.0;
-    mrcal_amd_factorization_t* f = NULL;            // of J*^T J* at the problem's state
-    int                        Nreg = 0;
-    int32_t                    reg_e0 = 0;          // the regularization rows' first entry in the problem's CSR
-    int32_t*                   d_regJp = NULL;      // [Nreg + 1], as in the problem's CSR
-    int32_t*                   d_regJi = NULL;
-    double*                    d_regJx = NULL;
-    TriCamDev*                 d_cams   = NULL;
-    double*                    d_frames = NULL;     // rt_ref_frame [Nframes][6] at the problem's state
-    hipStream_t                stream = NULL;       // without a factorization; with one, its stream is used
-    DeviceBuffers              mem;
+    std::vector<Camera>               cams;
+    std::unique_ptr<NoisePropagation> np;                  // with a problem: its factorization, regularization rows, sigma
+    TriCamDev*                        d_cams   = NULL;
+    double*                           d_frames = NULL;     // rt_ref_frame [Nframes][6] at the problem's state
+    hipStream_t                       stream = NULL;       // without a problem; with one, np's stream is used
+    DeviceBuffers                     mem;
     ~mrcal_amd_triangulation()
     {
         mem.free_all();
-        if(f) mrcal_amd_factorization_destroy(f);
         if(stream) (void)hipStreamDestroy(stream);
     }
 };
+
+namespace {
+
+bool check_cameras(int Ncameras, const mrcal_amd_triangulation_camera_t* cameras)
+{
+    if(Ncameras < 1 || cameras == NULL) { set_error("mrcal_amd_triangulation_create(): no cameras"); return false; }
+    for(int c = 0; c < Ncameras; c++)
+    {
+        const mrcal_lensmodel_type_t t = cameras[c].lensmodel.type;
+        if(!lens_supported((int)t)) { set_error("mrcal_amd_triangulation_create(): lens model %d is not supported", (int)t); return false; }
+        if(t == MRCAL_LENSMODEL_CAHVORE)
+            for(int i = 9; i < 12; i++)
+                if(cameras[c].intrinsics[i] != 0.)
+                {
+                    set_error("unproject() currently only works with a central projection. So I cannot unproject(CAHVORE,E!=0). Please set E=0 to centralize this model");
+                    return false;
+                }
+    }
+    return true;
+}
+
+bool check_cameras_against_problem(const mrcal_amd_problem* P, int Ncameras, const mrcal_amd_triangulation_camera_t* cameras)
+{
+    const Layout& L = P->L;
+    if(propagation_refuses_shard(P, "triangulation") || propagation_refuses_measurements(L)) return false;
+    for(int c = 0; c < Ncameras; c++)
+    {
+        if(cameras[c].icam_intrinsics < 0 || cameras[c].icam_intrinsics >= L.dims.Ncameras_intrinsics)
+        {
+            set_error("icam_intrinsics MUST be in [0,Ncameras_intrinsics-1]. got %d NOT in [0,%d]", cameras[c].icam_intrinsics, L.dims.Ncameras_intrinsics-1);
+            return false;
+        }
+        if(cameras[c].icam_extrinsics >= L.dims.Ncameras_extrinsics)
+        {
+            set_error("icam_extrinsics MUST be < 0 (at the reference) or in [0,Ncameras_extrinsics-1]. got %d NOT in [0,%d]", cameras[c].icam_extrinsics, L.dims.Ncameras_extrinsics-1);
+            return false;
+        }
+        if(memcmp(&cameras[c].lensmodel, &L.lensmodel, sizeof(mrcal_lensmodel_t)) != 0)
+        {
+            set_error("triangulation: camera %d does not have the problem's lens model", c);
+            return false;
+        }
+    }
+    return true;
+}
+
+// each camera's lens parameters, and the table the pair kernel reads. L: the problem's layout, or NULL
+bool upload_cameras(mrcal_amd_triangulation* t, const Layout* L, int Ncameras, const mrcal_amd_triangulation_camera_t* cameras)
+{
+    t->cams.resize((size_t)Ncameras);
+    std::vector<TriCamDev> table((size_t)Ncameras);
+    for(int c = 0; c < Ncameras; c++)
+    {
+        mrcal_amd_triangulation::Camera& cam = t->cams[c];
+        cam.lensmodel = cameras[c].lensmodel;
+        cam.cfg       = lens_config_of(cam.lensmodel);
+        cam.Ni        = lensmodel_num_params(cam.lensmodel);
+        if(!t->mem.upload(&cam.d_intr, cameras[c].intrinsics, (size_t)cam.Ni)) return false;
+        for(int k = 0; k < 6; k++) table[c].rt[k] = cameras[c].rt_cam_ref[k];
+        table[c].istate_i = table[c].istate_e = -1;
+        if(L != NULL)
+        {
+            if(L->i_state_intrinsics >= 0 && L->Nintr_state > 0)
+                table[c].istate_i = L->i_state_intrinsics + cameras[c].icam_intrinsics*L->Nintr_state;
+            if(L->i_state_extrinsics >= 0 && cameras[c].icam_extrinsics >= 0)
+                table[c].istate_e = L->i_state_extrinsics + 6*cameras[c].icam_extrinsics;
+        }
+    }
+    return t->mem.upload(&t->d_cams, table);
+}
+
+// the frames at the problem's state, if they are in it
+bool upload_frames(mrcal_amd_triangulation* t, mrcal_amd_problem* P)
+{
+    const Layout& L = P->L;
+    if(!L.sel.do_optimize_frames || L.dims.Nframes == 0) return true;
+    ProblemStateArrays s;
+    return problem_state_arrays(P, &s) && t->mem.upload(&t->d_frames, (const double*)s.rt_ref_frame.data(), (size_t)6*L.dims.Nframes);
+}
+
+} // namespace
 
 extern "C" {
 
@@ -561,301 +584,201 @@ mrcal_amd_triangulation_create(mrcal_amd_problem_t* P, int Ncameras, const mrcal
         set_error("no HIP device is visible: libmrcal_amd has no CPU fallback");
         return NULL;
     }
-    if(Ncameras < 1 || cameras == NULL) { set_error("mrcal_amd_triangulation_create(): no cameras"); return NULL; }
-    for(int c = 0; c < Ncameras; c++)
-    {
-        const mrcal_lensmodel_type_t t = cameras[c].lensmodel.type;
-        if(!lens_supported((int)t)) { set_error("mrcal_amd_triangulation_create(): lens model %d is not supported", (int)t); return NULL; }
-        if(t == MRCAL_LENSMODEL_CAHVORE)
-            for(int i = 9; i < 12; i++)
-                if(cameras[c].intrinsics[i] != 0.)
-                {
-                    set_error("unproject() currently only works with a central projection. So I cannot unproject(CAHVORE,E!=0). Please set E=0 to centralize this model");
-                    return NULL;
-                }
-    }
-    if(P != NULL)
-    {
-        const Layout& L = P->L;
-        if((int)P->board_sel.size() != L.dims.Nobservations_board || P->comm != NULL)
-        {
-            set_error("triangulation: this problem is a shard (it holds a part of the rows)");
-            return NULL;
-        }
-        if(L.Nmeas_triangulated > 0)
-        {
-            set_error("Some measurements other than boards, points and regularization are present. Don't know what to do");
-            return NULL;
-        }
-        if(L.Nmeas_regularization > 0 && L.Nmeas_boards + L.Nmeas_points == 0)
-        {
-            set_error("No non-regularization measurements. Don't know what to do");
-            return NULL;
-        }
-        for(int c = 0; c < Ncameras; c++)
-        {
-            if(cameras[c].icam_intrinsics < 0 || cameras[c].icam_intrinsics >= L.dims.Ncameras_intrinsics)
-            {
-                set_error("icam_intrinsics MUST be in [0,Ncameras_intrinsics-1]. got %d NOT in [0,%d]", cameras[c].icam_intrinsics, L.dims.Ncameras_intrinsics-1);
-                return NULL;
-            }
-            if(cameras[c].icam_extrinsics >= L.dims.Ncameras_extrinsics)
-            {
-                set_error("icam_extrinsics MUST be < 0 (at the reference) or in [0,Ncameras_extrinsics-1]. got %d NOT in [0,%d]", cameras[c].icam_extrinsics, L.dims.Ncameras_extrinsics-1);
-                return NULL;
-            }
-            if(memcmp(&cameras[c].lensmodel, &L.lensmodel, sizeof(mrcal_lensmodel_t)) != 0)
-            {
-                set_error("triangulation: camera %d does not have the problem's lens model", c);
-                return NULL;
-            }
-        }
-    }
+    if(!check_cameras(Ncameras, cameras)) return NULL;
+    if(P != NULL && !check_cameras_against_problem(P, Ncameras, cameras)) return NULL;
 
-    mrcal_amd_triangulation* t = new mrcal_amd_triangulation();
-    t->cams.resize((size_t)Ncameras);
-    std::vector<TriCamDev> table((size_t)Ncameras);
-    bool ok = true;
-    for(int c = 0; c < Ncameras && ok; c++)
+    std::unique_ptr<mrcal_amd_triangulation> t(new mrcal_amd_triangulation());
+    if(!upload_cameras(t.get(), P ? &P->L : NULL, Ncameras, cameras)) return NULL;
+    if(P == NULL)
     {
-        mrcal_amd_triangulation::Camera& cam = t->cams[c];
-        cam.lensmodel = cameras[c].lensmodel;
-        cam.cfg       = lens_config_of(cam.lensmodel);
-        cam.Ni        = lensmodel_num_params(cam.lensmodel);
-        ok = t->mem.upload(&cam.d_intr, cameras[c].intrinsics, (size_t)cam.Ni);
-        for(int k = 0; k < 6; k++) table[c].rt[k] = cameras[c].rt_cam_ref[k];
-        table[c].istate_i = table[c].istate_e = -1;
-        if(P != NULL)
-        {
-            const Layout& L = P->L;
-            if(L.i_state_intrinsics >= 0 && L.Nintr_state > 0)
-                table[c].istate_i = L.i_state_intrinsics + cameras[c].icam_intrinsics*L.Nintr_state;
-            if(L.i_state_extrinsics >= 0 && cameras[c].icam_extrinsics >= 0)
-                table[c].istate_e = L.i_state_extrinsics + 6*cameras[c].icam_extrinsics;
-        }
+        HIP_TRY(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking), return NULL);
+        return t.release();
     }
-    ok = ok && t->mem.upload(&t->d_cams, table);
-    if(ok && P == NULL) HIP_TRY(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking), ok = false);
-    if(!ok || P == NULL)
-    {
-        if(!ok) { delete t; return NULL; }
-        return t;
-    }
-
-    // the factorization at the problem's state (evaluates x and J there), the regularization rows of J, the frames, sigma
-    t->have_problem = true;
-    t->L = P->L;
-    const Layout& L = t->L;
-    t->f = mrcal_amd_factorization_create_from_problem(P);
-    if(t->f == NULL)
-    {
-        if(mrcal_amd_factorization_last_status() == 1)
-            set_error("Cannot compute the uncertainty: factorization computation failed");
-        delete t; return NULL;
-    }
-    if(!problem_ensure_jacobian(P)) { delete t; return NULL; }
-    HIP_TRY(hipStreamSynchronize(P->stream), ok = false);
-    t->Nreg = L.Nmeas_regularization;
-    if(ok && t->Nreg > 0)
-    {
-        std::vector<int32_t> Jp((size_t)t->Nreg + 1);
-        HIP_TRY(hipMemcpy(Jp.data(), P->d_Jp + L.i_meas_regularization, Jp.size()*sizeof(int32_t), hipMemcpyDeviceToHost), ok = false);
-        if(ok)
-        {
-            t->reg_e0 = Jp[0];
-            const size_t n = (size_t)(Jp[t->Nreg] - Jp[0]);
-            ok = t->mem.upload(&t->d_regJp, Jp) && t->mem.alloc(&t->d_regJi, n) && t->mem.alloc(&t->d_regJx, n);
-            if(ok && n > 0)
-            {
-                HIP_TRY(hipMemcpy(t->d_regJi, P->d_Ji + Jp[0], n*sizeof(int32_t), hipMemcpyDeviceToDevice), ok = false);
-                HIP_TRY(hipMemcpy(t->d_regJx, P->op[P->icur].Jv + Jp[0], n*sizeof(double), hipMemcpyDeviceToDevice), ok = false);
-            }
-        }
-    }
-    if(ok && L.sel.do_optimize_frames && L.dims.Nframes > 0)
-    {
-        // the frames at the solve: the seeds with the state unpacked over them
-        std::vector<double> b((size_t)std::max(L.Nstate, 1));
-        std::vector<double> intr_all((size_t)L.dims.Ncameras_intrinsics*L.Nintrinsics);
-        std::vector<mrcal_pose_t> rt((size_t)std::max(L.dims.Ncameras_extrinsics, 1));
-        std::vector<mrcal_pose_t> frames((size_t)L.dims.Nframes);
-        std::vector<mrcal_point3_t> points((size_t)std::max(L.dims.Npoints, 1));
-        mrcal_calobject_warp_t warp;
-        ok = mrcal_amd_problem_get_b_packed(P, b.data());
-        if(ok) HIP_TRY(hipMemcpy(frames.data(), P->d_seed_rt_ref_frame, frames.size()*sizeof(mrcal_pose_t), hipMemcpyDeviceToHost), ok = false);
-        if(ok)
-        {
-            unpack_state_to_arrays(b.data(), L, intr_all.data(), rt.data(), frames.data(), points.data(), &warp);
-            ok = t->mem.upload(&t->d_frames, (const double*)frames.data(), (size_t)6*L.dims.Nframes);
-        }
-    }
-    if(ok)
-    {
-        DeviceBuffers tmp;
-        double* d_sig = NULL;
-        double sig[2] = { 0.0, 0.0 };
-        hipStream_t st = factorization_stream(t->f);
-        ok = tmp.alloc(&d_sig, 2) && queue_observed_pixel_sums(P, d_sig, sig, st);
-        if(ok) HIP_TRY(hipStreamSynchronize(st), ok = false);
-        // (no observations to estimate from: an error only once the estimate is asked for)
-        if(ok && sig[1] != 0.0) ok = observed_pixel_uncertainty_from_sums(&t->sigma_estimate, sig, L.Nstate);
-    }
-    if(!ok) { delete t; return NULL; }
-    return t;
+    t->np = NoisePropagation::create(P, "triangulation", true);
+    if(!t->np || !upload_frames(t.get(), P)) return NULL;
+    return t.release();
 }
 
 double mrcal_amd_triangulation_observed_pixel_uncertainty(const mrcal_amd_triangulation_t* t)
 {
-    return t ? t->sigma_estimate : -1.0;
+    return t && t->np ? t->np->sigma_estimate : -1.0;
 }
+
+} // extern "C"
+
+namespace {
+
+// what one evaluate() asks for
+struct TriRequest
+{
+    int    N, method;
+    bool   with_cal, with_obs, stabilize;
+    double sigma;                   // of the calibration-time noise, if with_cal
+    double obs_stdev, obs_correlation;
+    NoisePropagation* np;           // the context's, if with_cal; else NULL
+    bool   grads() const { return with_cal || with_obs; }
+};
+
+bool check_request(TriRequest* r, const mrcal_amd_triangulation* t, const double* q, const int* icam,
+                   double q_calibration_stdev, const double* p, const double* Var_p_observation, const double* Var_p_calibration)
+{
+    if(t == NULL) { set_error("no triangulation context"); return false; }
+    if(r->method < 0 || r->method >= TRI_NMETHODS) { set_error("unknown triangulation method %d", r->method); return false; }
+    r->with_cal = q_calibration_stdev != 0.0;
+    r->with_obs = r->obs_stdev > 0.0;
+    if(r->obs_stdev < 0.0) { set_error("q_observation_stdev MUST be None or >= 0"); return false; }
+    if(r->method == TRI_LINDSTROM && r->grads())
+    {
+        set_error("Triangulation gradients not supported (yet?) with method=triangulate_lindstrom. It has slightly different inputs and slightly different gradients");
+        return false;
+    }
+    if(r->with_cal && !t->np)
+    {
+        set_error("optimization_inputs are not available, so I cannot propagate calibration-time noise");
+        return false;
+    }
+    if(r->N < 0 || (r->N > 0 && (q == NULL || icam == NULL || p == NULL)) || (r->with_obs && Var_p_observation == NULL) ||
+       (r->with_cal && Var_p_calibration == NULL))
+    {
+        set_error("mrcal_amd_triangulation_evaluate(): N >= 0, and q, icam, p and the covariances asked for must be given");
+        return false;
+    }
+    r->sigma = q_calibration_stdev;
+    if(r->with_cal && !(r->sigma > 0.0))
+    {
+        if(!(t->np->sigma_estimate > 0.0)) { set_error_no_sigma_estimate(); return false; }
+        r->sigma = t->np->sigma_estimate;
+    }
+    r->np = r->with_cal ? t->np.get() : NULL;
+    return true;
+}
+
+// the temporaries of one evaluate(): NULL where the request has no use for one
+struct TriBuffers
+{
+    DeviceBuffers mem;
+    double *q = NULL, *v = NULL, *gq = NULL, *gi = NULL, *s_q = NULL, *s_gv = NULL, *s_gi = NULL;
+    double *p = NULL, *vo = NULL, *F = NULL, *X = NULL, *FX = NULL, *JX = NULL, *var = NULL;
+    int    *cam = NULL, *row = NULL;
+};
+// iterative: a camera in use has no closed-form unprojection
+bool allocate(TriBuffers* b, const TriRequest& r, const PixelsByCamera& g, const int* icam, bool iterative)
+{
+    const size_t N = (size_t)r.N, n3 = 3*N;
+    bool ok = b->mem.upload(&b->q, g.qs) && b->mem.upload(&b->cam, icam, 2*N) && b->mem.upload(&b->row, g.rows) &&
+              b->mem.alloc(&b->v, 6*N) && b->mem.alloc(&b->p, 3*N);
+    if(r.grads()) ok = ok && b->mem.alloc(&b->gq, 12*N) && b->mem.alloc(&b->vo, 9*N);
+    if(r.grads() && iterative) ok = ok && b->mem.alloc(&b->s_q, 4*N) && b->mem.alloc(&b->s_gv, 12*N);
+    if(r.with_cal)
+    {
+        const size_t Ni = (size_t)r.np->L.Nintrinsics, Nstate = (size_t)r.np->L.Nstate;
+        ok = ok && b->mem.alloc(&b->gi, 6*N*Ni) && b->mem.alloc(&b->F, n3*Nstate) && b->mem.alloc(&b->X, n3*Nstate) &&
+             b->mem.alloc(&b->FX, n3*n3) && b->mem.alloc(&b->JX, (size_t)std::max(r.np->Nreg, 1)*n3) && b->mem.alloc(&b->var, n3*n3);
+        if(iterative) ok = ok && b->mem.alloc(&b->s_gi, 4*N*Ni);
+    }
+    return ok;
+}
+
+// each camera's pixels -> its rows of v, dv_dq, dv_di
+bool unproject_by_camera(const mrcal_amd_triangulation* t, const TriRequest& r, const PixelsByCamera& g, const TriBuffers& b, hipStream_t st)
+{
+    const int Ni = r.with_cal ? r.np->L.Nintrinsics : 0;
+    for(int c = 0; c < (int)t->cams.size(); c++)
+    {
+        const int n = g.off[c + 1] - g.off[c], o = g.off[c];
+        if(n == 0) continue;
+        const mrcal_amd_triangulation::Camera& cam = t->cams[c];
+        const int ni = r.with_cal ? Ni : cam.Ni;
+        HIP_TRY(launch_unproject_points((int)cam.lensmodel.type, cam.cfg, n, ni, b.q + (size_t)2*o, cam.d_intr, b.v + (size_t)3*o,
+                                        r.grads() ? b.gq + (size_t)6*o : NULL, r.with_cal ? b.gi + (size_t)3*o*Ni : NULL,
+                                        b.s_q ? b.s_q + (size_t)2*o : NULL, b.s_gv ? b.s_gv + (size_t)6*o : NULL,
+                                        b.s_gi ? b.s_gi + (size_t)2*o*Ni : NULL, false, st), return false);
+    }
+    return true;
+}
+
+TriPairsArgs pairs_args(const TriRequest& r)
+{
+    TriPairsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.N = r.N;
+    a.var = r.obs_stdev*r.obs_stdev;
+    const double sc = r.obs_stdev*r.obs_correlation;
+    a.var_cross = sc*sc;
+    if(!r.with_cal) return a;
+    const Layout* L = &r.np->L;
+    a.Ni          = L->Nintrinsics;
+    a.Nstate      = L->Nstate;
+    a.Nintr_state = L->Nintr_state;
+    a.intr0       = L->Ncore - L->Ncore_state;
+    a.Ncore_state = L->Ncore_state;
+    a.stabilize   = r.stabilize ? 1 : 0;
+    if(r.stabilize && L->sel.do_optimize_frames && L->i_state_frames >= 0 && L->dims.Nframes > 0)
+    {
+        a.Nframes   = L->dims.Nframes;
+        a.istate_f0 = L->i_state_frames;
+    }
+    return a;
+}
+
+bool launch_pairs(const mrcal_amd_triangulation* t, const TriRequest& r, const TriPairsArgs& a, const TriBuffers& b, hipStream_t st)
+{
+    hipError_t e = hipErrorInvalidValue;
+    switch(r.method)
+    {
+#define TRI_CASE(M) case M: e = launch_tri_pairs<M>(r.grads(), r.with_cal, a, t->d_cams, b.cam, b.row, b.v, b.gq, b.gi, t->d_frames, b.p, b.vo, b.F, st); break;
+    TRI_CASE(TRI_GEOMETRIC) TRI_CASE(TRI_LINDSTROM) TRI_CASE(TRI_LEECIVERA_L1) TRI_CASE(TRI_LEECIVERA_LINF)
+    TRI_CASE(TRI_LEECIVERA_MID2) TRI_CASE(TRI_LEECIVERA_WMID2)
+#undef TRI_CASE
+    }
+    HIP_TRY(e, return false);
+    return true;
+}
+
+// everything of one evaluate() that is queued on st; nothing is waited for
+bool queue_evaluate(const mrcal_amd_triangulation* t, const TriRequest& r, const PixelsByCamera& g, const TriBuffers& b, hipStream_t st,
+                    double* p, double* Var_p_observation, double* Var_p_calibration)
+{
+    NoisePropagation* np = r.np;
+    const int n3 = 3*r.N;
+    if(!unproject_by_camera(t, r, g, b, st) || !launch_pairs(t, r, pairs_args(r), b, st)) return false;
+    if(np != NULL)
+    {
+        if(!np->solve(b.F, n3, b.X) || !np->row_dots(b.F, n3, b.X, n3, b.FX) || !np->reg_rows_times(b.X, n3, b.JX) ||
+           !np->combine(b.FX, b.JX, n3, r.sigma, b.var))
+            return false;
+        HIP_TRY(hipMemcpyAsync(Var_p_calibration, b.var, (size_t)n3*n3*sizeof(double), hipMemcpyDeviceToHost, st), return false);
+    }
+    HIP_TRY(hipMemcpyAsync(p, b.p, (size_t)n3*sizeof(double), hipMemcpyDeviceToHost, st), return false);
+    if(r.with_obs) HIP_TRY(hipMemcpyAsync(Var_p_observation, b.vo, (size_t)9*r.N*sizeof(double), hipMemcpyDeviceToHost, st), return false);
+    return true;
+}
+
+} // namespace
+
+extern "C" {
 
 bool mrcal_amd_triangulation_evaluate(mrcal_amd_triangulation_t* t, int N, const double* q, const int* icam, int method,
                                       double q_calibration_stdev, double q_observation_stdev, double q_observation_stdev_correlation,
                                       bool stabilize_coords, double* p, double* Var_p_observation, double* Var_p_calibration)
 {
     last_error_string().clear();
-    if(t == NULL) { set_error("no triangulation context"); return false; }
-    if(method < 0 || method >= TRI_NMETHODS) { set_error("unknown triangulation method %d", method); return false; }
-    const bool with_cal = q_calibration_stdev != 0.0;
-    const bool with_obs = q_observation_stdev > 0.0;
-    if(q_observation_stdev < 0.0) { set_error("q_observation_stdev MUST be None or >= 0"); return false; }
-    if(method == TRI_LINDSTROM && (with_cal || with_obs))
-    {
-        set_error("Triangulation gradients not supported (yet?) with method=triangulate_lindstrom. It has slightly different inputs and slightly different gradients");
-        return false;
-    }
-    if(with_cal && !t->have_problem)
-    {
-        set_error("optimization_inputs are not available, so I cannot propagate calibration-time noise");
-        return false;
-    }
-    if(N < 0 || (N > 0 && (q == NULL || icam == NULL || p == NULL)) || (with_obs && Var_p_observation == NULL) || (with_cal && Var_p_calibration == NULL))
-    {
-        set_error("mrcal_amd_triangulation_evaluate(): N >= 0, and q, icam, p and the covariances asked for must be given");
-        return false;
-    }
-    double sigma = q_calibration_stdev;
-    if(with_cal && !(sigma > 0.0))
-    {
-        if(!(t->sigma_estimate > 0.0))
-        {
-            set_error("observed_pixel_uncertainty cannot be computed because we don't have any board or point observations");
-            return false;
-        }
-        sigma = t->sigma_estimate;
-    }
+    TriRequest r = { N, method, false, false, stabilize_coords, 0.0, q_observation_stdev, q_observation_stdev_correlation, NULL };
+    if(!check_request(&r, t, q, icam, q_calibration_stdev, p, Var_p_observation, Var_p_calibration)) return false;
     if(N == 0) return true;
     const int Ncameras = (int)t->cams.size();
-    for(int i = 0; i < 2*N; i++)
-        if(icam[i] < 0 || icam[i] >= Ncameras) { set_error("pair %d: camera %d is not in the table of %d", i/2, icam[i], Ncameras); return false; }
-
-    // the pixels grouped by camera: camera c's are rows [off[c], off[c+1])
-    const bool grads = with_cal || with_obs;
-    std::vector<int> off((size_t)Ncameras + 1, 0), fill((size_t)Ncameras, 0), rows((size_t)2*N);
-    for(int i = 0; i < 2*N; i++) off[(size_t)icam[i] + 1]++;
-    for(int c = 0; c < Ncameras; c++) off[c + 1] += off[c];
-    std::vector<double> qs((size_t)4*N);
-    for(int i = 0; i < 2*N; i++)
-    {
-        const int r = off[icam[i]] + fill[icam[i]]++;
-        rows[i] = r;
-        qs[(size_t)2*r] = q[(size_t)2*i]; qs[(size_t)2*r + 1] = q[(size_t)2*i + 1];
-    }
-    const Layout& L = t->L;
-    const int Ni     = with_cal ? L.Nintrinsics : 0;
-    const int Nstate = with_cal ? L.Nstate : 0;
-    const int n3     = 3*N;
+    PixelsByCamera g;
+    const int bad = group_pixels_by_camera(&g, Ncameras, N, q, icam);
+    if(bad >= 0) { set_error("pair %d: camera %d is not in the table of %d", bad/2, icam[bad], Ncameras); return false; }
     bool iterative = false;
-    for(int c = 0; c < Ncameras; c++) if(off[c + 1] > off[c] && !lens_has_closed_form_inverse(t->cams[c].lensmodel.type)) iterative = true;
+    for(int c = 0; c < Ncameras; c++)
+        if(g.off[c + 1] > g.off[c] && !lens_has_closed_form_inverse(t->cams[c].lensmodel.type)) iterative = true;
 
-    hipStream_t st = t->f ? factorization_stream(t->f) : t->stream;
-    DeviceBuffers tmp;
-    double *d_q = NULL, *d_v = NULL, *d_gq = NULL, *d_gi = NULL, *s_q = NULL, *s_gv = NULL, *s_gi = NULL;
-    double *d_p = NULL, *d_vo = NULL, *d_F = NULL, *d_X = NULL, *d_FX = NULL, *d_JX = NULL, *d_var = NULL;
-    int *d_cam = NULL, *d_row = NULL;
-    bool ok = tmp.upload(&d_q, qs) && tmp.upload(&d_cam, icam, (size_t)2*N) && tmp.upload(&d_row, rows) &&
-              tmp.alloc(&d_v, (size_t)6*N) && tmp.alloc(&d_p, (size_t)3*N);
-    if(grads) ok = ok && tmp.alloc(&d_gq, (size_t)12*N) && tmp.alloc(&d_vo, (size_t)9*N);
-    if(grads && iterative) ok = ok && tmp.alloc(&s_q, (size_t)4*N) && tmp.alloc(&s_gv, (size_t)12*N);
-    if(with_cal)
-    {
-        ok = ok && tmp.alloc(&d_gi, (size_t)6*N*Ni) && tmp.alloc(&d_F, (size_t)n3*Nstate) && tmp.alloc(&d_X, (size_t)n3*Nstate) &&
-             tmp.alloc(&d_FX, (size_t)n3*n3) && tmp.alloc(&d_JX, (size_t)std::max(t->Nreg, 1)*n3) && tmp.alloc(&d_var, (size_t)n3*n3);
-        if(iterative) ok = ok && tmp.alloc(&s_gi, (size_t)4*N*Ni);
-    }
-    if(!ok) return false;
-
-    for(int c = 0; c < Ncameras && ok; c++)
-    {
-        const int n = off[c + 1] - off[c], o = off[c];
-        if(n == 0) continue;
-        const mrcal_amd_triangulation::Camera& cam = t->cams[c];
-        const int ni = with_cal ? Ni : cam.Ni;
-        HIP_TRY(launch_unproject_points((int)cam.lensmodel.type, cam.cfg, n, ni, d_q + (size_t)2*o, cam.d_intr, d_v + (size_t)3*o,
-                                        grads ? d_gq + (size_t)6*o : NULL, with_cal ? d_gi + (size_t)3*o*Ni : NULL,
-                                        s_q ? s_q + (size_t)2*o : NULL, s_gv ? s_gv + (size_t)6*o : NULL,
-                                        s_gi ? s_gi + (size_t)2*o*Ni : NULL, false, st), ok = false);
-    }
-
-    TriPairsArgs a;
-    memset(&a, 0, sizeof(a));
-    a.N = N; a.Ni = Ni; a.Nstate = Nstate;
-    a.var = q_observation_stdev*q_observation_stdev;
-    {
-        const double sc = q_observation_stdev*q_observation_stdev_correlation;
-        a.var_cross = sc*sc;
-    }
-    if(with_cal)
-    {
-        a.Nintr_state = L.Nintr_state;
-        a.intr0       = L.Ncore - L.Ncore_state;
-        a.Ncore_state = L.Ncore_state;
-        a.stabilize   = stabilize_coords ? 1 : 0;
-        if(stabilize_coords && L.sel.do_optimize_frames && L.i_state_frames >= 0 && L.dims.Nframes > 0)
-        {
-            a.Nframes   = L.dims.Nframes;
-            a.istate_f0 = L.i_state_frames;
-        }
-    }
-    if(ok)
-    {
-        hipError_t e = hipErrorInvalidValue;
-        switch(method)
-        {
-#define TRI_CASE(M) case M: e = launch_tri_pairs<M>(grads, with_cal, a, t->d_cams, d_cam, d_row, d_v, d_gq, d_gi, t->d_frames, d_p, d_vo, d_F, st); break;
-        TRI_CASE(TRI_GEOMETRIC) TRI_CASE(TRI_LINDSTROM) TRI_CASE(TRI_LEECIVERA_L1) TRI_CASE(TRI_LEECIVERA_LINF)
-        TRI_CASE(TRI_LEECIVERA_MID2) TRI_CASE(TRI_LEECIVERA_WMID2)
-#undef TRI_CASE
-        }
-        HIP_TRY(e, ok = false);
-    }
-    if(ok && with_cal)
-    {
-        ok = factorization_solve_device(t->f, FSOLVE_A, d_F, n3, d_X);
-        if(ok)
-        {
-            const int64_t nw = (int64_t)n3*n3;
-            hipLaunchKernelGGL(tri_FX_kernel, dim3((unsigned)((nw + 3)/4)), dim3(256), 0, st, n3, Nstate, d_F, d_X, d_FX);
-            HIP_TRY(hipGetLastError(), ok = false);
-        }
-        if(ok && t->Nreg > 0)
-        {
-            const int64_t ne = (int64_t)t->Nreg*n3;
-            hipLaunchKernelGGL(tri_JX_kernel, dim3((unsigned)((ne + 255)/256)), dim3(256), 0, st, t->Nreg, n3, Nstate,
-                               t->d_regJp, t->reg_e0, t->d_regJi, t->d_regJx, d_X, d_JX);
-            HIP_TRY(hipGetLastError(), ok = false);
-        }
-        if(ok)
-        {
-            const int64_t ne = (int64_t)n3*n3;
-            hipLaunchKernelGGL(tri_var_kernel, dim3((unsigned)((ne + 255)/256)), dim3(256), 0, st, n3, t->Nreg, sigma, d_FX, d_JX, d_var);
-            HIP_TRY(hipGetLastError(), ok = false);
-        }
-        if(ok) HIP_TRY(hipMemcpyAsync(Var_p_calibration, d_var, (size_t)n3*n3*sizeof(double), hipMemcpyDeviceToHost, st), ok = false);
-    }
-    if(ok) HIP_TRY(hipMemcpyAsync(p, d_p, (size_t)3*N*sizeof(double), hipMemcpyDeviceToHost, st), ok = false);
-    if(ok && with_obs) HIP_TRY(hipMemcpyAsync(Var_p_observation, d_vo, (size_t)9*N*sizeof(double), hipMemcpyDeviceToHost, st), ok = false);
-    // (also on failure: the temporaries are freed below, and nothing queued may still be using them)
+    hipStream_t st = t->np ? t->np->stream : t->stream;
+    TriBuffers b;
+    if(!allocate(&b, r, g, icam, iterative)) return false;
+    bool ok = queue_evaluate(t, r, g, b, st, p, Var_p_observation, Var_p_calibration);
+    // (also on failure: the temporaries are freed on return, and nothing queued may still be using them)
     if(hipStreamSynchronize(st) != hipSuccess && ok) { set_error("mrcal_amd_triangulation_evaluate(): the device reported an error"); ok = false; }
     return ok;
 }

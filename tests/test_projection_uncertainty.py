@@ -324,6 +324,20 @@ def test_rrp_against_checker(amd, ref_api, icam):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("icam", (0, 1))
+def test_no_regularization_against_checker(amd, ref_api, icam):
+    """Without regularization rows the second term of C is empty (Nreg == 0). Camera 0 sits at the reference, camera 1
+    has extrinsics. (OPENCV4: OPENCV8 on these few frames is nearly singular without regularization)"""
+    oi = board_problem(amd._api, Ncameras=3, lensmodel="LENSMODEL_OPENCV4")
+    oi["do_apply_regularization"] = False
+    oi = _solved(amd, oi)
+    assert ref_api.num_measurements_regularization(**oi) == 0
+    for method in ("cross-reprojection-ccp", "cross-reprojection-rrp-Jfp"):
+        worst = _compare(amd, ref_api, oi, icam, method, some_points(23, seed=4))
+        print(f"no regularization, icam {icam}, {method}: worst error {worst:.3g} of the largest entry")
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("lensmodel", ("LENSMODEL_CAHVORE_linearity=0.00", "LENSMODEL_CAHVOR", "LENSMODEL_STEREOGRAPHIC",
                                        "LENSMODEL_SPLINED_STEREOGRAPHIC_order=3_Nx=8_Ny=6_fov_x_deg=80",
                                        "LENSMODEL_PINHOLE", "LENSMODEL_OPENCV5", "LENSMODEL_OPENCV12"))

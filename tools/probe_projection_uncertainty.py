@@ -7,8 +7,9 @@ solved), for a 60x40 grid of the imager unprojected to 10 m, camera 3:
       Too slow to run for the whole grid: --ref-points of them are timed and the per-point cost is scaled to the grid
   (b) the one-shot projection_uncertainty()
   (c) ProjectionUncertainty.evaluate() on a context made once
+  (d) making that context: ProjectionUncertainty() - the problem, K, the factorization, C - then close()
 
-(b) and (c) alternate within one run, --trials times; min / median / max are printed, and one JSON line at the end.
+(b), (c) and (d) alternate within one run, --trials times; min / median / max are printed, and one JSON line at the end.
 Under rocprofv3 --kernel-trace --memory-copy-trace --stats (--no-ref) it shows the kernels and the copies of (b)/(c)."""
 import argparse
 import json
@@ -25,6 +26,7 @@ def main():
     ap.add_argument("--trials", type=int, default=7)
     ap.add_argument("--ref-points", type=int, default=24)
     ap.add_argument("--no-ref", action="store_true")
+    ap.add_argument("--grid", default="60x40", help="WxH points on the imager (100x100: 10^4 points)")
     args = ap.parse_args()
     import mrcal_amd as mrcal
     from mrcal_amd.synthetic import make_calibration_problem
@@ -37,18 +39,21 @@ def main():
     icam = 3
     model = mrcal.cameramodel(optimization_inputs=oi, icam_intrinsics=icam)
     W, H = model.imagersize()
-    q = np.stack(np.meshgrid(np.linspace(0, W-1, 60), np.linspace(0, H-1, 40)), -1).reshape(-1, 2)
+    gw, gh = (int(n) for n in args.grid.split("x"))
+    q = np.stack(np.meshgrid(np.linspace(0, W-1, gw), np.linspace(0, H-1, gh)), -1).reshape(-1, 2)
     p = mrcal.unproject(q, *model.intrinsics(), normalize=True) * 10.0
-    out = dict(problem="8 cameras x 1000 frames x 10x10, OPENCV8, seed 0, solved", grid="60x40", icam=icam,
+    out = dict(problem="8 cameras x 1000 frames x 10x10, OPENCV8, seed 0, solved", grid=args.grid, icam=icam,
                solve_s=t_solve)
 
-    tb, tc = [], []
+    tb, tc, td = [], [], []
     u = mrcal.ProjectionUncertainty(model, observed_pixel_uncertainty=0.3)
     vbs, vcs = [], []
     for _ in range(args.trials):
         t0 = time.perf_counter(); vb = mrcal.projection_uncertainty(p, model, observed_pixel_uncertainty=0.3); tb.append(time.perf_counter() - t0)
         t0 = time.perf_counter(); vc = u.evaluate(p);                                               tc.append(time.perf_counter() - t0)
         vbs.append(vb); vcs.append(vc)
+        t0 = time.perf_counter(); ud = mrcal.ProjectionUncertainty(model, observed_pixel_uncertainty=0.3); td.append(time.perf_counter() - t0)
+        ud.close()
     rel = lambda a, b: float(np.nanmax(np.abs(a - b)) / np.nanmax(np.abs(b)))  # (unproject() leaves NaN at a few imager corners)
     out["b_calls_identical"] = all(np.array_equal(v, vbs[0], equal_nan=True) for v in vbs)
     out["c_calls_identical"] = all(np.array_equal(v, vcs[0], equal_nan=True) for v in vcs)
@@ -58,8 +63,10 @@ def main():
     stat = lambda t: dict(min_ms=1e3*min(t), median_ms=1e3*float(np.median(t)), max_ms=1e3*max(t))
     out["b_one_shot"] = stat(tb)
     out["c_evaluate"] = stat(tc)
+    out["d_create"] = stat(td)
     print(f"(b) one-shot projection_uncertainty(): {out['b_one_shot']}")
     print(f"(c) evaluate() on a reused context:    {out['c_evaluate']}")
+    print(f"(d) ProjectionUncertainty():           {out['d_create']}")
 
     if not args.no_ref:
         n = args.ref_points
