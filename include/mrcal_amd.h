@@ -952,6 +952,112 @@ bool   mrcal_amd_triangulation_evaluate(mrcal_amd_triangulation_t* t, int N, con
 double mrcal_amd_triangulation_observed_pixel_uncertainty(const mrcal_amd_triangulation_t* t);
 void   mrcal_amd_triangulation_destroy(mrcal_amd_triangulation_t* t);
 
+/* ---- stereo rectification and image reprojection ---------------------------
+   Reference: stereo.h / stereo.c (the prototypes below are the reference's), mrcal/stereo.py,
+   mrcal/image_transforms.py. The geometry (mrcal_rectified_resolution(), mrcal_rectified_system2()) is host code and
+   needs no GPU: csrc/stereo_geometry.cpp. The maps, the remap and the ranges are kernels: csrc/rectification.hip.
+   Host arrays in and out. Only MRCAL_LENSMODEL_LATLON and MRCAL_LENSMODEL_PINHOLE rectify */
+bool mrcal_rectified_resolution(/* in, out. > 0: used as given; < 0: autodetected and scaled */
+                                double* pixels_per_deg_az, double* pixels_per_deg_el,
+                                const mrcal_lensmodel_t* lensmodel, const double* intrinsics,
+                                const mrcal_point2_t* azel_fov_deg, const mrcal_point2_t* azel0_deg,
+                                const double* R_cam0_rect0, const mrcal_lensmodel_type_t rectification_model_type);
+bool mrcal_rectified_system2(unsigned int* imagersize_rectified, double* fxycxy_rectified, double* rt_rect0_ref,
+                             double* baseline,
+                             double* pixels_per_deg_az, double* pixels_per_deg_el,
+                             mrcal_point2_t* azel_fov_deg, mrcal_point2_t* azel0_deg,
+                             const double az_edge_margin_deg,
+                             const mrcal_lensmodel_t* lensmodel0, const double* intrinsics0,
+                             const double* rt_cam0_ref, const double* rt_cam1_ref,
+                             const mrcal_lensmodel_type_t rectification_model_type,
+                             bool az0_deg_autodetect, bool el0_deg_autodetect,
+                             bool az_fov_deg_autodetect, bool el_fov_deg_autodetect);
+/* az_edge_margin_deg = 10 */
+bool mrcal_rectified_system(unsigned int* imagersize_rectified, double* fxycxy_rectified, double* rt_rect0_ref,
+                            double* baseline,
+                            double* pixels_per_deg_az, double* pixels_per_deg_el,
+                            mrcal_point2_t* azel_fov_deg, mrcal_point2_t* azel0_deg,
+                            const mrcal_lensmodel_t* lensmodel0, const double* intrinsics0,
+                            const double* rt_cam0_ref, const double* rt_cam1_ref,
+                            const mrcal_lensmodel_type_t rectification_model_type,
+                            bool az0_deg_autodetect, bool el0_deg_autodetect,
+                            bool az_fov_deg_autodetect, bool el_fov_deg_autodetect);
+/* rectification_maps: float32 (2, Nel, Naz, 2): where in each camera's image every rectified pixel is looked up */
+bool mrcal_rectification_maps(float* rectification_maps,
+                              const mrcal_lensmodel_t* lensmodel0, const double* intrinsics0, const double* r_cam0_ref,
+                              const mrcal_lensmodel_t* lensmodel1, const double* intrinsics1, const double* r_cam1_ref,
+                              const mrcal_lensmodel_type_t rectification_model_type,
+                              const double* fxycxy_rectified, const unsigned int* imagersize_rectified,
+                              const double* r_rect0_ref);
+/* reference: image.h. stride in bytes */
+typedef struct { union { struct { int width, height; }; struct { int w, h; }; struct { int cols, rows; }; };
+                 int stride; uint16_t* data; } mrcal_image_uint16_t;
+typedef struct { union { struct { int width, height; }; struct { int w, h; }; struct { int cols, rows; }; };
+                 int stride; double*   data; } mrcal_image_double_t;
+/* range = 0 where the disparity is <= 0, < min, > max, or the range is not finite */
+bool mrcal_stereo_range_sparse(double* range, const double* disparity, const mrcal_point2_t* qrect0, const int N,
+                               const double disparity_min, const double disparity_max,
+                               const mrcal_lensmodel_type_t rectification_model_type,
+                               const double* fxycxy_rectified, const double baseline);
+bool mrcal_stereo_range_dense(mrcal_image_double_t* range, const mrcal_image_uint16_t* disparity_scaled,
+                              const uint16_t disparity_scale,
+                              const uint16_t disparity_scaled_min, const uint16_t disparity_scaled_max,
+                              const mrcal_lensmodel_type_t rectification_model_type,
+                              const double* fxycxy_rectified, const double baseline);
+/* mrcal_stereo_range_sparse() that also writes p (N,3) = range unproject(qrect0)/|unproject(qrect0)|, the points in
+   rectified camera-0 coordinates: mrcal.stereo_unproject(). range or p may be NULL */
+bool mrcal_amd_stereo_range_sparse(double* range, double* p, const double* disparity, const mrcal_point2_t* qrect0,
+                                   const int N, const double disparity_min, const double disparity_max,
+                                   const mrcal_lensmodel_type_t rectification_model_type,
+                                   const double* fxycxy_rectified, const double baseline);
+
+/* mrcal.image_transformation_map(): mapxy float32 (H_to, W_to, 2). Per pixel of the TO imager: v = unproject_to(pixel);
+   p = A (v, or with distance > 0: v/|v| distance) + t; mapxy = project_from(p). A (3x3) and t (3; NULL: 0) are the
+   caller's: a rotation R_from_to; R_from_to and t_from_to with a distance; the inverse homography inv(d R_to_from +
+   t_to_from n^T) for a plane. region: a closed contour (Nregion,2) in the FROM imager or NULL; pixels that land
+   outside it are -1 (at most 2048 vertices). The same bits on every call */
+bool mrcal_amd_image_transformation_map(float* mapxy,
+                                        const mrcal_lensmodel_t* lensmodel_from, const double* intrinsics_from,
+                                        const mrcal_lensmodel_t* lensmodel_to,   const double* intrinsics_to,
+                                        const unsigned int* imagersize_to,
+                                        const double* A, const double* t, double distance,
+                                        const double* region, int Nregion);
+/* mrcal.transform_image(): out[i] = image(mapxy[i]). Exact bilinear interpolation in float32 (cv2.remap()'s 1/32-pixel
+   fixed point is NOT imitated), or the nearest pixel (halves to even).
+   dtype: MRCAL_AMD_IMAGE_*; channels: 1 or 3, interleaved; every array dense.
+   MRCAL_AMD_BORDER_CONSTANT:    a neighbour outside the image is border_value[channel]; a non-finite map entry gives it
+   MRCAL_AMD_BORDER_TRANSPARENT: a pixel with any neighbour outside, or a non-finite map entry, keeps what out had */
+#define MRCAL_AMD_IMAGE_UINT8   0
+#define MRCAL_AMD_IMAGE_UINT16  1
+#define MRCAL_AMD_IMAGE_FLOAT   2
+#define MRCAL_AMD_INTER_NEAREST 0
+#define MRCAL_AMD_INTER_LINEAR  1
+#define MRCAL_AMD_BORDER_CONSTANT    0
+#define MRCAL_AMD_BORDER_TRANSPARENT 5
+bool mrcal_amd_transform_image(void* out, const void* image, int width, int height, int channels, int dtype,
+                               const float* mapxy, int width_out, int height_out,
+                               int interpolation, int border_mode, const double* border_value /*channels*/);
+/* The resident form: both rectification maps made once and kept on the device.
+   _maps():    mrcal_rectification_maps()'s array, the same bits
+   _rectify(): the two images (width0 x height0, width1 x height1) remapped to out0, out1 (Naz x Nel); the maps do
+               not leave the device
+   _range():   mrcal_stereo_range_dense() of a dense (Nel,Naz) disparity, on the device */
+typedef struct mrcal_amd_rectification mrcal_amd_rectification_t;
+mrcal_amd_rectification_t*
+mrcal_amd_rectification_create(const mrcal_lensmodel_t* lensmodel0, const double* intrinsics0, const double* r_cam0_ref,
+                               const mrcal_lensmodel_t* lensmodel1, const double* intrinsics1, const double* r_cam1_ref,
+                               const mrcal_lensmodel_type_t rectification_model_type,
+                               const double* fxycxy_rectified, const unsigned int* imagersize_rectified,
+                               const double* r_rect0_ref, double baseline);
+bool mrcal_amd_rectification_maps(mrcal_amd_rectification_t* r, float* rectification_maps);
+bool mrcal_amd_rectification_rectify(mrcal_amd_rectification_t* r, void* out0, void* out1,
+                                     const void* image0, int width0, int height0,
+                                     const void* image1, int width1, int height1, int channels, int dtype,
+                                     int interpolation, int border_mode, const double* border_value);
+bool mrcal_amd_rectification_range(mrcal_amd_rectification_t* r, double* range, const uint16_t* disparity_scaled,
+                                   uint16_t disparity_scale, uint16_t disparity_scaled_min, uint16_t disparity_scaled_max);
+void mrcal_amd_rectification_destroy(mrcal_amd_rectification_t* r);
+
 #ifdef __cplusplus
 }
 #endif

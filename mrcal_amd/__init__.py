@@ -76,6 +76,10 @@ from .model_analysis import (projection_uncertainty, ProjectionUncertainty, wors
 from .triangulation import (triangulate_geometric, triangulate_lindstrom, triangulate_leecivera_l1,
                             triangulate_leecivera_linf, triangulate_leecivera_mid2, triangulate_leecivera_wmid2,
                             triangulate, Triangulation)
+from .stereo import (rectified_resolution, rectified_system, rectification_maps, stereo_range, stereo_unproject,
+                     Rectification)
+from .image_transforms import (scale_focal__best_pinhole_fit, pinhole_model_for_reprojection, image_transformation_map,
+                               transform_image)
 from .utils import sample_imager, sample_imager_unproject
 
 # the callers either side of the path: the on-disk format of

@@ -1,0 +1,405 @@
+"""Stereo rectification: the rectified system, its maps, ranges from disparities.
+
+    models_rectified = mrcal_amd.rectified_system(models, az_fov_deg = 90, el_fov_deg = 50)
+    maps             = mrcal_amd.rectification_maps(models, models_rectified)
+    images_rectified = [mrcal_amd.transform_image(i, m) for i, m in zip(images, maps)]
+    ranges           = mrcal_amd.stereo_range(disparity, models_rectified, disparity_scale = 16)
+
+    with mrcal_amd.Rectification(models, models_rectified) as r:       # the maps are made once and stay on the device
+        for image0, image1 in frames:
+            rect0, rect1 = r.rectify(image0, image1)
+            ranges       = r.range(matcher(rect0, rect1), disparity_scale = 16)
+
+The names, keyword arguments, defaults, return shapes and exception messages are those of the reference's
+mrcal/stereo.py. rectified_system() and rectified_resolution() are host code (csrc/stereo_geometry.cpp) and need no
+GPU; the maps, the remap and the ranges are kernels (csrc/rectification.hip), and there is no CPU fallback for them.
+Out of scope: match_feature(), image file I/O, stereo matching itself, LONLAT rectification (which the reference's
+rectified_system() refuses too).
+"""
+import ctypes as C
+import numpy as np
+
+from ._cabi import _ptr
+from .poseutils import compose_Rt
+
+
+class _Point2(C.Structure):
+    _fields_ = [("x", C.c_double), ("y", C.c_double)]
+
+
+def _libs():
+    from . import _lib, _api
+    return _lib, _api
+
+
+def _rectification_model_type(lib, rectification_model):
+    return lib.lensmodel(rectification_model).type
+
+
+def rectified_resolution(model0, *, az_fov_deg, el_fov_deg, az0_deg, el0_deg, R_cam0_rect0,
+                         pixels_per_deg_az=-1., pixels_per_deg_el=-1., rectification_model='LENSMODEL_LATLON'):
+    """The resolution of the rectified system: (pixels_per_deg_az, pixels_per_deg_el)
+
+A value > 0 is used as given. A value < 0 scales the resolution model0 has at the centre (az0_deg, el0_deg) of the
+rectified view: -1 keeps it, -0.5 halves it. For LENSMODEL_LATLON and LENSMODEL_LONLAT the result is then adjusted so
+that the field of view is a whole number of pixels; for LENSMODEL_PINHOLE it is the resolution at the centre.
+Reference: mrcal.rectified_resolution(), mrcal_rectified_resolution()"""
+    lib, api = _libs()
+    lensmodel, intrinsics = model0.intrinsics()
+    m = lib.lensmodel(lensmodel)
+    intrinsics = np.ascontiguousarray(intrinsics, dtype=np.float64)
+    R = np.ascontiguousarray(R_cam0_rect0, dtype=np.float64)
+    if R.shape != (3, 3):
+        raise Exception(f"R_cam0_rect0 must have shape (3,3), got {R.shape}")
+    az, el = C.c_double(pixels_per_deg_az), C.c_double(pixels_per_deg_el)
+    fov, center = _Point2(az_fov_deg, el_fov_deg), _Point2(az0_deg, el0_deg)
+    f = lib.lib.mrcal_rectified_resolution
+    f.restype, f.argtypes = C.c_bool, [C.c_void_p]*7 + [C.c_int]
+    if not f(C.addressof(az), C.addressof(el), C.addressof(m), _ptr(intrinsics), C.addressof(fov), C.addressof(center),
+             _ptr(R), _rectification_model_type(lib, rectification_model)):
+        raise Exception("mrcal_rectified_resolution() failed:" + api._last_error())
+    return az.value, el.value
+
+
+def rectified_system(models, *, az_fov_deg, el_fov_deg, az0_deg=None, el0_deg=0, az_edge_margin_deg=10.,
+                     pixels_per_deg_az=-1., pixels_per_deg_el=-1., rectification_model='LENSMODEL_LATLON',
+                     return_metadata=False):
+    """The two rectified models of a stereo pair: LENSMODEL_LATLON (the default) or LENSMODEL_PINHOLE cameramodels with
+identical intrinsics, the same orientation, and camera 1 a baseline away along the rectified +x
+
+models: the two cameramodels. az_fov_deg, el_fov_deg: the field of view of the rectified images. az0_deg, el0_deg: its
+centre; az0_deg = None: the mean forward direction of the two cameras, shifted if need be so that the view stays
+az_edge_margin_deg away from the baseline. pixels_per_deg_az, pixels_per_deg_el: as for rectified_resolution().
+return_metadata: also a dict with az_fov_deg, el_fov_deg, az0_deg, el0_deg, pixels_per_deg_az, pixels_per_deg_el,
+baseline as they ended up. Runs on the host: no GPU is needed.
+Reference: mrcal.rectified_system(), mrcal_rectified_system2()"""
+    from .cameramodel import cameramodel
+    lib, api = _libs()
+    if len(models) != 2:
+        raise Exception("I need exactly 2 camera models")
+    for m in models:
+        lensmodel, intrinsics = m.intrinsics()
+        # (the one noncentral model)
+        if lensmodel.startswith("LENSMODEL_CAHVORE") and np.any(np.asarray(intrinsics)[-3:] != 0):
+            raise Exception("Stereo rectification is only possible with a central projection. Please centralize your models. This is CAHVORE, so set E=0 to centralize. This will ignore all noncentral effects near the lens")
+
+    lensmodel, intrinsics = models[0].intrinsics()
+    m = lib.lensmodel(lensmodel)
+    intrinsics = np.ascontiguousarray(intrinsics, dtype=np.float64)
+    rt0 = np.ascontiguousarray(models[0].rt_cam_ref(), dtype=np.float64)
+    rt1 = np.ascontiguousarray(models[1].rt_cam_ref(), dtype=np.float64)
+    imagersize = (C.c_uint*2)()
+    fxycxy, rt_rect0_ref = np.zeros(4), np.zeros(6)
+    baseline = C.c_double(0)
+    az, el = C.c_double(pixels_per_deg_az), C.c_double(pixels_per_deg_el)
+    autodetect = az0_deg is None
+    fov, center = _Point2(az_fov_deg, el_fov_deg), _Point2(0. if autodetect else az0_deg, el0_deg)
+    f = lib.lib.mrcal_rectified_system2
+    f.restype  = C.c_bool
+    f.argtypes = [C.c_void_p]*8 + [C.c_double] + [C.c_void_p]*4 + [C.c_int] + [C.c_bool]*4
+    if not f(C.addressof(imagersize), _ptr(fxycxy), _ptr(rt_rect0_ref), C.addressof(baseline),
+             C.addressof(az), C.addressof(el), C.addressof(fov), C.addressof(center),
+             float(az_edge_margin_deg), C.addressof(m), _ptr(intrinsics), _ptr(rt0), _ptr(rt1),
+             _rectification_model_type(lib, rectification_model), autodetect, False, False, False):
+        raise Exception("mrcal_rectified_system2() failed:" + api._last_error())
+
+    # rect1 has the orientation of rect0, and its origin at camera 1: rt_rect0_rect1 = (0,0,0, baseline,0,0)
+    rt_rect1_ref = rt_rect0_ref.copy()
+    rt_rect1_ref[3] -= baseline.value
+    Naz, Nel = int(imagersize[0]), int(imagersize[1])
+    models_rectified = tuple(cameramodel(intrinsics=(rectification_model, fxycxy.copy()), imagersize=(Naz, Nel), rt_cam_ref=rt)
+                             for rt in (rt_rect0_ref, rt_rect1_ref))
+    if not return_metadata:
+        return models_rectified
+    return models_rectified, dict(az_fov_deg=fov.x, el_fov_deg=fov.y, az0_deg=center.x, el0_deg=center.y,
+                                  pixels_per_deg_az=az.value, pixels_per_deg_el=el.value, baseline=baseline.value)
+
+
+def _validate_models_rectified(models_rectified):
+    """what rectified_system() returns: two LENSMODEL_LATLON or LENSMODEL_PINHOLE cameras with identical intrinsics and
+    orientation, the second a translation along the rectified +x away"""
+    if len(models_rectified) != 2:
+        raise Exception(f"Must have received exactly two models. Got {len(models_rectified)} instead")
+    intrinsics = [m.intrinsics() for m in models_rectified]
+    Rt01 = compose_Rt(models_rectified[0].Rt_cam_ref(), models_rectified[1].Rt_ref_cam())
+    if not ((intrinsics[0][0] == 'LENSMODEL_LATLON'  and intrinsics[1][0] == 'LENSMODEL_LATLON') or
+            (intrinsics[0][0] == 'LENSMODEL_PINHOLE' and intrinsics[1][0] == 'LENSMODEL_PINHOLE')):
+        raise Exception(f"Expected two models with the same  'LENSMODEL_LATLON' or 'LENSMODEL_PINHOLE' but got {intrinsics[0][0]} and {intrinsics[1][0]}")
+    d = np.asarray(intrinsics[0][1]) - np.asarray(intrinsics[1][1])
+    if np.dot(d, d) > 1e-6:
+        raise Exception("The two rectified models MUST have the same intrinsics values")
+    if tuple(int(x) for x in models_rectified[0].imagersize()) != tuple(int(x) for x in models_rectified[1].imagersize()):
+        raise Exception("The two rectified models MUST have the same imager size")
+    costh = (np.trace(Rt01[:3, :]) - 1.) / 2.
+    if costh < 0.999999:
+        raise Exception("The two rectified models MUST have the same relative rotation")
+    if np.dot(Rt01[3, 1:], Rt01[3, 1:]) > 1e-9:
+        raise Exception("The two rectified models MUST have a translation ONLY in the +x rectified direction")
+
+
+def _baseline(models_rectified):
+    Rt01 = compose_Rt(models_rectified[0].Rt_cam_ref(), models_rectified[1].Rt_ref_cam())
+    return float(np.linalg.norm(Rt01[3, :]))
+
+
+_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1, np.dtype(np.float32): 2}
+
+
+def _image_arguments(image, what="image"):
+    """-> dense array, width, height, channels, dtype code"""
+    if not isinstance(image, np.ndarray):
+        raise Exception(f"'{what}' must be a numpy array")
+    if image.dtype not in _DTYPES:
+        raise Exception(f"'{what}' must have dtype uint8, uint16 or float32, not {image.dtype}")
+    if not (image.ndim == 2 or (image.ndim == 3 and image.shape[2] == 3)) or image.size == 0:
+        raise Exception(f"'{what}' must have shape (H,W) or (H,W,3), got {image.shape}")
+    return np.ascontiguousarray(image), image.shape[1], image.shape[0], (1 if image.ndim == 2 else 3), _DTYPES[image.dtype]
+
+
+def _remap_modes(borderMode, interpolation):
+    if   borderMode is None or borderMode == 'constant'    or (not isinstance(borderMode, str) and borderMode == 0): border = 0
+    elif                       borderMode == 'transparent' or (not isinstance(borderMode, str) and borderMode == 5): border = 5
+    else: raise Exception(f"borderMode must be None, 'constant' (0) or 'transparent' (5), not {borderMode!r}")
+    if   interpolation is None or interpolation == 'linear'  or (not isinstance(interpolation, str) and interpolation == 1): interp = 1
+    elif                          interpolation == 'nearest' or (not isinstance(interpolation, str) and interpolation == 0): interp = 0
+    else: raise Exception(f"interpolation must be None, 'linear' (1) or 'nearest' (0), not {interpolation!r}")
+    return border, interp
+
+
+def _border_values(borderValue, channels):
+    b = np.atleast_1d(np.asarray(borderValue, dtype=np.float64)).ravel()
+    if b.size == 1: b = np.repeat(b, channels)
+    if b.size < channels:
+        raise Exception(f"borderValue must be a scalar or have a value per channel ({channels}), got {b.size}")
+    return np.ascontiguousarray(b[:channels])
+
+
+def _output_array(out, shape, dtype, transparent):
+    """-> (the dense array the library fills, the array to return)"""
+    if out is None:
+        o = np.zeros(shape, dtype=dtype)
+        return o, o
+    if not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != dtype:
+        raise Exception(f"'out' must be a numpy array of shape {shape} and dtype {np.dtype(dtype)}")
+    if out.flags.c_contiguous:
+        return out, out
+    return (np.ascontiguousarray(out) if transparent else np.empty(shape, dtype=dtype)), out
+
+
+class Rectification:
+    """The rectification of a stereo pair, resident: both maps are made on the device once and stay there.
+
+    models: the two cameramodels; models_rectified: what rectified_system() returned for them.
+      .maps()                          rectification_maps(): float32 (2, Nel, Naz, 2), the same bits
+      .rectify(image0, image1)         the two rectified images; the maps do not cross to the host and back
+      .range(disparity, ...)           stereo_range() of a dense (Nel, Naz) disparity"""
+
+    def __init__(self, models, models_rectified):
+        self.handle = None
+        _validate_models_rectified(models_rectified)
+        if len(models) != 2:
+            raise Exception("I need exactly 2 camera models")
+        lib, api = _libs()
+        self._L, self._api = lib.lib, api
+        self._models_rectified = tuple(models_rectified)
+        self.Naz, self.Nel = (int(x) for x in models_rectified[0].imagersize())
+        args, keep = [], []
+        for m in models:
+            lensmodel, intrinsics = m.intrinsics()
+            lm = lib.lensmodel(lensmodel)
+            intrinsics = np.ascontiguousarray(intrinsics, dtype=np.float64)
+            r = np.ascontiguousarray(m.rt_cam_ref()[:3], dtype=np.float64)
+            keep += [lm, intrinsics, r]
+            args += [C.addressof(lm), _ptr(intrinsics), _ptr(r)]
+        rectification_model, fxycxy = models_rectified[0].intrinsics()
+        fxycxy = np.ascontiguousarray(fxycxy, dtype=np.float64)
+        imagersize = (C.c_uint*2)(self.Naz, self.Nel)
+        r_rect0_ref = np.ascontiguousarray(models_rectified[0].rt_cam_ref()[:3], dtype=np.float64)
+        f = self._L.mrcal_amd_rectification_create
+        f.restype, f.argtypes = C.c_void_p, [C.c_void_p]*6 + [C.c_int] + [C.c_void_p]*3 + [C.c_double]
+        self.handle = f(*args, _rectification_model_type(lib, rectification_model), _ptr(fxycxy), C.addressof(imagersize),
+                        _ptr(r_rect0_ref), _baseline(models_rectified))
+        if not self.handle:
+            self.handle = None
+            raise Exception("rectification_maps() failed:" + api._last_error())
+        self._L.mrcal_amd_rectification_destroy.restype, self._L.mrcal_amd_rectification_destroy.argtypes = None, [C.c_void_p]
+
+    def _open(self):
+        if self.handle is None:
+            raise Exception("this Rectification has been closed")
+
+    def maps(self):
+        self._open()
+        maps = np.zeros((2, self.Nel, self.Naz, 2), dtype=np.float32)
+        f = self._L.mrcal_amd_rectification_maps
+        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2
+        if not f(self.handle, _ptr(maps)):
+            raise Exception("rectification_maps() failed:" + self._api._last_error())
+        return maps
+
+    def rectify(self, image0, image1, out=None):
+        """(image0 rectified, image1 rectified): linear interpolation, 0 outside the images. out: the two arrays to fill"""
+        self._open()
+        a0, w0, h0, c0, t0 = _image_arguments(image0, "image0")
+        a1, w1, h1, c1, t1 = _image_arguments(image1, "image1")
+        if (c0, t0) != (c1, t1):
+            raise Exception("image0 and image1 must have the same dtype and number of channels")
+        shape = (self.Nel, self.Naz) if c0 == 1 else (self.Nel, self.Naz, 3)
+        if out is not None and len(out) != 2:
+            raise Exception("'out' must be a pair of arrays")
+        (o0, r0), (o1, r1) = (_output_array(None if out is None else out[i], shape, a0.dtype, False) for i in (0, 1))
+        f = self._L.mrcal_amd_rectification_rectify
+        f.restype  = C.c_bool
+        f.argtypes = [C.c_void_p]*4 + [C.c_int]*2 + [C.c_void_p] + [C.c_int]*6 + [C.c_void_p]
+        if not f(self.handle, _ptr(o0), _ptr(o1), _ptr(a0), w0, h0, _ptr(a1), w1, h1, c0, t0, 1, 0, None):
+            raise Exception("rectify() failed:" + self._api._last_error())
+        if r0 is not o0: r0[...] = o0
+        if r1 is not o1: r1[...] = o1
+        return r0, r1
+
+    def range(self, disparity, *, disparity_scale=1, disparity_min=None, disparity_max=None,
+              disparity_scaled_min=None, disparity_scaled_max=None):
+        """stereo_range(disparity, models_rectified, ...) of a dense (Nel, Naz) disparity"""
+        self._open()
+        return stereo_range(disparity, self._models_rectified, disparity_scale=disparity_scale,
+                            disparity_min=disparity_min, disparity_max=disparity_max,
+                            disparity_scaled_min=disparity_scaled_min, disparity_scaled_max=disparity_scaled_max,
+                            _rectification=self)
+
+    def _range_dense(self, disparity_scaled, disparity_scale, dmin, dmax):
+        d = np.ascontiguousarray(disparity_scaled, dtype=np.uint16)
+        r = np.zeros(d.shape, dtype=np.float64)
+        f = self._L.mrcal_amd_rectification_range
+        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*3 + [C.c_uint16]*3
+        if not f(self.handle, _ptr(r), _ptr(d), int(disparity_scale), int(dmin), int(dmax)):
+            raise Exception("stereo_range() failed:" + self._api._last_error())
+        return r
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._L.mrcal_amd_rectification_destroy(self.handle)
+            self.handle = None
+    def __del__(self):
+        try:    self.close()
+        except Exception: pass
+    def __enter__(self): return self
+    def __exit__(self, *a): self.close()
+
+
+def rectification_maps(models, models_rectified):
+    """float32 (2, Nel, Naz, 2): for every pixel of the rectified images, where to look it up in the image of camera 0
+and of camera 1: maps[i] is what transform_image(image_i, maps[i]) takes. The one-shot form of
+Rectification(models, models_rectified).maps(). Reference: mrcal.rectification_maps(), mrcal_rectification_maps()"""
+    with Rectification(models, models_rectified) as r:
+        return r.maps()
+
+
+class _Image(C.Structure):
+    """mrcal_image_uint16_t, mrcal_image_double_t: the stride in bytes"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("stride", C.c_int), ("data", C.c_void_p)]
+
+
+def stereo_range(disparity, models_rectified, *, disparity_scale=1, disparity_min=None, disparity_scaled_min=None,
+                 disparity_max=None, disparity_scaled_max=None, qrect0=None, _rectification=None):
+    """Ranges from disparities; 0 where the disparity is invalid (<= 0, below the minimum, above the maximum) or the
+range is not finite
+
+Dense form (qrect0 is None): disparity is an (Nel, Naz) image from a stereo matcher, cast to uint16 as the reference
+does (an int16 image: the maximum defaults to 0x7FFF, so that its negative "invalid" marks stay invalid); the true
+disparity in pixels is disparity / disparity_scale. Sparse form: qrect0 (...,2), the pixels in the rectified image of
+camera 0 the disparities (...) belong to; they broadcast, and a scalar disparity gives a scalar.
+disparity_min/max are in pixels, disparity_scaled_min/max in the units of the given disparity.
+Reference: mrcal.stereo_range(), mrcal_stereo_range_dense(), mrcal_stereo_range_sparse()"""
+    if _rectification is None: _validate_models_rectified(models_rectified)     # (a Rectification has)
+    if disparity_min is not None and disparity_scaled_min is not None and disparity_min != disparity_scaled_min:
+        raise Exception("disparity_min and disparity_scaled_min may not both be given")
+    if disparity_max is not None and disparity_scaled_max is not None and disparity_max != disparity_scaled_max:
+        raise Exception("disparity_max and disparity_scaled_max may not both be given")
+    # an int16 image marks invalid pixels with negative values, which the cast to uint16 turns into large ones
+    if disparity_max is None and disparity_scaled_max is None and isinstance(disparity, np.ndarray) and disparity.dtype == np.int16:
+        disparity_scaled_max = 0x7FFF
+    # Each bound may come in pixels or in the units of the given disparity; the dense kernel wants the latter, the
+    # sparse one the former. Absent: 0, and the largest value the type holds
+    dense = qrect0 is None
+    def bound(pixels, scaled, absent):
+        if dense: return scaled if scaled is not None else absent if pixels is None else pixels*disparity_scale
+        return pixels if pixels is not None else absent if scaled is None else scaled/disparity_scale
+    lowest  = bound(disparity_min, disparity_scaled_min, 0)
+    highest = bound(disparity_max, disparity_scaled_max, 0xFFFF if dense else np.finfo(float).max)
+    if dense: disparity_scaled_min, disparity_scaled_max = lowest, highest
+    else:     disparity_min, disparity_max = lowest, highest
+
+    is_scalar = np.ndim(disparity) == 0
+    disparity = np.atleast_1d(np.asarray(disparity))
+    lib, api = _libs()
+    rectification_model, fxycxy = models_rectified[0].intrinsics()
+    fxycxy = np.ascontiguousarray(fxycxy, dtype=np.float64)
+    model_type = _rectification_model_type(lib, rectification_model)
+    baseline = _baseline(models_rectified)
+
+    if qrect0 is None:
+        W, H = (int(x) for x in models_rectified[0].imagersize())
+        if disparity.shape != (H, W):
+            raise Exception(f"qrect0 is None, so the given disparity and full rectified images MUST have the same dimensions. I have disparity.shape={disparity.shape} and models_rectified[0].imagersize()={(W, H)}")
+        d = np.ascontiguousarray(disparity.astype(np.uint16))
+        # (uint16 arguments: a bound beyond their range is the end of the range)
+        scale, dmin, dmax = (int(min(max(x, 0), 0xFFFF)) for x in (disparity_scale, disparity_scaled_min, disparity_scaled_max))
+        if _rectification is not None:
+            return _rectification._range_dense(d, scale, dmin, dmax)
+        r = np.zeros((H, W), dtype=np.float64)
+        image_d = _Image(W, H, W*2, d.ctypes.data)
+        image_r = _Image(W, H, W*8, r.ctypes.data)
+        f = lib.lib.mrcal_stereo_range_dense
+        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2 + [C.c_uint16]*3 + [C.c_int, C.c_void_p, C.c_double]
+        if not f(C.addressof(image_r), C.addressof(image_d), scale, dmin, dmax, model_type, _ptr(fxycxy), baseline):
+            raise Exception("mrcal_stereo_range_dense() failed:" + api._last_error())
+        return r
+
+    r = _range_sparse(disparity.astype(float) / disparity_scale, qrect0, float(disparity_min), float(disparity_max),
+                      model_type, fxycxy, baseline, False)
+    return r[0] if is_scalar and r.shape == (1,) else r
+
+
+def _range_sparse(disparity, qrect0, disparity_min, disparity_max, model_type, fxycxy, baseline, want_points):
+    """the broadcast batch through mrcal_amd_stereo_range_sparse(): ranges (...), or the points (...,3)"""
+    lib, api = _libs()
+    qrect0 = np.asarray(qrect0, dtype=np.float64)
+    if qrect0.ndim < 1 or qrect0.shape[-1] != 2:
+        raise Exception(f"qrect0 must have shape (...,2), got {qrect0.shape}")
+    lead = np.broadcast_shapes(disparity.shape, qrect0.shape[:-1])
+    d = np.ascontiguousarray(np.broadcast_to(disparity, lead), dtype=np.float64).ravel()
+    q = np.ascontiguousarray(np.broadcast_to(qrect0, lead + (2,)), dtype=np.float64).reshape(-1, 2)
+    N = d.shape[0]
+    out = np.zeros((N, 3) if want_points else (N,))
+    f = lib.lib.mrcal_amd_stereo_range_sparse
+    f.restype  = C.c_bool
+    f.argtypes = [C.c_void_p]*4 + [C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_double]
+    if not f(None if want_points else _ptr(out), _ptr(out) if want_points else None, _ptr(d), _ptr(q), N,
+             disparity_min, disparity_max, model_type, _ptr(fxycxy), baseline):
+        raise Exception("mrcal_stereo_range_sparse() failed:" + api._last_error())
+    return out.reshape(lead + ((3,) if want_points else ()))
+
+
+def stereo_unproject(disparity, models_rectified, *, ranges=None, disparity_scale=1, qrect0=None):
+    """The points (...,3), in the coordinates of the rectified camera 0, that disparities (or ranges) see: (0,0,0) where
+the disparity is invalid. Exactly one of disparity and ranges is given; qrect0 as in stereo_range().
+Reference: mrcal.stereo_unproject()"""
+    if (ranges is None) == (disparity is None):
+        raise Exception("Exactly one of (disparity,ranges) must be non-None")
+    lib, api = _libs()
+    if ranges is None and qrect0 is not None:
+        # one launch: the range and the unit vector it scales
+        _validate_models_rectified(models_rectified)
+        rectification_model, fxycxy = models_rectified[0].intrinsics()
+        is_scalar = np.ndim(disparity) == 0 and np.ndim(qrect0) == 1
+        d = np.atleast_1d(np.asarray(disparity)).astype(float) / disparity_scale
+        p = _range_sparse(d, qrect0, 0., np.finfo(float).max, _rectification_model_type(lib, rectification_model),
+                          np.ascontiguousarray(fxycxy, dtype=np.float64), _baseline(models_rectified), True)
+        return p[0] if is_scalar and p.shape == (1, 3) else p
+    if ranges is None:
+        ranges = stereo_range(disparity, models_rectified, disparity_scale=disparity_scale, qrect0=qrect0)
+    if qrect0 is None:
+        W, H = (int(x) for x in models_rectified[0].imagersize())
+        qrect0 = np.ascontiguousarray(np.stack(np.meshgrid(np.arange(W, dtype=float), np.arange(H, dtype=float)), axis=-1))
+    vrect0 = api.unproject(np.asarray(qrect0, dtype=float), *models_rectified[0].intrinsics(), normalize=True)
+    return vrect0 * np.asarray(ranges)[..., np.newaxis]
