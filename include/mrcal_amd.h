@@ -1058,6 +1058,58 @@ bool mrcal_amd_rectification_range(mrcal_amd_rectification_t* r, double* range, 
                                    uint16_t disparity_scale, uint16_t disparity_scaled_min, uint16_t disparity_scaled_max);
 void mrcal_amd_rectification_destroy(mrcal_amd_rectification_t* r);
 
+/* ---- match_feature: template matching between two images --------------------
+   mrcal.match_feature() (mrcal/stereo.py), which hands the correlation to cv2.matchTemplate(); here it is
+   csrc/match_feature.hip, planned on the host by csrc/match_plan.hpp. Both images (grayscale, dense, the same
+   MRCAL_AMD_IMAGE_* dtype) are uploaded once by _create(); _match() then finds N features of image0 in image1.
+
+   A feature: q1e (its estimate in image1), H01 (3x3, row-major: image1 pixels -> image0 pixels; the caller inverts its
+   H10, the library inverts nothing), the template's size (tw,th) and the search radius r, the same for all N:
+     1. tmin = rint(q1e - ((tw,th) - 1)/2), tmax = tmin + (tw,th) - 1: both inside image1, or the status is 3
+     2. the template = image0 remapped (bilinear, 0 outside, integers rounded to nearest: mrcal_amd_transform_image())
+        through H01 applied to the integer pixels tmin..tmax, in double, rounded to float32; the four corners of that
+        map inside image0, or the status is 4
+     3. the cut of image1 that is searched: qmin = max(tmin - r, 0) .. qmax = min(tmin + r + (tw,th) - 1, size - 1);
+        the match surface has (qmax - qmin + 1) - (tw,th) + 1 entries each way
+     4. per entry, over its window of the cut: IT = sum I T, SI = sum I, SI2 = sum I^2; ST, ST2 of the template; N = tw th.
+        Integer images: exact integers (uint8 in 32 bits: a template of more than 66051 pixels is refused; uint16 in 64
+        bits). float32: summed in double in a fixed order
+     5. the method's formula in double, rounded to float32:
+          SQDIFF  SI2 - 2 IT + ST2       SQDIFF_NORMED  that / sqrt(SI2 ST2)
+          CCORR   IT                     CCORR_NORMED   IT / sqrt(SI2 ST2)
+          CCOEFF  IT - SI ST/N           CCOEFF_NORMED  that / sqrt(max(SI2 - SI SI/N, 0) max(ST2 - ST ST/N, 0))
+        a denominator that is not > 0: 0 (SQDIFF_NORMED: 1)
+     6. the optimum: the minimum (SQDIFF, SQDIFF_NORMED) or the maximum; of equal ones the first in row-major order.
+        On the edge of the surface: status 1
+     7. the least-squares quadric through the 3x3 entries around it, its stationary point xy (det == 0 or a result
+        that is not finite: status 2); q1 = optimum + xy + qmin + q1e - tmin
+   status: 0 ok; 1 the optimum is on the edge; 2 the subpixel fit is degenerate; 3 the template is outside image1;
+   4 outside image0. A row that is not 0 has NaN in q1, optimum_subpixel_at and optimum_subpixel. _match() returns
+   false only for what is wrong whatever the data (sizes that are refused, a device error), never for a status.
+   qmin (N,2) and output_size (N,2: width, height; 0 for status 3 and 4) are what _matchoutput() and the caller need
+   to read a surface. _matchoutput(i) and _template(i) copy out what the last _match() left on the device: the
+   surface of feature i (float32, output_size[i] entries) and its template (tw x th pixels of the images' dtype).
+   No atomics: the same bits on every call */
+#define MRCAL_AMD_TM_SQDIFF        0
+#define MRCAL_AMD_TM_SQDIFF_NORMED 1
+#define MRCAL_AMD_TM_CCORR         2
+#define MRCAL_AMD_TM_CCORR_NORMED  3
+#define MRCAL_AMD_TM_CCOEFF        4
+#define MRCAL_AMD_TM_CCOEFF_NORMED 5
+typedef struct mrcal_amd_feature_matcher mrcal_amd_feature_matcher_t;
+mrcal_amd_feature_matcher_t*
+mrcal_amd_feature_matcher_create(const void* image0, int width0, int height0,
+                                 const void* image1, int width1, int height1, int dtype);
+bool mrcal_amd_feature_matcher_match(mrcal_amd_feature_matcher_t* m, int N,
+                                     const double* q1_estimate /*N,2*/, const double* H01 /*N,3,3*/,
+                                     int template_width, int template_height, int search_radius, int method,
+                                     double* q1 /*N,2*/, int* status /*N*/,
+                                     double* optimum_subpixel_at /*N,2*/, double* optimum_subpixel /*N*/,
+                                     int* qmin /*N,2*/, int* output_size /*N,2*/);
+bool mrcal_amd_feature_matcher_matchoutput(mrcal_amd_feature_matcher_t* m, int i, float* matchoutput);
+bool mrcal_amd_feature_matcher_template(mrcal_amd_feature_matcher_t* m, int i, void* template_image);
+void mrcal_amd_feature_matcher_destroy(mrcal_amd_feature_matcher_t* m);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@
 #include "host_state.hpp"
 #include "device_memory.hpp"
 #include "stereo_geometry.hpp"
+#include "remap.hpp"
 
 namespace mrcal_amd {
 
@@ -418,7 +419,8 @@ bool remap_arguments_ok(int width, int height, int channels, int dtype, int widt
     return true;
 }
 
-// device arrays; the arguments have been checked
+} // namespace
+// device arrays; the arguments have been checked (remap.hpp: match_feature.hip makes its templates with it)
 bool remap_device(const void* d_src, int W, int H, int C, int dtype, const float* d_map, void* d_out, int Nout,
                   int interp, int border_mode, const double* border_value)
 {
@@ -442,6 +444,7 @@ bool remap_device(const void* d_src, int W, int H, int C, int dtype, const float
     HIP_TRY(hipGetLastError(), return false);
     return true;
 }
+namespace {
 
 // host image -> remapped host image through a map that is on the device already
 bool remap_host_image(void* out, const void* image, int W, int H, int C, int dtype, const float* d_map, int Nout,

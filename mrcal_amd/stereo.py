@@ -10,10 +10,16 @@
             rect0, rect1 = r.rectify(image0, image1)
             ranges       = r.range(matcher(rect0, rect1), disparity_scale = 16)
 
+    q1, diagnostics  = mrcal_amd.match_feature(image0, image1, q0, H10 = H10, search_radius1 = 200, template_size1 = 41)
+
+    with mrcal_amd.FeatureMatcher(image0, image1) as matcher:          # both images are uploaded once
+        q1, status = matcher.match(q0, H10 = H10, search_radius1 = 200, template_size1 = 41)        # q0 (N,2)
+
 The names, keyword arguments, defaults, return shapes and exception messages are those of the reference's
 mrcal/stereo.py. rectified_system() and rectified_resolution() are host code (csrc/stereo_geometry.cpp) and need no
-GPU; the maps, the remap and the ranges are kernels (csrc/rectification.hip), and there is no CPU fallback for them.
-Out of scope: match_feature(), image file I/O, stereo matching itself, LONLAT rectification (which the reference's
+GPU; the maps, the remap and the ranges are kernels (csrc/rectification.hip), the template matching of match_feature()
+is csrc/match_feature.hip, and there is no CPU fallback for them.
+Out of scope: image file I/O, dense stereo matching, visualization, LONLAT rectification (which the reference's
 rectified_system() refuses too).
 """
 import ctypes as C
@@ -403,3 +409,257 @@ Reference: mrcal.stereo_unproject()"""
         qrect0 = np.ascontiguousarray(np.stack(np.meshgrid(np.arange(W, dtype=float), np.arange(H, dtype=float)), axis=-1))
     vrect0 = api.unproject(np.asarray(qrect0, dtype=float), *models_rectified[0].intrinsics(), normalize=True)
     return vrect0 * np.asarray(ranges)[..., np.newaxis]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# match_feature(): template matching between two images (csrc/match_feature.hip)
+
+# cv2's values: a caller's cv2.TM_* constants work unchanged
+TM_SQDIFF, TM_SQDIFF_NORMED, TM_CCORR, TM_CCORR_NORMED, TM_CCOEFF, TM_CCOEFF_NORMED = range(6)
+
+MATCH_OK, MATCH_OPTIMUM_ON_EDGE, MATCH_SUBPIXEL_DEGENERATE, MATCH_OUTSIDE_IMAGE1, MATCH_OUTSIDE_IMAGE0 = range(5)
+
+
+def apply_homography(H, q):
+    """The pixels q (...,2) mapped through the homography H (3,3), or (...,3,3) broadcasting with q: (...,2), in double
+
+Each coordinate is ((h0*x + h1*y) + h2) / ((h20*x + h21*y) + h22), evaluated in exactly that order.
+Reference: mrcal.apply_homography()"""
+    H, q = np.asarray(H, dtype=np.float64), np.asarray(q, dtype=np.float64)
+    if H.ndim < 2 or H.shape[-2:] != (3, 3):
+        raise Exception(f"H must have shape (...,3,3), got {H.shape}")
+    if q.ndim < 1 or q.shape[-1] != 2:
+        raise Exception(f"q must have shape (...,2), got {q.shape}")
+    x, y = q[..., 0], q[..., 1]
+    d = (H[..., 2, 0]*x + H[..., 2, 1]*y) + H[..., 2, 2]
+    return np.stack((((H[..., 0, 0]*x + H[..., 0, 1]*y) + H[..., 0, 2])/d,
+                     ((H[..., 1, 0]*x + H[..., 1, 1]*y) + H[..., 1, 2])/d), axis=-1)
+
+
+def _template_size(template_size1):
+    """-> (width, height), with the reference's refusals"""
+    try:
+        n = len(template_size1)
+    except TypeError:
+        n, template_size1 = 2, (template_size1, template_size1)
+    if n != 2:
+        raise Exception(f"template_size1 must be an interable of length 2 OR a scalar. Got an iterable of length {n}")
+    for t in template_size1:
+        if not (isinstance(t, (int, np.integer)) and t > 0):
+            raise Exception(f"Each element of template_size1 must be an integer > 0. Got {t}")
+    return int(template_size1[0]), int(template_size1[1])
+
+
+def _match_images(image0, image1):
+    for image in (image0, image1):
+        if not isinstance(image, np.ndarray) or image.ndim != 2:
+            raise Exception("match_feature() accepts ONLY grayscale images of shape (H,W)")
+    a0, w0, h0, _, t0 = _image_arguments(image0, "image0")
+    a1, w1, h1, _, t1 = _image_arguments(image1, "image1")
+    if t0 != t1:
+        raise Exception(f"image0 and image1 must have the same dtype, got {image0.dtype} and {image1.dtype}")
+    return (a0, w0, h0), (a1, w1, h1), t0
+
+
+def _match_features(q0, q1_estimate, H10):
+    """-> q0 (N,2), q1e (N,2), H01 (N,3,3), in double"""
+    if (H10 is None) == (q1_estimate is None):
+        raise Exception("Exactly one of (q1_estimate,H10) must be given")
+    q0 = np.asarray(q0, dtype=np.float64)
+    if q0.ndim != 2 or q0.shape[1] != 2:
+        raise Exception(f"q0 must have shape (N,2), got {q0.shape}")
+    N = q0.shape[0]
+    if H10 is None:
+        q1e = np.asarray(q1_estimate, dtype=np.float64)
+        if q1e.shape not in ((2,), (N, 2)):
+            raise Exception(f"q1_estimate must have shape (2,) or ({N},2), got {q1e.shape}")
+        q1e = np.ascontiguousarray(np.broadcast_to(q1e, (N, 2)))
+        H10 = np.tile(np.eye(3), (N, 1, 1))
+        H10[:, :2, 2] = q1e - q0
+    else:
+        H10 = np.asarray(H10, dtype=np.float64)
+        if H10.shape not in ((3, 3), (N, 3, 3)):
+            raise Exception(f"H10 must have shape (3,3) or ({N},3,3), got {H10.shape}")
+        H10 = np.ascontiguousarray(np.broadcast_to(H10, (N, 3, 3)))
+        q1e = apply_homography(H10, q0)
+    H01 = np.linalg.inv(H10) if N else np.zeros((0, 3, 3))
+    return q0, np.ascontiguousarray(q1e), np.ascontiguousarray(H01)
+
+
+def _match_method(method):
+    if method is None: return TM_CCORR_NORMED
+    if not (isinstance(method, (int, np.integer)) and TM_SQDIFF <= method <= TM_CCOEFF_NORMED):
+        raise Exception(f"method must be one of TM_SQDIFF ... TM_CCOEFF_NORMED (0..5), not {method!r}")
+    return int(method)
+
+
+def _match_radius(search_radius1):
+    if not (isinstance(search_radius1, (int, np.integer)) and search_radius1 >= 0):
+        raise Exception(f"search_radius1 must be an integer >= 0. Got {search_radius1}")
+    return int(min(search_radius1, 1 << 30))
+
+
+def _checkdims(image_shape, what, *qall):
+    """the reference's test of the template's corners, with its messages"""
+    for q in qall:
+        if q[0] < 0:                raise Exception(f"Too close to the left edge in {what}")
+        if q[1] < 0:                raise Exception(f"Too close to the top edge in {what} ")
+        if q[0] >= image_shape[1]:  raise Exception(f"Too close to the right edge in {what} ")
+        if q[1] >= image_shape[0]:  raise Exception(f"Too close to the bottom edge in {what} ")
+
+
+def _template_window(q1e, template_size):
+    """(tmin, tmax): the template's first and last pixel in image1"""
+    tmin = np.round(q1e - (np.array(template_size, dtype=float) - 1.)/2.)
+    return tmin, tmin + np.array(template_size, dtype=float) - 1
+
+
+class FeatureMatcher:
+    """Template matching between two images, resident: both images are uploaded once, and every match() finds a batch
+of features of image0 in image1.
+
+    image0, image1: grayscale (H,W) arrays of the same dtype: uint8, uint16 or float32.
+      .match(q0, *, search_radius1, template_size1, q1_estimate=None, H10=None, method=None, diagnostics=False)
+          q0 (N,2); q1_estimate: None, (2,) or (N,2); H10: None, (3,3) or (N,3,3): exactly one of the two.
+          -> q1 (N,2), status (N,): 0 ok; 1 the optimum is on the edge of the match surface; 2 the subpixel fit is
+          degenerate; 3 the template is outside image1; 4 outside image0. A row whose status is not 0 is NaN. No
+          status raises: only arguments that are wrong whatever the data do.
+          diagnostics=True: a third value, a list of N dicts as match_feature() returns them
+    What a match is: match_feature()"""
+
+    def __init__(self, image0, image1):
+        self.handle = None
+        (a0, w0, h0), (a1, w1, h1), dtype = _match_images(image0, image1)
+        lib, api = _libs()
+        self._L, self._api = lib.lib, api
+        self._dtype = a0.dtype
+        f = self._L.mrcal_amd_feature_matcher_create
+        f.restype, f.argtypes = C.c_void_p, [C.c_void_p, C.c_int, C.c_int]*2 + [C.c_int]
+        self.handle = f(_ptr(a0), w0, h0, _ptr(a1), w1, h1, dtype)
+        if not self.handle:
+            self.handle = None
+            raise Exception("match_feature() failed:" + api._last_error())
+        self._L.mrcal_amd_feature_matcher_destroy.restype, self._L.mrcal_amd_feature_matcher_destroy.argtypes = None, [C.c_void_p]
+
+    def match(self, q0, *, search_radius1, template_size1, q1_estimate=None, H10=None, method=None, diagnostics=False):
+        if self.handle is None:
+            raise Exception("this FeatureMatcher has been closed")
+        tw, th = _template_size(template_size1)
+        q0, q1e, H01 = _match_features(q0, q1_estimate, H10)
+        method, radius = _match_method(method), _match_radius(search_radius1)
+        N = q0.shape[0]
+        q1, status = np.full((N, 2), np.nan), np.zeros((N,), dtype=np.int32)
+        at, value = np.full((N, 2), np.nan), np.full((N,), np.nan)
+        qmin, size = np.zeros((N, 2), dtype=np.int32), np.zeros((N, 2), dtype=np.int32)
+        f = self._L.mrcal_amd_feature_matcher_match
+        f.restype, f.argtypes = C.c_bool, [C.c_void_p, C.c_int] + [C.c_void_p]*2 + [C.c_int]*4 + [C.c_void_p]*6
+        if not f(self.handle, N, _ptr(q1e), _ptr(H01), tw, th, radius, method,
+                 _ptr(q1), _ptr(status), _ptr(at), _ptr(value), _ptr(qmin), _ptr(size)):
+            raise Exception("match_feature() failed:" + self._api._last_error())
+        if not diagnostics:
+            return q1, status
+        get_surface, get_template = self._L.mrcal_amd_feature_matcher_matchoutput, self._L.mrcal_amd_feature_matcher_template
+        get_surface.restype = get_template.restype = C.c_bool
+        get_surface.argtypes = get_template.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        out = []
+        for i in range(N):
+            d = dict()
+            if status[i] not in (MATCH_OUTSIDE_IMAGE1, MATCH_OUTSIDE_IMAGE0):
+                d['matchoutput_image'] = np.zeros((size[i, 1], size[i, 0]), dtype=np.float32)
+                d['template']          = np.zeros((th, tw), dtype=self._dtype)
+                if not (get_surface(self.handle, i, _ptr(d['matchoutput_image'])) and get_template(self.handle, i, _ptr(d['template']))):
+                    raise Exception("match_feature() failed:" + self._api._last_error())
+            if status[i] == MATCH_OK:
+                d['matchoutput_optimum_subpixel_at'] = at[i].copy()
+                d['matchoutput_optimum_subpixel']    = float(value[i])
+                d['qshift_image1_matchoutput']       = qmin[i] + q1e[i] - _template_window(q1e[i], (tw, th))[0]
+            out.append(d)
+        return q1, status, out
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._L.mrcal_amd_feature_matcher_destroy(self.handle)
+            self.handle = None
+    def __del__(self):
+        try:    self.close()
+        except Exception: pass
+    def __enter__(self): return self
+    def __exit__(self, *a): self.close()
+
+
+def match_feature(image0, image1, q0, *, search_radius1, template_size1, q1_estimate=None, H10=None, method=None,
+                  visualize=False, return_plot_args=False):
+    """Finds in image1 the pixel q1 that shows what the pixel q0 of image0 shows: (q1, diagnostics)
+
+image0, image1: grayscale (H,W). q0 (2,). Exactly one of q1_estimate (2,), a guess of q1, and H10 (3,3), a homography
+that maps image0 pixels near q0 to image1 pixels (it corrects for the geometric difference between the images; for its
+construction from two camera models see the reference's docstring). template_size1: the size of the template in
+image1 pixels, a scalar or (width, height). search_radius1: how far from the estimate, in image1 pixels, to look; the
+search window is clipped to image1. method: one of TM_SQDIFF ... TM_CCOEFF_NORMED (cv2's values); None: TM_CCORR_NORMED.
+
+A match. With q1e = q1_estimate, or apply_homography(H10, q0), and ts = (width, height) of the template:
+  1. tmin = round(q1e - (ts-1)/2), tmax = tmin + ts - 1. Both must lie inside image1: "Too close to the ... edge in
+     image1" is raised otherwise
+  2. the template is transform_image(image0, map), map = float32(apply_homography(inv(H10), integer image1 pixels
+     tmin..tmax)). Its four corners must map inside image0: "Too close to the ... edge in image0"
+  3. image1 is cut to max(tmin - search_radius1, 0) .. min(tmin + search_radius1 + ts - 1, size - 1); the match
+     surface has (cut - ts + 1) entries each way
+  4. every entry gets the method's score of the template against the window of the cut that begins there, from the
+     window's sums IT = sum(I T), SI = sum(I), SI2 = sum(I I) and the template's ST, ST2, N = width height: exact
+     integers for integer images, double in a fixed order for float32; the formula in double, rounded to float32:
+       SQDIFF SI2 - 2 IT + ST2; CCORR IT; CCOEFF IT - SI ST/N;
+       SQDIFF_NORMED, CCORR_NORMED: those over sqrt(SI2 ST2);
+       CCOEFF_NORMED: CCOEFF over sqrt(max(SI2 - SI SI/N, 0) max(ST2 - ST ST/N, 0)).
+     A denominator that is not > 0 gives 0 (1 for SQDIFF_NORMED)
+  5. the optimum is the minimum (SQDIFF, SQDIFF_NORMED) or the maximum of the surface, the first one in row-major
+     order. If it lies on the edge of the surface there is no match: (None, diagnostics)
+  6. a quadric is fit to the 3x3 entries around the optimum, and q1 is where it is stationary, moved to image1
+
+diagnostics: matchoutput_image (the surface, float32), template (what was looked for), and for a match
+matchoutput_optimum_subpixel_at (in surface coordinates), matchoutput_optimum_subpixel (the fit's value there) and
+qshift_image1_matchoutput (q1 = matchoutput_optimum_subpixel_at + qshift_image1_matchoutput).
+The N = 1 case of FeatureMatcher.match(): many features of one pair of images are faster through that.
+
+Departures from the reference:
+  - images are uint8, uint16 or float32 (cv2 takes the first and the last);
+  - q0, H10 and q1_estimate are used in double; the reference rounds them to float32 first;
+  - the correlation is summed exactly (cv2.matchTemplate() uses a float32 FFT), so the same call gives the same bits;
+  - numpy.round rounds halves to even, and so does the library;
+  - a subpixel fit with a zero determinant or a result that is not finite gives (None, diagnostics); the reference
+    returns inf or nan there;
+  - the subpixel fit is the closed form of the reference's 9-point least squares (on the -1,0,1 grid the normal
+    equations are diagonal but for the coupling of c00, c20, c02);
+  - visualize and return_plot_args are refused: gnuplotlib is not part of this project.
+Reference: mrcal.match_feature()"""
+    if visualize or return_plot_args:
+        raise Exception("match_feature(visualize=True) is not available: gnuplotlib is not part of mrcal_amd")
+    tw, th = _template_size(template_size1)
+    _match_images(image0, image1)
+    if (H10 is None) == (q1_estimate is None):
+        raise Exception("Exactly one of (q1_estimate,H10) must be given")
+    q0 = np.asarray(q0, dtype=np.float64)
+    if q0.shape != (2,):
+        raise Exception(f"q0 must have shape (2,), got {q0.shape}")
+    _match_method(method), _match_radius(search_radius1)
+    if q1_estimate is not None:
+        q1_estimate = np.asarray(q1_estimate, dtype=np.float64)
+        if q1_estimate.shape != (2,):
+            raise Exception(f"q1_estimate must have shape (2,), got {q1_estimate.shape}")
+    elif np.shape(H10) != (3, 3):
+        raise Exception(f"H10 must have shape (3,3), got {np.shape(H10)}")
+    # The two "too close to the edge" refusals with the reference's messages, before anything goes to the device: the
+    # library's tests (statuses 3 and 4), restated
+    _, q1e, H01 = _match_features(q0[np.newaxis], q1_estimate, H10)
+    tmin, tmax = _template_window(q1e[0], (tw, th))
+    _checkdims(image1.shape, "image1", tmin, tmax)
+    corners = np.array(((tmin[0], tmin[1]), (tmin[0], tmax[1]), (tmax[0], tmin[1]), (tmax[0], tmax[1])))
+    _checkdims(image0.shape, "image0", *apply_homography(H01[0], corners).astype(np.float32))
+
+    with FeatureMatcher(image0, image1) as matcher:
+        q1, status, diagnostics = matcher.match(q0[np.newaxis], search_radius1=search_radius1, template_size1=(tw, th),
+                                                q1_estimate=q1_estimate, H10=H10, method=method, diagnostics=True)
+    if status[0] in (MATCH_OUTSIDE_IMAGE1, MATCH_OUTSIDE_IMAGE0):       # (a corner that is not a number)
+        raise Exception(f"Too close to the edge in image{0 if status[0] == MATCH_OUTSIDE_IMAGE0 else 1}")
+    if status[0] != MATCH_OK:
+        return None, diagnostics[0]
+    return q1[0], diagnostics[0]
