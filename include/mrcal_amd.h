@@ -1110,6 +1110,60 @@ bool mrcal_amd_feature_matcher_matchoutput(mrcal_amd_feature_matcher_t* m, int i
 bool mrcal_amd_feature_matcher_template(mrcal_amd_feature_matcher_t* m, int i, void* template_image);
 void mrcal_amd_feature_matcher_destroy(mrcal_amd_feature_matcher_t* m);
 
+/* ---- stereo_matching_sgm: dense disparities of a rectified pair -------------
+   The step between mrcal_amd_rectification_rectify() and mrcal_amd_rectification_range(), for which the reference's
+   tool leaves the library (cv2.StereoSGBM, mrcal.stereo_matching_libelas()): a semi-global matcher on a census cost,
+   csrc/stereo_sgm.hip, planned on the host by csrc/sgm_plan.hpp. Integer arithmetic throughout and no atomics: the
+   result is defined to the bit, and is the same bits on every call.
+
+   image0 (left) and image1 (right): rectified, one channel, dense, the same (H,W) and dtype, MRCAL_AMD_IMAGE_UINT8 or
+   _UINT16. D = disparity_max - disparity_min is a positive multiple of 16, at most 256; disparity_min may be
+   negative. The index i in [0,D) means the disparity d = disparity_min + i.
+     1. Census. Per image and pixel a 62-bit descriptor over the window 9 wide x 7 tall around the pixel, the centre
+        left out: a bit is (neighbour < centre). A neighbour outside the image is the nearest pixel inside (clamped
+        coordinates). Only Hamming distances are used: the order of the bits is free
+     2. Cost. C(y,x,i) = popcount(census0(y,x) XOR census1(y,x-d)); 62 where x-d is outside [0,W)
+     3. Aggregation. For each path direction r, with m = min_k L_r(p-r,k):
+          L_r(p,i) = C(p,i) + min(L_r(p-r,i), L_r(p-r,i-1) + P1, L_r(p-r,i+1) + P1, m + P2) - m
+        An i-1 or i+1 outside [0,D) takes no part. Where p-r is outside the image, L_r(p,.) = C(p,.). paths = 4:
+        (0,+-1), (+-1,0); paths = 8: the four diagonals too. S = sum_r L_r. 0 <= P1 <= P2 <= 193, so that
+        L_r <= 62 + P2 <= 255 and S <= 2040
+     4. Selection. i* = the FIRST index of the minimum of S(p,.). The pixel is invalid if some i with |i - i*| > 1 has
+        S(p,i) (100 - uniqueness_ratio) < S(p,i*) 100 (uniqueness_ratio in 0..99; 0: no test). The scaled index is
+        16 i*, and where 0 < i* < D-1, with a = S(i*-1), c = S(i*+1), den = max(a + c - 2 S(i*), 1):
+        16 i* + floor(((a - c) 16 + den)/(2 den)), a FLOOR of a numerator that may be negative
+     5. Left-right check; disp12_max_diff < 0: none. The right image's index i1(y,x1) = the smallest i that minimises
+        S(y, x1 + d, i) over the i whose x1 + d is inside the image. A left pixel is invalid if x - d* is outside the
+        image, or if |i1(y, x - d*) - i*| > disp12_max_diff
+     6. disparity: int16 (H,W): 16 disparity_min + the scaled index; an invalid pixel holds 16 (disparity_min - 1).
+        A range whose scaled values leave int16 is refused. The scale is cv2's: MRCAL_AMD_STEREO_SGM_DISPARITY_SCALE
+   Not here: cv2's Birchfield-Tomasi cost on Sobel-filtered images, its adaptive P2, the speckle filter, colour
+   input, ELAS.
+   _create(): the handle owns every device buffer a match of that size needs (a problem that does not fit the free
+   device memory is refused with its size); _match(): host arrays in and out; _stage_milliseconds(): how long the
+   census, the paths, the selection and the left-right check of the last _match() took on the device (4 values).
+   mrcal_amd_rectification_disparity(): the two images are rectified (linear interpolation, 0 outside) into device
+   buffers and matched there: the rectified images do not cross to the host and back */
+#define MRCAL_AMD_STEREO_SGM_DISPARITY_SCALE 16
+typedef struct
+{
+    int disparity_min, disparity_max;   /* 0, required */
+    int P1, P2;                         /* 10, 120 */
+    int paths;                          /* 8 */
+    int uniqueness_ratio;               /* 10 */
+    int disp12_max_diff;                /* 1 */
+} mrcal_amd_stereo_sgm_params_t;
+typedef struct mrcal_amd_stereo_sgm mrcal_amd_stereo_sgm_t;
+mrcal_amd_stereo_sgm_t*
+mrcal_amd_stereo_sgm_create(int width, int height, int dtype, const mrcal_amd_stereo_sgm_params_t* params);
+bool mrcal_amd_stereo_sgm_match(mrcal_amd_stereo_sgm_t* m, const void* image0, const void* image1, int16_t* disparity);
+bool mrcal_amd_stereo_sgm_stage_milliseconds(mrcal_amd_stereo_sgm_t* m, float* milliseconds /*4*/);
+void mrcal_amd_stereo_sgm_destroy(mrcal_amd_stereo_sgm_t* m);
+bool mrcal_amd_rectification_disparity(mrcal_amd_rectification_t* r,
+                                       const void* image0, int width0, int height0,
+                                       const void* image1, int width1, int height1, int dtype,
+                                       const mrcal_amd_stereo_sgm_params_t* params, int16_t* disparity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@
 #include "device_memory.hpp"
 #include "stereo_geometry.hpp"
 #include "remap.hpp"
+#include "stereo_sgm.hpp"
 
 namespace mrcal_amd {
 
@@ -676,6 +677,40 @@ bool mrcal_amd_rectification_range(mrcal_amd_rectification_t* r, double* range, 
     last_error_string().clear();
     if(!rectification_given(r) || !have_device()) return false;
     return range_dense(range, disparity_scaled, r->W, r->H, r->range_args, disparity_scale, disparity_scaled_min, disparity_scaled_max);
+}
+
+// image pair -> disparity: both images rectified straight into the matcher's device buffers (stereo_sgm.hip)
+bool mrcal_amd_rectification_disparity(mrcal_amd_rectification_t* r,
+                                       const void* image0, int width0, int height0,
+                                       const void* image1, int width1, int height1, int dtype,
+                                       const mrcal_amd_stereo_sgm_params_t* params, int16_t* disparity)
+{
+    last_error_string().clear();
+    if(!rectification_given(r) || !have_device()) return false;
+    if(!remap_arguments_ok(width0, height0, 1, dtype, r->W, r->H, MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT) ||
+       !remap_arguments_ok(width1, height1, 1, dtype, r->W, r->H, MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT))
+        return false;
+    mrcal_amd_stereo_sgm_t* m = mrcal_amd_stereo_sgm_create(r->W, r->H, dtype, params);
+    if(m == NULL) return false;
+    const void* image[2] = { image0, image1 };
+    const int   W[2] = { width0, width1 }, H[2] = { height0, height1 };
+    bool ok = true;
+    {
+        DeviceBuffers tmp;
+        for(int i = 0; i < 2 && ok; i++)
+        {
+            uint8_t* d_src = NULL;
+            ok = tmp.upload(&d_src, (const uint8_t*)image[i], (size_t)W[i]*H[i]*dtype_size(dtype)) &&
+                 remap_device(d_src, W[i], H[i], 1, dtype, r->map[i], sgm_device_image(m, i), r->W*r->H,
+                              MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT, NULL);
+        }
+        // (its copy waits for the launches: the images may go when this returns)
+        ok = ok && sgm_match_device(m, disparity);
+        if(!ok) (void)hipDeviceSynchronize();
+    }
+    // (destroy clears nothing: the error of a failure stays)
+    mrcal_amd_stereo_sgm_destroy(m);
+    return ok;
 }
 
 void mrcal_amd_rectification_destroy(mrcal_amd_rectification_t* r) { delete r; }

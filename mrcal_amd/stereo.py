@@ -9,8 +9,15 @@
         for image0, image1 in frames:
             rect0, rect1 = r.rectify(image0, image1)
             ranges       = r.range(matcher(rect0, rect1), disparity_scale = 16)
+            # or, the rectified images staying on the device:
+            ranges       = r.range(r.disparity(image0, image1, disparity_max = 128), disparity_scale = 16)
 
-    q1, diagnostics  = mrcal_amd.match_feature(image0, image1, q0, H10 = H10, search_radius1 = 200, template_size1 = 41)
+    disparity = mrcal_amd.stereo_matching_sgm(rect0, rect1, disparity_max = 128)      # int16, scaled by 16
+
+    with mrcal_amd.StereoMatcherSGM(rect0.shape, rect0.dtype, disparity_max = 128) as sgm:     # the buffers are made once
+        disparity = sgm.match(rect0, rect1)
+
+    q1, diagnostics = mrcal_amd.match_feature(image0, image1, q0, H10 = H10, search_radius1 = 200, template_size1 = 41)
 
     with mrcal_amd.FeatureMatcher(image0, image1) as matcher:          # both images are uploaded once
         q1, status = matcher.match(q0, H10 = H10, search_radius1 = 200, template_size1 = 41)        # q0 (N,2)
@@ -18,8 +25,9 @@
 The names, keyword arguments, defaults, return shapes and exception messages are those of the reference's
 mrcal/stereo.py. rectified_system() and rectified_resolution() are host code (csrc/stereo_geometry.cpp) and need no
 GPU; the maps, the remap and the ranges are kernels (csrc/rectification.hip), the template matching of match_feature()
-is csrc/match_feature.hip, and there is no CPU fallback for them.
-Out of scope: image file I/O, dense stereo matching, visualization, LONLAT rectification (which the reference's
+is csrc/match_feature.hip, the dense matching of stereo_matching_sgm() is csrc/stereo_sgm.hip, and there is no CPU
+fallback for them.
+Out of scope: image file I/O, cv2.StereoSGBM's and libelas's own pixel-for-pixel output, visualization, LONLAT rectification (which the reference's
 rectified_system() refuses too).
 """
 import ctypes as C
@@ -198,6 +206,7 @@ class Rectification:
     models: the two cameramodels; models_rectified: what rectified_system() returned for them.
       .maps()                          rectification_maps(): float32 (2, Nel, Naz, 2), the same bits
       .rectify(image0, image1)         the two rectified images; the maps do not cross to the host and back
+      .disparity(image0, image1, ...)  stereo_matching_sgm() of the rectified images, which stay on the device
       .range(disparity, ...)           stereo_range() of a dense (Nel, Naz) disparity"""
 
     def __init__(self, models, models_rectified):
@@ -271,6 +280,27 @@ class Rectification:
                             disparity_min=disparity_min, disparity_max=disparity_max,
                             disparity_scaled_min=disparity_scaled_min, disparity_scaled_max=disparity_scaled_max,
                             _rectification=self)
+
+    def disparity(self, image0, image1, **params):
+        """stereo_matching_sgm(*rectify(image0, image1), **params), the same bits: int16 (Nel, Naz). The rectified images
+        are made and matched on the device and do not cross to the host. image0, image1: grayscale, uint8 or uint16"""
+        self._open()
+        p = _sgm_params(**params)
+        for image in (image0, image1):
+            if not isinstance(image, np.ndarray) or image.ndim != 2 or image.size == 0:
+                raise Exception("stereo_matching_sgm() accepts ONLY grayscale images of shape (H,W)")
+        if image0.dtype != image1.dtype:
+            raise Exception(f"stereo_matching_sgm(): image0 and image1 must have the same dtype, got {image0.dtype} and {image1.dtype}")
+        dtype = _SGM_DTYPES[_sgm_dtype(image0.dtype)]
+        a0, a1 = np.ascontiguousarray(image0), np.ascontiguousarray(image1)
+        out = np.zeros((self.Nel, self.Naz), dtype=np.int16)
+        f = self._L.mrcal_amd_rectification_disparity
+        f.restype  = C.c_bool
+        f.argtypes = [C.c_void_p]*2 + [C.c_int]*2 + [C.c_void_p] + [C.c_int]*3 + [C.c_void_p]*2
+        if not f(self.handle, _ptr(a0), a0.shape[1], a0.shape[0], _ptr(a1), a1.shape[1], a1.shape[0], dtype,
+                 C.addressof(p), _ptr(out)):
+            raise Exception("stereo_matching_sgm() failed:" + self._api._last_error())
+        return out
 
     def _range_dense(self, disparity_scaled, disparity_scale, dmin, dmax):
         d = np.ascontiguousarray(disparity_scaled, dtype=np.uint16)
@@ -663,3 +693,167 @@ Reference: mrcal.match_feature()"""
     if status[0] != MATCH_OK:
         return None, diagnostics[0]
     return q1[0], diagnostics[0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# stereo_matching_sgm(): dense disparities of a rectified pair (csrc/stereo_sgm.hip)
+
+# cv2's scale of a StereoSGBM disparity image
+STEREO_SGM_DISPARITY_SCALE = 16
+
+
+class _SgmParams(C.Structure):
+    """mrcal_amd_stereo_sgm_params_t"""
+    _fields_ = [(n, C.c_int) for n in ("disparity_min", "disparity_max", "P1", "P2", "paths", "uniqueness_ratio",
+                                       "disp12_max_diff")]
+
+
+def _sgm_int(name, value):
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+        raise Exception(f"stereo_matching_sgm(): {name} must be an integer. Got {value!r}")
+    return int(value)
+
+
+def _sgm_params(*, disparity_min=0, disparity_max, P1=10, P2=120, paths=8, uniqueness_ratio=10, disp12_max_diff=1):
+    """-> _SgmParams, with the refusals of csrc/sgm_plan.hpp (sgm_params_ok()) in its words, made before any device work"""
+    dmin, dmax = _sgm_int("disparity_min", disparity_min), _sgm_int("disparity_max", disparity_max)
+    P1, P2, paths = _sgm_int("P1", P1), _sgm_int("P2", P2), _sgm_int("paths", paths)
+    ratio, diff = _sgm_int("uniqueness_ratio", uniqueness_ratio), _sgm_int("disp12_max_diff", disp12_max_diff)
+    D = dmax - dmin
+    if D <= 0 or D > 256 or D % 16 != 0:
+        raise Exception(f"stereo_matching_sgm(): disparity_max - disparity_min must be a positive multiple of 16, at most 256. Got {D}")
+    if not (0 <= P1 <= P2 <= 193):
+        raise Exception(f"stereo_matching_sgm(): must have 0 <= P1 <= P2 <= 193. Got P1 = {P1}, P2 = {P2}")
+    if paths not in (4, 8):
+        raise Exception(f"stereo_matching_sgm(): paths must be 4 or 8. Got {paths}")
+    if not (0 <= ratio <= 99):
+        raise Exception(f"stereo_matching_sgm(): uniqueness_ratio must be in 0..99. Got {ratio}")
+    if STEREO_SGM_DISPARITY_SCALE*(dmin - 1) < -32768 or STEREO_SGM_DISPARITY_SCALE*dmax > 32767:
+        raise Exception(f"stereo_matching_sgm(): disparities {dmin}..{dmax} scaled by 16 leave int16 (at most -2047..2047)")
+    return _SgmParams(dmin, dmax, P1, P2, paths, ratio, max(min(diff, 1 << 20), -1))
+
+
+_SGM_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1}
+
+
+def _sgm_dtype(dtype):
+    try:    dtype = np.dtype(dtype)
+    except TypeError: dtype = None
+    if dtype not in _SGM_DTYPES:
+        raise Exception(f"stereo_matching_sgm(): images must have dtype uint8 or uint16, not {dtype}")
+    return dtype
+
+
+def _sgm_images(image0, image1, shape=None, dtype=None):
+    """-> the two dense arrays; the refusals before any device work"""
+    for image in (image0, image1):
+        if not isinstance(image, np.ndarray) or image.ndim != 2 or image.size == 0:
+            raise Exception("stereo_matching_sgm() accepts ONLY grayscale images of shape (H,W)" +
+                            (f", got {image.shape}" if isinstance(image, np.ndarray) else ""))
+    if image0.shape != image1.shape:
+        raise Exception(f"stereo_matching_sgm(): image0 and image1 must have the same shape, got {image0.shape} and {image1.shape}")
+    if image0.dtype != image1.dtype:
+        raise Exception(f"stereo_matching_sgm(): image0 and image1 must have the same dtype, got {image0.dtype} and {image1.dtype}")
+    _sgm_dtype(image0.dtype)
+    if shape is not None and (image0.shape != shape or image0.dtype != dtype):
+        raise Exception(f"stereo_matching_sgm(): this matcher was made for images of shape {shape} and dtype {dtype}, "
+                        f"got {image0.shape} and {image0.dtype}")
+    return np.ascontiguousarray(image0), np.ascontiguousarray(image1)
+
+
+class StereoMatcherSGM:
+    """Dense stereo matching, resident: every device buffer a match of one image size needs is made once, and every
+match() reuses them.
+
+    shape: (H,W) of the rectified images; dtype: uint8 or uint16; the parameters: those of stereo_matching_sgm().
+      .match(image0, image1, out=None)   -> int16 (H,W); out: the array to fill
+      .stage_milliseconds()              how long the census, the paths, the selection and the left-right check of the
+                                         last match() took on the device
+    What a disparity image is: stereo_matching_sgm()"""
+
+    def __init__(self, shape, dtype, **params):
+        self.handle = None
+        self._params = _sgm_params(**params)
+        self._dtype = _sgm_dtype(dtype)
+        try:    shape = tuple(int(n) for n in shape)
+        except TypeError: shape = ()
+        if len(shape) != 2 or shape[0] <= 0 or shape[1] <= 0:
+            raise Exception(f"stereo_matching_sgm(): shape must be (H,W), got {shape}")
+        self.shape = shape
+        lib, api = _libs()
+        self._L, self._api = lib.lib, api
+        f = self._L.mrcal_amd_stereo_sgm_create
+        f.restype, f.argtypes = C.c_void_p, [C.c_int]*3 + [C.c_void_p]
+        self.handle = f(shape[1], shape[0], _SGM_DTYPES[self._dtype], C.addressof(self._params))
+        if not self.handle:
+            self.handle = None
+            raise Exception("stereo_matching_sgm() failed:" + api._last_error())
+        self._L.mrcal_amd_stereo_sgm_destroy.restype, self._L.mrcal_amd_stereo_sgm_destroy.argtypes = None, [C.c_void_p]
+
+    def match(self, image0, image1, out=None):
+        if self.handle is None:
+            raise Exception("this StereoMatcherSGM has been closed")
+        a0, a1 = _sgm_images(image0, image1, self.shape, self._dtype)
+        o, r = _output_array(out, self.shape, np.int16, False)
+        f = self._L.mrcal_amd_stereo_sgm_match
+        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*4
+        if not f(self.handle, _ptr(a0), _ptr(a1), _ptr(o)):
+            raise Exception("stereo_matching_sgm() failed:" + self._api._last_error())
+        if r is not o: r[...] = o
+        return r
+
+    def stage_milliseconds(self):
+        if self.handle is None:
+            raise Exception("this StereoMatcherSGM has been closed")
+        ms = np.zeros((4,), dtype=np.float32)
+        f = self._L.mrcal_amd_stereo_sgm_stage_milliseconds
+        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2
+        if not f(self.handle, _ptr(ms)):
+            raise Exception("stereo_matching_sgm() failed:" + self._api._last_error())
+        return dict(zip(("census", "paths", "select", "check"), (float(x) for x in ms)))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._L.mrcal_amd_stereo_sgm_destroy(self.handle)
+            self.handle = None
+    def __del__(self):
+        try:    self.close()
+        except Exception: pass
+    def __enter__(self): return self
+    def __exit__(self, *a): self.close()
+
+
+def stereo_matching_sgm(image0, image1, *, disparity_min=0, disparity_max, P1=10, P2=120, paths=8, uniqueness_ratio=10,
+                        disp12_max_diff=1):
+    """The disparity image of a rectified pair, by semi-global matching on a census cost: int16 (H,W), the disparity in
+pixels times STEREO_SGM_DISPARITY_SCALE = 16 (cv2's scale); an invalid pixel holds 16 (disparity_min - 1)
+
+image0 (left), image1 (right): rectified, grayscale (H,W), the same shape and dtype, uint8 or uint16.
+D = disparity_max - disparity_min must be a positive multiple of 16, at most 256; disparity_min may be negative;
+0 <= P1 <= P2 <= 193; paths is 4 or 8; uniqueness_ratio is in 0..99 (0: no test); disp12_max_diff < 0: no left-right check.
+The result goes straight into stereo_range(disparity, models_rectified, disparity_scale = 16, disparity_min = ...).
+
+Everything is integer arithmetic, and the result is defined to the bit. The index i in [0,D) means d = disparity_min + i.
+  1. census: per image and pixel 62 bits over the window 9 wide x 7 tall around the pixel, without the centre: a bit is
+     (neighbour < centre); a neighbour outside the image is the nearest pixel inside
+  2. C(y,x,i) = popcount(census0(y,x) XOR census1(y,x-d)); 62 where x-d is outside the image
+  3. per path direction r: L_r(p,i) = C(p,i) + min(L_r(p-r,i), L_r(p-r,i-1) + P1, L_r(p-r,i+1) + P1, m + P2) - m,
+     m = min_k L_r(p-r,k); an i-1, i+1 outside [0,D) takes no part; where p-r is outside the image L_r(p,.) = C(p,.).
+     paths = 4: left, right, up, down; 8: the diagonals too. S = sum_r L_r
+  4. i* = the first index of the minimum of S(p,.). Invalid if some i with |i - i*| > 1 has
+     S(p,i) (100 - uniqueness_ratio) < S(p,i*) 100. Where 0 < i* < D-1, with a = S(i*-1), c = S(i*+1),
+     den = max(a + c - 2 S(i*), 1): the scaled index is 16 i* + floor(((a - c) 16 + den)/(2 den)); elsewhere 16 i*
+  5. the right image's i1(y,x1) = the smallest i that minimises S(y, x1 + d, i) over the i with x1 + d inside the image.
+     A left pixel is invalid if x - d* is outside the image, or |i1(y, x - d*) - i*| > disp12_max_diff
+  6. the result is 16 disparity_min + the scaled index
+
+The N = 1 case of StereoMatcherSGM.match(): a sequence of pairs of one size is faster through that.
+Shaped like the reference's mrcal.stereo_matching_libelas(). Not here: cv2.StereoSGBM's Birchfield-Tomasi cost on
+Sobel-filtered images, its adaptive P2, the speckle filter (connected components), colour input, and ELAS itself:
+nothing imitates either matcher pixel for pixel."""
+    params = dict(disparity_min=disparity_min, disparity_max=disparity_max, P1=P1, P2=P2, paths=paths,
+                  uniqueness_ratio=uniqueness_ratio, disp12_max_diff=disp12_max_diff)
+    _sgm_params(**params)
+    a0, a1 = _sgm_images(image0, image1)
+    with StereoMatcherSGM(a0.shape, a0.dtype, **params) as matcher:
+        return matcher.match(a0, a1)
