@@ -1137,13 +1137,20 @@ void mrcal_amd_feature_matcher_destroy(mrcal_amd_feature_matcher_t* m);
         image, or if |i1(y, x - d*) - i*| > disp12_max_diff
      6. disparity: int16 (H,W): 16 disparity_min + the scaled index; an invalid pixel holds 16 (disparity_min - 1).
         A range whose scaled values leave int16 is refused. The scale is cv2's: MRCAL_AMD_STEREO_SGM_DISPARITY_SCALE
-   Not here: cv2's Birchfield-Tomasi cost on Sobel-filtered images, its adaptive P2, the speckle filter, colour
-   input, ELAS.
+   Not here: cv2's Birchfield-Tomasi cost on Sobel-filtered images, its adaptive P2, colour input, ELAS.
    _create(): the handle owns every device buffer a match of that size needs (a problem that does not fit the free
    device memory is refused with its size); _match(): host arrays in and out; _stage_milliseconds(): how long the
    census, the paths, the selection and the left-right check of the last _match() took on the device (4 values).
    mrcal_amd_rectification_disparity(): the two images are rectified (linear interpolation, 0 outside) into device
-   buffers and matched there: the rectified images do not cross to the host and back */
+   buffers and matched there: the rectified images do not cross to the host and back.
+   The speckle filter ("filter_speckles", below) is a stage of its own after step 6, on request only:
+   _set_speckle_filter(m, window_size, range), cv2.StereoSGBM's speckleWindowSize and speckleRange. window_size = 0
+   (what a new matcher has): no filter, nothing of it runs and the result is that of steps 1-6. window_size > 0: every
+   later _match() filters the disparity image on the device before it is copied out, with new_value =
+   16 (disparity_min - 1), max_speckle_size = window_size, max_diff = 16 range. The labels and counts lie in S, which is
+   dead by then: the matcher allocates nothing more. _speckle_milliseconds(): how long that stage of the last _match()
+   took (0 without the filter); _stage_milliseconds() keeps its 4 values.
+   mrcal_amd_rectification_disparity_filtered() is mrcal_amd_rectification_disparity() with the two integers */
 #define MRCAL_AMD_STEREO_SGM_DISPARITY_SCALE 16
 typedef struct
 {
@@ -1163,6 +1170,43 @@ bool mrcal_amd_rectification_disparity(mrcal_amd_rectification_t* r,
                                        const void* image0, int width0, int height0,
                                        const void* image1, int width1, int height1, int dtype,
                                        const mrcal_amd_stereo_sgm_params_t* params, int16_t* disparity);
+bool mrcal_amd_stereo_sgm_set_speckle_filter(mrcal_amd_stereo_sgm_t* m, int window_size, int range);
+bool mrcal_amd_stereo_sgm_speckle_milliseconds(mrcal_amd_stereo_sgm_t* m, float* milliseconds /*1*/);
+bool mrcal_amd_rectification_disparity_filtered(mrcal_amd_rectification_t* r,
+                                                const void* image0, int width0, int height0,
+                                                const void* image1, int width1, int height1, int dtype,
+                                                const mrcal_amd_stereo_sgm_params_t* params,
+                                                int speckle_window_size, int speckle_range, int16_t* disparity);
+
+/* ---- filter_speckles: small regions of a disparity image become invalid ------
+   cv2.filterSpeckles(img, newVal, maxSpeckleSize, maxDiff) for CV_16S, which cv2.StereoSGBM applies to its result and
+   the reference's mrcal-stereo tool recommends (--sgbm-speckle-window-size 200 --sgbm-speckle-range 2); here it is
+   csrc/speckle_filter.hip, planned on the host by csrc/speckle_plan.hpp. On an int16 image (H,W), dense:
+     1. A pixel equal to new_value takes no part and is never changed
+     2. Two 4-neighbours (left/right, up/down) that both take part are joined if |a - b| <= max_diff. The difference is
+        taken in 32 bits: -32768 beside 32767 differs by 65535. A max_diff above 65535 means 65535
+     3. The regions are the connected components of that graph
+     4. Every pixel of a region of size <= max_speckle_size becomes new_value; everything else is unchanged.
+        max_speckle_size = 0 changes nothing
+   Only original values are compared and the relation is symmetric, so the result does not depend on the order in
+   which cv2's flood fill, or anything else, visits the pixels. "Equal to cv2" rests on a transcription of cv2's loop
+   (tests/speckle_checker.py: filter_speckles_loops()) that a graph formulation is held to, not on cv2 itself.
+   Connected-component labelling by union-find: a label is an int32 pixel index, two roots are joined by pointing the
+   larger at the smaller, so a region's root is its smallest index and a region's size an integer sum: integer atomics
+   whose result does not depend on the order, no floating point, the same bits on every call.
+   Refused: an image that is empty or has more than 2^28 pixels, a new_value outside int16, a negative
+   max_speckle_size or max_diff, an image that does not fit the free device memory (10 bytes a pixel).
+   _create(): the handle owns ONE device allocation for images of that size; _apply(): host arrays, in == out is
+   allowed; _milliseconds(): how long the last _apply() took on the device, without the copies;
+   _pass_milliseconds(): the same pass by pass (4 values: the tiles' labels, the joins across the tiles' borders, the
+   roots and sizes, the result) */
+typedef struct mrcal_amd_speckle_filter mrcal_amd_speckle_filter_t;
+mrcal_amd_speckle_filter_t* mrcal_amd_speckle_filter_create(int width, int height);
+bool mrcal_amd_speckle_filter_apply(mrcal_amd_speckle_filter_t* f, const int16_t* in, int16_t* out,
+                                    int new_value, int max_speckle_size, int max_diff);
+bool mrcal_amd_speckle_filter_milliseconds(mrcal_amd_speckle_filter_t* f, float* milliseconds /*1*/);
+bool mrcal_amd_speckle_filter_pass_milliseconds(mrcal_amd_speckle_filter_t* f, float* milliseconds /*4*/);
+void mrcal_amd_speckle_filter_destroy(mrcal_amd_speckle_filter_t* f);
 
 #ifdef __cplusplus
 }

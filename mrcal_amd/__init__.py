@@ -79,7 +79,8 @@ from .triangulation import (triangulate_geometric, triangulate_lindstrom, triang
 from .stereo import (rectified_resolution, rectified_system, rectification_maps, stereo_range, stereo_unproject,
                      Rectification, apply_homography, match_feature, FeatureMatcher,
                      TM_SQDIFF, TM_SQDIFF_NORMED, TM_CCORR, TM_CCORR_NORMED, TM_CCOEFF, TM_CCOEFF_NORMED,
-                     stereo_matching_sgm, StereoMatcherSGM, STEREO_SGM_DISPARITY_SCALE)
+                     stereo_matching_sgm, StereoMatcherSGM, STEREO_SGM_DISPARITY_SCALE,
+                     filter_speckles, SpeckleFilter)
 from .image_transforms import (scale_focal__best_pinhole_fit, pinhole_model_for_reprojection, image_transformation_map,
                                transform_image)
 from .utils import sample_imager, sample_imager_unproject

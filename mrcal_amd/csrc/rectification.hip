@@ -30,6 +30,7 @@
 #include "stereo_geometry.hpp"
 #include "remap.hpp"
 #include "stereo_sgm.hpp"
+#include "speckle_plan.hpp"
 
 namespace mrcal_amd {
 
@@ -685,13 +686,29 @@ bool mrcal_amd_rectification_disparity(mrcal_amd_rectification_t* r,
                                        const void* image1, int width1, int height1, int dtype,
                                        const mrcal_amd_stereo_sgm_params_t* params, int16_t* disparity)
 {
+    return mrcal_amd_rectification_disparity_filtered(r, image0, width0, height0, image1, width1, height1, dtype, params, 0, 0, disparity);
+}
+
+bool mrcal_amd_rectification_disparity_filtered(mrcal_amd_rectification_t* r,
+                                                const void* image0, int width0, int height0,
+                                                const void* image1, int width1, int height1, int dtype,
+                                                const mrcal_amd_stereo_sgm_params_t* params,
+                                                int speckle_window_size, int speckle_range, int16_t* disparity)
+{
     last_error_string().clear();
+    {
+        // (refused before any device work; the matcher says the same again)
+        SpeckleParams p; std::string why;
+        if(!speckle_params_of_matcher(&p, &why, 0, 1, speckle_window_size, speckle_range)) { set_error("%s", why.c_str()); return false; }
+    }
     if(!rectification_given(r) || !have_device()) return false;
     if(!remap_arguments_ok(width0, height0, 1, dtype, r->W, r->H, MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT) ||
        !remap_arguments_ok(width1, height1, 1, dtype, r->W, r->H, MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT))
         return false;
     mrcal_amd_stereo_sgm_t* m = mrcal_amd_stereo_sgm_create(r->W, r->H, dtype, params);
     if(m == NULL) return false;
+    // (a window of 0: no filter, and nothing of it runs)
+    if(!mrcal_amd_stereo_sgm_set_speckle_filter(m, speckle_window_size, speckle_range)) { mrcal_amd_stereo_sgm_destroy(m); return false; }
     const void* image[2] = { image0, image1 };
     const int   W[2] = { width0, width1 }, H[2] = { height0, height1 };
     bool ok = true;

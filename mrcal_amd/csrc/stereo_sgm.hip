@@ -27,6 +27,8 @@
 //                          gives the right image's index i1
 //   sgm_check_kernel       a lane a pixel, a launch AFTER the selection: every i1 is written before any is read
 // No floating-point values, no atomics.
+// On request only (mrcal_amd_stereo_sgm_set_speckle_filter()), the speckle filter of speckle_filter.hip runs on the
+// disparity image after the check, its labels and counts in S, which nothing reads any more by then.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -36,6 +38,7 @@
 #include "device_memory.hpp"
 #include "sgm_plan.hpp"
 #include "stereo_sgm.hpp"
+#include "speckle_filter.hpp"
 
 namespace mrcal_amd {
 
@@ -430,8 +433,12 @@ struct mrcal_amd_stereo_sgm
     uint8_t*      pool = NULL;
     SgmPlan       plan;
     SgmParams     params;
-    hipEvent_t    stage[5] = { NULL, NULL, NULL, NULL, NULL };      // before the census, and after each stage
+    hipEvent_t    stage[6] = { NULL, NULL, NULL, NULL, NULL, NULL };    // before the census, and after each stage; the last: after the speckle filter
     bool          timed = false;
+    // the speckle filter (speckle_filter.hip), on request only: its labels and counts lie in S, which is dead by then
+    bool          speckle_on = false;
+    SpeckleParams speckle = { 0, 0, 0 };
+    SpeckleGrids  speckle_grids;
     ~mrcal_amd_stereo_sgm() { for(hipEvent_t e : stage) if(e != NULL) (void)hipEventDestroy(e); }
 };
 
@@ -486,6 +493,12 @@ bool sgm_match_device(mrcal_amd_stereo_sgm* m, int16_t* disparity)
                        a, m->params.disp12_max_diff, index_left, index_right, d_disparity);
     HIP_TRY(hipGetLastError(), return false);
     HIP_TRY(hipEventRecord(m->stage[4], NULL), return false);
+    if(m->speckle_on)
+    {
+        // S is 2 D >= 32 bytes a pixel and nothing reads it after the selection: the filter's 8 bytes a pixel go there
+        if(!speckle_filter_device(m->speckle_grids, m->speckle, d_disparity, S)) return false;
+        HIP_TRY(hipEventRecord(m->stage[5], NULL), return false);
+    }
     // (the copy waits for the launches)
     HIP_TRY(hipMemcpy(disparity, d_disparity, (size_t)plan.W*plan.H*sizeof(int16_t), hipMemcpyDeviceToHost), return false);
     m->timed = true;
@@ -516,7 +529,7 @@ mrcal_amd_stereo_sgm_create(int width, int height, int dtype, const mrcal_amd_st
     mrcal_amd_stereo_sgm* m = new mrcal_amd_stereo_sgm;
     m->plan = plan; m->params = p;
     if(!m->mem.alloc(&m->pool, plan.bytes)) { delete m; return NULL; }
-    for(int i = 0; i < 5; i++)
+    for(int i = 0; i < 6; i++)
         HIP_TRY(hipEventCreate(&m->stage[i]), delete m; return NULL);
     return m;
 }
@@ -538,6 +551,35 @@ bool mrcal_amd_stereo_sgm_stage_milliseconds(mrcal_amd_stereo_sgm_t* m, float* m
     if(!m->timed) { set_error("stereo_matching_sgm(): no match has been made yet"); return false; }
     for(int i = 0; i < 4; i++)
         HIP_TRY(hipEventElapsedTime(&milliseconds[i], m->stage[i], m->stage[i+1]), return false);
+    return true;
+}
+
+bool mrcal_amd_stereo_sgm_set_speckle_filter(mrcal_amd_stereo_sgm_t* m, int window_size, int range)
+{
+    last_error_string().clear();
+    if(!sgm_given(m)) return false;
+    SpeckleParams p;
+    std::string why;
+    if(!speckle_params_of_matcher(&p, &why, m->params.disparity_min, SGM_DISPARITY_SCALE, window_size, range))
+    {
+        set_error("%s", why.c_str());
+        return false;
+    }
+    m->speckle = p;
+    m->speckle_on = window_size > 0;
+    if(m->speckle_on) m->speckle_grids = speckle_grids(m->plan.W, m->plan.H);
+    m->timed = false;
+    return true;
+}
+
+bool mrcal_amd_stereo_sgm_speckle_milliseconds(mrcal_amd_stereo_sgm_t* m, float* milliseconds)
+{
+    last_error_string().clear();
+    if(!sgm_given(m)) return false;
+    if(!m->timed) { set_error("stereo_matching_sgm(): no match has been made yet"); return false; }
+    *milliseconds = 0.f;
+    if(m->speckle_on)
+        HIP_TRY(hipEventElapsedTime(milliseconds, m->stage[4], m->stage[5]), return false);
     return true;
 }
 

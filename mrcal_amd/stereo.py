@@ -17,6 +17,11 @@
     with mrcal_amd.StereoMatcherSGM(rect0.shape, rect0.dtype, disparity_max = 128) as sgm:     # the buffers are made once
         disparity = sgm.match(rect0, rect1)
 
+    # cv2's speckle filter, on request: as a stage of the matcher (also of StereoMatcherSGM and Rectification.disparity()) ...
+    disparity = mrcal_amd.stereo_matching_sgm(rect0, rect1, disparity_max = 128, speckle_window_size = 200, speckle_range = 2)
+    # ... or on a disparity image from anywhere
+    disparity = mrcal_amd.filter_speckles(disparity, new_value = -16, max_speckle_size = 200, max_diff = 32)
+
     q1, diagnostics = mrcal_amd.match_feature(image0, image1, q0, H10 = H10, search_radius1 = 200, template_size1 = 41)
 
     with mrcal_amd.FeatureMatcher(image0, image1) as matcher:          # both images are uploaded once
@@ -25,8 +30,8 @@
 The names, keyword arguments, defaults, return shapes and exception messages are those of the reference's
 mrcal/stereo.py. rectified_system() and rectified_resolution() are host code (csrc/stereo_geometry.cpp) and need no
 GPU; the maps, the remap and the ranges are kernels (csrc/rectification.hip), the template matching of match_feature()
-is csrc/match_feature.hip, the dense matching of stereo_matching_sgm() is csrc/stereo_sgm.hip, and there is no CPU
-fallback for them.
+is csrc/match_feature.hip, the dense matching of stereo_matching_sgm() is csrc/stereo_sgm.hip, the connected-component
+labelling of filter_speckles() is csrc/speckle_filter.hip, and there is no CPU fallback for them.
 Out of scope: image file I/O, cv2.StereoSGBM's and libelas's own pixel-for-pixel output, visualization, LONLAT rectification (which the reference's
 rectified_system() refuses too).
 """
@@ -281,10 +286,12 @@ class Rectification:
                             disparity_scaled_min=disparity_scaled_min, disparity_scaled_max=disparity_scaled_max,
                             _rectification=self)
 
-    def disparity(self, image0, image1, **params):
+    def disparity(self, image0, image1, *, speckle_window_size=0, speckle_range=0, **params):
         """stereo_matching_sgm(*rectify(image0, image1), **params), the same bits: int16 (Nel, Naz). The rectified images
-        are made and matched on the device and do not cross to the host. image0, image1: grayscale, uint8 or uint16"""
+        are made and matched on the device and do not cross to the host. image0, image1: grayscale, uint8 or uint16.
+        speckle_window_size > 0: the disparity image is filtered there too (filter_speckles())"""
         self._open()
+        speckle = _speckle_keywords(speckle_window_size, speckle_range)
         p = _sgm_params(**params)
         for image in (image0, image1):
             if not isinstance(image, np.ndarray) or image.ndim != 2 or image.size == 0:
@@ -294,11 +301,18 @@ class Rectification:
         dtype = _SGM_DTYPES[_sgm_dtype(image0.dtype)]
         a0, a1 = np.ascontiguousarray(image0), np.ascontiguousarray(image1)
         out = np.zeros((self.Nel, self.Naz), dtype=np.int16)
-        f = self._L.mrcal_amd_rectification_disparity
-        f.restype  = C.c_bool
-        f.argtypes = [C.c_void_p]*2 + [C.c_int]*2 + [C.c_void_p] + [C.c_int]*3 + [C.c_void_p]*2
-        if not f(self.handle, _ptr(a0), a0.shape[1], a0.shape[0], _ptr(a1), a1.shape[1], a1.shape[0], dtype,
-                 C.addressof(p), _ptr(out)):
+        images = (self.handle, _ptr(a0), a0.shape[1], a0.shape[0], _ptr(a1), a1.shape[1], a1.shape[0], dtype, C.addressof(p))
+        if speckle[0] == 0:             # (no filter: the entry point without it)
+            f = self._L.mrcal_amd_rectification_disparity
+            f.restype  = C.c_bool
+            f.argtypes = [C.c_void_p]*2 + [C.c_int]*2 + [C.c_void_p] + [C.c_int]*3 + [C.c_void_p]*2
+            ok = f(*images, _ptr(out))
+        else:
+            f = self._L.mrcal_amd_rectification_disparity_filtered
+            f.restype  = C.c_bool
+            f.argtypes = [C.c_void_p]*2 + [C.c_int]*2 + [C.c_void_p] + [C.c_int]*3 + [C.c_void_p] + [C.c_int]*2 + [C.c_void_p]
+            ok = f(*images, *speckle, _ptr(out))
+        if not ok:
             raise Exception("stereo_matching_sgm() failed:" + self._api._last_error())
         return out
 
@@ -765,14 +779,17 @@ class StereoMatcherSGM:
     """Dense stereo matching, resident: every device buffer a match of one image size needs is made once, and every
 match() reuses them.
 
-    shape: (H,W) of the rectified images; dtype: uint8 or uint16; the parameters: those of stereo_matching_sgm().
+    shape: (H,W) of the rectified images; dtype: uint8 or uint16; the parameters: those of stereo_matching_sgm(),
+    speckle_window_size and speckle_range among them.
       .match(image0, image1, out=None)   -> int16 (H,W); out: the array to fill
       .stage_milliseconds()              how long the census, the paths, the selection and the left-right check of the
                                          last match() took on the device
+      .speckle_milliseconds()            ... and the speckle filter (0 without it)
     What a disparity image is: stereo_matching_sgm()"""
 
-    def __init__(self, shape, dtype, **params):
+    def __init__(self, shape, dtype, *, speckle_window_size=0, speckle_range=0, **params):
         self.handle = None
+        self._speckle = _speckle_keywords(speckle_window_size, speckle_range)
         self._params = _sgm_params(**params)
         self._dtype = _sgm_dtype(dtype)
         try:    shape = tuple(int(n) for n in shape)
@@ -789,6 +806,12 @@ match() reuses them.
             self.handle = None
             raise Exception("stereo_matching_sgm() failed:" + api._last_error())
         self._L.mrcal_amd_stereo_sgm_destroy.restype, self._L.mrcal_amd_stereo_sgm_destroy.argtypes = None, [C.c_void_p]
+        if self._speckle[0] > 0:        # (0: nothing of the filter is touched)
+            f = self._L.mrcal_amd_stereo_sgm_set_speckle_filter
+            f.restype, f.argtypes = C.c_bool, [C.c_void_p, C.c_int, C.c_int]
+            if not f(self.handle, *self._speckle):
+                self.close()
+                raise Exception("stereo_matching_sgm() failed:" + api._last_error())
 
     def match(self, image0, image1, out=None):
         if self.handle is None:
@@ -812,6 +835,17 @@ match() reuses them.
             raise Exception("stereo_matching_sgm() failed:" + self._api._last_error())
         return dict(zip(("census", "paths", "select", "check"), (float(x) for x in ms)))
 
+    def speckle_milliseconds(self):
+        """how long the speckle filter of the last match() took on the device; 0 without it"""
+        if self.handle is None:
+            raise Exception("this StereoMatcherSGM has been closed")
+        ms = C.c_float(0)
+        f = self._L.mrcal_amd_stereo_sgm_speckle_milliseconds
+        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2
+        if not f(self.handle, C.addressof(ms)):
+            raise Exception("stereo_matching_sgm() failed:" + self._api._last_error())
+        return float(ms.value)
+
     def close(self):
         if getattr(self, "handle", None):
             self._L.mrcal_amd_stereo_sgm_destroy(self.handle)
@@ -824,7 +858,7 @@ match() reuses them.
 
 
 def stereo_matching_sgm(image0, image1, *, disparity_min=0, disparity_max, P1=10, P2=120, paths=8, uniqueness_ratio=10,
-                        disp12_max_diff=1):
+                        disp12_max_diff=1, speckle_window_size=0, speckle_range=0):
     """The disparity image of a rectified pair, by semi-global matching on a census cost: int16 (H,W), the disparity in
 pixels times STEREO_SGM_DISPARITY_SCALE = 16 (cv2's scale); an invalid pixel holds 16 (disparity_min - 1)
 
@@ -846,14 +880,170 @@ Everything is integer arithmetic, and the result is defined to the bit. The inde
   5. the right image's i1(y,x1) = the smallest i that minimises S(y, x1 + d, i) over the i with x1 + d inside the image.
      A left pixel is invalid if x - d* is outside the image, or |i1(y, x - d*) - i*| > disp12_max_diff
   6. the result is 16 disparity_min + the scaled index
+  7. on request only: speckle_window_size > 0 (cv2.StereoSGBM's speckleWindowSize and speckleRange) filters that result
+     on the device before it is copied out: filter_speckles(result, new_value = 16 (disparity_min - 1),
+     max_speckle_size = speckle_window_size, max_diff = 16 speckle_range). speckle_window_size = 0, the default:
+     no filter, the result of steps 1-6 and nothing else runs
 
 The N = 1 case of StereoMatcherSGM.match(): a sequence of pairs of one size is faster through that.
 Shaped like the reference's mrcal.stereo_matching_libelas(). Not here: cv2.StereoSGBM's Birchfield-Tomasi cost on
-Sobel-filtered images, its adaptive P2, the speckle filter (connected components), colour input, and ELAS itself:
-nothing imitates either matcher pixel for pixel."""
+Sobel-filtered images, its adaptive P2, colour input, and ELAS itself: nothing imitates either matcher pixel for pixel."""
     params = dict(disparity_min=disparity_min, disparity_max=disparity_max, P1=P1, P2=P2, paths=paths,
                   uniqueness_ratio=uniqueness_ratio, disp12_max_diff=disp12_max_diff)
+    _speckle_keywords(speckle_window_size, speckle_range)
     _sgm_params(**params)
     a0, a1 = _sgm_images(image0, image1)
-    with StereoMatcherSGM(a0.shape, a0.dtype, **params) as matcher:
+    with StereoMatcherSGM(a0.shape, a0.dtype, speckle_window_size=speckle_window_size, speckle_range=speckle_range,
+                          **params) as matcher:
         return matcher.match(a0, a1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# filter_speckles(): small regions of a disparity image become invalid (csrc/speckle_filter.hip)
+
+_SPECKLE_MAX_PIXELS = 1 << 28
+_INT32_MAX = (1 << 31) - 1
+
+
+def _speckle_int(name, value):
+    """the refusals of csrc/speckle_plan.hpp in its words, made before any device work"""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value < 0:
+        raise Exception(f"filter_speckles(): {name} must be a non-negative integer. Got {value!r}")
+    return int(value)
+
+
+def _speckle_keywords(speckle_window_size, speckle_range):
+    """-> (window size, range) as the library's two ints. Beyond 2^31 - 1 pixels no region is larger, and a range of
+    4096 is already a max_diff above 65535"""
+    return (min(_speckle_int("speckle_window_size", speckle_window_size), _INT32_MAX),
+            min(_speckle_int("speckle_range", speckle_range), 4096))
+
+
+def _speckle_params(new_value, max_speckle_size, max_diff):
+    if isinstance(new_value, (bool, np.bool_)) or not isinstance(new_value, (int, np.integer)):
+        raise Exception(f"filter_speckles(): new_value must be an integer. Got {new_value!r}")
+    if not (-32768 <= new_value <= 32767):
+        raise Exception(f"filter_speckles(): new_value must be in -32768..32767. Got {new_value}")
+    return (int(new_value), min(_speckle_int("max_speckle_size", max_speckle_size), _INT32_MAX),
+            min(_speckle_int("max_diff", max_diff), 65535))
+
+
+def _speckle_shape(shape):
+    try:    shape = tuple(int(n) for n in shape)
+    except TypeError: shape = ()
+    if len(shape) != 2:
+        raise Exception(f"filter_speckles(): shape must be (H,W), got {shape}")
+    if shape[0] <= 0 or shape[1] <= 0 or shape[0]*shape[1] > _SPECKLE_MAX_PIXELS:
+        raise Exception(f"filter_speckles(): images of {shape[1]} x {shape[0]} pixels cannot be filtered")
+    return shape
+
+
+def _speckle_image(disparity, shape=None):
+    if not isinstance(disparity, np.ndarray) or disparity.ndim != 2 or disparity.dtype != np.int16:
+        raise Exception("filter_speckles(): the disparity image must be a 2-D int16 array" +
+                        (f", got shape {disparity.shape} and dtype {disparity.dtype}" if isinstance(disparity, np.ndarray) else ""))
+    _speckle_shape(disparity.shape)
+    if shape is not None and disparity.shape != shape:
+        raise Exception(f"filter_speckles(): this filter was made for images of shape {shape}, got {disparity.shape}")
+
+
+def _speckle_out(out, shape):
+    if out is not None and (not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != np.int16):
+        raise Exception(f"filter_speckles(): 'out' must be a numpy array of shape {shape} and dtype int16")
+
+
+class SpeckleFilter:
+    """filter_speckles(), resident: the device buffers for one image size are made once, and every filter() reuses them.
+
+    shape: (H,W) of the disparity images.
+      .filter(disparity, *, new_value, max_speckle_size, max_diff, out=None)   -> int16 (H,W); out: the array to
+                                         fill, which may be disparity itself
+      .milliseconds()                    how long the last filter() took on the device, without the copies
+      .pass_milliseconds()               ... pass by pass: the tiles' labels, the joins across the tiles' borders, the
+                                         roots and sizes, the result
+    What the filter is: filter_speckles()"""
+
+    def __init__(self, shape):
+        self.handle = None
+        self.shape = _speckle_shape(shape)
+        lib, api = _libs()
+        self._L, self._api = lib.lib, api
+        f = self._L.mrcal_amd_speckle_filter_create
+        f.restype, f.argtypes = C.c_void_p, [C.c_int]*2
+        self.handle = f(self.shape[1], self.shape[0])
+        if not self.handle:
+            self.handle = None
+            raise Exception("filter_speckles() failed:" + api._last_error())
+        self._L.mrcal_amd_speckle_filter_destroy.restype, self._L.mrcal_amd_speckle_filter_destroy.argtypes = None, [C.c_void_p]
+
+    def filter(self, disparity, *, new_value, max_speckle_size, max_diff, out=None):
+        if self.handle is None:
+            raise Exception("this SpeckleFilter has been closed")
+        _speckle_image(disparity, self.shape)
+        params = _speckle_params(new_value, max_speckle_size, max_diff)
+        _speckle_out(out, self.shape)
+        a = np.ascontiguousarray(disparity)
+        # (the library takes in == out: a dense `out` is filled straight away, disparity itself included)
+        o, r = _output_array(out, self.shape, np.int16, False)
+        f = self._L.mrcal_amd_speckle_filter_apply
+        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*3 + [C.c_int]*3
+        if not f(self.handle, _ptr(a), _ptr(o), *params):
+            raise Exception("filter_speckles() failed:" + self._api._last_error())
+        if r is not o: r[...] = o
+        return r
+
+    def milliseconds(self):
+        if self.handle is None:
+            raise Exception("this SpeckleFilter has been closed")
+        ms = C.c_float(0)
+        f = self._L.mrcal_amd_speckle_filter_milliseconds
+        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2
+        if not f(self.handle, C.addressof(ms)):
+            raise Exception("filter_speckles() failed:" + self._api._last_error())
+        return float(ms.value)
+
+    def pass_milliseconds(self):
+        if self.handle is None:
+            raise Exception("this SpeckleFilter has been closed")
+        ms = np.zeros((4,), dtype=np.float32)
+        f = self._L.mrcal_amd_speckle_filter_pass_milliseconds
+        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2
+        if not f(self.handle, _ptr(ms)):
+            raise Exception("filter_speckles() failed:" + self._api._last_error())
+        return dict(zip(("label", "merge", "count", "apply"), (float(x) for x in ms)))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._L.mrcal_amd_speckle_filter_destroy(self.handle)
+            self.handle = None
+    def __del__(self):
+        try:    self.close()
+        except Exception: pass
+    def __enter__(self): return self
+    def __exit__(self, *a): self.close()
+
+
+def filter_speckles(disparity, *, new_value, max_speckle_size, max_diff, out=None):
+    """A disparity image without its speckles: the connected regions of similar disparity that are too small to be a
+surface become invalid. int16 (H,W) in, int16 (H,W) out: a new array, or `out`, which may be `disparity` itself.
+
+  1. a pixel equal to new_value takes no part and is never changed
+  2. two 4-neighbours (left/right, up/down) that both take part are joined if |a - b| <= max_diff; the difference is
+     taken in 32 bits (-32768 beside 32767 differs by 65535), and a max_diff above 65535 means 65535
+  3. the regions are the connected components of that graph
+  4. every pixel of a region of size <= max_speckle_size becomes new_value; everything else is unchanged.
+     max_speckle_size = 0 changes nothing
+
+This is cv2.filterSpeckles(img, newVal, maxSpeckleSize, maxDiff) for CV_16S, the filter cv2.StereoSGBM applies with
+newVal = 16 (minDisparity - 1), maxSpeckleSize = speckleWindowSize, maxDiff = 16 speckleRange, and the reference's
+mrcal-stereo recommends (--sgbm-speckle-window-size 200 --sgbm-speckle-range 2). cv2's flood fill compares original
+values only and the relation is symmetric, so the result does not depend on the order of the scan; "equal to cv2" rests
+on a transcription of cv2's loop that the tests hold a graph formulation to (tests/speckle_checker.py), not on cv2
+itself. Integer arithmetic on the device (csrc/speckle_filter.hip), the same bits on every call; no CPU fallback.
+stereo_matching_sgm(..., speckle_window_size = ..., speckle_range = ...) applies it before the disparity image leaves
+the device. The N = 1 case of SpeckleFilter.filter()."""
+    _speckle_image(disparity)
+    _speckle_params(new_value, max_speckle_size, max_diff)
+    _speckle_out(out, disparity.shape)
+    with SpeckleFilter(disparity.shape) as f:
+        return f.filter(disparity, new_value=new_value, max_speckle_size=max_speckle_size, max_diff=max_diff, out=out)
