@@ -487,39 +487,92 @@ void copy_out_full(const double* __restrict__ tile, gdouble* __restrict__ out,
     }
 }
 
-// the MFMAs of one Gram k-step, candidates resolved at compile time (problem.hpp)
-template<int NBLK, int MM> struct GramCand
+// One Gram k-step: the packing of problem.hpp, resolved at compile time
+template<int NBLK> struct GramPack
 {
-    static constexpr int      c    = gram_cand(NBLK, MM);
-    static constexpr GramDesc d    = gram_cand_desc(NBLK, c);
-    static constexpr bool     roty = gram_rotated_y(NBLK);
-    static constexpr int srcA = (d.kind == GRAM_YY) ? 1 : 0;                       // X, or Y / Y_0
-    static constexpr int srcB = (d.kind == GRAM_XX) ? 0 : (roty ? 1 : 1 + d.q);   // X, Y or Y_q
-    static constexpr int rotB = (d.kind == GRAM_XX || roty) ? d.q : 0;
+    static constexpr int NOP   = gram_packing(NBLK).nop;
+    static constexpr int NREAD = gram_nreads(NBLK);
+    static constexpr int NM    = gram_nmfma_blk(NBLK);
 };
-struct GramRd { double v[4]; };     // the LDS reads of one k-step: X, then Y or Y_0..Y_2
-template<int NBLK, int NACC, int... MM>
-__device__ __forceinline__ void gram_mfmas(double (&acc)[NACC], const double (&op)[4][4], std::integer_sequence<int, MM...>)
+template<int NBLK, int O> struct GramOp
 {
-    ((acc[MM] = __builtin_amdgcn_mfma_f64_4x4x4f64(op[GramCand<NBLK,MM>::srcA][0],
-                                                   op[GramCand<NBLK,MM>::srcB][GramCand<NBLK,MM>::rotB],
+    static constexpr int src = gram_packing(NBLK).op[O].src, rot = gram_packing(NBLK).op[O].rot;
+    static constexpr int b0  = gram_packing(NBLK).op[O].blk[0], b1 = gram_packing(NBLK).op[O].blk[1];
+    static constexpr int b2  = gram_packing(NBLK).op[O].blk[2], b3 = gram_packing(NBLK).op[O].blk[3];
+};
+template<int NBLK, int MM> struct GramMfmaOps
+{
+    static constexpr int a = gram_packing(NBLK).mfma[MM].a, b = gram_packing(NBLK).mfma[MM].b;
+};
+template<int N> struct GramRd { double v[N]; };     // the LDS reads of one k-step, in operand order
+// operand O from the reads and the operands before it. (Only the rotations that the packing names exist)
+template<int NBLK, int O, int NOP, int NREAD>
+__device__ __forceinline__ void gram_operand(double (&op)[NOP], const GramRd<NREAD>& rd)
+{
+    using o = GramOp<NBLK,O>;
+    if constexpr(o::src < 0)
+    {
+        static_assert(O < NREAD, "the reads come first");
+        op[O] = rd.v[O];
+    }
+    else
+    {
+        static_assert(o::src < O && o::rot >= 1 && o::rot <= 3, "a rotation follows its source");
+        // slot s takes slot s + rot: lane i takes lane i + 4 rot = i - (16 - 4 rot) (mod 16)
+        op[O] = row_ror_f64<16 - 4*o::rot>(op[o::src]);
+    }
+}
+template<int NBLK, int NOP, int NREAD, int... O>
+__device__ __forceinline__ void gram_operands(double (&op)[NOP], const GramRd<NREAD>& rd, std::integer_sequence<int, O...>)
+{
+    (gram_operand<NBLK,O>(op, rd), ...);
+}
+template<int NBLK, int NACC, int NOP, int... MM>
+__device__ __forceinline__ void gram_mfmas(double (&acc)[NACC], const double (&op)[NOP], std::integer_sequence<int, MM...>)
+{
+    ((acc[MM] = __builtin_amdgcn_mfma_f64_4x4x4f64(op[GramMfmaOps<NBLK,MM>::a],
+                                                   op[GramMfmaOps<NBLK,MM>::b],
                                                    acc[MM], 0, 0, 0)), ...);
 }
-// One k-step of the Gram: slot rotations + MFMAs. (Rotations nobody uses are
-// dropped by the compiler)
-template<int NBLK, int NM>
-__device__ __forceinline__ void gram_step_ops(double (&acc)[NM], const GramRd& rd)
+// One k-step of the Gram: slot rotations + MFMAs
+template<int NBLK, int NM, int NREAD>
+__device__ __forceinline__ void gram_step_ops(double (&acc)[NM], const GramRd<NREAD>& rd)
 {
-    double op[4][4];    // [read][slot rotation]
-#pragma unroll
-    for(int g=0; g<4; g++)
-    {
-        op[g][0] = rd.v[g];
-        op[g][1] = row_ror_f64<12>(op[g][0]);
-        op[g][2] = row_ror_f64<8 >(op[g][0]);
-        op[g][3] = row_ror_f64<4 >(op[g][0]);
-    }
+    constexpr int NOP = GramPack<NBLK>::NOP;
+    static_assert(NM == GramPack<NBLK>::NM && NREAD == GramPack<NBLK>::NREAD, "the packing's sizes");
+    double op[NOP];
+    gram_operands<NBLK>(op, rd, std::make_integer_sequence<int, NOP>{});
     gram_mfmas<NBLK>(acc, op, std::make_integer_sequence<int, NM>{});
+}
+// The column blocks that this lane's slot s holds in each LDS read of a k-step, 4 bits a read
+template<int NBLK, int... Q>
+__device__ __forceinline__ unsigned gram_slot_blocks(int s, std::integer_sequence<int, Q...>)
+{
+    constexpr unsigned p0 = (((unsigned)GramOp<NBLK,Q>::b0 << (4*Q)) | ...), p1 = (((unsigned)GramOp<NBLK,Q>::b1 << (4*Q)) | ...);
+    constexpr unsigned p2 = (((unsigned)GramOp<NBLK,Q>::b2 << (4*Q)) | ...), p3 = (((unsigned)GramOp<NBLK,Q>::b3 << (4*Q)) | ...);
+    return s == 0 ? p0 : s == 1 ? p1 : s == 2 ? p2 : p3;
+}
+// This lane's LDS byte address of each read of a k-step, for step 0 of a FULL half-tile: base = its row of the step
+// (which rows those are: gram_copy_fused()) and its column within a block; a block is 4 doubles wide.
+// gram_partial_addresses() derives the set for a partial half from this one where it is needed: a second set kept
+// beside it (the compiler hoists both out of the pass loop) costs, with up to 8 reads a k-step, registers that the
+// projection needs
+template<int NREAD>
+__device__ __forceinline__ void gram_full_addresses(unsigned (&a)[NREAD], unsigned base, unsigned blocks)
+{
+    static_assert(NREAD <= 8, "4 bits a read");
+#pragma unroll
+    for(int q=0;q<NREAD;q++) a[q] = base + (((blocks >> (4*q)) & 0xfu) << 5);
+}
+// ... and for the consecutive rows 4s .. 4s+3 of a partial half: 15 rows less per 16 lanes. (The empty asm keeps
+// the subtractions where they are: NREAD vector instructions per partial half, the last of a board)
+template<int KS, int NREAD>
+__device__ __forceinline__ void gram_partial_addresses(unsigned (&a)[NREAD], const unsigned (&full)[NREAD])
+{
+    unsigned skew = (unsigned)((threadIdx.x >> 4)*15*KS*sizeof(double));
+    asm volatile("" : "+v"(skew));
+#pragma unroll
+    for(int q=0;q<NREAD;q++) a[q] = full[q] - skew;
 }
 
 // a's lanes 32..63 and b's lanes 0..31 trade places (a[32+i] <-> b[i]): v_permlane32_swap_b32 on both halves of the
@@ -548,7 +601,7 @@ __device__ __forceinline__ double lds_read_b64_at(unsigned lds_byte_address)
 
 // Step S of the fused loop over a FULL half-tile (64 rows = 16 k-steps) with K
 // nonzeros per row (K even, compile time). The MFMAs of a k-step keep the
-// FP64 pipe busy for ~160 cycles during which the wave can issue anything else:
+// FP64 pipe busy for 16 cycles each (112 at OPENCV8's 7) during which the wave can issue anything else:
 // the copy-out of row group S (R = 64/(K/2) rows, one wave-wide 16 B/lane store)
 // rides in that shadow. Every LDS instruction and wait here is explicit:
 //     request the Gram operands of step S+1
@@ -557,31 +610,33 @@ __device__ __forceinline__ double lds_read_b64_at(unsigned lds_byte_address)
 //     wait for everything requested; store row group S
 // Lanes past the last whole row of a group (64 % (K/2) of them) repeat the
 // work of the first lanes: same address, same data.
-// "these registers are written by the DS reads waited for here"
-template<int NREAD>
-__device__ __forceinline__ void lgkm_wait0(GramRd& a, d2_t& b)
+// lgkm_wait: "these registers are written by the DS reads waited for here", N younger requests may stay in flight
+template<int N, int NREAD>
+__device__ __forceinline__ void lgkm_wait(GramRd<NREAD>& a, d2_t& b)
 {
-    if(NREAD == 2)      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a.v[0]), "+v"(a.v[1]), "+v"(b) :: "memory");
-    else if(NREAD == 3) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a.v[0]), "+v"(a.v[1]), "+v"(a.v[2]), "+v"(b) :: "memory");
-    else                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a.v[0]), "+v"(a.v[1]), "+v"(a.v[2]), "+v"(a.v[3]), "+v"(b) :: "memory");
+    static_assert(N >= 0 && N <= 15, "lgkmcnt is a 4-bit counter");
+    asm volatile("s_waitcnt lgkmcnt(%0)" :: "n"(N) : "memory");
+    // (volatile statements keep their order: whoever reads these registers comes after the wait)
+#pragma unroll
+    for(int q=0;q<NREAD;q++) asm volatile("" : "+v"(a.v[q]));
+    asm volatile("" : "+v"(b));
 }
-template<int S, bool FULL, bool STORE, int NBLK, int K, int KS, int NM>
+template<int S, bool FULL, bool STORE, int NBLK, int K, int KS, int NM, int NREAD>
 __device__ __forceinline__
-void fused_step(double (&acc)[NM], GramRd& cur, const unsigned (&gram_a)[4], unsigned tile_a0,
+void fused_step(double (&acc)[NM], GramRd<NREAD>& cur, const unsigned (&gram_a)[NREAD], unsigned tile_a0,
                 gdouble* __restrict__ out, int A0, int A1, int B0, int B1, unsigned gofs, int rsub, int nrows)
 {
     // a partial half (FULL = false: the last corners of a board): the steps past
     // its rows are skipped, the stores are predicated on the row
     if(!FULL && 4*S >= nrows) return;
     constexpr int PAIRS = K/2, R = 64/PAIRS, NGRP = (64 + R - 1)/R;
-    constexpr int NREAD = gram_nreads(NBLK);
     // (STORE = false, round 6: the Gram alone - the solve's J-free mode. The same MFMAs on the same operands in the
     //  same order: the same bits in the Gram)
     constexpr bool have_grp = STORE && S < NGRP;
     constexpr int  u  = S & 1;
     constexpr int  go = (S >> 1)*2*R*KS*(int)sizeof(double);         // LDS byte offset of the group's double step
     constexpr int  rb = S*R;                                          // its first row
-    GramRd nxt = cur;
+    GramRd<NREAD> nxt = cur;
     if(S < 15)
     {
         // FULL: k-step s takes the tile rows s, s+16, s+32, s+48 (gram_copy_fused)
@@ -599,15 +654,13 @@ void fused_step(double (&acc)[NM], GramRd& cur, const unsigned (&gram_a)[4], uns
     {
         // the only wait for Gram operands: NREAD + 2 requests are younger than step 0's
         d2_t none = {0.0, 0.0};
-        if(!FULL || !have_grp) lgkm_wait0<NREAD>(cur, none);      // (no copy-out reads behind them: NREAD younger requests, not NREAD + 2 - wait for all)
-        else if(NREAD == 2) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(cur.v[0]), "+v"(cur.v[1]), "+v"(none) :: "memory");
-        else if(NREAD == 3) asm volatile("s_waitcnt lgkmcnt(5)" : "+v"(cur.v[0]), "+v"(cur.v[1]), "+v"(cur.v[2]), "+v"(none) :: "memory");
-        else                asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(cur.v[0]), "+v"(cur.v[1]), "+v"(cur.v[2]), "+v"(cur.v[3]), "+v"(none) :: "memory");
+        if(!FULL || !have_grp) lgkm_wait<0>(cur, none);      // (no copy-out reads behind them: NREAD younger requests, not NREAD + 2 - wait for all)
+        else                   lgkm_wait<NREAD + 2>(cur, none);
     }
     __builtin_amdgcn_sched_barrier(0);
     gram_step_ops<NBLK>(acc, cur);
     __builtin_amdgcn_sched_barrier(0);
-    lgkm_wait0<NREAD>(nxt, v);
+    lgkm_wait<0>(nxt, v);
     if(have_grp)
     {
         gdouble* __restrict__ o = out + rb*K;       // wave-uniform
@@ -621,24 +674,23 @@ void fused_step(double (&acc)[NM], GramRd& cur, const unsigned (&gram_a)[4], uns
     __builtin_amdgcn_sched_barrier(0);
     cur = nxt;
 }
-template<bool FULL, bool STORE, int NBLK, int K, int KS, int NM, int... S>
+template<bool FULL, bool STORE, int NBLK, int K, int KS, int NM, int NREAD, int... S>
 __device__ __forceinline__
-void fused_steps(double (&acc)[NM], GramRd& cur, const unsigned (&gram_a)[4], unsigned tile_a0,
+void fused_steps(double (&acc)[NM], GramRd<NREAD>& cur, const unsigned (&gram_a)[NREAD], unsigned tile_a0,
                  gdouble* __restrict__ out, int A0, int A1, int B0, int B1, unsigned gofs, int rsub, int nrows,
                  std::integer_sequence<int, S...>)
 {
     (fused_step<S,FULL,STORE,NBLK,K,KS>(acc, cur, gram_a, tile_a0, out, A0, A1, B0, B1, gofs, rsub, nrows), ...);
 }
-template<bool FULL, bool STORE, int NBLK, int K, int KS, int NM>
+template<bool FULL, bool STORE, int NBLK, int K, int KS, int NM, int NREAD>
 __device__ __forceinline__
-void gram_copy_fused(double (&acc)[NM], const double* __restrict__ tile, const int (&goffs)[4],
+void gram_copy_fused(double (&acc)[NM], const double* __restrict__ tile, const unsigned (&gram_full)[NREAD],
                      gdouble* __restrict__ out, int A0, int A1, int B0, int B1, unsigned gofs, int rsub, int nrows)
 {
-    constexpr int NREAD = gram_nreads(NBLK);
-    static_assert(NREAD >= 2 && NREAD <= 4, "board tiles have 5..8 column blocks");
+    static_assert(NREAD >= 2 && NREAD <= 8, "a k-step's requests and the copy-out's two fit the wait counter");
     const unsigned tile_a0 = (unsigned)(size_t)tile;
     // WHICH four tile rows make up a k-step is free (the Gram is a sum over all
-    // rows). Consecutive rows (4s .. 4s+3, goffs) sit 58 dwords apart: the two
+    // rows). Consecutive rows (4s .. 4s+3) sit 58 dwords apart: the two
     // rows that a 32-lane half of the wave reads overlap in 26 of their 32 LDS
     // banks - 795 of the kernel's 1028 active LDS cycles were bank conflicts. A
     // full half-tile therefore takes rows s, s+16, s+32, s+48: 16 rows apart is
@@ -646,13 +698,14 @@ void gram_copy_fused(double (&acc)[NM], const double* __restrict__ tile, const i
     // consecutive rows: it stops after ceil(nrows/4) steps.) Measured: the
     // conflict cycles halve (the rest are the tile writes and the copy-out
     // reads); the kernel's time does not move - the LDS is not what it waits for
-    const unsigned row_skew = FULL ? (unsigned)((threadIdx.x >> 4)*15*KS*sizeof(double)) : 0u;
-    unsigned gram_a[4];
+    unsigned gram_a[NREAD];
+    if(FULL)
+    {
 #pragma unroll
-    for(int q=0;q<4;q++) gram_a[q] = tile_a0 + row_skew + (unsigned)(goffs[q < NREAD ? q : 0]*sizeof(double));
-    GramRd cur;
-#pragma unroll
-    for(int q=0;q<4;q++) cur.v[q] = 0.0;
+        for(int q=0;q<NREAD;q++) gram_a[q] = gram_full[q];
+    }
+    else gram_partial_addresses<KS>(gram_a, gram_full);
+    GramRd<NREAD> cur;
 #pragma unroll
     for(int q=0;q<NREAD;q++) cur.v[q] = lds_read_b64_at<0>(gram_a[q]);
     fused_steps<FULL,STORE,NBLK,K,KS>(acc, cur, gram_a, tile_a0, out, A0, A1, B0, B1, gofs, rsub, nrows,
@@ -797,11 +850,10 @@ void board_observation(const DeviceProblem& P,
     const double inv_fx  = 1.0/intr[0], inv_fy  = 1.0/intr[1];
 
     // Gram operands (problem.hpp): at k-step s this lane reads
-    // tile[4 s + lane/16][gram_read_col(iread, lane)] for each of the NREAD operands
+    // tile[its row of the step][gram_read_col(iread, lane)] for each of the NREAD operands
     constexpr int NREAD = gram_nreads(NBLK);
-    int goffs[4];
-#pragma unroll
-    for(int q=0;q<4;q++) goffs[q] = (lane >> 4)*KS + gram_read_col(NBLK, q < NREAD ? q : 0, lane);
+    const unsigned gram_base   = (unsigned)(size_t)tile + (unsigned)(((lane >> 4)*16*KS + (lane & 3))*sizeof(double));
+    unsigned       gram_blocks = gram_slot_blocks<NBLK>((lane >> 2) & 3, std::make_integer_sequence<int, NREAD>{});
     double acc[NM];
 #pragma unroll
     for(int mm=0;mm<NM;mm++) acc[mm] = 0.0;
@@ -1044,6 +1096,14 @@ void board_observation(const DeviceProblem& P,
             if(nc <= 0) break;
             const int nrows = 2*((nc < 32) ? nc : 32);
 
+            // The Gram's read addresses. With every variable optimized they are loop invariants that the compiler
+            // keeps in registers for the life of the wave. The general kernels have no registers to spare through
+            // the projection: they form them here, 2 instructions a read, from one register (the empty asm is
+            // what keeps them here)
+            if(!ALLOPT) asm volatile("" : "+v"(gram_blocks));
+            unsigned gram_full[NREAD];
+            gram_full_addresses(gram_full, gram_base, gram_blocks);
+
             // WAR: the previous half's tile reads are complete (in-order LDS)
             __builtin_amdgcn_wave_barrier();
             {
@@ -1078,13 +1138,13 @@ void board_observation(const DeviceProblem& P,
                 const bool kfull = ALLOPT ? has_ext : (k == KFULL);
                 if(nrows == 64)
                 {
-                    if(kfull) gram_copy_fused<true,STORE_J,NBLK,KFULL,  KS>(acc, tile, goffs, out, co_A0, co_A1, co_B0, co_B1, co_gofs, rs, 64);
-                    else      gram_copy_fused<true,STORE_J,NBLK,KFULL-6,KS>(acc, tile, goffs, out, co_A0, co_A1, co_B0, co_B1, co_gofs, rs, 64);
+                    if(kfull) gram_copy_fused<true,STORE_J,NBLK,KFULL,  KS>(acc, tile, gram_full, out, co_A0, co_A1, co_B0, co_B1, co_gofs, rs, 64);
+                    else      gram_copy_fused<true,STORE_J,NBLK,KFULL-6,KS>(acc, tile, gram_full, out, co_A0, co_A1, co_B0, co_B1, co_gofs, rs, 64);
                 }
                 else
                 {
-                    if(kfull) gram_copy_fused<false,STORE_J,NBLK,KFULL,  KS>(acc, tile, goffs, out, co_A0, co_A1, co_B0, co_B1, co_gofs, rs, nrows);
-                    else      gram_copy_fused<false,STORE_J,NBLK,KFULL-6,KS>(acc, tile, goffs, out, co_A0, co_A1, co_B0, co_B1, co_gofs, rs, nrows);
+                    if(kfull) gram_copy_fused<false,STORE_J,NBLK,KFULL,  KS>(acc, tile, gram_full, out, co_A0, co_A1, co_B0, co_B1, co_gofs, rs, nrows);
+                    else      gram_copy_fused<false,STORE_J,NBLK,KFULL-6,KS>(acc, tile, gram_full, out, co_A0, co_A1, co_B0, co_B1, co_gofs, rs, nrows);
                 }
                 TSACC(5, tcur);
                 continue;
@@ -1134,11 +1194,15 @@ void board_observation(const DeviceProblem& P,
                 // without a corner, which stored zeros
                 // (the full halves of the usual problems take the fused path above)
                 const int nsteps = (nrows + 3) >> 2;
+                unsigned gram_a[NREAD];
+                gram_partial_addresses<KS>(gram_a, gram_full);
+                typedef __attribute__((address_space(3))) const double lds_cdouble;
                 for(int s = 0; s < nsteps; s++)
                 {
-                    GramRd rd;
+                    // (ordinary loads: the compiler overlaps a step's reads with the MFMAs of the one before)
+                    GramRd<NREAD> rd;
 #pragma unroll
-                    for(int q=0;q<4;q++) rd.v[q] = (q < NREAD) ? tile[s*4*KS + goffs[q]] : 0.0;
+                    for(int q=0;q<NREAD;q++) rd.v[q] = reinterpret_cast<lds_cdouble*>(gram_a[q])[s*4*KS];
                     gram_step_ops<NBLK>(acc, rd);
                 }
             }

@@ -129,119 +129,154 @@ __host__ __device__ inline int tile_stride(int ndist) { return (4*tile_nblk(ndis
 //   A lane = 16 k + 4 slot + i     B lane = 16 k + 4 slot + j     D lane = 16 i + 4 slot + j
 // G is cut into 4x4 blocks (NBLK = ncols/4 of them per side). An operand is ONE
 // LDS read per lane, tile[row 4 step + l/16][4 blk(slot) + l%4], which serves
-// as A or B alike and holds one column block per slot:
-//   X     blocks (0,1,2,3): lane l reads column l%16, 16 contiguous doubles per row
-//   Y_q   q = 0..ny-1, ny = NBLK-4 < 4: the remaining blocks in cyclic order,
-//         slot s holds block 4 + (s+q) % ny
-//   Y     (ny = 4) blocks (4,5,6,7)
-// and the block pairs come from
-//   X . rot_r(X), r = 0,1,2   (rot_r: slots rotated by DPP row_ror, no LDS traffic)
-//                             r = 0 the diagonal blocks, r = 1 (s,s+1) incl. the
-//                             mirrored (3,0), r = 2 (0,2),(1,3) [slots 2,3 repeat them]
-//   ny < 4:  X . Y_q (all of X x Y in ny instructions), Y_0 . Y_0, Y_0 . Y_1
-//   ny = 4:  Y . rot_r(Y) r = 0,1,2 and X . rot_r(Y) r = 0..3
-// 8 MFMAs, 4 LDS reads and 2 rotations per step for the 27 columns of OPENCV8,
-// where gathering every pair's operands separately costs 2 reads per MFMA and
-// makes the LDS pipe (shared by all the waves of a CU) the limit, and forming
-// everything from X, Y and their rotations costs 10 MFMAs.
+// as A or B alike and holds one column block per slot - any four blocks: the
+// lane's column is a loop invariant, so an arbitrary choice costs an address
+// register and nothing else. An operand may instead be another one with its
+// slots rotated (DPP row_ror, no LDS traffic, two vector moves).
+// An MFMA multiplies two operands slot by slot: slot s yields the block pair
+// (A.blk[s], B.blk[s]). A packing (GramPacking) lists the operands and the
+// MFMAs of one k-step so that every unordered block pair sits in exactly one
+// "valid" slot; the other slots repeat a pair and are ignored downstream.
+// NBLK(NBLK+1)/2 pairs in 4 slots an instruction: 7 MFMAs for the 7 blocks
+// (27 columns) of OPENCV8, 28 pairs in 28 slots, and 6 for 6 blocks, where
+// forming everything from X = (0,1,2,3), Y = the rest and their rotations costs
+// 10, and X, its rotations and cyclic operands Y_q (slot s: block 4 + (s+q) % ny)
+// cost 8 and 7. The matrix instructions and the rotations' moves go down the
+// one FP64 pipe that limits the board kernel, the LDS reads do not: at 6 and 7
+// blocks every operand is a read, 8 a k-step for 7 blocks (measured: LEDGER,
+// "The Gram in the fewest matrix instructions"). 5 and 8 blocks keep X, Y and
+// rotations.
 // The accumulators are stored as they are, gram[iobs][m][lane]: lane l of
 // accumulator m holds G[4 bA + l/16][4 bB + l%4], (bA,bB) the pair in slot (l%16)/4.
-enum { GRAM_XX = 0, GRAM_YY, GRAM_XY };
-struct GramDesc { int kind, q; };     // q: the rotation r, or the index of the Y_q operand
-__host__ __device__ constexpr int  gram_nx(int nblk) { return nblk < 4 ? nblk : 4; }
-__host__ __device__ constexpr int  gram_ny(int nblk) { return nblk - gram_nx(nblk); }
-__host__ __device__ constexpr bool gram_rotated_y(int nblk) { return gram_ny(nblk) == 4; }
-// LDS reads per step: X, then Y (ny = 4) or Y_0..Y_{ny-1}
-__host__ __device__ constexpr int  gram_nreads(int nblk) { return 1 + (gram_rotated_y(nblk) ? 1 : gram_ny(nblk)); }
-// the candidate accumulators, in order: XX r=0,1,2 | YY | XY
-__host__ __device__ constexpr int  gram_ncand(int nblk)
+enum { GRAM_MAXOP = 10, GRAM_MAXMFMA = 10 };
+struct GramOperand
 {
-    const int ny = gram_ny(nblk);
-    if(ny == 0) return 3;
-    if(ny == 4) return 3 + 3 + 4;
-    return 3 + (ny >= 2 ? 2 : 1) + ny;
+    int blk[4];     // the column block in each slot
+    int src, rot;   // src < 0: an LDS read. Else operand `src` rotated: slot s holds src's slot (s + rot) % 4
+};
+struct GramMfma { int a, b, valid; };  // operands; bit s of valid: slot s holds a pair that no other slot does
+struct GramPacking
+{
+    int nop, nmfma;
+    GramOperand op[GRAM_MAXOP];       // the LDS reads first: read number = operand number
+    GramMfma    mfma[GRAM_MAXMFMA];
+};
+__host__ __device__ constexpr void gram_add_read(GramPacking& p, int b0, int b1, int b2, int b3)
+{
+    p.op[p.nop++] = GramOperand{ {b0, b1, b2, b3}, -1, 0 };
 }
-__host__ __device__ constexpr GramDesc gram_cand_desc(int nblk, int c)
+__host__ __device__ constexpr void gram_add_rot(GramPacking& p, int src, int rot)
 {
-    const int ny  = gram_ny(nblk);
-    const int nyy = (ny == 4) ? 3 : (ny >= 2 ? 2 : (ny == 1 ? 1 : 0));
-    if(c < 3)       return GramDesc{ GRAM_XX, c };
-    if(c < 3 + nyy) return GramDesc{ GRAM_YY, c - 3 };
-    return GramDesc{ GRAM_XY, c - 3 - nyy };
+    const GramOperand& o = p.op[src];
+    p.op[p.nop++] = GramOperand{ {o.blk[rot & 3], o.blk[(1+rot) & 3], o.blk[(2+rot) & 3], o.blk[(3+rot) & 3]}, src, rot };
 }
-// slot s of candidate c: its block pair; false if the slot is unused or repeats another
-__host__ __device__ constexpr bool gram_slot_pair(int nblk, int c, int s, int* bA, int* bB)
+__host__ __device__ constexpr void gram_add_mfma(GramPacking& p, int a, int b, int valid = 0xf)
 {
-    const int nx = gram_nx(nblk), ny = gram_ny(nblk);
-    const GramDesc d = gram_cand_desc(nblk, c);
-    int a = 0, b = 0;
-    bool ok = true;
-    if(d.kind == GRAM_XX)
-    {
-        a = s; b = (s + d.q) & 3;
-        ok = a < nx && b < nx && !(d.q == 2 && s >= 2);
-    }
-    else if(ny == 4)
-    {
-        b = 4 + ((s + d.q) & 3);
-        if(d.kind == GRAM_YY) { a = 4 + s; ok = !(d.q == 2 && s >= 2); }
-        else                  { a = s;     ok = a < nx; }
-    }
-    else if(d.kind == GRAM_XY)
-    {
-        a = s; b = 4 + (s + d.q) % ny;
-        ok = a < nx;
-    }
-    else
-    {
-        a = 4 + s % ny; b = 4 + (s + d.q) % ny;
-        ok = s < ny && (d.q == 0 || ny == 3 || s == 0);
-    }
-    *bA = a; *bB = b;
-    return ok;
+    p.mfma[p.nmfma++] = GramMfma{ a, b, valid };
 }
-__host__ __device__ constexpr bool gram_cand_valid(int nblk, int c)
+// board tiles have 5..8 column blocks (NDIST = 0..12)
+__host__ __device__ constexpr GramPacking gram_packing(int nblk)
 {
-    int a = 0, b = 0;
-    return gram_slot_pair(nblk,c,0,&a,&b) || gram_slot_pair(nblk,c,1,&a,&b) ||
-           gram_slot_pair(nblk,c,2,&a,&b) || gram_slot_pair(nblk,c,3,&a,&b);
+    GramPacking p{};
+    if(nblk == 5)
+    {
+        gram_add_read(p, 0,1,2,3);                  // 0: X
+        gram_add_read(p, 4,4,4,4);                  // 1: Y
+        gram_add_rot (p, 0, 1);                     // 2: X1 = (1,2,3,0)
+        gram_add_rot (p, 0, 2);                     // 3: X2 = (2,3,0,1)
+        gram_add_mfma(p, 0, 0);                     // the diagonal blocks of X
+        gram_add_mfma(p, 0, 2);                     // (0,1) (1,2) (2,3) and the mirrored (3,0)
+        gram_add_mfma(p, 0, 3, 0x3);                // (0,2) (1,3)
+        gram_add_mfma(p, 1, 1, 0x1);                // (4,4)
+        gram_add_mfma(p, 0, 1);                     // (s,4)
+    }
+    else if(nblk == 6)
+    {
+        gram_add_read(p, 0,1,2,3);                  // 0: X
+        gram_add_read(p, 1,2,3,0);                  // 1: X1
+        gram_add_read(p, 4,5,4,5);                  // 2: Y_0
+        gram_add_read(p, 5,4,5,4);                  // 3: Y_1
+        gram_add_read(p, 0,1,4,5);                  // 4: P
+        gram_add_read(p, 2,3,4,5);                  // 5: Q
+        gram_add_mfma(p, 0, 0);                     // the diagonal blocks of X
+        gram_add_mfma(p, 0, 1);                     // (0,1) (1,2) (2,3) and the mirrored (3,0)
+        gram_add_mfma(p, 0, 2);                     // (0,4) (1,5) (2,4) (3,5)
+        gram_add_mfma(p, 0, 3);                     // (0,5) (1,4) (2,5) (3,4)
+        gram_add_mfma(p, 4, 5);                     // (0,2) (1,3) (4,4) (5,5)
+        gram_add_mfma(p, 2, 3, 0x1);                // (4,5)
+    }
+    else if(nblk == 7)
+    {
+        gram_add_read(p, 0,1,2,3);                  // 0: X
+        gram_add_read(p, 1,2,3,0);                  // 1: X1
+        gram_add_read(p, 4,5,6,4);                  // 2, 3, 4: Y_q, slot s holds block 4 + (s+q)%3
+        gram_add_read(p, 5,6,4,5);
+        gram_add_read(p, 6,4,5,6);
+        gram_add_read(p, 4,6,4,5);                  // 5: Z
+        gram_add_read(p, 0,1,5,6);                  // 6: P
+        gram_add_read(p, 2,3,5,6);                  // 7: Q
+        gram_add_mfma(p, 0, 0);                     // the diagonal blocks of X
+        gram_add_mfma(p, 0, 1);                     // (0,1) (1,2) (2,3) and the mirrored (3,0)
+        gram_add_mfma(p, 0, 2);                     // X x Y: (s, 4 + (s+q)%3), q = 0,1,2
+        gram_add_mfma(p, 0, 3);
+        gram_add_mfma(p, 0, 4);
+        gram_add_mfma(p, 2, 5);                     // (4,4) (5,6) (6,4) (4,5)
+        gram_add_mfma(p, 6, 7);                     // (0,2) (1,3) (5,5) (6,6)
+    }
+    else if(nblk == 8)
+    {
+        gram_add_read(p, 0,1,2,3);                  // 0: X
+        gram_add_read(p, 4,5,6,7);                  // 1: Y
+        gram_add_rot (p, 0, 1);                     // 2, 3: X1, X2
+        gram_add_rot (p, 0, 2);
+        gram_add_rot (p, 1, 1);                     // 4, 5, 6: Y1, Y2, Y3
+        gram_add_rot (p, 1, 2);
+        gram_add_rot (p, 1, 3);
+        gram_add_mfma(p, 0, 0);
+        gram_add_mfma(p, 0, 2);
+        gram_add_mfma(p, 0, 3, 0x3);
+        gram_add_mfma(p, 1, 1);
+        gram_add_mfma(p, 1, 4);
+        gram_add_mfma(p, 1, 5, 0x3);
+        gram_add_mfma(p, 0, 1);                     // X x Y: (s, 4 + (s+r)%4), r = 0..3
+        gram_add_mfma(p, 0, 4);
+        gram_add_mfma(p, 0, 5);
+        gram_add_mfma(p, 0, 6);
+    }
+    return p;
 }
-// number of accumulators, and the candidate behind accumulator m
-__host__ __device__ constexpr int gram_nmfma_blk(int nblk)
+// LDS reads per step (they come first among the operands)
+__host__ __device__ constexpr int gram_nreads(int nblk)
 {
+    const GramPacking p = gram_packing(nblk);
     int n = 0;
-    for(int c = 0; c < gram_ncand(nblk); c++) if(gram_cand_valid(nblk, c)) n++;
+    for(int o = 0; o < p.nop; o++) if(p.op[o].src < 0) n++;
     return n;
 }
-__host__ __device__ constexpr int gram_cand(int nblk, int m)
-{
-    for(int c = 0; c < gram_ncand(nblk); c++)
-        if(gram_cand_valid(nblk, c)) { if(m == 0) return c; m--; }
-    return -1;
-}
+// number of accumulators. (Spelt out: device code asks at run time)
+__host__ __device__ constexpr int gram_nmfma_blk(int nblk) { return nblk == 8 ? 10 : (nblk >= 5 && nblk <= 7) ? nblk : 0; }
+static_assert(gram_packing(5).nmfma == gram_nmfma_blk(5) && gram_packing(6).nmfma == gram_nmfma_blk(6) &&
+              gram_packing(7).nmfma == gram_nmfma_blk(7) && gram_packing(8).nmfma == gram_nmfma_blk(8), "gram_nmfma_blk()");
 __host__ __device__ inline int gram_stride(int ndist) { return gram_nmfma_blk(tile_nblk(ndist))*64; }
 // position pos = 64 m + lane of a stored Gram -> the entry G[i][j] it holds.
 // diag: the entry is in a diagonal 4x4 block, where (i,j) and (j,i) are both
 // stored; elsewhere only one of them is (i > j can happen: mirrored blocks).
-// Returns false for the unused slots
+// Returns false for the slots that repeat a pair
 __host__ __device__ inline bool gram_pos_to_entry(int nblk, int pos, int* i, int* j, bool* diag)
 {
-    const int lane = pos & 63, s = (lane >> 2) & 3;
-    const int c = gram_cand(nblk, pos >> 6);
-    int bA = 0, bB = 0;
-    if(c < 0 || !gram_slot_pair(nblk, c, s, &bA, &bB)) return false;
+    const GramPacking p = gram_packing(nblk);
+    const int lane = pos & 63, s = (lane >> 2) & 3, m = pos >> 6;
+    if(m >= p.nmfma || !((p.mfma[m].valid >> s) & 1)) return false;
+    const int bA = p.op[p.mfma[m].a].blk[s], bB = p.op[p.mfma[m].b].blk[s];
     *i = 4*bA + (lane >> 4);
     *j = 4*bB + (lane & 3);
     *diag = (bA == bB);
     return true;
 }
-// tile column this lane reads for operand `iread` (0: X; then Y or Y_q)
+// tile column this lane reads for operand `iread` < gram_nreads()
 __host__ __device__ inline int gram_read_col(int nblk, int iread, int lane)
 {
-    if(iread == 0) return lane & 15;
-    const int ny = gram_ny(nblk), s = (lane >> 2) & 3;
-    if(ny == 4) return 16 + (lane & 15);
-    return 16 + 4*((s + (iread - 1)) % ny) + (lane & 3);
+    return 4*gram_packing(nblk).op[iread].blk[(lane >> 2) & 3] + (lane & 3);
 }
 
 struct DeviceProblem
