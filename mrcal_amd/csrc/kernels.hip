@@ -566,10 +566,13 @@ __device__ __forceinline__ void gram_full_addresses(unsigned (&a)[NREAD], unsign
 }
 // ... and for the consecutive rows 4s .. 4s+3 of a partial half: 15 rows less per 16 lanes. (The empty asm keeps
 // the subtractions where they are: NREAD vector instructions per partial half, the last of a board)
-template<int KS, int NREAD>
+// (ROWL, the tile with one row a lane - problem.hpp, board_gram_row(): the lanes' rows of a full k-step start at
+//  0, 16, 1, 17, those of a partial one at 0, 32, 2, 34)
+template<int KS, bool ROWL, int NREAD>
 __device__ __forceinline__ void gram_partial_addresses(unsigned (&a)[NREAD], const unsigned (&full)[NREAD])
 {
-    unsigned skew = (unsigned)((threadIdx.x >> 4)*15*KS*sizeof(double));
+    const int kq = threadIdx.x >> 4;
+    unsigned skew = (unsigned)((board_gram_row(ROWL, true, 0, kq) - board_gram_row(ROWL, false, 0, kq))*KS*(int)sizeof(double));
     asm volatile("" : "+v"(skew));
 #pragma unroll
     for(int q=0;q<NREAD;q++) a[q] = full[q] - skew;
@@ -621,7 +624,13 @@ __device__ __forceinline__ void lgkm_wait(GramRd<NREAD>& a, d2_t& b)
     for(int q=0;q<NREAD;q++) asm volatile("" : "+v"(a.v[q]));
     asm volatile("" : "+v"(b));
 }
-template<int S, bool FULL, bool STORE, int NBLK, int K, int KS, int NM, int NREAD>
+// ROWL (the kernels with everything optimized): the tile holds one row a lane, logical row r of the half in tile row
+// board_tile_row(r) (problem.hpp), and a k-step reads the rows board_gram_row(): 32 (S%2) + 2 (S/2) + (0, 16, 1, 17)[k]
+// in a full half, 4S - 31 [S >= 8] + (0, 32, 2, 34)[k] in a partial one.
+// The copy-out goes through the tile's two blocks of 32 logical rows one after the other, ceil(32/R) row groups each:
+// inside a block the tile row of r is r + 31 (r%2), so a lane whose rows keep their parity over a double step has
+// loop-invariant offsets as before (copy_out_invariants()), and the second block is the first one tile row further
+template<int S, bool FULL, bool STORE, bool ROWL, int NBLK, int K, int KS, int NM, int NREAD>
 __device__ __forceinline__
 void fused_step(double (&acc)[NM], GramRd<NREAD>& cur, const unsigned (&gram_a)[NREAD], unsigned tile_a0,
                 gdouble* __restrict__ out, int A0, int A1, int B0, int B1, unsigned gofs, int rsub, int nrows)
@@ -629,18 +638,24 @@ void fused_step(double (&acc)[NM], GramRd<NREAD>& cur, const unsigned (&gram_a)[
     // a partial half (FULL = false: the last corners of a board): the steps past
     // its rows are skipped, the stores are predicated on the row
     if(!FULL && 4*S >= nrows) return;
-    constexpr int PAIRS = K/2, R = 64/PAIRS, NGRP = (64 + R - 1)/R;
+    constexpr int PAIRS = K/2, R = 64/PAIRS;
+    constexpr int BLKROWS = ROWL ? 32 : 64;                           // logical rows that the copy-out takes in one sweep
+    constexpr int NGB  = (BLKROWS + R - 1)/R, NGRP = (64/BLKROWS)*NGB;
+    static_assert(NGRP <= 16 && R >= 4 && 4*NGB <= BLKROWS, "a row group a step, its first row not before the step's own four");
     // (STORE = false, round 6: the Gram alone - the solve's J-free mode. The same MFMAs on the same operands in the
     //  same order: the same bits in the Gram)
     constexpr bool have_grp = STORE && S < NGRP;
-    constexpr int  u  = S & 1;
-    constexpr int  go = (S >> 1)*2*R*KS*(int)sizeof(double);         // LDS byte offset of the group's double step
-    constexpr int  rb = S*R;                                          // its first row
+    constexpr int  blk = S / NGB, g = S % NGB;                        // the group's block of rows, its number in there
+    constexpr int  u  = g & 1;
+    constexpr int  go = ((g >> 1)*2*R + (ROWL ? blk : 0))*KS*(int)sizeof(double);   // LDS byte offset of the group's double step
+    constexpr int  rb = blk*BLKROWS + g*R;                            // its first row
+    constexpr int  re = (blk + 1)*BLKROWS;                            // the end of its block
     GramRd<NREAD> nxt = cur;
     if(S < 15)
     {
         // FULL: k-step s takes the tile rows s, s+16, s+32, s+48 (gram_copy_fused)
-        constexpr int so = (S < 15 ? S+1 : 0)*(FULL ? 1 : 4)*KS*(int)sizeof(double);
+        constexpr int S1 = S < 15 ? S+1 : 0;
+        constexpr int so = board_gram_row(ROWL, FULL, S1, 0)*KS*(int)sizeof(double);
 #pragma unroll
         for(int q=0;q<NREAD;q++) nxt.v[q] = lds_read_b64_at<so>(gram_a[q]);
     }
@@ -666,23 +681,23 @@ void fused_step(double (&acc)[NM], GramRd<NREAD>& cur, const unsigned (&gram_a)[
         gdouble* __restrict__ o = out + rb*K;       // wave-uniform
         if(FULL)
         {
-            if(rb + R - 1 < 64)      __builtin_nontemporal_store(v, reinterpret_cast<gdouble2*>(&o[gofs]));
-            else if(rsub < 64 - rb)  __builtin_nontemporal_store(v, reinterpret_cast<gdouble2*>(&o[gofs]));
+            if(rb + R - 1 < re)      __builtin_nontemporal_store(v, reinterpret_cast<gdouble2*>(&o[gofs]));
+            else if(rsub < re - rb)  __builtin_nontemporal_store(v, reinterpret_cast<gdouble2*>(&o[gofs]));
         }
-        else if(rb + rsub < nrows)   __builtin_nontemporal_store(v, reinterpret_cast<gdouble2*>(&o[gofs]));
+        else if(rb + rsub < (nrows < re ? nrows : re)) __builtin_nontemporal_store(v, reinterpret_cast<gdouble2*>(&o[gofs]));
     }
     __builtin_amdgcn_sched_barrier(0);
     cur = nxt;
 }
-template<bool FULL, bool STORE, int NBLK, int K, int KS, int NM, int NREAD, int... S>
+template<bool FULL, bool STORE, bool ROWL, int NBLK, int K, int KS, int NM, int NREAD, int... S>
 __device__ __forceinline__
 void fused_steps(double (&acc)[NM], GramRd<NREAD>& cur, const unsigned (&gram_a)[NREAD], unsigned tile_a0,
                  gdouble* __restrict__ out, int A0, int A1, int B0, int B1, unsigned gofs, int rsub, int nrows,
                  std::integer_sequence<int, S...>)
 {
-    (fused_step<S,FULL,STORE,NBLK,K,KS>(acc, cur, gram_a, tile_a0, out, A0, A1, B0, B1, gofs, rsub, nrows), ...);
+    (fused_step<S,FULL,STORE,ROWL,NBLK,K,KS>(acc, cur, gram_a, tile_a0, out, A0, A1, B0, B1, gofs, rsub, nrows), ...);
 }
-template<bool FULL, bool STORE, int NBLK, int K, int KS, int NM, int NREAD>
+template<bool FULL, bool STORE, bool ROWL, int NBLK, int K, int KS, int NM, int NREAD>
 __device__ __forceinline__
 void gram_copy_fused(double (&acc)[NM], const double* __restrict__ tile, const unsigned (&gram_full)[NREAD],
                      gdouble* __restrict__ out, int A0, int A1, int B0, int B1, unsigned gofs, int rsub, int nrows)
@@ -695,20 +710,23 @@ void gram_copy_fused(double (&acc)[NM], const double* __restrict__ tile, const u
     // banks - 795 of the kernel's 1028 active LDS cycles were bank conflicts. A
     // full half-tile therefore takes rows s, s+16, s+32, s+48: 16 rows apart is
     // 928 = 32 (mod 64) dwords, disjoint banks. (A partial one keeps the
-    // consecutive rows: it stops after ceil(nrows/4) steps.) Measured: the
+    // consecutive rows: it stops after ceil(nrows/4) steps.) Measured then: the
     // conflict cycles halve (the rest are the tile writes and the copy-out
-    // reads); the kernel's time does not move - the LDS is not what it waits for
+    // reads); the kernel's time does not move - the LDS was not what it waited
+    // for. Since the Gram takes 8 reads a k-step it is: the packings' operands
+    // (problem.hpp) and the tile's rows by lane (ROWL) are chosen for the banks.
+    // These are LOGICAL rows: board_gram_row() says which tile rows hold them
     unsigned gram_a[NREAD];
     if(FULL)
     {
 #pragma unroll
         for(int q=0;q<NREAD;q++) gram_a[q] = gram_full[q];
     }
-    else gram_partial_addresses<KS>(gram_a, gram_full);
+    else gram_partial_addresses<KS,ROWL>(gram_a, gram_full);
     GramRd<NREAD> cur;
 #pragma unroll
     for(int q=0;q<NREAD;q++) cur.v[q] = lds_read_b64_at<0>(gram_a[q]);
-    fused_steps<FULL,STORE,NBLK,K,KS>(acc, cur, gram_a, tile_a0, out, A0, A1, B0, B1, gofs, rsub, nrows,
+    fused_steps<FULL,STORE,ROWL,NBLK,K,KS>(acc, cur, gram_a, tile_a0, out, A0, A1, B0, B1, gofs, rsub, nrows,
                                 std::make_integer_sequence<int, 16>{});
 }
 
@@ -729,7 +747,8 @@ void gram_copy_fused(double (&acc)[NM], const double* __restrict__ tile, const u
 // The copy-out invariants of a lane (copy_out_full) when every variable group
 // is optimized: k and the CSR -> tile column map are compile-time constants
 // (divisions by constants, selects on constants)
-template<int K, int NDIST, int KS, bool HAS_EXT>
+// ROWL: the rows are where board_tile_row() puts them, row r of a block of 32 in tile row r + 31 (r%2) (fused_step())
+template<int K, int NDIST, int KS, bool HAS_EXT, bool ROWL>
 __device__ __forceinline__
 void copy_out_invariants(int lane, int& A0, int& A1, int& B0, int& B1, unsigned& gofs, int& rsub)
 {
@@ -748,10 +767,11 @@ void copy_out_invariants(int lane, int& A0, int& A1, int& B0, int& B1, unsigned&
         return col;
     };
     const int y0 = rsub & 1, y1 = (rsub + RPI) & 1;
-    A0 = (rsub*KS       + tcol(c0,   y0))*(int)sizeof(double);
-    A1 = (rsub*KS       + tcol(c0+1, y0))*(int)sizeof(double);
-    B0 = ((rsub+RPI)*KS + tcol(c0,   y1))*(int)sizeof(double);
-    B1 = ((rsub+RPI)*KS + tcol(c0+1, y1))*(int)sizeof(double);
+    const int ra = rsub + (ROWL ? 31*y0 : 0), rb = rsub + RPI + (ROWL ? 31*y1 : 0);
+    A0 = (ra*KS + tcol(c0,   y0))*(int)sizeof(double);
+    A1 = (ra*KS + tcol(c0+1, y0))*(int)sizeof(double);
+    B0 = (rb*KS + tcol(c0,   y1))*(int)sizeof(double);
+    B1 = (rb*KS + tcol(c0+1, y1))*(int)sizeof(double);
     gofs = (unsigned)(rsub*K + c0);
 }
 
@@ -782,6 +802,10 @@ void board_observation(const DeviceProblem& P,
     constexpr int KS     = NCOLS4 | 1;          // odd LDS row stride
     constexpr int NM     = gram_nmfma_blk(NBLK); // accumulators (problem.hpp)
     static_assert(NBLK <= 8, "the Gram scheme covers 32 tile columns");
+    // The tile's rows (problem.hpp, board_tile_row()): with everything optimized a lane writes tile row `lane` and
+    // computes the corner that makes it the right one, board_lane_corner(); the general kernels keep the rows in
+    // order, lane = corner
+    constexpr bool ROWL = ALLOPT;
 
     const int lane = threadIdx.x;
 #ifdef BOARD_TS
@@ -852,7 +876,8 @@ void board_observation(const DeviceProblem& P,
     // Gram operands (problem.hpp): at k-step s this lane reads
     // tile[its row of the step][gram_read_col(iread, lane)] for each of the NREAD operands
     constexpr int NREAD = gram_nreads(NBLK);
-    const unsigned gram_base   = (unsigned)(size_t)tile + (unsigned)(((lane >> 4)*16*KS + (lane & 3))*sizeof(double));
+    const int      gram_row0   = board_gram_row(ROWL, true, 0, lane >> 4);      // its row of a full half's k-step 0
+    const unsigned gram_base   = (unsigned)(size_t)tile + (unsigned)((gram_row0*KS + (lane & 3))*sizeof(double));
     unsigned       gram_blocks = gram_slot_blocks<NBLK>((lane >> 2) & 3, std::make_integer_sequence<int, NREAD>{});
     double acc[NM];
 #pragma unroll
@@ -887,8 +912,8 @@ void board_observation(const DeviceProblem& P,
     int co_rsub_c = 0;
     if(ALLOPT)
     {
-        if(has_ext) copy_out_invariants<KFULL,   NDIST, KS, true >(lane, co_A0, co_A1, co_B0, co_B1, co_gofs, co_rsub_c);
-        else        copy_out_invariants<KFULL-6, NDIST, KS, false>(lane, co_A0, co_A1, co_B0, co_B1, co_gofs, co_rsub_c);
+        if(has_ext) copy_out_invariants<KFULL,   NDIST, KS, true,  ROWL>(lane, co_A0, co_A1, co_B0, co_B1, co_gofs, co_rsub_c);
+        else        copy_out_invariants<KFULL-6, NDIST, KS, false, ROWL>(lane, co_A0, co_A1, co_B0, co_B1, co_gofs, co_rsub_c);
     }
     else if(co_fast)
     {
@@ -923,7 +948,7 @@ void board_observation(const DeviceProblem& P,
 #endif
     for(int pt0 = 0; pt0 < NPTS; pt0 += 64)
     {
-        const int  pt    = pt0 + lane;
+        const int  pt    = pt0 + (ROWL ? board_lane_corner(lane) : lane);
         const bool valid = pt < NPTS;
 
         // both rows of this corner, at the fixed tile columns
@@ -1083,11 +1108,13 @@ void board_observation(const DeviceProblem& P,
         // corners (lanes 0..31) and the x rows of the last 32 (lanes 32..63) trade places: v_permlane32_swap
         // (gfx950) exchanges the upper half of one register with the lower half of another, two per double.
         // After it slot 0 of a lane holds its row of the first half, slot 1 its row of the second.
-        // (A 16-lane group now writes every second tile row, two lanes to a bank: SQ_LDS_BANK_CONFLICT went up by 220
-        //  per observation while the instructions halved. The conflict-free variant - lanes 0..7 of each 16-lane row
-        //  on the first half's corners, lanes 8..15 on the second's, a DPP rotation by 8 and two selects per value,
-        //  16 consecutive rows per group - was built: same bits, 74.8 us against 73.5. It is the instruction count
-        //  on the VGPR->LDS path that matters, not the conflicts)
+        // WHERE a lane writes its row (problem.hpp, board_tile_row()). The rows in order - lane l to row
+        // 2 (l % 32) + l / 32, the general kernels - make a 16-lane group write every second tile row, two lanes to a
+        // bank: 448 conflict cycles per 10x10 observation, more than half of the kernel's. (A conflict-free variant of
+        // THAT order - a DPP rotation by 8 and two selects per value - was built in round 6 and lost, 74.8 us against
+        // 73.5: instructions on the VGPR->LDS path.) With everything optimized a lane writes row l and computes the
+        // corner that belongs there (board_lane_corner()): no conflict, no instruction added; the Gram and the
+        // copy-out read the rows where that puts them (fused_step()). LEDGER, "the tile's rows by lane"
 #pragma unroll
         for(int c=0;c<NCOLS4;c++) permlane32_swap_f64(row[0][c], row[1][c]);
         for(int h = 0; h < 2; h++)
@@ -1107,7 +1134,9 @@ void board_observation(const DeviceProblem& P,
             // WAR: the previous half's tile reads are complete (in-order LDS)
             __builtin_amdgcn_wave_barrier();
             {
-                double* __restrict__ t0 = tile + (size_t)(2*(lane & 31) + (lane >> 5))*KS;
+                // (ablation bit 32, measurement builds: the rows-in-order kernels write row `lane` too - no two lanes
+                //  of a 16-lane group to a bank - and every result is wrong: what the write conflicts cost, LEDGER)
+                double* __restrict__ t0 = tile + (size_t)(ROWL || ABLATE(P, 32) ? lane : 2*(lane & 31) + (lane >> 5))*KS;
                 // h is wave-uniform: a scalar branch around two copies of the stores, each reading its own slot's
                 // registers. (Left to itself the compiler merges the two arms into ONE set of stores behind 2*NCOLS4
                 // selects on an all-ones or all-zeros mask, which sit between a pass's arithmetic and the half's first
@@ -1138,13 +1167,13 @@ void board_observation(const DeviceProblem& P,
                 const bool kfull = ALLOPT ? has_ext : (k == KFULL);
                 if(nrows == 64)
                 {
-                    if(kfull) gram_copy_fused<true,STORE_J,NBLK,KFULL,  KS>(acc, tile, gram_full, out, co_A0, co_A1, co_B0, co_B1, co_gofs, rs, 64);
-                    else      gram_copy_fused<true,STORE_J,NBLK,KFULL-6,KS>(acc, tile, gram_full, out, co_A0, co_A1, co_B0, co_B1, co_gofs, rs, 64);
+                    if(kfull) gram_copy_fused<true,STORE_J,ROWL,NBLK,KFULL,  KS>(acc, tile, gram_full, out, co_A0, co_A1, co_B0, co_B1, co_gofs, rs, 64);
+                    else      gram_copy_fused<true,STORE_J,ROWL,NBLK,KFULL-6,KS>(acc, tile, gram_full, out, co_A0, co_A1, co_B0, co_B1, co_gofs, rs, 64);
                 }
                 else
                 {
-                    if(kfull) gram_copy_fused<false,STORE_J,NBLK,KFULL,  KS>(acc, tile, gram_full, out, co_A0, co_A1, co_B0, co_B1, co_gofs, rs, nrows);
-                    else      gram_copy_fused<false,STORE_J,NBLK,KFULL-6,KS>(acc, tile, gram_full, out, co_A0, co_A1, co_B0, co_B1, co_gofs, rs, nrows);
+                    if(kfull) gram_copy_fused<false,STORE_J,ROWL,NBLK,KFULL,  KS>(acc, tile, gram_full, out, co_A0, co_A1, co_B0, co_B1, co_gofs, rs, nrows);
+                    else      gram_copy_fused<false,STORE_J,ROWL,NBLK,KFULL-6,KS>(acc, tile, gram_full, out, co_A0, co_A1, co_B0, co_B1, co_gofs, rs, nrows);
                 }
                 TSACC(5, tcur);
                 continue;
@@ -1195,7 +1224,7 @@ void board_observation(const DeviceProblem& P,
                 // (the full halves of the usual problems take the fused path above)
                 const int nsteps = (nrows + 3) >> 2;
                 unsigned gram_a[NREAD];
-                gram_partial_addresses<KS>(gram_a, gram_full);
+                gram_partial_addresses<KS,false>(gram_a, gram_full);
                 typedef __attribute__((address_space(3))) const double lds_cdouble;
                 for(int s = 0; s < nsteps; s++)
                 {

@@ -120,7 +120,29 @@ __host__ __device__ inline int tile_xcol  (int ndist) { return 4 + ndist + 14; }
 __host__ __device__ inline int tile_ncols (int ndist) { return 4 + ndist + 15; }
 __host__ __device__ inline int tile_nblk  (int ndist) { return (tile_ncols(ndist) + 3) >> 2; }
 // LDS row stride in doubles: odd (conflict-free per-lane column writes), >= 4 nblk
-__host__ __device__ inline int tile_stride(int ndist) { return (4*tile_nblk(ndist)) | 1; }
+__host__ __device__ inline int tile_stride_blk(int nblk) { return (4*nblk) | 1; }
+__host__ __device__ inline int tile_stride(int ndist) { return tile_stride_blk(tile_nblk(ndist)); }
+// The ROWS of the tile. A pass of the board kernel takes 64 corners, a lane each, and sends their 128 rows through
+// the 64-row tile in two halves of 32 corners; logical row r = 2 c + xy of a half is the x or y row of its corner c.
+// The kernels with everything optimized write one tile row a lane, lanes 0..31 the half's x rows and lanes 32..63
+// its y rows: sixteen lanes, sixteen consecutive rows of odd stride, no two on one LDS bank. Which corner a lane
+// takes is then free, and it is chosen for the Gram: a full k-step s sums the logical rows s, s+16, s+32, s+48 -
+// corners c, c+8, c+16, c+24 - and the two rows that a 32-lane half of the wave reads must lie 16 tile rows
+// (32 banks) apart. In-half lane j takes corner j/2 + 16 (j%2): corner c sits in lane 2c (mod 32) + c/16, the corners
+// 8 apart in lanes 16 apart. The other board kernels keep lane = corner and the rows in order, tile row = r.
+__host__ __device__ constexpr int board_lane_corner(int lane) { return (lane & 32) | ((lane >> 1) & 15) | ((lane & 1) << 4); }
+__host__ __device__ constexpr int board_tile_row(bool row_a_lane, int r)
+{
+    return row_a_lane ? 32*(r & 1) + ((r & ~1) & 31) + (r >> 5) : r;
+}
+// The tile row that lanes 16k..16k+15 read at k-step s of the Gram: a full half sums the logical rows s + 16k in a
+// k-step, a partial one (the last corners of a board) the rows 4s + k. The kernel adds a lane's row of step 0 and
+// the step's row for k = 0: board_gram_row(s, k) = board_gram_row(s, 0) + board_gram_row(0, k) in both layouts
+// (tests/hostcheck/gram_banks_check.cpp)
+__host__ __device__ constexpr int board_gram_row(bool row_a_lane, bool full, int s, int k)
+{
+    return board_tile_row(row_a_lane, full ? s + 16*k : 4*s + k);
+}
 
 // Per-board-observation Gram matrix G = Tt T of the tile, formed with
 // v_mfma_f64_4x4x4f64 (4 independent 4x4 products per instruction, one per
@@ -146,6 +168,13 @@ __host__ __device__ inline int tile_stride(int ndist) { return (4*tile_nblk(ndis
 // blocks every operand is a read, 8 a k-step for 7 blocks (measured: LEDGER,
 // "The Gram in the fewest matrix instructions"). 5 and 8 blocks keep X, Y and
 // rotations.
+// WHICH four blocks share an operand decides its LDS bank conflicts. A 32-lane
+// half of a ds_read_b64 reads two tile rows, 16 rows apart in a full half-tile:
+// 16 odd strides = 32 (mod 64) dwords, and a column block is 8 dwords wide, so
+// block b of the one row and block b+4 of the other share their banks. At 6 and
+// 7 blocks no operand holds a block together with the block four positions on
+// (Z, P and Q at 7 and X2, Z at 6 are chosen for that): every read of a full
+// half is conflict-free. gram_read_extra_cycles() counts it.
 // The accumulators are stored as they are, gram[iobs][m][lane]: lane l of
 // accumulator m holds G[4 bA + l/16][4 bB + l%4], (bA,bB) the pair in slot (l%16)/4.
 enum { GRAM_MAXOP = 10, GRAM_MAXMFMA = 10 };
@@ -194,16 +223,16 @@ __host__ __device__ constexpr GramPacking gram_packing(int nblk)
     {
         gram_add_read(p, 0,1,2,3);                  // 0: X
         gram_add_read(p, 1,2,3,0);                  // 1: X1
-        gram_add_read(p, 4,5,4,5);                  // 2: Y_0
-        gram_add_read(p, 5,4,5,4);                  // 3: Y_1
-        gram_add_read(p, 0,1,4,5);                  // 4: P
-        gram_add_read(p, 2,3,4,5);                  // 5: Q
+        gram_add_read(p, 2,3,0,1);                  // 2: X2
+        gram_add_read(p, 4,5,4,5);                  // 3: Y_0
+        gram_add_read(p, 5,4,5,4);                  // 4: Y_1
+        gram_add_read(p, 4,5,5,4);                  // 5: Z
         gram_add_mfma(p, 0, 0);                     // the diagonal blocks of X
         gram_add_mfma(p, 0, 1);                     // (0,1) (1,2) (2,3) and the mirrored (3,0)
-        gram_add_mfma(p, 0, 2);                     // (0,4) (1,5) (2,4) (3,5)
-        gram_add_mfma(p, 0, 3);                     // (0,5) (1,4) (2,5) (3,4)
-        gram_add_mfma(p, 4, 5);                     // (0,2) (1,3) (4,4) (5,5)
-        gram_add_mfma(p, 2, 3, 0x1);                // (4,5)
+        gram_add_mfma(p, 0, 2, 0x3);                // (0,2) (1,3)
+        gram_add_mfma(p, 0, 3);                     // (0,4) (1,5) (2,4) (3,5)
+        gram_add_mfma(p, 0, 4);                     // (0,5) (1,4) (2,5) (3,4)
+        gram_add_mfma(p, 3, 5, 0x7);                // (4,4) (5,5) (4,5)
     }
     else if(nblk == 7)
     {
@@ -212,16 +241,16 @@ __host__ __device__ constexpr GramPacking gram_packing(int nblk)
         gram_add_read(p, 4,5,6,4);                  // 2, 3, 4: Y_q, slot s holds block 4 + (s+q)%3
         gram_add_read(p, 5,6,4,5);
         gram_add_read(p, 6,4,5,6);
-        gram_add_read(p, 4,6,4,5);                  // 5: Z
-        gram_add_read(p, 0,1,5,6);                  // 6: P
-        gram_add_read(p, 2,3,5,6);                  // 7: Q
+        gram_add_read(p, 4,5,6,5);                  // 5: Z
+        gram_add_read(p, 0,1,6,6);                  // 6: P
+        gram_add_read(p, 2,3,4,5);                  // 7: Q
         gram_add_mfma(p, 0, 0);                     // the diagonal blocks of X
         gram_add_mfma(p, 0, 1);                     // (0,1) (1,2) (2,3) and the mirrored (3,0)
         gram_add_mfma(p, 0, 2);                     // X x Y: (s, 4 + (s+q)%3), q = 0,1,2
         gram_add_mfma(p, 0, 3);
         gram_add_mfma(p, 0, 4);
-        gram_add_mfma(p, 2, 5);                     // (4,4) (5,6) (6,4) (4,5)
-        gram_add_mfma(p, 6, 7);                     // (0,2) (1,3) (5,5) (6,6)
+        gram_add_mfma(p, 2, 5);                     // (4,4) (5,5) (6,6) (4,5)
+        gram_add_mfma(p, 6, 7);                     // (0,2) (1,3) (6,4) (6,5)
     }
     else if(nblk == 8)
     {
@@ -278,6 +307,35 @@ __host__ __device__ inline int gram_read_col(int nblk, int iread, int lane)
 {
     return 4*gram_packing(nblk).op[iread].blk[(lane >> 2) & 3] + (lane & 3);
 }
+// Extra LDS cycles (what SQ_LDS_BANK_CONFLICT counts) of ONE k-step's read of operand `iread`, by the bank rule of
+// ds_read_b64: the two 32-lane halves of the wave are served one after the other; the bank of a dword is its index
+// mod 64; lanes of a half at the same address are one access; a half costs as many cycles as its busiest bank has
+// distinct dwords. The rows are the kernel's (kernels.hip, gram_copy_fused()): lanes 16k..16k+15 read row s + 16k of
+// a full half-tile and row 4s + k of a partial one; s shifts every address alike and changes nothing. Host only
+inline int gram_read_extra_cycles(int nblk, int iread, bool full)
+{
+    const int ks = tile_stride_blk(nblk);
+    int extra = 0;
+    for(int half = 0; half < 2; half++)
+    {
+        int dwords[64][64], n[64] = {0};        // the distinct dwords asked of each bank
+        for(int lane = 32*half; lane < 32*half + 32; lane++)
+        {
+            const int row = (full ? 16 : 1)*(lane >> 4);
+            for(int w = 0; w < 2; w++)
+            {
+                const int dword = 2*(row*ks + gram_read_col(nblk, iread, lane)) + w, bank = dword & 63;
+                bool seen = false;
+                for(int i = 0; i < n[bank]; i++) seen = seen || dwords[bank][i] == dword;
+                if(!seen) dwords[bank][n[bank]++] = dword;
+            }
+        }
+        int busiest = 1;
+        for(int bank = 0; bank < 64; bank++) if(n[bank] > busiest) busiest = n[bank];
+        extra += busiest - 1;
+    }
+    return extra;
+}
 
 struct DeviceProblem
 {
@@ -304,7 +362,8 @@ struct DeviceProblem
 #ifdef MRCAL_AMD_DEV
     // MEASUREMENT BUILDS ONLY (bash csrc/build.sh -DMRCAL_AMD_DEV [-DBOARD_TS ...] -> libmrcal_amd_dev.so; the shipped
     // library has neither field nor any of the code behind them). Ablation knob of tools/probe_board.py: bit0 skip the J
-    // copy-out, bit1 skip the MFMAs, bit2 skip the projection arithmetic, bit4 exit after the start-up loads
+    // copy-out, bit1 skip the MFMAs, bit2 skip the projection arithmetic, bit4 exit after the start-up loads,
+    // bit5 (32) write the tile's rows by lane where the kernel keeps them in order (wrong results, no write conflicts)
     int debug_ablate;
     long long* debug_ts;     // per-observation phase timestamps (-DBOARD_TS)
 #endif
