@@ -1208,6 +1208,75 @@ bool mrcal_amd_speckle_filter_milliseconds(mrcal_amd_speckle_filter_t* f, float*
 bool mrcal_amd_speckle_filter_pass_milliseconds(mrcal_amd_speckle_filter_t* f, float* milliseconds /*4*/);
 void mrcal_amd_speckle_filter_destroy(mrcal_amd_speckle_filter_t* f);
 
+/* ---- stereo_point_cloud: disparities to a compacted, coloured cloud of points ----
+   What the reference's mrcal-stereo --write-point-cloud delivers, from the disparities a matcher left on the device:
+   csrc/point_cloud.hip, planned on the host by csrc/point_cloud_plan.hpp. Only the kept points cross to the host.
+   A pixel (x,y) of the dense (Nel,Naz) disparity image is KEPT when all of these hold:
+     1. Disparity. With d the disparity cast to uint16, as mrcal_stereo_range_dense() takes it: d > 0,
+        d >= disparity_scaled_min, d <= disparity_scaled_max (for an int16 image the maximum defaults to 0x7FFF, so that
+        its negative "invalid" marks stay invalid)
+     2. Range. range = the range mrcal_stereo_range_dense() gives for d/disparity_scale at (x,y), from the same device
+        function, is finite and > 0. A negative LATLON range, which mrcal_stereo_range_dense() returns, is dropped here
+     3. Range limits. range_min <= range <= range_max (0 and infinity: no limits)
+     4. Colour pixel, if a colour image of camera 0 is given. With (mx,my) the float32 rectification map of camera 0 at
+        (x,y): ix = floorf(mx + 0.5f), iy = floorf(my + 0.5f), the additions in float32, are finite and inside the
+        image. The colour is image[iy, ix]: the reference's "nearest pixel of the original image", from the map the
+        rectification holds instead of a projection of every point. Departure: a map entry of -0.5 exactly is inside
+        here (pixel 0) and outside in the reference
+   The point is p_rect0 = range v, v the unit observation vector of the rectified pixel (LATLON: (sin az, cos az sin el,
+   cos az cos el); PINHOLE: (ux, uy, 1)/|.|), and p = R p_rect0 + t with Rt_out_rect0 (4,3) = R, then t, made on the host.
+   Rt_out_rect0 = NULL: p = p_rect0 and no product is made, so that the points carry the bits of
+   mrcal_amd_stereo_range_sparse()'s p. The arithmetic is in double; a point is stored as float64 or, rounded once at
+   the store, as float32 (what a .ply holds).
+   Order: the kept pixels appear in ascending linear index y Naz + x. The outputs: points (N,3); color (N,) or (N,3) of
+   the image's type (uint8 or uint16; 1 or 3 interleaved channels); index (N,) int32, the linear index of each point.
+   Deterministic: validity is decided ONCE, by cloud_mask_kernel, and stored a bit a pixel; an integer scan of the
+   per-workgroup counts gives every workgroup its place; cloud_scatter_kernel reads the bits. No atomics, no workgroup
+   waits for another, the same bits on every call.
+   Refused: an image that is empty or has more than 2^28 pixels or does not fit the free device memory,
+   disparity_scaled_min >= disparity_scaled_max, range_min > range_max or not a number, a colour image that is not
+   uint8 or uint16 with 1 or 3 channels, a colour image without a map.
+   Two calls: _compute() uploads the disparities (host, dense) and the colour image, runs the kernels and returns N;
+   _read() copies the N records into the caller's arrays, any of which may be NULL. The output buffers on the device
+   are kept from call to call and grow when N outgrows them (csrc/point_cloud_plan.hpp: cloud_capacity()).
+   _create(): device_map0: the rectification map of camera 0 ON THE DEVICE, (Nel,Naz,2) float32, aligned to 16 bytes,
+   which must outlive the object; NULL: none (no colours then). _set_map(): a map of the HOST's instead, copied.
+   _stage_milliseconds(): how long the mask, the scan and the scatter of the last _compute() took on the device.
+   mrcal_amd_rectification_point_cloud*(): the same through the object a rectification owns, with its map of camera 0;
+   _of_images() rectifies the pair, matches it (and filters the speckles: "stereo_matching_sgm") and makes the cloud
+   without the rectified images or the disparities leaving the device. There the disparity fields of the parameters
+   are the matcher's and are not read: scale 16, minimum 16 disparity_min, maximum 0x7FFF; a negative disparity_min is
+   refused, as the cast to uint16 has no meaning for negative disparities */
+typedef struct mrcal_amd_point_cloud mrcal_amd_point_cloud_t;
+typedef struct
+{
+    uint16_t      disparity_scale, disparity_scaled_min, disparity_scaled_max;
+    double        range_min, range_max;         /* 0 and INFINITY: no limits */
+    const double* Rt_out_rect0;                 /* (4,3) or NULL */
+    int           points_float32;               /* the points are stored as float32, not float64 */
+    const void*   image;                        /* the colour image of camera 0, dense, on the host; NULL: no colours */
+    int           image_width, image_height, image_channels, image_dtype;      /* MRCAL_AMD_IMAGE_UINT8 or _UINT16 */
+} mrcal_amd_point_cloud_params_t;
+mrcal_amd_point_cloud_t*
+mrcal_amd_point_cloud_create(const mrcal_lensmodel_type_t rectification_model_type, const double* fxycxy_rectified,
+                             double baseline, int width, int height, const float* device_map0);
+bool mrcal_amd_point_cloud_set_map(mrcal_amd_point_cloud_t* c, const float* map0);
+bool mrcal_amd_point_cloud_compute(mrcal_amd_point_cloud_t* c, const uint16_t* disparity_scaled,
+                                   const mrcal_amd_point_cloud_params_t* params, int* N);
+bool mrcal_amd_point_cloud_read(mrcal_amd_point_cloud_t* c, void* points, void* color, int32_t* index);
+bool mrcal_amd_point_cloud_stage_milliseconds(mrcal_amd_point_cloud_t* c, float* milliseconds /*3*/);
+void mrcal_amd_point_cloud_destroy(mrcal_amd_point_cloud_t* c);
+bool mrcal_amd_rectification_point_cloud(mrcal_amd_rectification_t* r, const uint16_t* disparity_scaled,
+                                         const mrcal_amd_point_cloud_params_t* params, int* N);
+bool mrcal_amd_rectification_point_cloud_of_images(mrcal_amd_rectification_t* r,
+                                                   const void* image0, int width0, int height0,
+                                                   const void* image1, int width1, int height1, int dtype,
+                                                   const mrcal_amd_stereo_sgm_params_t* sgm_params,
+                                                   int speckle_window_size, int speckle_range,
+                                                   const mrcal_amd_point_cloud_params_t* params, int* N);
+bool mrcal_amd_rectification_point_cloud_read(mrcal_amd_rectification_t* r, void* points, void* color, int32_t* index);
+bool mrcal_amd_rectification_point_cloud_stage_milliseconds(mrcal_amd_rectification_t* r, float* milliseconds /*3*/);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,10 +80,10 @@ from .stereo import (rectified_resolution, rectified_system, rectification_maps,
                      Rectification, apply_homography, match_feature, FeatureMatcher,
                      TM_SQDIFF, TM_SQDIFF_NORMED, TM_CCORR, TM_CCORR_NORMED, TM_CCOEFF, TM_CCOEFF_NORMED,
                      stereo_matching_sgm, StereoMatcherSGM, STEREO_SGM_DISPARITY_SCALE,
-                     filter_speckles, SpeckleFilter)
+                     filter_speckles, SpeckleFilter, stereo_point_cloud, StereoPointCloud)
 from .image_transforms import (scale_focal__best_pinhole_fit, pinhole_model_for_reprojection, image_transformation_map,
                                transform_image)
-from .utils import sample_imager, sample_imager_unproject
+from .utils import sample_imager, sample_imager_unproject, write_point_cloud_as_ply
 
 # the callers either side of the path: the on-disk format of
 # a calibration, host-side pose arithmetic, the seeding. As in the reference, the class

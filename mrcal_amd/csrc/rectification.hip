@@ -31,6 +31,8 @@
 #include "remap.hpp"
 #include "stereo_sgm.hpp"
 #include "speckle_plan.hpp"
+#include "stereo_range_device.hpp"
+#include "point_cloud.hpp"
 
 namespace mrcal_amd {
 
@@ -467,27 +469,7 @@ bool remap_host_image(void* out, const void* image, int W, int H, int C, int dty
 ////////////////////////////////////////////////////////////////////////////////
 // 3. the ranges (stereo.c:1263-1417; the derivation: the docstring of mrcal.stereo_range())
 ////////////////////////////////////////////////////////////////////////////////
-struct RangeArgs { double fx, fy, cx, cy, baseline; int latlon; };
-
-// The range of the point seen at (qx, qy) in the rectified camera 0 and `disparity` pixels to the left of that in
-// camera 1; 0 if that is not finite.
-//   LATLON:  the two rays leave the ends of the baseline at the azimuths az0 and az1 = az0 - disparity/fx, measured from
-//            its normal. In the triangle they make with the baseline the angle at the point is the parallax az0 - az1
-//            and the angle at camera 1 is pi/2 + az1: by the law of sines range = baseline cos(az1)/sin(parallax)
-//   PINHOLE: the depth along the rectified axis is z = baseline fx/disparity, and the point is z (tan az0, tan el, 1)
-__device__ __forceinline__
-double stereo_range_one(double disparity, double qx, double qy, const RangeArgs& a)
-{
-    const double ux = (qx - a.cx)/a.fx, parallax = disparity/a.fx;
-    double range;
-    if(a.latlon) range = a.baseline*cos(ux - parallax)/sin(parallax);
-    else
-    {
-        const double uy = (qy - a.cy)/a.fy;
-        range = a.baseline/parallax*sqrt(ux*ux + uy*uy + 1.);
-    }
-    return isfinite(range) ? range : 0.0;
-}
+// RangeArgs, stereo_range_one() and stereo_unit_vector(): stereo_range_device.hpp, shared with point_cloud.hip
 
 __global__ __launch_bounds__(256)
 void stereo_range_dense_kernel(RangeArgs a, int N, int W, const uint16_t* __restrict__ disparity_scaled,
@@ -514,20 +496,8 @@ void stereo_range_sparse_kernel(RangeArgs a, int N, const double* __restrict__ d
     if(range != NULL) range[i] = r;
     if(p != NULL)
     {
-        const double ux = (qx - a.cx)/a.fx, uy = (qy - a.cy)/a.fy;
         double v[3];
-        if(a.latlon)
-        {
-            double sx, cx, sy, cy;
-            sincos(ux, &sx, &cx);
-            sincos(uy, &sy, &cy);
-            v[0] = sx; v[1] = cx*sy; v[2] = cx*cy;
-        }
-        else
-        {
-            const double s = 1.0/sqrt(ux*ux + uy*uy + 1.0);
-            v[0] = ux*s; v[1] = uy*s; v[2] = s;
-        }
+        stereo_unit_vector(v, qx, qy, a);
         for(int k=0;k<3;k++) p[3*(size_t)i + k] = r*v[k];
     }
 }
@@ -581,7 +551,19 @@ struct mrcal_amd_rectification
     float*        map[2] = { NULL, NULL };     // each its own allocation: [Nel][Naz][2]
     int           W = 0, H = 0;
     RangeArgs     range_args;
+    // point_cloud.hip's object, made by the first cloud: it reads map[0] where it lies
+    mrcal_amd_point_cloud_t* cloud = NULL;
+    mrcal_lensmodel_type_t   rectification_model_type = MRCAL_LENSMODEL_LATLON;
+    double                   fxycxy[4] = { 0., 0., 0., 0. };
+    ~mrcal_amd_rectification() { mrcal_amd_point_cloud_destroy(cloud); }
 };
+
+static mrcal_amd_point_cloud_t* rectification_cloud(mrcal_amd_rectification* r)
+{
+    if(r->cloud == NULL)
+        r->cloud = mrcal_amd_point_cloud_create(r->rectification_model_type, r->fxycxy, r->range_args.baseline, r->W, r->H, r->map[0]);
+    return r->cloud;
+}
 
 static bool rectification_given(const mrcal_amd_rectification* r)
 {
@@ -628,6 +610,8 @@ mrcal_amd_rectification_create(const mrcal_lensmodel_t* lensmodel0, const double
     mrcal_amd_rectification* r = new mrcal_amd_rectification;
     r->W = W; r->H = H;
     range_arguments(&r->range_args, rectification_model_type, fxycxy_rectified, baseline);
+    r->rectification_model_type = rectification_model_type;
+    for(int i=0;i<4;i++) r->fxycxy[i] = fxycxy_rectified[i];
     mrcal_lensmodel_t rectified; memset(&rectified, 0, sizeof(rectified));
     rectified.type = rectification_model_type;
     const mrcal_lensmodel_t* lensmodels[2] = { lensmodel0, lensmodel1 };
@@ -728,6 +712,88 @@ bool mrcal_amd_rectification_disparity_filtered(mrcal_amd_rectification_t* r,
     // (destroy clears nothing: the error of a failure stays)
     mrcal_amd_stereo_sgm_destroy(m);
     return ok;
+}
+
+// ---- the point cloud (point_cloud.hip) through the rectification's map of camera 0
+bool mrcal_amd_rectification_point_cloud(mrcal_amd_rectification_t* r, const uint16_t* disparity_scaled,
+                                         const mrcal_amd_point_cloud_params_t* params, int* N)
+{
+    last_error_string().clear();
+    if(!rectification_given(r) || !have_device()) return false;
+    mrcal_amd_point_cloud_t* c = rectification_cloud(r);
+    return c != NULL && mrcal_amd_point_cloud_compute(c, disparity_scaled, params, N);
+}
+
+// image pair -> cloud: rectified into the matcher's buffers, matched (and filtered) there, and the cloud made of the
+// disparities where the matcher left them
+bool mrcal_amd_rectification_point_cloud_of_images(mrcal_amd_rectification_t* r,
+                                                   const void* image0, int width0, int height0,
+                                                   const void* image1, int width1, int height1, int dtype,
+                                                   const mrcal_amd_stereo_sgm_params_t* sgm_params,
+                                                   int speckle_window_size, int speckle_range,
+                                                   const mrcal_amd_point_cloud_params_t* params, int* N)
+{
+    last_error_string().clear();
+    if(sgm_params == NULL || params == NULL || N == NULL) { set_error("stereo_point_cloud(): an argument is NULL"); return false; }
+    if(sgm_params->disparity_min < 0)
+    {
+        set_error("stereo_point_cloud(): disparity_min must not be negative: the cast to uint16 of stereo_range() has no meaning for negative disparities. Got %d",
+                  sgm_params->disparity_min);
+        return false;
+    }
+    {
+        SpeckleParams p; std::string why;
+        if(!speckle_params_of_matcher(&p, &why, 0, 1, speckle_window_size, speckle_range)) { set_error("%s", why.c_str()); return false; }
+    }
+    if(!rectification_given(r) || !have_device()) return false;
+    if(!remap_arguments_ok(width0, height0, 1, dtype, r->W, r->H, MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT) ||
+       !remap_arguments_ok(width1, height1, 1, dtype, r->W, r->H, MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT))
+        return false;
+    mrcal_amd_point_cloud_t* c = rectification_cloud(r);
+    if(c == NULL) return false;
+    mrcal_amd_stereo_sgm_t* m = mrcal_amd_stereo_sgm_create(r->W, r->H, dtype, sgm_params);
+    if(m == NULL) return false;
+    if(!mrcal_amd_stereo_sgm_set_speckle_filter(m, speckle_window_size, speckle_range)) { mrcal_amd_stereo_sgm_destroy(m); return false; }
+    // the disparities are the matcher's: its scale, and everything from its smallest disparity up is valid
+    mrcal_amd_point_cloud_params_t p = *params;
+    p.disparity_scale      = 16;
+    p.disparity_scaled_min = (uint16_t)(16*sgm_params->disparity_min);
+    p.disparity_scaled_max = 0x7FFF;
+    const void* image[2] = { image0, image1 };
+    const int   W[2] = { width0, width1 }, H[2] = { height0, height1 };
+    bool ok = true;
+    {
+        DeviceBuffers tmp;
+        for(int i = 0; i < 2 && ok; i++)
+        {
+            uint8_t* d_src = NULL;
+            ok = tmp.upload(&d_src, (const uint8_t*)image[i], (size_t)W[i]*H[i]*dtype_size(dtype)) &&
+                 remap_device(d_src, W[i], H[i], 1, dtype, r->map[i], sgm_device_image(m, i), r->W*r->H,
+                              MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT, NULL);
+        }
+        const int16_t* d_disparity = NULL;
+        // (the cloud waits for its launches, and so for these: the images and the matcher may go when this returns)
+        ok = ok && sgm_match_device_resident(m, &d_disparity) && point_cloud_compute_device(c, (const uint16_t*)d_disparity, &p, N);
+        if(!ok) (void)hipDeviceSynchronize();
+    }
+    mrcal_amd_stereo_sgm_destroy(m);
+    return ok;
+}
+
+bool mrcal_amd_rectification_point_cloud_read(mrcal_amd_rectification_t* r, void* points, void* color, int32_t* index)
+{
+    last_error_string().clear();
+    if(!rectification_given(r)) return false;
+    if(r->cloud == NULL) { set_error("stereo_point_cloud(): no cloud has been computed yet"); return false; }
+    return mrcal_amd_point_cloud_read(r->cloud, points, color, index);
+}
+
+bool mrcal_amd_rectification_point_cloud_stage_milliseconds(mrcal_amd_rectification_t* r, float* milliseconds)
+{
+    last_error_string().clear();
+    if(!rectification_given(r)) return false;
+    if(r->cloud == NULL) { set_error("stereo_point_cloud(): no cloud has been computed yet"); return false; }
+    return mrcal_amd_point_cloud_stage_milliseconds(r->cloud, milliseconds);
 }
 
 void mrcal_amd_rectification_destroy(mrcal_amd_rectification_t* r) { delete r; }

@@ -505,6 +505,44 @@ bool sgm_match_device(mrcal_amd_stereo_sgm* m, int16_t* disparity)
     return true;
 }
 
+// sgm_match_device() without the copy to the host, launch for launch: that function and its path stay as they were
+bool sgm_match_device_resident(mrcal_amd_stereo_sgm* m, const int16_t** d_disparity_out)
+{
+    const SgmPlan& plan = m->plan;
+    SgmArgs a;
+    a.W = plan.W; a.H = plan.H; a.D = plan.D; a.dmin = m->params.disparity_min; a.P1 = m->params.P1; a.P2 = m->params.P2;
+    uint64_t* census[2] = { (uint64_t*)(m->pool + plan.census[0]), (uint64_t*)(m->pool + plan.census[1]) };
+    uint16_t* S           = (uint16_t*)(m->pool + plan.S);
+    uint8_t*  index_left  = m->pool + plan.index_left;
+    uint8_t*  index_right = m->pool + plan.index_right;
+    int16_t*  d_disparity = (int16_t*)(m->pool + plan.disparity);
+    m->timed = false;           // (no event is recorded: the stages of this path are not reported)
+
+    const dim3 census_grid(plan.census_grid[0], plan.census_grid[1]), census_block(SGM_CENSUS_TILE_X, 4);
+    for(int i = 0; i < 2; i++)
+    {
+        if(plan.dtype == MRCAL_AMD_IMAGE_UINT8)
+            hipLaunchKernelGGL(sgm_census_kernel<uint8_t>,  census_grid, census_block, 0, NULL, plan.W, plan.H, (const uint8_t*)(m->pool + plan.image[i]),  census[i]);
+        else
+            hipLaunchKernelGGL(sgm_census_kernel<uint16_t>, census_grid, census_block, 0, NULL, plan.W, plan.H, (const uint16_t*)(m->pool + plan.image[i]), census[i]);
+    }
+    for(int r = 0; r < m->params.paths; r++)
+    {
+#define SGM_CALL(NPL) sgm_launch_path<NPL>(plan, a, SGM_DIRECTIONS[r][0], SGM_DIRECTIONS[r][1], r == 0, census[0], census[1], S)
+        SGM_PER_LANE(plan.per_lane, SGM_CALL)
+#undef SGM_CALL
+    }
+#define SGM_CALL(NPL) sgm_launch_select<NPL>(plan, a, m->params.uniqueness_ratio, S, index_left, index_right, d_disparity)
+    SGM_PER_LANE(plan.per_lane, SGM_CALL)
+#undef SGM_CALL
+    hipLaunchKernelGGL(sgm_check_kernel, dim3(plan.check_grid), dim3(SGM_CHECK_THREADS), 0, NULL,
+                       a, m->params.disp12_max_diff, index_left, index_right, d_disparity);
+    HIP_TRY(hipGetLastError(), return false);
+    if(m->speckle_on && !speckle_filter_device(m->speckle_grids, m->speckle, d_disparity, S)) return false;
+    *d_disparity_out = d_disparity;
+    return true;
+}
+
 } // namespace mrcal_amd
 
 extern "C" {

@@ -11,5 +11,9 @@ namespace mrcal_amd {
 void* sgm_device_image(mrcal_amd_stereo_sgm* m, int i);
 // matches the two images that lie there; disparity (H,W) on the host
 bool sgm_match_device(mrcal_amd_stereo_sgm* m, int16_t* disparity);
+// ... and leaves the disparities where they are: *d_disparity is the (H,W) int16 image on the device, aligned to 256
+// bytes, complete once the work this queued in the NULL stream is. It is the matcher's: gone with it, and overwritten
+// by its next match
+bool sgm_match_device_resident(mrcal_amd_stereo_sgm* m, const int16_t** d_disparity);
 
 } // namespace mrcal_amd

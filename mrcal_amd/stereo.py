@@ -22,6 +22,13 @@
     # ... or on a disparity image from anywhere
     disparity = mrcal_amd.filter_speckles(disparity, new_value = -16, max_speckle_size = 200, max_diff = 32)
 
+    # the points themselves, compacted and coloured from camera 0: only the valid ones cross to the host
+    points, color, index = mrcal_amd.stereo_point_cloud(disparity, models_rectified, models = models, image0 = image0,
+                                                        disparity_scale = 16, dtype = np.float32)
+    mrcal_amd.write_point_cloud_as_ply("points.ply", points, color = color)
+    with mrcal_amd.Rectification(models, models_rectified) as r:       # ... from the image pair, everything in between on the device
+        points, color, index = r.point_cloud_of_images(image0, image1, disparity_max = 128, dtype = np.float32)
+
     q1, diagnostics = mrcal_amd.match_feature(image0, image1, q0, H10 = H10, search_radius1 = 200, template_size1 = 41)
 
     with mrcal_amd.FeatureMatcher(image0, image1) as matcher:          # both images are uploaded once
@@ -31,7 +38,8 @@ The names, keyword arguments, defaults, return shapes and exception messages are
 mrcal/stereo.py. rectified_system() and rectified_resolution() are host code (csrc/stereo_geometry.cpp) and need no
 GPU; the maps, the remap and the ranges are kernels (csrc/rectification.hip), the template matching of match_feature()
 is csrc/match_feature.hip, the dense matching of stereo_matching_sgm() is csrc/stereo_sgm.hip, the connected-component
-labelling of filter_speckles() is csrc/speckle_filter.hip, and there is no CPU fallback for them.
+labelling of filter_speckles() is csrc/speckle_filter.hip, the compaction of stereo_point_cloud() is
+csrc/point_cloud.hip, and there is no CPU fallback for them.
 Out of scope: image file I/O, cv2.StereoSGBM's and libelas's own pixel-for-pixel output, visualization, LONLAT rectification (which the reference's
 rectified_system() refuses too).
 """
@@ -212,7 +220,11 @@ class Rectification:
       .maps()                          rectification_maps(): float32 (2, Nel, Naz, 2), the same bits
       .rectify(image0, image1)         the two rectified images; the maps do not cross to the host and back
       .disparity(image0, image1, ...)  stereo_matching_sgm() of the rectified images, which stay on the device
-      .range(disparity, ...)           stereo_range() of a dense (Nel, Naz) disparity"""
+      .range(disparity, ...)           stereo_range() of a dense (Nel, Naz) disparity
+      .point_cloud(disparity, ...)     stereo_point_cloud() of it: the kept points, their colours and pixel indices
+      .point_cloud_of_images(image0, image1, ...)   the same from the image pair; the rectified images and the
+                                       disparities stay on the device
+      .point_cloud_stage_milliseconds()  how long the mask, the scan and the scatter of the last cloud took"""
 
     def __init__(self, models, models_rectified):
         self.handle = None
@@ -221,7 +233,7 @@ class Rectification:
             raise Exception("I need exactly 2 camera models")
         lib, api = _libs()
         self._L, self._api = lib.lib, api
-        self._models_rectified = tuple(models_rectified)
+        self._models, self._models_rectified = tuple(models), tuple(models_rectified)
         self.Naz, self.Nel = (int(x) for x in models_rectified[0].imagersize())
         args, keep = [], []
         for m in models:
@@ -315,6 +327,61 @@ class Rectification:
         if not ok:
             raise Exception("stereo_matching_sgm() failed:" + self._api._last_error())
         return out
+
+    def point_cloud(self, disparity, *, image0=None, disparity_scale=1, disparity_min=None, disparity_max=None,
+                        disparity_scaled_min=None, disparity_scaled_max=None, range_min=None, range_max=None,
+                        frame='ref', dtype=np.float64):
+        """stereo_point_cloud(disparity, models_rectified, models = models, ...) of a dense (Nel, Naz) disparity on the host:
+        (points, color, index), the same bits. The map of camera 0 is the one that lies on the device"""
+        self._open()
+        image = _cloud_image(image0, "image0", self._models)
+        d, scale, dmin, dmax = _cloud_disparity(disparity, (self.Nel, self.Naz), disparity_scale, disparity_min, disparity_max,
+                                                disparity_scaled_min, disparity_scaled_max)
+        rmin, rmax, Rt, float32 = _cloud_frame(self._models_rectified, self._models, range_min, range_max, frame, dtype)
+        p, keep = _cloud_params(scale, dmin, dmax, rmin, rmax, Rt, float32, image)
+        N = C.c_int(0)
+        f = self._L.mrcal_amd_rectification_point_cloud
+        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*4
+        if not f(self.handle, _ptr(d), C.addressof(p), C.addressof(N)):
+            raise Exception("stereo_point_cloud() failed:" + self._api._last_error())
+        return _cloud_read(self._L.mrcal_amd_rectification_point_cloud_read, self.handle, self._api, N.value, float32, image)
+
+    def point_cloud_of_images(self, image0, image1, *, color_image=None, frame='ref', dtype=np.float64,
+                                  range_min=None, range_max=None, speckle_window_size=0, speckle_range=0, **sgm_params):
+        """point_cloud(disparity(image0, image1, ...), image0 = color_image or image0, disparity_scale = 16,
+        disparity_min = disparity_min, ...), the same bits: (points, color, index). The pair is rectified, matched, on
+        request filtered, and made a cloud of on the device: neither the rectified images nor the disparities cross to the
+        host. image0, image1: grayscale, uint8 or uint16. color_image: the image of camera 0 the colours come from, gray or
+        BGR, of its imager size; None: image0. A negative disparity_min is refused: stereo_range()'s cast to uint16 has no
+        meaning for negative disparities"""
+        self._open()
+        speckle = _speckle_keywords(speckle_window_size, speckle_range)
+        p_sgm = _sgm_params(**sgm_params)
+        if p_sgm.disparity_min < 0:
+            raise Exception(f"stereo_point_cloud(): disparity_min must not be negative: the cast to uint16 of stereo_range() has no meaning for negative disparities. Got {p_sgm.disparity_min}")
+        for image in (image0, image1):
+            if not isinstance(image, np.ndarray) or image.ndim != 2 or image.size == 0:
+                raise Exception("stereo_matching_sgm() accepts ONLY grayscale images of shape (H,W)")
+        if image0.dtype != image1.dtype:
+            raise Exception(f"stereo_matching_sgm(): image0 and image1 must have the same dtype, got {image0.dtype} and {image1.dtype}")
+        sgm_dtype = _SGM_DTYPES[_sgm_dtype(image0.dtype)]
+        image = _cloud_image(image0 if color_image is None else color_image, "image0" if color_image is None else "color_image", self._models)
+        rmin, rmax, Rt, float32 = _cloud_frame(self._models_rectified, self._models, range_min, range_max, frame, dtype)
+        p, keep = _cloud_params(0, 0, 0, rmin, rmax, Rt, float32, image)       # (the disparity fields: the library's, from the matcher's)
+        a0, a1 = np.ascontiguousarray(image0), np.ascontiguousarray(image1)
+        N = C.c_int(0)
+        f = self._L.mrcal_amd_rectification_point_cloud_of_images
+        f.restype  = C.c_bool
+        f.argtypes = [C.c_void_p]*2 + [C.c_int]*2 + [C.c_void_p] + [C.c_int]*3 + [C.c_void_p] + [C.c_int]*2 + [C.c_void_p]*2
+        if not f(self.handle, _ptr(a0), a0.shape[1], a0.shape[0], _ptr(a1), a1.shape[1], a1.shape[0], sgm_dtype, C.addressof(p_sgm),
+                 *speckle, C.addressof(p), C.addressof(N)):
+            raise Exception("stereo_point_cloud() failed:" + self._api._last_error())
+        return _cloud_read(self._L.mrcal_amd_rectification_point_cloud_read, self.handle, self._api, N.value, float32, image)
+
+    def point_cloud_stage_milliseconds(self):
+        """how long the mask, the scan and the scatter of the last cloud took on the device"""
+        self._open()
+        return _cloud_stage_milliseconds(self._L.mrcal_amd_rectification_point_cloud_stage_milliseconds, self.handle, self._api)
 
     def _range_dense(self, disparity_scaled, disparity_scale, dmin, dmax):
         d = np.ascontiguousarray(disparity_scaled, dtype=np.uint16)
@@ -1047,3 +1114,241 @@ the device. The N = 1 case of SpeckleFilter.filter()."""
     _speckle_out(out, disparity.shape)
     with SpeckleFilter(disparity.shape) as f:
         return f.filter(disparity, new_value=new_value, max_speckle_size=max_speckle_size, max_diff=max_diff, out=out)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# stereo_point_cloud(): disparities to a compacted, coloured cloud of points (csrc/point_cloud.hip)
+
+_CLOUD_MAX_PIXELS = 1 << 28
+_CLOUD_FRAMES = ('ref', 'cam0', 'rect0')
+_CLOUD_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1}
+
+
+class _CloudParams(C.Structure):
+    """mrcal_amd_point_cloud_params_t"""
+    _fields_ = [("disparity_scale", C.c_uint16), ("disparity_scaled_min", C.c_uint16), ("disparity_scaled_max", C.c_uint16),
+                ("range_min", C.c_double), ("range_max", C.c_double), ("Rt_out_rect0", C.c_void_p), ("points_float32", C.c_int),
+                ("image", C.c_void_p), ("image_width", C.c_int), ("image_height", C.c_int), ("image_channels", C.c_int),
+                ("image_dtype", C.c_int)]
+
+
+def _cloud_disparity(disparity, shape, disparity_scale, disparity_min, disparity_max, disparity_scaled_min, disparity_scaled_max):
+    """-> (the dense uint16 image, scale, scaled minimum, scaled maximum) as stereo_range()'s dense form makes them"""
+    if not isinstance(disparity, np.ndarray) or disparity.ndim != 2 or disparity.dtype.kind not in 'iuf':
+        raise Exception("stereo_point_cloud(): the disparity must be a 2-D numeric numpy array" +
+                        (f", got shape {disparity.shape} and dtype {disparity.dtype}" if isinstance(disparity, np.ndarray) else ""))
+    if disparity.shape != shape:
+        raise Exception(f"stereo_point_cloud(): the disparity and the rectified images MUST have the same dimensions. I have disparity.shape={disparity.shape} and models_rectified[0].imagersize()={(shape[1], shape[0])}")
+    if shape[0]*shape[1] > _CLOUD_MAX_PIXELS:
+        raise Exception(f"stereo_point_cloud(): a disparity image of {shape[1]} x {shape[0]} pixels cannot be made a cloud of: at most {_CLOUD_MAX_PIXELS} pixels")
+    if disparity_min is not None and disparity_scaled_min is not None and disparity_min != disparity_scaled_min:
+        raise Exception("disparity_min and disparity_scaled_min may not both be given")
+    if disparity_max is not None and disparity_scaled_max is not None and disparity_max != disparity_scaled_max:
+        raise Exception("disparity_max and disparity_scaled_max may not both be given")
+    if disparity_max is None and disparity_scaled_max is None and disparity.dtype == np.int16:
+        disparity_scaled_max = 0x7FFF
+    lowest  = disparity_scaled_min if disparity_scaled_min is not None else 0      if disparity_min is None else disparity_min*disparity_scale
+    highest = disparity_scaled_max if disparity_scaled_max is not None else 0xFFFF if disparity_max is None else disparity_max*disparity_scale
+    scale, dmin, dmax = (int(min(max(x, 0), 0xFFFF)) for x in (disparity_scale, lowest, highest))
+    if dmin >= dmax:
+        raise Exception(f"stereo_point_cloud(): must have disparity_scaled_max > disparity_scaled_min. Got {dmax} and {dmin}")
+    return np.ascontiguousarray(disparity.astype(np.uint16)), scale, dmin, dmax
+
+
+def _cloud_image_of_any_size(image, what):
+    """-> (dense array, width, height, channels, dtype code) of a colour image"""
+    if not isinstance(image, np.ndarray) or image.dtype not in _CLOUD_DTYPES:
+        raise Exception(f"stereo_point_cloud(): '{what}' must be a numpy array of dtype uint8 or uint16" +
+                        (f", not {image.dtype}" if isinstance(image, np.ndarray) else ""))
+    if not (image.ndim == 2 or (image.ndim == 3 and image.shape[2] == 3)) or image.size == 0:
+        raise Exception(f"stereo_point_cloud(): '{what}' must have shape (H,W) or (H,W,3), got {image.shape}")
+    return np.ascontiguousarray(image), image.shape[1], image.shape[0], (1 if image.ndim == 2 else 3), _CLOUD_DTYPES[image.dtype]
+
+
+def _cloud_image(image, what, models):
+    """... of a colour image of camera 0, or None"""
+    if image is None:
+        return None
+    if models is None:
+        raise Exception(f"stereo_point_cloud(): '{what}' needs 'models': the colours are read through the rectification map of camera 0")
+    arguments = _cloud_image_of_any_size(image, what)
+    W, H = (int(x) for x in models[0].imagersize())
+    if image.shape[:2] != (H, W):
+        raise Exception(f"stereo_point_cloud(): '{what}' must have the imager size of camera 0, (H,W) = {(H, W)}, got {image.shape[:2]}")
+    return arguments
+
+
+def _cloud_frame(models_rectified, models, range_min, range_max, frame, dtype):
+    """-> (range_min, range_max, Rt_out_rect0 (4,3) or None, the points are float32)"""
+    if frame not in _CLOUD_FRAMES:
+        raise Exception(f"stereo_point_cloud(): frame must be one of {_CLOUD_FRAMES}, not {frame!r}")
+    if frame == 'cam0' and models is None:
+        raise Exception("stereo_point_cloud(): frame='cam0' needs 'models'")
+    try:    dtype = np.dtype(dtype)
+    except TypeError: dtype = None
+    if dtype is None or dtype not in (np.dtype(np.float64), np.dtype(np.float32)):      # (None == np.dtype(float) holds)
+        raise Exception(f"stereo_point_cloud(): dtype must be float64 or float32, not {dtype}")
+    rmin = 0. if range_min is None else float(range_min)
+    rmax = np.inf if range_max is None else float(range_max)
+    if not rmin <= rmax:
+        raise Exception(f"stereo_point_cloud(): must have range_min <= range_max. Got {rmin:g} and {rmax:g}")
+    if   frame == 'ref':  Rt = models_rectified[0].Rt_ref_cam()
+    elif frame == 'cam0': Rt = compose_Rt(models[0].Rt_cam_ref(), models_rectified[0].Rt_ref_cam())
+    else:                 Rt = None
+    if Rt is not None: Rt = np.ascontiguousarray(Rt, dtype=np.float64)
+    return rmin, rmax, Rt, dtype == np.float32
+
+
+def _cloud_params(scale, dmin, dmax, rmin, rmax, Rt, float32, image):
+    """-> (_CloudParams, what it points to)"""
+    p = _CloudParams(scale, dmin, dmax, rmin, rmax, None if Rt is None else Rt.ctypes.data, int(float32), None, 0, 0, 0, 0)
+    if image is not None:
+        p.image, p.image_width, p.image_height, p.image_channels, p.image_dtype = image[0].ctypes.data, *image[1:]
+    return p, (Rt, image)
+
+
+def _cloud_read(read, handle, api, N, float32, image):
+    points = np.zeros((N, 3), dtype=np.float32 if float32 else np.float64)
+    index  = np.zeros((N,), dtype=np.int32)
+    color  = None if image is None else np.zeros((N,) if image[3] == 1 else (N, 3), dtype=image[0].dtype)
+    read.restype, read.argtypes = C.c_bool, [C.c_void_p]*4
+    if not read(handle, _ptr(points), _ptr(color), _ptr(index)):
+        raise Exception("stereo_point_cloud() failed:" + api._last_error())
+    return points, color, index
+
+
+def _cloud_stage_milliseconds(f, handle, api):
+    ms = np.zeros((3,), dtype=np.float32)
+    f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2
+    if not f(handle, _ptr(ms)):
+        raise Exception("stereo_point_cloud() failed:" + api._last_error())
+    return dict(zip(("mask", "scan", "scatter"), (float(x) for x in ms)))
+
+
+class StereoPointCloud:
+    """stereo_point_cloud() without the camera models, resident: the device buffers for one size of disparity image are
+made once, and every point_cloud() reuses them; the output buffers grow when a cloud outgrows them.
+
+    models_rectified: what rectified_system() returned. map0: None, or the float32 (Nel,Naz,2) rectification map of
+    camera 0, rectification_maps(...)[0], which a colour image is read through.
+      .point_cloud(disparity, *, image0=None, ..., frame='ref' or 'rect0', dtype=np.float64)  -> (points, color, index)
+      .stage_milliseconds()     how long the mask, the scan and the scatter of the last cloud took on the device
+    What a cloud is: stereo_point_cloud(). A Rectification has its own: Rectification.point_cloud()"""
+
+    def __init__(self, models_rectified, *, map0=None):
+        self.handle = None
+        _validate_models_rectified(models_rectified)
+        self._models_rectified = tuple(models_rectified)
+        self.Naz, self.Nel = (int(x) for x in models_rectified[0].imagersize())
+        if map0 is not None:
+            if not isinstance(map0, np.ndarray) or map0.dtype != np.float32 or map0.shape != (self.Nel, self.Naz, 2):
+                raise Exception(f"stereo_point_cloud(): map0 must be a float32 numpy array of shape {(self.Nel, self.Naz, 2)}")
+            map0 = np.ascontiguousarray(map0)
+        if self.Nel*self.Naz > _CLOUD_MAX_PIXELS:
+            raise Exception(f"stereo_point_cloud(): a disparity image of {self.Naz} x {self.Nel} pixels cannot be made a cloud of: at most {_CLOUD_MAX_PIXELS} pixels")
+        lib, api = _libs()
+        self._L, self._api = lib.lib, api
+        rectification_model, fxycxy = models_rectified[0].intrinsics()
+        fxycxy = np.ascontiguousarray(fxycxy, dtype=np.float64)
+        f = self._L.mrcal_amd_point_cloud_create
+        f.restype, f.argtypes = C.c_void_p, [C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p]
+        self.handle = f(_rectification_model_type(lib, rectification_model), _ptr(fxycxy), _baseline(models_rectified),
+                        self.Naz, self.Nel, None)
+        if not self.handle:
+            self.handle = None
+            raise Exception("stereo_point_cloud() failed:" + api._last_error())
+        self._L.mrcal_amd_point_cloud_destroy.restype, self._L.mrcal_amd_point_cloud_destroy.argtypes = None, [C.c_void_p]
+        self._has_map = map0 is not None
+        if self._has_map:
+            f = self._L.mrcal_amd_point_cloud_set_map
+            f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2
+            if not f(self.handle, _ptr(map0)):
+                self.close()
+                raise Exception("stereo_point_cloud() failed:" + api._last_error())
+
+    def point_cloud(self, disparity, *, image0=None, disparity_scale=1, disparity_min=None, disparity_max=None,
+                    disparity_scaled_min=None, disparity_scaled_max=None, range_min=None, range_max=None,
+                    frame='ref', dtype=np.float64):
+        if self.handle is None:
+            raise Exception("this StereoPointCloud has been closed")
+        if frame == 'cam0':
+            raise Exception("stereo_point_cloud(): frame='cam0' needs 'models'")
+        if image0 is not None:
+            if not self._has_map:
+                raise Exception("stereo_point_cloud(): 'image0' needs the rectification map of camera 0, and no map0 was given")
+            image0 = _cloud_image_of_any_size(image0, "image0")       # (whatever image map0 leads into)
+        d, scale, dmin, dmax = _cloud_disparity(disparity, (self.Nel, self.Naz), disparity_scale, disparity_min, disparity_max,
+                                                disparity_scaled_min, disparity_scaled_max)
+        rmin, rmax, Rt, float32 = _cloud_frame(self._models_rectified, None, range_min, range_max, frame, dtype)
+        p, keep = _cloud_params(scale, dmin, dmax, rmin, rmax, Rt, float32, image0)
+        N = C.c_int(0)
+        f = self._L.mrcal_amd_point_cloud_compute
+        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*4
+        if not f(self.handle, _ptr(d), C.addressof(p), C.addressof(N)):
+            raise Exception("stereo_point_cloud() failed:" + self._api._last_error())
+        return _cloud_read(self._L.mrcal_amd_point_cloud_read, self.handle, self._api, N.value, float32, image0)
+
+    def stage_milliseconds(self):
+        if self.handle is None:
+            raise Exception("this StereoPointCloud has been closed")
+        return _cloud_stage_milliseconds(self._L.mrcal_amd_point_cloud_stage_milliseconds, self.handle, self._api)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._L.mrcal_amd_point_cloud_destroy(self.handle)
+            self.handle = None
+    def __del__(self):
+        try:    self.close()
+        except Exception: pass
+    def __enter__(self): return self
+    def __exit__(self, *a): self.close()
+
+
+def stereo_point_cloud(disparity, models_rectified, *, models=None, image0=None, disparity_scale=1, disparity_min=None,
+                       disparity_max=None, disparity_scaled_min=None, disparity_scaled_max=None, range_min=None,
+                       range_max=None, frame='ref', dtype=np.float64):
+    """The points a dense disparity image sees, compacted and coloured: (points (N,3), color, index (N,) int32)
+
+What mrcal-stereo --write-point-cloud makes, on the device: only the N kept points cross to the host.
+write_point_cloud_as_ply(filename, points, color = color) writes them.
+
+disparity: the (Nel, Naz) image of a stereo matcher, in units of 1/disparity_scale pixels. models_rectified: what
+rectified_system() returned. models: the two cameramodels: needed for image0 and for frame = 'cam0', and for nothing
+else: without them no rectification map is made. image0: the image of camera 0 the colours come from, (H,W) gray or
+(H,W,3) BGR, uint8 or uint16, of camera 0's imager size; None: color is None. frame: the coordinate system of the
+points: 'ref' (the default: what mrcal-stereo writes), 'cam0', or 'rect0', the rectified camera 0. dtype: float64, or
+float32, which is what a .ply holds.
+
+A pixel (x,y) is KEPT when all of these hold:
+  1. with d the disparity cast to uint16, as stereo_range() does: d > 0, d >= disparity_scaled_min,
+     d <= disparity_scaled_max. disparity_min/max are the same bounds in pixels; an int16 image defaults the maximum
+     to 0x7FFF, so that its negative "invalid" marks stay invalid
+  2. its range, stereo_range()'s from the same device code, is finite and > 0. A negative LATLON range, which
+     stereo_range() returns, is dropped here
+  3. range_min <= range <= range_max, where given
+  4. with image0: ix = floorf(mx + 0.5f), iy = floorf(my + 0.5f), additions in float32, of the float32 rectification
+     map (mx,my) of camera 0 at (x,y), are finite and inside image0. The colour is image0[iy, ix]: the reference's
+     nearest pixel of the original image, taken from the map instead of a projection of every point. A map entry of
+     -0.5 exactly is inside here and outside in the reference
+The point is range times the unit observation vector of (x,y), moved to `frame` by a transform made on the host, in
+double and rounded once if dtype is float32; frame = 'rect0' makes no product and gives the bits of stereo_unproject(
+disparity/disparity_scale, models_rectified, qrect0 = the pixel grid). The kept pixels come in ascending y Naz + x, which
+is what index holds. Validity is decided once and stored a bit a pixel; an integer scan places every workgroup's
+points: no atomics, the same bits on every call (csrc/point_cloud.hip). No CPU fallback.
+The one-shot form of Rectification.point_cloud() (with models) and of StereoPointCloud.point_cloud() (without).
+Reference: mrcal-stereo's --write-point-cloud; mrcal.stereo_unproject(), mrcal.write_point_cloud_as_ply()"""
+    _validate_models_rectified(models_rectified)
+    if models is not None and len(models) != 2:
+        raise Exception("I need exactly 2 camera models")
+    W, H = (int(x) for x in models_rectified[0].imagersize())
+    _cloud_image(image0, "image0", models)
+    _cloud_disparity(disparity, (H, W), disparity_scale, disparity_min, disparity_max, disparity_scaled_min, disparity_scaled_max)
+    _cloud_frame(models_rectified, models, range_min, range_max, frame, dtype)
+    kw = dict(disparity_scale=disparity_scale, disparity_min=disparity_min, disparity_max=disparity_max,
+              disparity_scaled_min=disparity_scaled_min, disparity_scaled_max=disparity_scaled_max,
+              range_min=range_min, range_max=range_max, frame=frame, dtype=dtype)
+    if models is None:
+        with StereoPointCloud(models_rectified) as c:
+            return c.point_cloud(disparity, **kw)
+    with Rectification(models, models_rectified) as r:
+        return r.point_cloud(disparity, image0=image0, **kw)

@@ -1,5 +1,5 @@
 """Sampling the imager on a grid (mrcal/utils.py:268-437): sample_imager() is host numpy, sample_imager_unproject()
-runs over unproject() (the GPU)."""
+runs over unproject() (the GPU). write_point_cloud_as_ply() (mrcal/utils.py:1578-1750) is host numpy."""
 import numpy as np
 
 
@@ -23,3 +23,66 @@ def sample_imager_unproject(gridn_width, gridn_height, imager_width, imager_heig
         return np.array([unproject(grid, lensmodel[i], intrinsics_data[i], normalize=normalize)
                          for i in range(len(lensmodel))]), grid
     return unproject(grid, lensmodel, intrinsics_data, normalize=normalize), grid
+
+
+def write_point_cloud_as_ply(filename, points, *, color=None, binary=True):
+    """Writes a point cloud to a .ply file
+
+points: (N,3); or (N,4), a grayscale intensity in the last column; or (N,6), a BGR colour in the last three. color: the
+colours apart from the points, which are (N,3) then: (N,) grayscale or (N,3) BGR. The file holds float32 x y z and, per
+point, `uchar intensity` or `uchar red green blue` (BGR in, RGB out). binary: little-endian binary (the default) or ascii.
+The argument forms, the checks and their messages are the reference's. Departures:
+  - ascii writes exactly the properties the header declares, the coordinates as %.9g, which a float32 survives. The
+    reference writes %.1f and, for BGR, a seventh column that its header does not declare
+  - uint16 colours, and colours of any type outside 0..255, are refused; the reference truncates them
+  - N = 0 writes a valid file with no vertices
+Host numpy: needs no GPU. Reference: mrcal.write_point_cloud_as_ply()"""
+    points = np.asarray(points)
+    if points.ndim != 2:
+        raise Exception(f"points.shape must be (N,3) or (N,4) or (N,6), but points.ndim={points.ndim}")
+    N, Ntrailing = points.shape
+    if not (Ntrailing == 3 or Ntrailing == 4 or Ntrailing == 6):
+        raise Exception(f"points.shape[-1] must be one of (3,4,6) to indicate no-color or grayscale or bgr colors respectively. Instead got points.shape[-1] = {points.shape[-1]}")
+    if color is not None:
+        color = np.asarray(color)
+        if Ntrailing != 3:
+            raise Exception("Both 'points' and 'color' are specifying color information. At most one of those should provide it")
+        if color.ndim > 2:
+            raise Exception(f"color.shape must be (N,) or (N,3), but color.ndim={color.ndim}")
+        if color.ndim < 1 or N != color.shape[0]:
+            raise Exception(f"Inconsistent point counts: len(points)={len(points)} but len(color)={len(color) if color.ndim else 0}")
+        if not (color.shape == (N,) or color.shape == (N, 3)):
+            raise Exception(f"color.shape must be (N,) or (N,3), but color.shape={color.shape}")
+        if color.dtype == np.uint16:
+            raise Exception("write_point_cloud_as_ply(): colours are written as uchar, and uint16 colours would be truncated: scale them to uint8 first")
+    elif Ntrailing == 4:
+        color, points = points[:, 3], points[:, :3]
+    elif Ntrailing == 6:
+        color, points = points[:, 3:], points[:, :3]
+
+    # points (N,3); color None, (N,) or (N,3)
+    if color is not None and color.size and not (np.all(color >= 0) and np.all(color <= 255)):
+        raise Exception("write_point_cloud_as_ply(): colours are written as uchar and must lie in 0..255")
+    if color is None:
+        dtype, header_color = np.dtype([('xyz', '<f4', 3)]), ''
+    elif color.ndim == 1:
+        dtype, header_color = np.dtype([('xyz', '<f4', 3), ('i', np.uint8)]), 'property uchar intensity\n'
+    else:
+        dtype, header_color = np.dtype([('xyz', '<f4', 3), ('rgb', np.uint8, 3)]), 'property uchar red\nproperty uchar green\nproperty uchar blue\n'
+    header = (f"ply\nformat {'binary_little_endian' if binary else 'ascii'} 1.0\nelement vertex {N}\n"
+              f"property float x\nproperty float y\nproperty float z\n{header_color}end_header\n").encode()
+
+    record = np.zeros((N,), dtype=dtype)
+    record['xyz'] = points.astype(np.float32)
+    if color is not None and color.ndim == 1: record['i']   = color.astype(np.uint8)
+    if color is not None and color.ndim == 2: record['rgb'] = color[:, ::-1].astype(np.uint8)
+    with open(filename, 'wb') as f:
+        f.write(header)
+        if binary:
+            record.tofile(f)
+        else:
+            for r in record:
+                fields = ["%.9g" % x for x in r['xyz']]
+                if color is not None:
+                    fields += ["%d" % c for c in np.atleast_1d(r['i'] if color.ndim == 1 else r['rgb'])]
+                f.write((" ".join(fields) + "\n").encode())
