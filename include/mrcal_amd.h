@@ -1277,6 +1277,69 @@ bool mrcal_amd_rectification_point_cloud_of_images(mrcal_amd_rectification_t* r,
 bool mrcal_amd_rectification_point_cloud_read(mrcal_amd_rectification_t* r, void* points, void* color, int32_t* index);
 bool mrcal_amd_rectification_point_cloud_stage_milliseconds(mrcal_amd_rectification_t* r, float* milliseconds /*3*/);
 
+/* ---- chessboard corners: the calibration board detected in one grey image ----
+   What the reference gets from an external detector (mrgingham) through mrcal.compute_chessboard_corners():
+   csrc/chessboard.hip, planned on the host by csrc/chessboard_plan.hpp; the lattice is found on the host by
+   csrc/chessboard_grid.cpp. It imitates no other detector pixel for pixel; it finds the same physical corners.
+   The image I: grey, uint8 or uint16, (H,W), dense rows. All of a..c is integer arithmetic.
+     a. Blur. B = I (*) [1 2 1]^T [1 2 1], the plain integer sum: B <= 16 max(I). Nothing is divided
+     b. Response: the ChESS detector of Bennett & Lasenby. The ring s[0..15] is B at the offsets (dx,dy)
+          (5,0) (5,2) (3,3) (2,5) (0,5) (-2,5) (-3,3) (-5,2) (-5,0) (-5,-2) (-3,-3) (-2,-5) (0,-5) (2,-5) (3,-3) (5,-2)
+          SR  = sum_{n<4} |(s[n] + s[n+8]) - (s[n+4] + s[n+12])|
+          DR  = sum_{n<8} |s[n] - s[n+8]|
+          S16 = sum s          S5 = B(p) + B at its four 4-neighbours
+          R   = 5 SR - 5 DR - |5 S16 - 16 S5|          as an int32: the paper's sum - diff - 16 mean response, times 5
+        For uint16 input every intermediate stays below 2^27. R is this for 6 <= x < W-6 and 6 <= y < H-6 and 0
+        elsewhere: no coordinate is ever clamped
+     c. Candidates. Rmax = max R over the image (>= 0: the border). A pixel p is a candidate when R(p) > 0, and
+        256 R(p) > threshold_256 Rmax (a 64-bit product), and for every other p' of the (2 nms_radius + 1)^2 window
+        inside the image R(p') < R(p), or R(p') == R(p) and p' comes after p in row-major order. The candidates are
+        listed in row-major order; the first max_candidates of them are kept and the rest counted: overflow
+     d. Refinement, on I in double: the fixed point of cv2.cornerSubPix. q = (x,y) of the candidate; the window offsets
+        i,j in [-5,5] with weights exp(-(i/5)^2) exp(-(j/5)^2); I sampled bilinearly at coordinates clamped to the image
+        (x to [0,W-1]: x0 = floor(x), x1 = min(x0 + 1, W-1)); gx = (I(q+(i+1,j)) - I(q+(i-1,j)))/2, gy likewise;
+        G = sum w g g^T; singular when !(det G > 1e-10 (trace G)^2): status 1; d = G^-1 sum w g g^T (i,j)^T; q += d;
+        |q - start| > 3.5 px along x or y: status 2; stop when |d| < 1e-5 px or after 20 iterations: status 0. A
+        candidate that fails has NaN coordinates
+     e. The board: the complete width x height lattice (3..256 corners a side) among the refined candidates of status
+        0, or none (whole boards only, like mrgingham). Row-major, (height,width,2). The labelling is proper: with the image's y pointing down,
+        (mean +i edge) x (mean +j edge) > 0, +i along a row and +j along a column of the board. Of the 2 proper
+        labellings (4 when width == height) the one whose mean +i edge, made a unit vector, has the largest x
+   Deterministic: the maximum is an INTEGER atomicMax; the compaction is point_cloud.hip's (a mask bit a pixel, one
+   integer scan, a scatter from the bits); the sums of d are reduced in a fixed order. The same bits on every call.
+   Refused: bytes_per_pixel other than 1 or 2, an image smaller than 32 x 32 or of more than 2^28 pixels or that does
+   not fit free_device_bytes, threshold_256 outside 0..255, nms_radius outside 1..16, max_candidates outside 1..65536.
+   _create(): free_device_bytes: what the device has free; 0: ask it. _candidates(): uploads the image (host, dense),
+   runs a..d, returns how many candidates are kept (*N) and whether more were found (*overflow); the caller's arrays
+   q (N,2) double, response (N,) int32, status (N,) int32 hold max_candidates entries and may be NULL. _find_board():
+   _candidates() and e; *found = 0: no board, which is no error. _stage_milliseconds(): upload, response, candidates,
+   refine (the device's events), grid (the host's clock; 0 after _candidates()) of the last call.
+   mrcal_amd_chessboard_grid(): e alone, on the host, for N points that are given: it needs no device. response
+   orders the seeds (NULL: the order given), status NULL: all 0 */
+typedef struct mrcal_amd_chessboard_detector mrcal_amd_chessboard_detector_t;
+typedef struct
+{
+    int threshold_256;          /* 51 */
+    int nms_radius;             /* 7 */
+    int max_candidates;         /* 4096 */
+} mrcal_amd_chessboard_params_t;
+#define MRCAL_AMD_CHESSBOARD_STAGES 5
+mrcal_amd_chessboard_detector_t*
+mrcal_amd_chessboard_detector_create(int width, int height, int bytes_per_pixel,
+                                     const mrcal_amd_chessboard_params_t* params, size_t free_device_bytes);
+bool mrcal_amd_chessboard_detector_candidates(mrcal_amd_chessboard_detector_t* d, const void* image,
+                                              int* N, int* overflow, double* q, int32_t* response, int32_t* status);
+bool mrcal_amd_chessboard_detector_find_board(mrcal_amd_chessboard_detector_t* d, const void* image,
+                                              int board_width, int board_height, int* found, double* corners);
+/* for the tests: the response image (height,width) int32, Rmax and the pixels (N,2) of the candidates of the last call;
+   any of them may be NULL */
+bool mrcal_amd_chessboard_detector_read_response(mrcal_amd_chessboard_detector_t* d, int32_t* response, int32_t* response_max,
+                                                 int32_t* candidate_xy);
+bool mrcal_amd_chessboard_detector_stage_milliseconds(mrcal_amd_chessboard_detector_t* d, float* milliseconds /*5*/);
+void mrcal_amd_chessboard_detector_destroy(mrcal_amd_chessboard_detector_t* d);
+bool mrcal_amd_chessboard_grid(int N, const double* q, const int32_t* response, const int32_t* status,
+                               int board_width, int board_height, int* found, double* corners);
+
 #ifdef __cplusplus
 }
 #endif

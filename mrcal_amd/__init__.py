@@ -83,7 +83,9 @@ from .stereo import (rectified_resolution, rectified_system, rectification_maps,
                      filter_speckles, SpeckleFilter, stereo_point_cloud, StereoPointCloud)
 from .image_transforms import (scale_focal__best_pinhole_fit, pinhole_model_for_reprojection, image_transformation_map,
                                transform_image)
-from .utils import sample_imager, sample_imager_unproject, write_point_cloud_as_ply
+from .utils import sample_imager, sample_imager_unproject, write_point_cloud_as_ply, mapping_file_framenocameraindex
+from .chessboard import (find_chessboard_corners, chessboard_corner_candidates, ChessboardDetector, chessboard_grid,
+                         compute_chessboard_corners, load_image_gray)
 
 # the callers either side of the path: the on-disk format of
 # a calibration, host-side pose arithmetic, the seeding. As in the reference, the class

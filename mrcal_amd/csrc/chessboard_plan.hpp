@@ -1,0 +1,125 @@
+// What chessboard.hip works out on the host before it touches the device: the arguments that are refused and the
+// messages, where the image, the response, the mask words, the bases, the maximum and the candidate records lie in the
+// ONE pooled allocation a detector owns, and the launch geometry of the five kernels. Plain structs in and out, no HIP
+// type or call. tests/hostcheck/chessboard_grid_check.cpp runs it under the host sanitizers.
+//
+// What a corner is: include/mrcal_amd.h, "chessboard corners".
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string>
+
+namespace mrcal_amd {
+
+#define CB_THREADS 256                  // of every kernel but the scan
+#define CB_TX 64                        // a tile of cb_response_kernel and cb_candidates_kernel: 64 x 16 pixels. A wavefront
+#define CB_TY 16                        //   is a row of it: its verdicts are ONE __ballot, one mask word
+#define CB_HALO 6                       // of the image around a tile of R: 5 for the ring and 1 for the blur
+#define CB_RING 5                       // of the blurred image around a tile of R
+#define CB_NMS_RADIUS_MAX 16            // the LDS tile of cb_candidates_kernel is laid out for this radius
+#define CB_CHUNK_WORDS 16               // mask words a workgroup of cb_scatter_kernel places: the unit of the scan
+#define CB_SCAN_THREADS 1024            // cb_scan_kernel is ONE workgroup of these
+#define CB_MIN_SIDE 32
+#define CB_MAX_PIXELS (1L << 28)
+#define CB_MAX_CANDIDATES 65536
+#define CB_ALIGN 256                    // of the parts of the pool, in bytes
+#define CB_WINDOW 5                     // the refinement window: offsets -5..5
+#define CB_REFINE_ITERATIONS 20
+#define CB_STATUS_OK 0
+#define CB_STATUS_SINGULAR 1
+#define CB_STATUS_LEFT 2
+
+static_assert(CB_THREADS == 4*CB_TX && CB_TY % 4 == 0, "a wavefront is a row of the tile, four rows at a time");
+static_assert(CB_MAX_PIXELS < (1L << 31), "a pixel index is an int32");
+
+struct ChessboardPlan
+{
+    int      W = 0, H = 0, bytes_per_pixel = 0;
+    int      threshold_256 = 0, nms_radius = 0, max_candidates = 0;
+    unsigned tiles_x = 0, tiles_y = 0;  // of the response and candidates kernels: ONE grid dimension, tiles_x tiles_y
+    unsigned words_per_row = 0;         // = tiles_x: bit b of word (y, k) is pixel (64 k + b, y)
+    unsigned chunks = 0;                // workgroups of the scatter: CB_CHUNK_WORDS words each, in row-major word order
+    unsigned scan_per_thread = 0;       // chunks a thread of the scan sums: chunks <= CB_SCAN_THREADS scan_per_thread
+    unsigned refine_groups = 0;         // workgroups of the refinement: a wavefront a candidate, max_candidates of them
+    // offsets into the pool, in bytes
+    size_t   image = 0;                 // bytes_per_pixel a pixel
+    size_t   response = 0;              // int32 a pixel
+    size_t   words = 0;                 // uint64 [chunks CB_CHUNK_WORDS]; those past H words_per_row stay 0
+    size_t   bases = 0;                 // uint32 [chunks + 1]: the exclusive scan of the chunks' counts, and the total
+    size_t   response_max = 0;          // int32
+    size_t   xy = 0;                    // int32 [max_candidates][2]
+    size_t   candidate_response = 0;    // int32 [max_candidates]
+    size_t   q = 0;                     // double [max_candidates][2]
+    size_t   status = 0;                // int32 [max_candidates]
+    size_t   bytes = 0;                 // of the pool
+};
+
+inline size_t cb_aligned(size_t n) { return (n + CB_ALIGN - 1)/CB_ALIGN*CB_ALIGN; }
+
+// the whole plan. free_bytes: what the device has free. false: a refusal, with the reason in *error
+inline bool chessboard_plan(ChessboardPlan* plan, std::string* error, int W, int H, int bytes_per_pixel,
+                            int threshold_256, int nms_radius, int max_candidates, size_t free_bytes)
+{
+    *plan = ChessboardPlan();
+    char buf[256];
+    buf[0] = 0;
+    if(!(bytes_per_pixel == 1 || bytes_per_pixel == 2))
+        snprintf(buf, sizeof(buf), "find_chessboard_corners(): images must have dtype uint8 or uint16, not %d bytes a pixel", bytes_per_pixel);
+    else if(W < CB_MIN_SIDE || H < CB_MIN_SIDE)
+        snprintf(buf, sizeof(buf), "find_chessboard_corners(): an image of %d x %d pixels is too small: at least %d x %d",
+                 W, H, CB_MIN_SIDE, CB_MIN_SIDE);
+    else if((long)W*(long)H > CB_MAX_PIXELS)
+        snprintf(buf, sizeof(buf), "find_chessboard_corners(): an image of %d x %d pixels is too large: at most %ld pixels",
+                 W, H, CB_MAX_PIXELS);
+    else if(threshold_256 < 0 || threshold_256 > 255)
+        snprintf(buf, sizeof(buf), "find_chessboard_corners(): threshold_256 must be in 0..255, got %d", threshold_256);
+    else if(nms_radius < 1 || nms_radius > CB_NMS_RADIUS_MAX)
+        snprintf(buf, sizeof(buf), "find_chessboard_corners(): nms_radius must be in 1..%d, got %d", CB_NMS_RADIUS_MAX, nms_radius);
+    else if(max_candidates < 1 || max_candidates > CB_MAX_CANDIDATES)
+        snprintf(buf, sizeof(buf), "find_chessboard_corners(): max_candidates must be in 1..%d, got %d", CB_MAX_CANDIDATES, max_candidates);
+    if(buf[0] != 0) { *error = buf; return false; }
+
+    const size_t N = (size_t)W*(size_t)H;
+    ChessboardPlan p;
+    p.W = W; p.H = H; p.bytes_per_pixel = bytes_per_pixel;
+    p.threshold_256 = threshold_256; p.nms_radius = nms_radius; p.max_candidates = max_candidates;
+    p.tiles_x         = (unsigned)((W + CB_TX - 1)/CB_TX);
+    p.tiles_y         = (unsigned)((H + CB_TY - 1)/CB_TY);
+    p.words_per_row   = p.tiles_x;
+    const size_t words = (size_t)p.words_per_row*(size_t)H;
+    p.chunks          = (unsigned)((words + CB_CHUNK_WORDS - 1)/CB_CHUNK_WORDS);
+    p.scan_per_thread = (p.chunks + CB_SCAN_THREADS - 1)/CB_SCAN_THREADS;
+    p.refine_groups   = ((unsigned)max_candidates + CB_THREADS/64 - 1)/(CB_THREADS/64);
+    p.image              = 0;
+    p.response           = cb_aligned(N*(size_t)bytes_per_pixel);
+    p.words              = p.response           + cb_aligned(N*sizeof(int32_t));
+    p.bases              = p.words              + cb_aligned((size_t)p.chunks*CB_CHUNK_WORDS*sizeof(uint64_t));
+    p.response_max       = p.bases              + cb_aligned(((size_t)p.chunks + 1)*sizeof(uint32_t));
+    p.xy                 = p.response_max       + cb_aligned(sizeof(int32_t));
+    p.candidate_response = p.xy                 + cb_aligned((size_t)max_candidates*2*sizeof(int32_t));
+    p.q                  = p.candidate_response + cb_aligned((size_t)max_candidates*sizeof(int32_t));
+    p.status             = p.q                  + cb_aligned((size_t)max_candidates*2*sizeof(double));
+    p.bytes              = p.status             + cb_aligned((size_t)max_candidates*sizeof(int32_t));
+    if(p.bytes > free_bytes)
+    {
+        snprintf(buf, sizeof(buf), "find_chessboard_corners(): %d x %d pixels need %zu bytes of device memory; %zu are free",
+                 W, H, p.bytes, free_bytes);
+        *error = buf;
+        return false;
+    }
+    *plan = p;
+    return true;
+}
+
+// a board that cannot be looked for (a seed is the middle of 3 x 3 corners)
+inline bool chessboard_board_ok(std::string* error, int board_width, int board_height)
+{
+    if(board_width >= 3 && board_height >= 3 && board_width <= 256 && board_height <= 256) return true;
+    char buf[256];
+    snprintf(buf, sizeof(buf), "find_chessboard_corners(): a board has 3..256 corners a side, got %d x %d", board_width, board_height);
+    *error = buf;
+    return false;
+}
+
+} // namespace mrcal_amd

@@ -86,3 +86,53 @@ Host numpy: needs no GPU. Reference: mrcal.write_point_cloud_as_ply()"""
                 if color is not None:
                     fields += ["%d" % c for c in np.atleast_1d(r['i'] if color.ndim == 1 else r['rgb'])]
                 f.write((" ".join(fields) + "\n").encode())
+
+
+def mapping_file_framenocameraindex(*files_per_camera):
+    """Image filenames to frame numbers: a dict from filename to (framenumber, cameraindex)
+
+    mapping_file_framenocameraindex(('img5-cam2.jpg', 'img6-cam2.jpg'), ('img6-cam3.jpg', 'img7-cam3.jpg'))
+    -> {'img5-cam2.jpg': (5, 0), 'img6-cam2.jpg': (6, 0), 'img6-cam3.jpg': (6, 1), 'img7-cam3.jpg': (7, 1)}
+
+One argument a camera: the filenames of its images; cameraindex counts the arguments. Within a camera the longest
+leading and trailing strings common to all its filenames are removed; what varies in between, which must be numeric,
+and the digits next to it are the frame number, which is neither sequential nor starts at 0. A camera with ONE image
+gets frame number 0. A middle that is not numeric is an error with several cameras, and sequential numbers with one.
+Host code. Reference: mrcal.mapping_file_framenocameraindex() (mrcal/utils.py)"""
+    import re
+    empty = [i for i in range(len(files_per_camera)) if len(files_per_camera[i]) == 0]
+    if len(empty) > 0:
+        raise Exception("These camera globs matched no files: {}".format(empty))
+
+    def common(a, b, from_the_end):
+        if from_the_end: a, b = a[::-1], b[::-1]
+        n = 0
+        while n < len(a) and n < len(b) and a[n] == b[n]: n += 1
+        return a[:n][::-1] if from_the_end else a[:n]
+
+    def framenumbers(files):
+        if len(files) == 1:
+            return [0]
+        leading = trailing = files[0]
+        for f in files[1:]:
+            leading, trailing = common(leading, f, False), common(trailing, f, True)
+        end = -len(trailing) if len(trailing) > 0 else None
+        for f in files:
+            if not re.match("^[0-9]+$", f[len(leading):end]):
+                raise Exception(("Image filenames MUST be of the form 'something..number..something'\n" +
+                                 "where the somethings are common to all the filenames. File '{}'\n" +
+                                 "has a non-numeric middle: '{}'. The somethings are: '{}' and '{}'\n" +
+                                 "Did you forget to pass globs for each camera separately?").format(f, f[len(leading):end], leading, trailing))
+        before = re.match("^(.*?)([0-9]*)$", leading).group(2)
+        after  = re.match("^([0-9]*)(.*?)$", trailing).group(1)
+        return [int(before + f[len(leading):end] + after) for f in files]
+
+    mapping = {}
+    for icamera, files in enumerate(files_per_camera):
+        try:
+            numbers = framenumbers(files)
+        except Exception:
+            if len(files_per_camera) != 1: raise
+            numbers = range(len(files))
+        mapping.update(zip(files, [(n, icamera) for n in numbers]))
+    return mapping
