@@ -1340,6 +1340,72 @@ void mrcal_amd_chessboard_detector_destroy(mrcal_amd_chessboard_detector_t* d);
 bool mrcal_amd_chessboard_grid(int N, const double* q, const int32_t* response, const int32_t* status,
                                int board_width, int board_height, int* found, double* corners);
 
+/* ---- equalization: CLAHE and stretch of a grey image, before it is rectified and matched ----
+   What the reference's tools do to every raw image first: mrcal-stereo --equalization {clahe,stretch} and
+   mrcal-triangulate --clahe through cv2.createCLAHE(), setClipLimit(8), apply(); mrcal_image_uint8_load() stretches a
+   16-bit image to 8 bits. Here it is csrc/equalize.hip, planned on the host by csrc/equalize_plan.hpp.
+   cv2 is no part of this project: what follows is the published algorithm of OpenCV's clahe.cpp, quirks included, and
+   this text is the authority. Equality with cv2 itself is NOT tested. tests/equalize_checker.py restates it twice.
+
+   CLAHE. The image: grey, dense (H,W), uint8 (histSize = 256) or uint16 (histSize = 65536); the result has its shape
+   and type. clip_limit (8.0 is mrcal's value; <= 0: nothing is clipped); tiles_x, tiles_y (8, 8).
+     1. Padding. None if W % tiles_x == 0 and H % tiles_y == 0. Otherwise the image is padded on the right by
+        tiles_x - W % tiles_x and at the bottom by tiles_y - H % tiles_y, BOTH, even where one side is divisible: that
+        side gets a whole tiles_x (tiles_y) more. The padding is BORDER_REFLECT_101 (numpy.pad(mode='reflect')): the
+        pixel at index W-1+k is the one at W-1-k. The padded image is never made on the device: a padded pixel is
+        read at its reflected index
+     2. tw = Wpad/tiles_x, th = Hpad/tiles_y, total = tw th; lutScale = float32(histSize - 1) / float32(total);
+        clip = max(int(clip_limit total / histSize), 1), the product and the quotient in double, truncated
+     3. Per tile of the padded image: h = its histogram; clipped = sum_i max(h[i] - clip, 0); h[i] = min(h[i], clip);
+        batch = clipped / histSize, residual = clipped - batch histSize (integers); every h[i] += batch; if
+        residual > 0: step = max(histSize / residual, 1), and h[i] += 1 for i = 0, step, 2 step, ... while
+        i < histSize and fewer than residual bins have been incremented (bin i: i % step == 0 and i/step < residual);
+        lut[i] = saturate(rint(float32(sum_{k<=i} h[k]) lutScale)), the sum an integer, rint halves to even
+     4. Per pixel (x,y) of the image (not of the padding), with value v, in float32, EVERY operation rounded on its
+        own (nothing is fused): txf = float32(x) (1.f/float32(tw)) - 0.5f; tx1 = floor(txf); xa = txf - tx1;
+        xa1 = 1.f - xa; then tx1 and tx2 = tx1 + 1 are clamped to [0, tiles_x - 1]. The same in y.
+          res = (lut[ty1][tx1][v] xa1 + lut[ty1][tx2][v] xa) ya1 + (lut[ty2][tx1][v] xa1 + lut[ty2][tx2][v] xa) ya
+        The result is saturate(rint(res)), halves to even
+   Stretch. uint8 or uint16 in, uint8 out: out = uint8(0.5f + float32(v - min) 255.f / float32(max - min)), the
+   product before the quotient, in float32, truncated; min and max over the whole image, as integers. Departures from
+   image.c: its loop misses a maximum that comes before the first smaller pixel (the true extremes are used here), and
+   it divides by zero for a constant image (here: all zeros).
+   Histograms are integer sums and the extremes integer minima and maxima: integer atomics whose result does not depend
+   on the order, no floating-point atomic anywhere, the same bits on every call.
+   Refused: a method or type that is none of the above, an image that is empty or has more than 2^28 pixels, tiles
+   below 1 or more than 4096 in all, a clip_limit that is not a number, an image so small that the padding exceeds
+   W-1 or H-1 (a reflection reaches no further), an image that does not fit the free device memory.
+   _create(): the handle owns ONE device allocation: the image, the result, the histograms, the LUTs. _apply(): host
+   arrays, dense. _stage_milliseconds(): how long the histograms, the LUTs and the interpolation of the last _apply()
+   took on the device (stretch: the extremes, 0, the map).
+   mrcal_amd_rectification_set_equalization(): MRCAL_AMD_EQUALIZE_NONE (what a new handle has): nothing of this runs
+   and every result is what it was. Otherwise every later _rectify(), _disparity(), _disparity_filtered() and
+   _point_cloud_of_images() equalizes each raw image on the device between its upload and the remap; the images are
+   then grey. With stretch the rectified images, and the matcher, are uint8 whatever the input. In
+   _point_cloud_of_images() a colour image that IS image0 (the same pointer and size, one channel) is taken equalized,
+   from where it lies on the device; any other is used as it is.
+   mrcal_amd_feature_matcher_create_equalized(): _create(), both images equalized on the device after the upload
+   (uint8 or uint16 then; with stretch the templates are uint8) */
+#define MRCAL_AMD_EQUALIZE_NONE    0
+#define MRCAL_AMD_EQUALIZE_CLAHE   1
+#define MRCAL_AMD_EQUALIZE_STRETCH 2
+typedef struct
+{
+    int    method;              /* MRCAL_AMD_EQUALIZE_* */
+    double clip_limit;          /* 8.0 */
+    int    tiles_x, tiles_y;    /* 8, 8 */
+} mrcal_amd_equalize_params_t;
+typedef struct mrcal_amd_equalizer mrcal_amd_equalizer_t;
+mrcal_amd_equalizer_t* mrcal_amd_equalizer_create(int width, int height, int dtype, const mrcal_amd_equalize_params_t* params);
+bool mrcal_amd_equalizer_apply(mrcal_amd_equalizer_t* e, const void* in, void* out);
+bool mrcal_amd_equalizer_stage_milliseconds(mrcal_amd_equalizer_t* e, float* milliseconds /*3: histogram, lut, apply*/);
+void mrcal_amd_equalizer_destroy(mrcal_amd_equalizer_t* e);
+bool mrcal_amd_rectification_set_equalization(mrcal_amd_rectification_t* r, const mrcal_amd_equalize_params_t* params);
+mrcal_amd_feature_matcher_t*
+mrcal_amd_feature_matcher_create_equalized(const void* image0, int width0, int height0,
+                                           const void* image1, int width1, int height1, int dtype,
+                                           const mrcal_amd_equalize_params_t* params);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,7 @@
 #include "host_state.hpp"
 #include "device_memory.hpp"
 #include "remap.hpp"
+#include "equalize.hpp"
 #include "match_plan.hpp"
 
 namespace mrcal_amd {
@@ -490,6 +491,41 @@ mrcal_amd_feature_matcher_create(const void* image0, int width0, int height0,
         uint8_t* d = NULL;
         if(!m->images.upload(&d, (const uint8_t*)host[i], (size_t)m->W[i]*m->H[i]*match_pixel_bytes(dtype))) { delete m; return NULL; }
         m->image[i] = d;
+    }
+    return m;
+}
+
+// _create(), both images equalized on the device after the upload (equalize.hip)
+mrcal_amd_feature_matcher_t*
+mrcal_amd_feature_matcher_create_equalized(const void* image0, int width0, int height0,
+                                           const void* image1, int width1, int height1, int dtype,
+                                           const mrcal_amd_equalize_params_t* params)
+{
+    const EqualizeParams equalization = equalize_params_of(params);
+    if(equalization.method == EQUALIZE_METHOD_NONE)
+        return mrcal_amd_feature_matcher_create(image0, width0, height0, image1, width1, height1, dtype);
+    last_error_string().clear();
+    std::string why;
+    if(!match_sizes_ok(&why, 0, 1, 1, 0, width0, height0, width1, height1, dtype) ||
+       !equalize_params_ok(&why, width0, height0, dtype, equalization) ||
+       !equalize_params_ok(&why, width1, height1, dtype, equalization))
+    { set_error("%s", why.c_str()); return NULL; }
+    if(!mf_have_device()) return NULL;
+    mrcal_amd_feature_matcher* m = new mrcal_amd_feature_matcher;
+    m->W[0] = width0; m->H[0] = height0; m->W[1] = width1; m->H[1] = height1;
+    const void* host[2] = { image0, image1 };
+    {
+        // the raw images, the histograms and the LUTs go when this scope ends; the equalized images are the matcher's
+        DeviceBuffers tmp;
+        for(int i = 0; i < 2; i++)
+        {
+            uint8_t* d_raw = NULL; const void* d = NULL;
+            if(!(tmp.upload(&d_raw, (const uint8_t*)host[i], (size_t)m->W[i]*m->H[i]*match_pixel_bytes(dtype)) &&
+                 equalize_resident(m->images, tmp, equalization, d_raw, m->W[i], m->H[i], dtype, &d, &m->dtype)))
+            { (void)hipDeviceSynchronize(); delete m; return NULL; }
+            m->image[i] = (void*)d;
+        }
+        HIP_TRY(hipStreamSynchronize(NULL), delete m; return NULL);
     }
     return m;
 }

@@ -276,7 +276,7 @@ static void cloud_launch_scatter(const mrcal_amd_point_cloud* c, const CloudArgs
 }
 
 bool point_cloud_compute_device(mrcal_amd_point_cloud_t* c, const uint16_t* d_disparity,
-                                const mrcal_amd_point_cloud_params_t* params, int* N)
+                                const mrcal_amd_point_cloud_params_t* params, int* N, const void* d_color_image)
 {
     c->N = -1;
     c->timed = false;
@@ -311,9 +311,11 @@ bool point_cloud_compute_device(mrcal_amd_point_cloud_t* c, const uint16_t* d_di
 
     // (the colour image goes when this returns: the work is waited for before that)
     DeviceBuffers tmp;
-    uint8_t* d_image = NULL;
-    if(channels > 0 && !tmp.upload(&d_image, (const uint8_t*)rq.image, (size_t)rq.image_width*rq.image_height*channels*channel_bytes))
+    uint8_t* d_uploaded = NULL;
+    if(channels > 0 && d_color_image == NULL &&
+       !tmp.upload(&d_uploaded, (const uint8_t*)rq.image, (size_t)rq.image_width*rq.image_height*channels*channel_bytes))
         return false;
+    const void* d_image = d_color_image != NULL ? d_color_image : d_uploaded;
 
     uint64_t* words  = (uint64_t*)(c->pool + plan.words);
     uint32_t* counts = (uint32_t*)(c->pool + plan.counts);

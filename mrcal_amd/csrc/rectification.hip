@@ -31,6 +31,7 @@
 #include "remap.hpp"
 #include "stereo_sgm.hpp"
 #include "speckle_plan.hpp"
+#include "equalize.hpp"
 #include "stereo_range_device.hpp"
 #include "point_cloud.hpp"
 
@@ -450,11 +451,46 @@ bool remap_device(const void* d_src, int W, int H, int C, int dtype, const float
 }
 namespace {
 
-// host image -> remapped host image through a map that is on the device already
+// a raw image of the host on the device, equalized there if that is asked for (equalize.hip): *d_image, of *dtype_image
+// (stretch makes uint8 of uint16). Everything is tmp's, and queued in the NULL stream
+bool upload_equalized(DeviceBuffers& tmp, const EqualizeParams& equalization, const void* image, int W, int H, int dtype,
+                      const void** d_image, int* dtype_image)
+{
+    uint8_t* d_src = NULL;
+    return tmp.upload(&d_src, (const uint8_t*)image, (size_t)W*H*dtype_size(dtype)) &&
+           equalize_resident(tmp, tmp, equalization, d_src, W, H, dtype, d_image, dtype_image);
+}
+
+// the images an equalization takes: false, and why
+bool equalization_arguments_ok(const EqualizeParams& equalization, int width, int height, int channels, int dtype)
+{
+    if(equalization.method == EQUALIZE_METHOD_NONE) return true;
+    if(channels != 1) { set_error("equalize(): an image that is equalized is grey, not of %d channels", channels); return false; }
+    std::string why;
+    if(equalize_params_ok(&why, width, height, dtype, equalization)) return true;
+    set_error("%s", why.c_str());
+    return false;
+}
+
+// host image -> remapped host image through a map that is on the device already. equalization: of the image, on the
+// device, before the remap; out is then of the equalized type
 bool remap_host_image(void* out, const void* image, int W, int H, int C, int dtype, const float* d_map, int Nout,
-                      int interp, int border_mode, const double* border_value)
+                      int interp, int border_mode, const double* border_value,
+                      const EqualizeParams& equalization = EqualizeParams())
 {
     DeviceBuffers tmp;
+    if(equalization.method != EQUALIZE_METHOD_NONE)
+    {
+        const void* d_image = NULL; uint8_t* d_out = NULL;
+        int dtype_image = dtype;
+        if(!upload_equalized(tmp, equalization, image, W, H, dtype, &d_image, &dtype_image)) return false;
+        const size_t nout = (size_t)Nout*C*dtype_size(dtype_image);
+        if(!(border_mode == MRCAL_AMD_BORDER_TRANSPARENT ? tmp.upload(&d_out, (const uint8_t*)out, nout) : tmp.alloc(&d_out, nout)))
+            return false;
+        if(!remap_device(d_image, W, H, C, dtype_image, d_map, d_out, Nout, interp, border_mode, border_value)) return false;
+        HIP_TRY(hipMemcpy(out, d_out, nout, hipMemcpyDeviceToHost), (void)hipDeviceSynchronize(); return false);
+        return true;
+    }
     uint8_t *d_src = NULL, *d_out = NULL;
     const size_t nsrc = (size_t)W*H*C*dtype_size(dtype), nout = (size_t)Nout*C*dtype_size(dtype);
     if(!tmp.upload(&d_src, (const uint8_t*)image, nsrc)) return false;
@@ -555,6 +591,8 @@ struct mrcal_amd_rectification
     mrcal_amd_point_cloud_t* cloud = NULL;
     mrcal_lensmodel_type_t   rectification_model_type = MRCAL_LENSMODEL_LATLON;
     double                   fxycxy[4] = { 0., 0., 0., 0. };
+    // of every raw image, between its upload and the remap (equalize.hip); the method NONE: none
+    EqualizeParams           equalization;
     ~mrcal_amd_rectification() { mrcal_amd_point_cloud_destroy(cloud); }
 };
 
@@ -652,8 +690,25 @@ bool mrcal_amd_rectification_rectify(mrcal_amd_rectification_t* r, void* out0, v
     if(!remap_arguments_ok(width0, height0, channels, dtype, r->W, r->H, interpolation, border_mode) ||
        !remap_arguments_ok(width1, height1, channels, dtype, r->W, r->H, interpolation, border_mode))
         return false;
-    return remap_host_image(out0, image0, width0, height0, channels, dtype, r->map[0], r->W*r->H, interpolation, border_mode, border_value)
-        && remap_host_image(out1, image1, width1, height1, channels, dtype, r->map[1], r->W*r->H, interpolation, border_mode, border_value);
+    if(!equalization_arguments_ok(r->equalization, width0, height0, channels, dtype) ||
+       !equalization_arguments_ok(r->equalization, width1, height1, channels, dtype))
+        return false;
+    return remap_host_image(out0, image0, width0, height0, channels, dtype, r->map[0], r->W*r->H, interpolation, border_mode, border_value, r->equalization)
+        && remap_host_image(out1, image1, width1, height1, channels, dtype, r->map[1], r->W*r->H, interpolation, border_mode, border_value, r->equalization);
+}
+
+bool mrcal_amd_rectification_set_equalization(mrcal_amd_rectification_t* r, const mrcal_amd_equalize_params_t* params)
+{
+    last_error_string().clear();
+    if(!rectification_given(r)) return false;
+    if(params == NULL) { set_error("equalize(): the parameters are NULL"); return false; }
+    const EqualizeParams p = equalize_params_of(params);
+    // (what can be refused without an image; the rest when one comes)
+    std::string why;
+    if(!equalize_params_ok(&why, p.tiles_x > 0 ? p.tiles_x : 1, p.tiles_y > 0 ? p.tiles_y : 1, MRCAL_AMD_IMAGE_UINT8, p))
+    { set_error("%s", why.c_str()); return false; }
+    r->equalization = p;
+    return true;
 }
 
 bool mrcal_amd_rectification_range(mrcal_amd_rectification_t* r, double* range, const uint16_t* disparity_scaled,
@@ -689,7 +744,11 @@ bool mrcal_amd_rectification_disparity_filtered(mrcal_amd_rectification_t* r,
     if(!remap_arguments_ok(width0, height0, 1, dtype, r->W, r->H, MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT) ||
        !remap_arguments_ok(width1, height1, 1, dtype, r->W, r->H, MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT))
         return false;
-    mrcal_amd_stereo_sgm_t* m = mrcal_amd_stereo_sgm_create(r->W, r->H, dtype, params);
+    if(!equalization_arguments_ok(r->equalization, width0, height0, 1, dtype) ||
+       !equalization_arguments_ok(r->equalization, width1, height1, 1, dtype))
+        return false;
+    const int dtype_matched = equalize_dtype_out(r->equalization.method, dtype);
+    mrcal_amd_stereo_sgm_t* m = mrcal_amd_stereo_sgm_create(r->W, r->H, dtype_matched, params);
     if(m == NULL) return false;
     // (a window of 0: no filter, and nothing of it runs)
     if(!mrcal_amd_stereo_sgm_set_speckle_filter(m, speckle_window_size, speckle_range)) { mrcal_amd_stereo_sgm_destroy(m); return false; }
@@ -700,9 +759,9 @@ bool mrcal_amd_rectification_disparity_filtered(mrcal_amd_rectification_t* r,
         DeviceBuffers tmp;
         for(int i = 0; i < 2 && ok; i++)
         {
-            uint8_t* d_src = NULL;
-            ok = tmp.upload(&d_src, (const uint8_t*)image[i], (size_t)W[i]*H[i]*dtype_size(dtype)) &&
-                 remap_device(d_src, W[i], H[i], 1, dtype, r->map[i], sgm_device_image(m, i), r->W*r->H,
+            const void* d_src = NULL; int dtype_src = dtype;
+            ok = upload_equalized(tmp, r->equalization, image[i], W[i], H[i], dtype, &d_src, &dtype_src) &&
+                 remap_device(d_src, W[i], H[i], 1, dtype_src, r->map[i], sgm_device_image(m, i), r->W*r->H,
                               MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT, NULL);
         }
         // (its copy waits for the launches: the images may go when this returns)
@@ -749,9 +808,13 @@ bool mrcal_amd_rectification_point_cloud_of_images(mrcal_amd_rectification_t* r,
     if(!remap_arguments_ok(width0, height0, 1, dtype, r->W, r->H, MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT) ||
        !remap_arguments_ok(width1, height1, 1, dtype, r->W, r->H, MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT))
         return false;
+    if(!equalization_arguments_ok(r->equalization, width0, height0, 1, dtype) ||
+       !equalization_arguments_ok(r->equalization, width1, height1, 1, dtype))
+        return false;
+    const int dtype_matched = equalize_dtype_out(r->equalization.method, dtype);
     mrcal_amd_point_cloud_t* c = rectification_cloud(r);
     if(c == NULL) return false;
-    mrcal_amd_stereo_sgm_t* m = mrcal_amd_stereo_sgm_create(r->W, r->H, dtype, sgm_params);
+    mrcal_amd_stereo_sgm_t* m = mrcal_amd_stereo_sgm_create(r->W, r->H, dtype_matched, sgm_params);
     if(m == NULL) return false;
     if(!mrcal_amd_stereo_sgm_set_speckle_filter(m, speckle_window_size, speckle_range)) { mrcal_amd_stereo_sgm_destroy(m); return false; }
     // the disparities are the matcher's: its scale, and everything from its smallest disparity up is valid
@@ -761,19 +824,24 @@ bool mrcal_amd_rectification_point_cloud_of_images(mrcal_amd_rectification_t* r,
     p.disparity_scaled_max = 0x7FFF;
     const void* image[2] = { image0, image1 };
     const int   W[2] = { width0, width1 }, H[2] = { height0, height1 };
+    const bool  equalized_colors = r->equalization.method != EQUALIZE_METHOD_NONE && p.image != NULL && p.image == image0 &&
+                                   p.image_width == width0 && p.image_height == height0 && p.image_channels == 1 && p.image_dtype == dtype;
+    const void* d_color = NULL;
     bool ok = true;
     {
         DeviceBuffers tmp;
         for(int i = 0; i < 2 && ok; i++)
         {
-            uint8_t* d_src = NULL;
-            ok = tmp.upload(&d_src, (const uint8_t*)image[i], (size_t)W[i]*H[i]*dtype_size(dtype)) &&
-                 remap_device(d_src, W[i], H[i], 1, dtype, r->map[i], sgm_device_image(m, i), r->W*r->H,
+            const void* d_src = NULL; int dtype_src = dtype;
+            ok = upload_equalized(tmp, r->equalization, image[i], W[i], H[i], dtype, &d_src, &dtype_src) &&
+                 remap_device(d_src, W[i], H[i], 1, dtype_src, r->map[i], sgm_device_image(m, i), r->W*r->H,
                               MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT, NULL);
+            // colours from image0 itself: from the equalized one, where it lies
+            if(ok && i == 0 && equalized_colors) { d_color = d_src; p.image_dtype = dtype_src; }
         }
         const int16_t* d_disparity = NULL;
         // (the cloud waits for its launches, and so for these: the images and the matcher may go when this returns)
-        ok = ok && sgm_match_device_resident(m, &d_disparity) && point_cloud_compute_device(c, (const uint16_t*)d_disparity, &p, N);
+        ok = ok && sgm_match_device_resident(m, &d_disparity) && point_cloud_compute_device(c, (const uint16_t*)d_disparity, &p, N, d_color);
         if(!ok) (void)hipDeviceSynchronize();
     }
     mrcal_amd_stereo_sgm_destroy(m);

@@ -1,0 +1,228 @@
+"""Image equalization: what the reference's tools do to a raw image before they rectify and match it.
+
+    image = mrcal_amd.equalize_clahe(image)                          # cv2.createCLAHE(), setClipLimit(8), apply()
+    image = mrcal_amd.equalize_stretch(image16)                      # uint16 -> uint8, mrcal_image_uint8_load()'s stretch
+
+    with mrcal_amd.ImageEqualizer(image.shape, image.dtype, method = 'clahe') as e:    # the buffers are made once
+        for image in images:
+            equalized = e.apply(image)
+
+    # or where the images go next, on the device, between the upload and the remap:
+    with mrcal_amd.Rectification(models, models_rectified) as r:
+        disparity = r.disparity(image0, image1, disparity_max = 128, equalization = 'clahe')
+    q1, diagnostics = mrcal_amd.match_feature(image0, image1, q0, H10 = H10, search_radius1 = 200, template_size1 = 41,
+                                              equalization = 'clahe')
+
+The definition, to the bit, is in include/mrcal_amd.h ("equalization"); the kernels are csrc/equalize.hip, and there is
+no CPU fallback for them. Out of scope: the reference's 'fieldscale' equalization, colour input.
+"""
+import ctypes as C
+import numpy as np
+
+from ._cabi import _ptr
+
+
+EQUALIZE_NONE, EQUALIZE_CLAHE, EQUALIZE_STRETCH = 0, 1, 2
+_METHODS = {None: EQUALIZE_NONE, 'clahe': EQUALIZE_CLAHE, 'stretch': EQUALIZE_STRETCH}
+_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1}
+_MAX_PIXELS = 1 << 28
+_MAX_TILES = 4096
+
+
+class _EqualizeParams(C.Structure):
+    """mrcal_amd_equalize_params_t"""
+    _fields_ = [("method", C.c_int), ("clip_limit", C.c_double), ("tiles_x", C.c_int), ("tiles_y", C.c_int)]
+
+
+def _libs():
+    from . import _lib, _api
+    return _lib, _api
+
+
+def _method(method, none_allowed):
+    if isinstance(method, str) and method in _METHODS:
+        return _METHODS[method]
+    if method is None and none_allowed:
+        return EQUALIZE_NONE
+    raise Exception(f"equalize(): the method must be {'None, ' if none_allowed else ''}'clahe' or 'stretch', not {method!r}")
+
+
+def _shape(shape):
+    try:    shape = tuple(int(n) for n in shape)
+    except TypeError: shape = ()
+    if len(shape) != 2:
+        raise Exception(f"equalize(): shape must be (H,W), got {shape}")
+    if shape[0] <= 0 or shape[1] <= 0 or shape[0]*shape[1] > _MAX_PIXELS:
+        raise Exception(f"equalize(): images of {shape[1]} x {shape[0]} pixels cannot be equalized")
+    return shape
+
+
+def _dtype(dtype):
+    try:    dtype = np.dtype(dtype)
+    except TypeError: dtype = None
+    if dtype not in _DTYPES or dtype is None:
+        raise Exception(f"equalize(): images are uint8 or uint16, not {dtype}")
+    return dtype
+
+
+def _clahe_arguments(clip_limit, tiles):
+    """-> (clip_limit, tiles_x, tiles_y): the refusals of csrc/equalize_plan.hpp that need no image"""
+    if isinstance(clip_limit, (bool, np.bool_)) or not isinstance(clip_limit, (int, float, np.integer, np.floating)) or clip_limit != clip_limit:
+        raise Exception(f"equalize(): clip_limit must be a number. Got {clip_limit!r}")
+    try:    t = tuple(tiles)
+    except TypeError: t = ()
+    if len(t) != 2 or any(isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) for n in t):
+        raise Exception(f"equalize(): tiles must be two integers (tiles_x, tiles_y). Got {tiles!r}")
+    if t[0] < 1 or t[1] < 1 or t[0]*t[1] > _MAX_TILES:
+        raise Exception(f"equalize(): tiles must be at least (1,1) and at most {_MAX_TILES} in all. Got ({t[0]},{t[1]})")
+    return float(clip_limit), int(t[0]), int(t[1])
+
+
+def _tiles_fit(shape, tiles_x, tiles_y):
+    H, W = shape
+    if W % tiles_x == 0 and H % tiles_y == 0:
+        return
+    px, py = tiles_x - W % tiles_x, tiles_y - H % tiles_y
+    if px > W - 1 or py > H - 1:
+        raise Exception(f"equalize(): an image of {W} x {H} pixels is too small for ({tiles_x},{tiles_y}) tiles: it would be padded by "
+                        f"({px},{py}) pixels, and a reflection reaches ({W - 1},{H - 1})")
+
+
+def _image(image, what="image", shape=None, dtype=None):
+    """a grey uint8 or uint16 image, or the refusal"""
+    if not isinstance(image, np.ndarray):
+        raise Exception(f"equalize(): '{what}' must be a numpy array")
+    if image.ndim == 3:
+        raise Exception(f"equalize(): '{what}' must be a grayscale image of shape (H,W), got {image.shape}: convert a colour image first")
+    if image.ndim != 2:
+        raise Exception(f"equalize(): '{what}' must be a grayscale image of shape (H,W), got {image.shape}")
+    if image.dtype not in _DTYPES:
+        raise Exception(f"equalize(): '{what}' must have dtype uint8 or uint16, not {image.dtype}")
+    _shape(image.shape)
+    if shape is not None and (image.shape != shape or image.dtype != dtype):
+        raise Exception(f"equalize(): this equalizer was made for images of shape {shape} and dtype {dtype}, got {image.shape} and {image.dtype}")
+
+
+def equalization_params(equalization, clahe_clip_limit, clahe_tiles, images=()):
+    """The keywords equalization = None | 'clahe' | 'stretch', clahe_clip_limit, clahe_tiles that Rectification and
+    FeatureMatcher take -> (mrcal_amd_equalize_params_t or None, the dtype the equalized images have or None). Every
+    refusal is made here, before any device work"""
+    method = _method(equalization, True)
+    if method == EQUALIZE_NONE:
+        return None, None
+    clip_limit, tiles_x, tiles_y = _clahe_arguments(clahe_clip_limit, clahe_tiles)
+    for i, image in enumerate(images):
+        _image(image, f"image{i}")
+        if method == EQUALIZE_CLAHE:
+            _tiles_fit(image.shape, tiles_x, tiles_y)
+    dtype = None
+    if len(images) > 0:
+        dtype = np.dtype(np.uint8) if method == EQUALIZE_STRETCH else images[0].dtype
+    return _EqualizeParams(method, clip_limit, tiles_x, tiles_y), dtype
+
+
+class ImageEqualizer:
+    """equalize_clahe() and equalize_stretch(), resident: the device buffers for one image size and type are made once,
+and every apply() reuses them.
+
+    shape: (H,W); dtype: uint8 or uint16; method: 'clahe' (clip_limit = 8.0, tiles = (8,8)) or 'stretch'.
+      .apply(image, out=None)       -> the equalized image: of the image's dtype for 'clahe', uint8 for 'stretch'
+      .stage_milliseconds()         how long the histograms, the LUTs and the interpolation of the last apply() took on
+                                    the device, without the copies ('stretch': the extremes, 0, the map)"""
+
+    def __init__(self, shape, dtype, method='clahe', *, clip_limit=8.0, tiles=(8, 8)):
+        self.handle = None
+        self.shape, self.dtype = _shape(shape), _dtype(dtype)
+        m = _method(method, False)
+        clip_limit, tiles_x, tiles_y = _clahe_arguments(clip_limit, tiles)
+        if m == EQUALIZE_CLAHE:
+            _tiles_fit(self.shape, tiles_x, tiles_y)
+        self.dtype_out = np.dtype(np.uint8) if m == EQUALIZE_STRETCH else self.dtype
+        lib, api = _libs()
+        self._L, self._api = lib.lib, api
+        p = _EqualizeParams(m, clip_limit, tiles_x, tiles_y)
+        f = self._L.mrcal_amd_equalizer_create
+        f.restype, f.argtypes = C.c_void_p, [C.c_int]*3 + [C.c_void_p]
+        self.handle = f(self.shape[1], self.shape[0], _DTYPES[self.dtype], C.addressof(p))
+        if not self.handle:
+            self.handle = None
+            raise Exception("equalize() failed:" + api._last_error())
+        self._L.mrcal_amd_equalizer_destroy.restype, self._L.mrcal_amd_equalizer_destroy.argtypes = None, [C.c_void_p]
+
+    def apply(self, image, out=None):
+        if self.handle is None:
+            raise Exception("this ImageEqualizer has been closed")
+        _image(image, "image", self.shape, self.dtype)
+        _out(out, self.shape, self.dtype_out)
+        a = np.ascontiguousarray(image)
+        dense = out is not None and out.flags.c_contiguous and out is not image and not np.shares_memory(out, a)
+        o = out if dense else np.zeros(self.shape, dtype=self.dtype_out)
+        f = self._L.mrcal_amd_equalizer_apply
+        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*3
+        if not f(self.handle, _ptr(a), _ptr(o)):
+            raise Exception("equalize() failed:" + self._api._last_error())
+        if out is None:
+            return o
+        if o is not out: out[...] = o
+        return out
+
+    def stage_milliseconds(self):
+        if self.handle is None:
+            raise Exception("this ImageEqualizer has been closed")
+        ms = np.zeros((3,), dtype=np.float32)
+        f = self._L.mrcal_amd_equalizer_stage_milliseconds
+        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2
+        if not f(self.handle, _ptr(ms)):
+            raise Exception("equalize() failed:" + self._api._last_error())
+        return dict(zip(("histogram", "lut", "apply"), (float(x) for x in ms)))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._L.mrcal_amd_equalizer_destroy(self.handle)
+            self.handle = None
+    def __del__(self):
+        try:    self.close()
+        except Exception: pass
+    def __enter__(self): return self
+    def __exit__(self, *a): self.close()
+
+
+def _out(out, shape, dtype):
+    if out is not None and (not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != dtype):
+        raise Exception(f"equalize(): 'out' must be a numpy array of shape {shape} and dtype {np.dtype(dtype)}")
+
+
+def equalize_clahe(image, *, clip_limit=8.0, tiles=(8, 8), out=None):
+    """Contrast-limited adaptive histogram equalization of a grey image: what cv2.createCLAHE(clipLimit = clip_limit,
+tileGridSize = tiles).apply(image) is published to compute (OpenCV's clahe.cpp), which the reference's mrcal-stereo
+--clahe and mrcal-triangulate --clahe apply with a clip limit of 8 to every image before they rectify and match it.
+uint8 or uint16 (H,W) in; the same shape and dtype out: a new array, or `out`.
+
+  1. if W is no multiple of tiles[0] or H none of tiles[1], the image is padded on the right and at the bottom up to
+     the next multiple, BOTH sides, the divisible one by a whole tiles[.], by reflection (numpy.pad(mode = 'reflect'))
+  2. per tile: the histogram is clipped at max(int(clip_limit tile_pixels / histSize), 1), the excess is handed back
+     evenly, the remainder to every step-th bin, and the LUT is the prefix sum scaled to the value range in float32
+  3. per pixel: the LUTs of the four tiles around it, read at its value, interpolated bilinearly in float32
+
+The exact arithmetic, operation by operation, is in include/mrcal_amd.h ("equalization"). cv2 is no part of this
+project: the tests hold the kernels (csrc/equalize.hip) to two numpy transcriptions of that text
+(tests/equalize_checker.py), EQUAL in every pixel, and not to cv2 itself. clip_limit <= 0: nothing is clipped. Integer
+histograms, no floating-point atomics: the same bits on every call. The one-shot form of ImageEqualizer.apply()."""
+    _image(image)
+    clip_limit, tiles_x, tiles_y = _clahe_arguments(clip_limit, tiles)
+    _tiles_fit(image.shape, tiles_x, tiles_y)
+    _out(out, image.shape, image.dtype)
+    with ImageEqualizer(image.shape, image.dtype, 'clahe', clip_limit=clip_limit, tiles=(tiles_x, tiles_y)) as e:
+        return e.apply(image, out=out)
+
+
+def equalize_stretch(image, *, out=None):
+    """The image's values stretched to 0..255: out = uint8(0.5 + (v - min) 255 / (max - min)) in float32, truncated, with
+min and max over the whole image. uint8 or uint16 (H,W) in, uint8 out: a new array, or `out`. What the reference's
+mrcal_image_uint8_load() does to a 16-bit image (image.c), and mrcal-stereo --equalization stretch; unlike it, the true
+extremes are used (its loop misses a maximum that comes before the first smaller pixel) and a constant image, for which
+it divides by zero, gives all zeros. The one-shot form of ImageEqualizer.apply()."""
+    _image(image)
+    _out(out, image.shape, np.uint8)
+    with ImageEqualizer(image.shape, image.dtype, 'stretch') as e:
+        return e.apply(image, out=out)

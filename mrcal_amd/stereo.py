@@ -48,6 +48,7 @@ import numpy as np
 
 from ._cabi import _ptr
 from .poseutils import compose_Rt
+from .equalization import equalization_params, _EqualizeParams
 
 
 class _Point2(C.Structure):
@@ -224,7 +225,11 @@ class Rectification:
       .point_cloud(disparity, ...)     stereo_point_cloud() of it: the kept points, their colours and pixel indices
       .point_cloud_of_images(image0, image1, ...)   the same from the image pair; the rectified images and the
                                        disparities stay on the device
-      .point_cloud_stage_milliseconds()  how long the mask, the scan and the scatter of the last cloud took"""
+      .point_cloud_stage_milliseconds()  how long the mask, the scan and the scatter of the last cloud took
+    rectify(), disparity() and point_cloud_of_images() take equalization = None | 'clahe' | 'stretch',
+    clahe_clip_limit = 8.0, clahe_tiles = (8,8): each raw image (grayscale, uint8 or uint16) is equalized on the device
+    between its upload and the remap (equalize_clahe(), equalize_stretch()), the same bits as equalizing it first.
+    With 'stretch' the rectified images are uint8. None: nothing of it runs"""
 
     def __init__(self, models, models_rectified):
         self.handle = None
@@ -260,6 +265,18 @@ class Rectification:
         if self.handle is None:
             raise Exception("this Rectification has been closed")
 
+    def _equalize(self, params):
+        """what the calls that follow do to their raw images; None: nothing, which a handle that was never told
+        otherwise does by itself"""
+        if params is None and not getattr(self, "_equalizing", False):
+            return
+        f = self._L.mrcal_amd_rectification_set_equalization
+        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2
+        p = params if params is not None else _EqualizeParams(0, 8.0, 8, 8)
+        if not f(self.handle, C.addressof(p)):
+            raise Exception("equalize() failed:" + self._api._last_error())
+        self._equalizing = params is not None
+
     def maps(self):
         self._open()
         maps = np.zeros((2, self.Nel, self.Naz, 2), dtype=np.float32)
@@ -269,9 +286,14 @@ class Rectification:
             raise Exception("rectification_maps() failed:" + self._api._last_error())
         return maps
 
-    def rectify(self, image0, image1, out=None):
-        """(image0 rectified, image1 rectified): linear interpolation, 0 outside the images. out: the two arrays to fill"""
+    def rectify(self, image0, image1, out=None, *, equalization=None, clahe_clip_limit=8.0, clahe_tiles=(8, 8)):
+        """(image0 rectified, image1 rectified): linear interpolation, 0 outside the images. out: the two arrays to fill.
+        equalization: of the raw images, on the device, before the remap (grayscale, uint8 or uint16, then)"""
         self._open()
+        if equalization is None:
+            eq, dtype_out = None, None
+        else:
+            eq, dtype_out = equalization_params(equalization, clahe_clip_limit, clahe_tiles, (image0, image1))
         a0, w0, h0, c0, t0 = _image_arguments(image0, "image0")
         a1, w1, h1, c1, t1 = _image_arguments(image1, "image1")
         if (c0, t0) != (c1, t1):
@@ -279,7 +301,9 @@ class Rectification:
         shape = (self.Nel, self.Naz) if c0 == 1 else (self.Nel, self.Naz, 3)
         if out is not None and len(out) != 2:
             raise Exception("'out' must be a pair of arrays")
-        (o0, r0), (o1, r1) = (_output_array(None if out is None else out[i], shape, a0.dtype, False) for i in (0, 1))
+        (o0, r0), (o1, r1) = (_output_array(None if out is None else out[i], shape, a0.dtype if dtype_out is None else dtype_out, False)
+                              for i in (0, 1))
+        self._equalize(eq)
         f = self._L.mrcal_amd_rectification_rectify
         f.restype  = C.c_bool
         f.argtypes = [C.c_void_p]*4 + [C.c_int]*2 + [C.c_void_p] + [C.c_int]*6 + [C.c_void_p]
@@ -298,10 +322,12 @@ class Rectification:
                             disparity_scaled_min=disparity_scaled_min, disparity_scaled_max=disparity_scaled_max,
                             _rectification=self)
 
-    def disparity(self, image0, image1, *, speckle_window_size=0, speckle_range=0, **params):
+    def disparity(self, image0, image1, *, speckle_window_size=0, speckle_range=0,
+                  equalization=None, clahe_clip_limit=8.0, clahe_tiles=(8, 8), **params):
         """stereo_matching_sgm(*rectify(image0, image1), **params), the same bits: int16 (Nel, Naz). The rectified images
         are made and matched on the device and do not cross to the host. image0, image1: grayscale, uint8 or uint16.
-        speckle_window_size > 0: the disparity image is filtered there too (filter_speckles())"""
+        speckle_window_size > 0: the disparity image is filtered there too (filter_speckles()).
+        equalization: of the raw images, there too, before the remap"""
         self._open()
         speckle = _speckle_keywords(speckle_window_size, speckle_range)
         p = _sgm_params(**params)
@@ -311,6 +337,8 @@ class Rectification:
         if image0.dtype != image1.dtype:
             raise Exception(f"stereo_matching_sgm(): image0 and image1 must have the same dtype, got {image0.dtype} and {image1.dtype}")
         dtype = _SGM_DTYPES[_sgm_dtype(image0.dtype)]
+        eq = None if equalization is None else equalization_params(equalization, clahe_clip_limit, clahe_tiles, (image0, image1))[0]
+        self._equalize(eq)
         a0, a1 = np.ascontiguousarray(image0), np.ascontiguousarray(image1)
         out = np.zeros((self.Nel, self.Naz), dtype=np.int16)
         images = (self.handle, _ptr(a0), a0.shape[1], a0.shape[0], _ptr(a1), a1.shape[1], a1.shape[0], dtype, C.addressof(p))
@@ -347,13 +375,16 @@ class Rectification:
         return _cloud_read(self._L.mrcal_amd_rectification_point_cloud_read, self.handle, self._api, N.value, float32, image)
 
     def point_cloud_of_images(self, image0, image1, *, color_image=None, frame='ref', dtype=np.float64,
-                                  range_min=None, range_max=None, speckle_window_size=0, speckle_range=0, **sgm_params):
+                                  range_min=None, range_max=None, speckle_window_size=0, speckle_range=0,
+                                  equalization=None, clahe_clip_limit=8.0, clahe_tiles=(8, 8), **sgm_params):
         """point_cloud(disparity(image0, image1, ...), image0 = color_image or image0, disparity_scale = 16,
         disparity_min = disparity_min, ...), the same bits: (points, color, index). The pair is rectified, matched, on
         request filtered, and made a cloud of on the device: neither the rectified images nor the disparities cross to the
         host. image0, image1: grayscale, uint8 or uint16. color_image: the image of camera 0 the colours come from, gray or
         BGR, of its imager size; None: image0. A negative disparity_min is refused: stereo_range()'s cast to uint16 has no
-        meaning for negative disparities"""
+        meaning for negative disparities. equalization: of the raw images, on the device, before the remap; the colours
+        are then those of the EQUALIZED image0 (as in the reference's mrcal-stereo), unless a color_image is given,
+        which is used as it is"""
         self._open()
         speckle = _speckle_keywords(speckle_window_size, speckle_range)
         p_sgm = _sgm_params(**sgm_params)
@@ -365,10 +396,18 @@ class Rectification:
         if image0.dtype != image1.dtype:
             raise Exception(f"stereo_matching_sgm(): image0 and image1 must have the same dtype, got {image0.dtype} and {image1.dtype}")
         sgm_dtype = _SGM_DTYPES[_sgm_dtype(image0.dtype)]
-        image = _cloud_image(image0 if color_image is None else color_image, "image0" if color_image is None else "color_image", self._models)
-        rmin, rmax, Rt, float32 = _cloud_frame(self._models_rectified, self._models, range_min, range_max, frame, dtype)
-        p, keep = _cloud_params(0, 0, 0, rmin, rmax, Rt, float32, image)       # (the disparity fields: the library's, from the matcher's)
+        eq, dtype_equalized = (None, None) if equalization is None else \
+            equalization_params(equalization, clahe_clip_limit, clahe_tiles, (image0, image1))
         a0, a1 = np.ascontiguousarray(image0), np.ascontiguousarray(image1)
+        # (image0 as its own colour image: the SAME array, which the library then takes equalized, where it lies)
+        image = _cloud_image(a0 if color_image is None else color_image, "image0" if color_image is None else "color_image", self._models)
+        rmin, rmax, Rt, float32 = _cloud_frame(self._models_rectified, self._models, range_min, range_max, frame, dtype)
+        if eq is not None and color_image is not None and image[0].ctypes.data == a0.ctypes.data:
+            image = (image[0].copy(),) + tuple(image[1:])                           # (given: used as it is, also where it is image0)
+        p, keep = _cloud_params(0, 0, 0, rmin, rmax, Rt, float32, image)       # (the disparity fields: the library's, from the matcher's)
+        if eq is not None and color_image is None and dtype_equalized != a0.dtype:
+            image = (np.zeros((0,), dtype=dtype_equalized),) + tuple(image[1:])      # (what the colours are read into: 'stretch' makes uint8)
+        self._equalize(eq)
         N = C.c_int(0)
         f = self._L.mrcal_amd_rectification_point_cloud_of_images
         f.restype  = C.c_bool
@@ -636,17 +675,27 @@ of features of image0 in image1.
           degenerate; 3 the template is outside image1; 4 outside image0. A row whose status is not 0 is NaN. No
           status raises: only arguments that are wrong whatever the data do.
           diagnostics=True: a third value, a list of N dicts as match_feature() returns them
+    equalization = None | 'clahe' | 'stretch', clahe_clip_limit = 8.0, clahe_tiles = (8,8): both images (uint8 or uint16
+    then) are equalized on the device after the upload (equalize_clahe(), equalize_stretch()), the same bits as
+    equalizing them first; with 'stretch' the templates are uint8. None: nothing of it runs.
     What a match is: match_feature()"""
 
-    def __init__(self, image0, image1):
+    def __init__(self, image0, image1, *, equalization=None, clahe_clip_limit=8.0, clahe_tiles=(8, 8)):
         self.handle = None
         (a0, w0, h0), (a1, w1, h1), dtype = _match_images(image0, image1)
+        eq, dtype_equalized = (None, None) if equalization is None else \
+            equalization_params(equalization, clahe_clip_limit, clahe_tiles, (image0, image1))
         lib, api = _libs()
         self._L, self._api = lib.lib, api
-        self._dtype = a0.dtype
-        f = self._L.mrcal_amd_feature_matcher_create
-        f.restype, f.argtypes = C.c_void_p, [C.c_void_p, C.c_int, C.c_int]*2 + [C.c_int]
-        self.handle = f(_ptr(a0), w0, h0, _ptr(a1), w1, h1, dtype)
+        self._dtype = a0.dtype if eq is None else dtype_equalized
+        if eq is None:
+            f = self._L.mrcal_amd_feature_matcher_create
+            f.restype, f.argtypes = C.c_void_p, [C.c_void_p, C.c_int, C.c_int]*2 + [C.c_int]
+            self.handle = f(_ptr(a0), w0, h0, _ptr(a1), w1, h1, dtype)
+        else:
+            f = self._L.mrcal_amd_feature_matcher_create_equalized
+            f.restype, f.argtypes = C.c_void_p, [C.c_void_p, C.c_int, C.c_int]*2 + [C.c_int, C.c_void_p]
+            self.handle = f(_ptr(a0), w0, h0, _ptr(a1), w1, h1, dtype, C.addressof(eq))
         if not self.handle:
             self.handle = None
             raise Exception("match_feature() failed:" + api._last_error())
@@ -699,7 +748,7 @@ of features of image0 in image1.
 
 
 def match_feature(image0, image1, q0, *, search_radius1, template_size1, q1_estimate=None, H10=None, method=None,
-                  visualize=False, return_plot_args=False):
+                  visualize=False, return_plot_args=False, equalization=None, clahe_clip_limit=8.0, clahe_tiles=(8, 8)):
     """Finds in image1 the pixel q1 that shows what the pixel q0 of image0 shows: (q1, diagnostics)
 
 image0, image1: grayscale (H,W). q0 (2,). Exactly one of q1_estimate (2,), a guess of q1, and H10 (3,3), a homography
@@ -740,12 +789,16 @@ Departures from the reference:
     returns inf or nan there;
   - the subpixel fit is the closed form of the reference's 9-point least squares (on the -1,0,1 grid the normal
     equations are diagonal but for the coupling of c00, c20, c02);
-  - visualize and return_plot_args are refused: gnuplotlib is not part of this project.
+  - visualize and return_plot_args are refused: gnuplotlib is not part of this project;
+  - equalization = 'clahe' | 'stretch' (with clahe_clip_limit, clahe_tiles) equalizes both images on the device first, as
+    the reference's mrcal-triangulate --clahe does on the host before it calls this: FeatureMatcher.
 Reference: mrcal.match_feature()"""
     if visualize or return_plot_args:
         raise Exception("match_feature(visualize=True) is not available: gnuplotlib is not part of mrcal_amd")
     tw, th = _template_size(template_size1)
     _match_images(image0, image1)
+    if equalization is not None:
+        equalization_params(equalization, clahe_clip_limit, clahe_tiles, (image0, image1))
     if (H10 is None) == (q1_estimate is None):
         raise Exception("Exactly one of (q1_estimate,H10) must be given")
     q0 = np.asarray(q0, dtype=np.float64)
@@ -766,7 +819,7 @@ Reference: mrcal.match_feature()"""
     corners = np.array(((tmin[0], tmin[1]), (tmin[0], tmax[1]), (tmax[0], tmin[1]), (tmax[0], tmax[1])))
     _checkdims(image0.shape, "image0", *apply_homography(H01[0], corners).astype(np.float32))
 
-    with FeatureMatcher(image0, image1) as matcher:
+    with FeatureMatcher(image0, image1, equalization=equalization, clahe_clip_limit=clahe_clip_limit, clahe_tiles=clahe_tiles) as matcher:
         q1, status, diagnostics = matcher.match(q0[np.newaxis], search_radius1=search_radius1, template_size1=(tw, th),
                                                 q1_estimate=q1_estimate, H10=H10, method=method, diagnostics=True)
     if status[0] in (MATCH_OUTSIDE_IMAGE1, MATCH_OUTSIDE_IMAGE0):       # (a corner that is not a number)
