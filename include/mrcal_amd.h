@@ -1406,6 +1406,88 @@ mrcal_amd_feature_matcher_create_equalized(const void* image0, int width0, int h
                                            const void* image1, int width1, int height1, int dtype,
                                            const mrcal_amd_equalize_params_t* params);
 
+/* ---- regional statistics: the residuals of a solve, binned over a grid of each imager ----
+   What mrcal-calibrate-cameras looks at between the solve and the .cameramodel file (mrcal/calibration.py:1720-1866,
+   _report_regional_statistics()). Here it is csrc/regional_stats.hip, planned on the host by
+   csrc/regional_stats_plan.hpp, all the cameras of a problem in one pass. This text is the authority;
+   tests/valid_region_checker.py restates it in plain loops.
+
+   The inputs are the problem's: x at its current state (the board measurements, weighted as they are in x), the
+   board observations (qx, qy, weight) and the camera of each. Camera c has an imager of W x H pixels and a grid of
+   gridn_width x gridn_height cells; gridn_height <= 0: int(round(H/W*gridn_width)), the product (H/W)*gridn_width in
+   double, halves to even, for each camera by its own imager. Both must be >= 2.
+     - the centres: cx[i] = i*((W-1)/(gridn_width-1)) for i < gridn_width-1, one division and one multiplication in
+       double, and cx[gridn_width-1] = W-1; cy[j] likewise from H and gridn_height: np.linspace(), and
+       sample_imager(). wcell = (W-1)/(gridn_width-1), hcell = (H-1)/(gridn_height-1)
+     - a corner takes part if its weight is > 0. It is in cell (i,j) of its camera iff |qx - cx[i]| < wcell/2 and
+       |qy - cy[j]| < hcell/2, each a subtraction, an absolute value and a comparison in double, both strict: a corner
+       on a border between cells is in neither, a corner beyond the outermost half cells in none. Every cell is
+       asked on its own, as the reference asks: with the centres rounded, a corner within an ulp of a border can meet
+       the inequalities of both cells beside it, and then it is in both
+     - per cell, over the x and y residuals of its corners pooled, n values (even): count = n; n <= 5: mean = stdev =
+       0; else mean = sum/n and stdev = sqrt(sum((v - mean)^2)/n), the population deviation in two passes
+     - the order of the sums: the cell's corners in ascending measurement index, value v = 2k the x and v = 2k+1 the
+       y residual of its k-th corner; lane l of 64 adds the values l, l+64, l+128, ... in that order, the 64 lanes are
+       added by the butterfly s += s[lane ^ 32], ^ 16, ^ 8, ^ 4, ^ 2, ^ 1. The deviations (each d*d rounded before it
+       is added) go the same way. It depends on nothing but the inputs; no floating-point atomic anywhere: the same
+       bits on every call. (Integer atomics count the corners of a cell; a count has no order.)
+   _create() evaluates x at the problem's state and keeps mean, stdev and count of every camera on the device; the
+   problem may be destroyed afterwards. Refused: a problem without board observations (only they are binned: point
+   observations and regularization are ignored), a problem that is a shard, a grid dimension < 2, more than 2^20 cells
+   in all. _grid(): camera icam's grid. _get(): its arrays, [gridn_height][gridn_width], any of them NULL to skip.
+   _binning_ms(): the device time of _create()'s launches */
+typedef struct mrcal_amd_regional_statistics mrcal_amd_regional_statistics_t;
+mrcal_amd_regional_statistics_t* mrcal_amd_regional_statistics_create(mrcal_amd_problem_t* problem, int gridn_width, int gridn_height);
+bool   mrcal_amd_regional_statistics_grid(const mrcal_amd_regional_statistics_t* s, int icam_intrinsics, int* gridn_width, int* gridn_height);
+bool   mrcal_amd_regional_statistics_get(const mrcal_amd_regional_statistics_t* s, int icam_intrinsics,
+                                         double* mean, double* stdev, int32_t* count);
+double mrcal_amd_regional_statistics_binning_ms(const mrcal_amd_regional_statistics_t* s);
+void   mrcal_amd_regional_statistics_destroy(mrcal_amd_regional_statistics_t* s);
+
+/* ---- valid-intrinsics region: making one from a solve, and applying one ----
+   Making (mrcal/calibration.py:1611-1717, _compute_valid_intrinsics_region()). _mask(): on the device, the grid of
+   sample_imager() (the centres above) is unprojected through (lensmodel, intrinsics) to unit vectors, multiplied by
+   distance (distance <= 0: left as they are, and evaluated at infinity), given to the uncertainty context for the
+   worst-direction standard deviation; then, a cell a lane: an uncertainty that is not finite counts as 1e9;
+   mask = uncertainty < threshold_uncertainty, and unless the lens model is LENSMODEL_SPLINED_*, also mean <
+   threshold_mean (signed, as the reference's code has it), stdev < threshold_stdev, count > threshold_count, from the
+   regional statistics of camera icam_intrinsics, which must be on the same grid (s may be NULL for a splined model).
+   mask [gridn_height][gridn_width] bytes is what crosses to the host, and the uncertainties as evaluate() gives them
+   if uncertainty is not NULL.
+
+   The outline of a mask, _region_outline() (host code, csrc/region_outline.cpp). cv2 is no part of this project; this
+   is the definition, and no equality with cv2.findContours() is claimed:
+     - the set cells fall into 8-connected components
+     - the outline of a component is its outer border, followed from cell centre to cell centre beginning at its
+       topmost cell, the leftmost of that row, clockwise on the screen (x to the right, y down): with the 8 directions
+       numbered clockwise from east, a cell entered by direction d looks at its neighbours clockwise beginning at
+       d + 5 (one past the way back) and goes to the first that is set; the first cell begins looking at east. The
+       walk ends when it stands on the first cell about to repeat its first move. A hole has no part in it
+     - a spur one cell wide is walked out and back; a component of one cell is that one cell
+     - only the cells where the direction changes are kept, as (x,y) = (column, row); the first vertex is not repeated
+     - the area of a component is the shoelace area of these vertices; the component with the largest area is the one
+       reported, the first in raster order (of the components' first cells) among equals. A line of cells, and a
+       single cell, have area 0 and fewer than 3 vertices: closed they have fewer than 4 points, an empty region
+   It returns the number of vertices and writes the first min(count, capacity) of them; -1: bad arguments.
+
+   Applying (mrcal/model_analysis.py:2106-2149, is_within_valid_intrinsics_region()). vertices [Nvertices][2] is a
+   closed contour (the last vertex repeats the first), the edges join consecutive vertices. A point is inside by the
+   even-odd rule, STRICTLY inside: a point on an edge or on a vertex is outside, as with shapely's contains(). A lane
+   a point; up to _lds_vertices() = 4096 vertices are held in LDS, a contour with more is read from global memory by
+   the same code. With integer vertices and integer-valued points (pixel centres), all below 2^24 in size, the
+   decision is exact: every product is an integer a double holds. For other points the decision within rounding of
+   an edge is not specified. No vertices: every point is outside. _contains(): N points q [N][2] of the host.
+   _image(): every pixel centre of a W x H image in one launch, out [H][W] */
+bool mrcal_amd_valid_region_mask(mrcal_amd_uncertainty_t* u, const mrcal_amd_regional_statistics_t* s, int icam_intrinsics,
+                                 const mrcal_lensmodel_t* lensmodel, const double* intrinsics, int W, int H,
+                                 int gridn_width, int gridn_height, double distance,
+                                 double threshold_uncertainty, double threshold_mean, double threshold_stdev, double threshold_count,
+                                 uint8_t* mask, double* uncertainty);
+int  mrcal_amd_region_outline(const uint8_t* mask, int gridn_width, int gridn_height, int32_t* vertices, int capacity, int64_t* area2);
+int  mrcal_amd_valid_region_lds_vertices(void);
+bool mrcal_amd_valid_region_contains(uint8_t* out, const double* q, int64_t N, const double* vertices, int Nvertices);
+bool mrcal_amd_valid_region_image(uint8_t* out, int W, int H, const double* vertices, int Nvertices);
+
 #ifdef __cplusplus
 }
 #endif

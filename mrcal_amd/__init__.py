@@ -84,7 +84,8 @@ from .stereo import (rectified_resolution, rectified_system, rectification_maps,
 from .equalization import equalize_clahe, equalize_stretch, ImageEqualizer
 from .image_transforms import (scale_focal__best_pinhole_fit, pinhole_model_for_reprojection, image_transformation_map,
                                transform_image)
-from .utils import sample_imager, sample_imager_unproject, write_point_cloud_as_ply, mapping_file_framenocameraindex
+from .utils import (sample_imager, sample_imager_unproject, write_point_cloud_as_ply, mapping_file_framenocameraindex,
+                    measurements_board, residuals_board, measurements_point, residuals_point)
 from .chessboard import (find_chessboard_corners, chessboard_corner_candidates, ChessboardDetector, chessboard_grid,
                          compute_chessboard_corners, load_image_gray)
 
@@ -97,6 +98,9 @@ from .poseutils import (identity_R, identity_r, identity_Rt, identity_rt, R_from
 from .cameramodel import cameramodel, CameramodelParseException
 from .calibration import (ref_calibration_object, align_procrustes_points_Rt01, traverse_sensor_links,
                           estimate_monocular_calobject_poses_Rt_tocam, estimate_joint_frame_poses, seed_stereographic)
+from . import calibration
+from .valid_region import (RegionalStatistics, valid_intrinsics_regions, is_within_valid_intrinsics_region,
+                           valid_intrinsics_mask, imagergrid_using)
 
 
 def gpu_available():

@@ -325,3 +325,30 @@ def seed_stereographic(imagersizes, focal_estimate, indices_frame_camera, observ
     return (np.array([i[1] for i in intrinsics]),
             _pu.rt_from_Rt(Rt_cam_ref).reshape(-1, 6),
             rt_ref_frame)
+
+
+# ----------------------------------------------------------------------------- after the solve: the valid-intrinsics region
+def _report_regional_statistics(model, gridn_width=20, gridn_height=None):
+    """(mean, stdev, count, using): the residuals of the model's solve that belong to its camera, binned over a
+    gridn_width x gridn_height grid of its imager, each (gridn_height,gridn_width); using: the gnuplotlib expression of
+    imagergrid_using(). gridn_height=None: int(round(H/W*gridn_width)). On the GPU (mrcal_amd.RegionalStatistics, which
+    bins all the cameras of a solve at once). Reference: mrcal/calibration.py:1720-1866"""
+    from .valid_region import report_regional_statistics
+    return report_regional_statistics(model, gridn_width, gridn_height)
+
+
+def _compute_valid_intrinsics_region(model, threshold_uncertainty, threshold_mean, threshold_stdev, threshold_count,
+                                     distance, gridn_width=30, gridn_height=None, *,
+                                     uncertainty=None, statistics=None, return_details=False):
+    """The valid-intrinsics region of the model's camera: a closed contour (N,2) int32 in pixels, or np.zeros((0,2)) for an
+    empty region. A cell of the grid is valid where the worst-direction projection uncertainty at `distance`
+    (<= 0: at infinity) is below threshold_uncertainty and, unless the lens model is splined, the cell's residuals have
+    mean < threshold_mean (signed), stdev < threshold_stdev and count > threshold_count; the region is the outline of
+    the largest 8-connected set of valid cells (include/mrcal_amd.h, "valid-intrinsics region": our own definition of
+    the outline, not cv2's). uncertainty: a ProjectionUncertainty of this model, statistics: a RegionalStatistics of its
+    solve on this grid, to use instead of making them. return_details: also dict(mask, uncertainty, mean, stdev, count).
+    Reference: mrcal/calibration.py:1611-1717"""
+    from .valid_region import compute_valid_intrinsics_region
+    return compute_valid_intrinsics_region(model, threshold_uncertainty, threshold_mean, threshold_stdev, threshold_count,
+                                           distance, gridn_width, gridn_height,
+                                           uncertainty=uncertainty, statistics=statistics, return_details=return_details)

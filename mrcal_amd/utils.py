@@ -136,3 +136,72 @@ Host code. Reference: mrcal.mapping_file_framenocameraindex() (mrcal/utils.py)""
             numbers = range(len(files))
         mapping.update(zip(files, [(n, icamera) for n in numbers]))
     return mapping
+
+
+def _all_measurements(optimization_inputs):
+    from . import optimizer_callback
+    return optimizer_callback(**optimization_inputs, no_jacobian=True, no_factorization=True)[1]
+
+
+def measurements_board(optimization_inputs, *, icam_intrinsics=None, x=None, return_observations=False, i_cam=None):
+    """The board measurements of a solve, (N,2): the WEIGHTED reprojection errors of every board corner that is not an
+    outlier (weight > 0), of all cameras or of camera icam_intrinsics; x: the measurement vector if it is at hand,
+    else optimizer_callback() evaluates it. return_observations: also the pixels (N,2) they were observed at. No board
+    observations: (0,2) arrays. i_cam: the older name of icam_intrinsics. A numpy selection on the host.
+    Reference: mrcal.measurements_board()"""
+    from . import measurement_index_boards, num_measurements_boards
+    observations_board = optimization_inputs.get('observations_board')
+    if observations_board is None or np.size(observations_board) == 0:
+        empty = np.zeros((0, 2), dtype=float)
+        return (empty, np.zeros((0, 2), dtype=float)) if return_observations else empty
+    observations_board = np.asarray(observations_board)
+    if i_cam is not None:
+        icam_intrinsics = i_cam
+    if x is None:
+        x = _all_measurements(optimization_inputs)
+    imeas0 = measurement_index_boards(0, **optimization_inputs)
+    Nmeas  = num_measurements_boards(**optimization_inputs)
+    x_board = np.asarray(x)[imeas0:imeas0 + Nmeas].reshape(observations_board.shape[:-1] + (2,))
+    keep = observations_board[..., 2] > 0.0
+    if icam_intrinsics is not None:
+        camera = np.asarray(optimization_inputs['indices_frame_camintrinsics_camextrinsics'])[:, 1]
+        keep[camera != icam_intrinsics, ...] = False
+    if return_observations:
+        return x_board[keep], observations_board[keep][..., :2]
+    return x_board[keep]
+
+
+def residuals_board(*args, residuals=None, **kwargs):
+    """measurements_board() under its older name, with x called residuals"""
+    return measurements_board(*args, x=residuals, **kwargs)
+
+
+def measurements_point(optimization_inputs, *, icam_intrinsics=None, x=None, return_observations=False):
+    """The measurements of the discrete point observations of a solve, (N,2): the weighted reprojection errors of every
+    point observation that is not an outlier, of all cameras or of camera icam_intrinsics. Otherwise as
+    measurements_board(). Reference: mrcal.measurements_point()"""
+    from . import measurement_index_points, num_measurements_points
+    observations_point = optimization_inputs.get('observations_point')
+    if observations_point is None or np.size(observations_point) == 0:
+        empty = np.zeros((0, 2), dtype=float)
+        return (empty, np.zeros((0, 2), dtype=float)) if return_observations else empty
+    observations_point = np.asarray(observations_point)
+    if x is None:
+        x = _all_measurements(optimization_inputs)
+    Nobservations = len(observations_point)
+    imeas0 = measurement_index_points(0, **optimization_inputs)
+    Nmeas  = num_measurements_points(**optimization_inputs)
+    # (the reprojection error is the first two measurements of an observation)
+    x_point = np.asarray(x)[imeas0:imeas0 + Nmeas].reshape(Nobservations, -1)[:, :2]
+    keep = observations_point[..., 2] > 0.0
+    if icam_intrinsics is not None:
+        camera = np.asarray(optimization_inputs['indices_point_camintrinsics_camextrinsics'])[:, 1]
+        keep[camera != icam_intrinsics] = False
+    if return_observations:
+        return x_point[keep], observations_point[keep][..., :2]
+    return x_point[keep]
+
+
+def residuals_point(*args, residuals=None, **kwargs):
+    """measurements_point() under its older name, with x called residuals"""
+    return measurements_point(*args, x=residuals, **kwargs)
