@@ -1315,7 +1315,44 @@ bool mrcal_amd_rectification_point_cloud_stage_milliseconds(mrcal_amd_rectificat
    _candidates() and e; *found = 0: no board, which is no error. _stage_milliseconds(): upload, response, candidates,
    refine (the device's events), grid (the host's clock; 0 after _candidates()) of the last call.
    mrcal_amd_chessboard_grid(): e alone, on the host, for N points that are given: it needs no device. response
-   orders the seeds (NULL: the order given), status NULL: all 0 */
+   orders the seeds (NULL: the order given), status NULL: all 0
+
+   The image pyramid (opt-in: pyramid_levels = n > 0; with n = 0 everything above is all there is, to the bit). For
+   corners that are blurred over several pixels, or boards whose squares cover hundreds of pixels: a..e at one scale
+   see them badly or not at all. What mrgingham's decimation level is in the reference.
+     p1. Decimation. Level 0 is I. Level l+1 has floor(W_l/2) x floor(H_l/2) pixels,
+           I_{l+1}(x,y) = (I_l(2x,2y) + I_l(2x+1,2y) + I_l(2x,2y+1) + I_l(2x+1,2y+1) + 2) >> 2
+         in integers, the same for uint8 and uint16; an odd last row or column is dropped. A point q of level l+1 lies
+         at up(q) = 2 q + 0.5 of level l. pyramid_levels = n asks for the levels 0..n, n in 0..8; every level has at
+         least 32 pixels a side, so n <= the largest n with min(W >> n, H >> n) >= 32, and a larger one is refused
+         with that number in the message
+     p2. Where the board is looked for: coarsest first. For L = n, n-1, .., 0: a..e on I_L, with the same
+         threshold_256, nms_radius and max_candidates, in pixels of level L. The first L at which e yields a complete
+         board is the detection level; no such L: no board
+     p3. Descent, each corner on its own. A corner starts with level L and its position q_L there. For l = L-1 .. 0 a
+         corner whose level is l+1 is refined on I_l by d, started from the FLOAT up(q_{l+1}): the window, the
+         weights, the 20 iterations and the stop rule are d's, and "left" is +-3.5 px around that start. The corner
+         moves to level l (position: the refined point) when the status is 0 and max(|dx|,|dy|) <= tau between the
+         refined point and its start, in pixels of level l; otherwise it stays where it is for good. Reported: the
+         last accepted position carried to level 0 by repeated up(), and the level it was accepted at
+     tau = 0.3 px (CB_DESCENT_AGREEMENT in csrc/chessboard_plan.hpp). Measured with the numpy checker
+     (tests/chessboard_pyramid_checker.py) on rendered 7 x 5 boards of 30, 60 and 110 px squares turned by 17 degrees,
+     noise of 1 grey level, then a Gaussian blur of sigma px: with sigma <= 3 every step of every corner disagrees by
+     at most 0.200 px (reached at sigma = 0) and every corner reaches level 0; at sigma = 4 the steps to level 0 disagree
+     by 0.003 .. 0.66 px with nothing between that separates good from bad, and tau = 0.3 brings 17 or 18 of 35 corners
+     to level 0; at sigma = 6 every refinement on level 0 leaves its box (status 2) and every corner stays at level 1.
+     So tau stays at the 0.3 px it was proposed with (the table).
+     The level is what mrcal.compute_chessboard_corners() reads as the weight 2^-level.
+   _create_pyramid(): _create() and pyramid_levels; the pool grows by the level images (1/3 of the image) and the
+   board's corner records. _find_board_pyramid(): uploads the image, makes the levels, p2 and p3; corners
+   (board_height, board_width, 2) in level-0 pixels, levels (board_height, board_width) int32, *detection_level (-1:
+   not found). On a detector with pyramid_levels = 0: _find_board()'s corners to the bit, levels 0. _candidates() and
+   _find_board() of a detector with levels look at level 0 alone. _read_response() and _stage_milliseconds() speak
+   of the level that was looked at last: the detection level, or 0 when no board was found (the upload is the one of
+   the image). _read_level(): the image of a level as the last call left it, dense, of the image's type (levels above
+   0 exist after _find_board_pyramid()). _pyramid_milliseconds(): the decimation and the descent by the device's
+   events; per_level [pyramid_levels + 1]: the host's clock around each level tried (a..e and the read-back of its
+   candidates), 0 for a level that was not tried */
 typedef struct mrcal_amd_chessboard_detector mrcal_amd_chessboard_detector_t;
 typedef struct
 {
@@ -1337,6 +1374,18 @@ bool mrcal_amd_chessboard_detector_read_response(mrcal_amd_chessboard_detector_t
                                                  int32_t* candidate_xy);
 bool mrcal_amd_chessboard_detector_stage_milliseconds(mrcal_amd_chessboard_detector_t* d, float* milliseconds /*5*/);
 void mrcal_amd_chessboard_detector_destroy(mrcal_amd_chessboard_detector_t* d);
+#define MRCAL_AMD_CHESSBOARD_MAX_PYRAMID_LEVELS 8
+mrcal_amd_chessboard_detector_t*
+mrcal_amd_chessboard_detector_create_pyramid(int width, int height, int bytes_per_pixel,
+                                             const mrcal_amd_chessboard_params_t* params, int pyramid_levels,
+                                             size_t free_device_bytes);
+bool mrcal_amd_chessboard_detector_find_board_pyramid(mrcal_amd_chessboard_detector_t* d, const void* image,
+                                                      int board_width, int board_height, double* corners,
+                                                      int32_t* levels /* [board_height*board_width] */,
+                                                      int* detection_level, int* found);
+bool mrcal_amd_chessboard_detector_read_level(mrcal_amd_chessboard_detector_t* d, int level, void* image_out);
+bool mrcal_amd_chessboard_detector_pyramid_milliseconds(mrcal_amd_chessboard_detector_t* d, float* decimate, float* descent,
+                                                        float* per_level /* [pyramid_levels + 1] */);
 bool mrcal_amd_chessboard_grid(int N, const double* q, const int32_t* response, const int32_t* status,
                                int board_width, int board_height, int* found, double* corners);
 

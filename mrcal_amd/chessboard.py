@@ -33,6 +33,7 @@ _CB_MIN_SIDE = 32
 _CB_MAX_PIXELS = 1 << 28
 _CB_NMS_RADIUS_MAX = 16
 _CB_MAX_CANDIDATES = 65536
+_CB_MAX_LEVELS = 8
 _CB_DTYPES = {np.dtype(np.uint8): 1, np.dtype(np.uint16): 2}
 _CB_STAGES = ("upload", "response", "candidates", "refine", "grid")
 STATUS_OK, STATUS_SINGULAR, STATUS_LEFT_WINDOW = 0, 1, 2
@@ -76,6 +77,22 @@ def _params(threshold_256, nms_radius, max_candidates):
     return _Params(int(threshold_256), int(nms_radius), int(max_candidates))
 
 
+def _pyramid_levels(pyramid_levels, shape=None):
+    """the refusals of chessboard_pyramid_plan(); shape: (H,W), already looked at by _shape()"""
+    n = pyramid_levels
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n <= _CB_MAX_LEVELS:
+        raise Exception(f"find_chessboard_corners(): pyramid_levels must be in 0..{_CB_MAX_LEVELS}, got {n}")
+    if shape is not None:
+        H, W = shape
+        most = 0
+        while most < _CB_MAX_LEVELS and min(W >> (most + 1), H >> (most + 1)) >= _CB_MIN_SIDE: most += 1
+        if n > most:
+            raise Exception(f"find_chessboard_corners(): an image of {W} x {H} pixels is too small for pyramid_levels = {n}: "
+                            f"level {most + 1} would have {W >> (most + 1)} x {H >> (most + 1)} pixels, at least "
+                            f"{_CB_MIN_SIDE} x {_CB_MIN_SIDE}; at most pyramid_levels = {most}")
+    return int(n)
+
+
 def _image(image, shape=None, dtype=None):
     if not isinstance(image, np.ndarray) or image.ndim != 2:
         raise Exception("find_chessboard_corners() accepts ONLY grayscale images of shape (H,W)" +
@@ -101,29 +118,44 @@ class ChessboardDetector:
     """find_chessboard_corners() resident: the device buffers for one shape and dtype of image are made once and every
 call reuses them.
 
-    shape: (H,W) of the images; dtype: uint8 or uint16; threshold_256, nms_radius, max_candidates: as in
-    find_chessboard_corners()
+    shape: (H,W) of the images; dtype: uint8 or uint16; threshold_256, nms_radius, max_candidates, pyramid_levels: as
+    in find_chessboard_corners()
       .candidates(image)        -> (q (N,2) float64, response (N,) int32, status (N,) int32); .overflow: more than
-                                   max_candidates were found, and the first in row-major order were kept
-      .find_board(image, W, H=None)  -> (H,W,2) float64, or None
-      .response()               -> (the (H,W) int32 response image, its maximum, the pixels (N,2) int32 of the candidates)
-                                   of the last call
+                                   max_candidates were found, and the first in row-major order were kept. Level 0 alone
+      .find_board(image, W, H=None, return_levels=False)  -> (H,W,2) float64, or None; with return_levels
+                                   (corners, levels (H,W) int32) or (None, None). With pyramid_levels > 0 the board is
+                                   looked for from the coarsest level down and each corner is refined as far down as
+                                   the levels agree; .detection_level: where it was found (None: nowhere)
+      .response()               -> (the int32 response image, its maximum, the pixels (N,2) int32 of the candidates)
+                                   of the level the last call looked at last: (H,W) without a pyramid. After a
+                                   find_board() through the levels the pixels are None: their number stays inside
+      .level_image(level)       the image of a level of the last call, as the device holds it
       .stage_milliseconds()     how long the upload, the response, the candidates, the refinement (on the device) and
-                                the lattice (on the host; 0 after candidates()) of the last call took
+                                the lattice (on the host; 0 after candidates()) of the last call took; with a pyramid,
+                                of the level it looked at last
+      .pyramid_milliseconds()   of the last find_board() through the levels: dict(decimate, descent: on the device;
+                                per_level: the host's clock around each level tried, 0 for the others)
       .close(); a context manager"""
 
-    def __init__(self, shape, dtype=np.uint8, *, threshold_256=51, nms_radius=7, max_candidates=4096):
+    def __init__(self, shape, dtype=np.uint8, *, threshold_256=51, nms_radius=7, max_candidates=4096, pyramid_levels=0):
         self.handle = None
         self.overflow, self._N = False, 0
+        self.detection_level, self._last_level = None, 0
         self.shape = _shape(shape)
         self.dtype = _dtype(dtype)
         p = _params(threshold_256, nms_radius, max_candidates)
+        self.pyramid_levels = _pyramid_levels(pyramid_levels, self.shape)
         self.max_candidates = p.max_candidates
         lib, api = _libs()
         self._L, self._api = lib.lib, api
-        f = self._L.mrcal_amd_chessboard_detector_create
-        f.restype, f.argtypes = C.c_void_p, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
-        self.handle = f(self.shape[1], self.shape[0], _CB_DTYPES[self.dtype], C.addressof(p), 0)
+        if self.pyramid_levels == 0:
+            f = self._L.mrcal_amd_chessboard_detector_create
+            f.restype, f.argtypes = C.c_void_p, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+            self.handle = f(self.shape[1], self.shape[0], _CB_DTYPES[self.dtype], C.addressof(p), 0)
+        else:
+            f = self._L.mrcal_amd_chessboard_detector_create_pyramid
+            f.restype, f.argtypes = C.c_void_p, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t]
+            self.handle = f(self.shape[1], self.shape[0], _CB_DTYPES[self.dtype], C.addressof(p), self.pyramid_levels, 0)
         if not self.handle:
             self.handle = None
             raise Exception("find_chessboard_corners() failed:" + api._last_error())
@@ -144,29 +176,72 @@ call reuses them.
         if not f(self.handle, _ptr(image), C.addressof(N), C.addressof(overflow), _ptr(q), _ptr(response), _ptr(status)):
             raise Exception("find_chessboard_corners() failed:" + self._api._last_error())
         self.overflow, self._N = bool(overflow.value), N.value
+        self.detection_level, self._last_level = None, 0
         return q[:N.value].copy(), response[:N.value].copy(), status[:N.value].copy()
 
-    def find_board(self, image, W, H=None):
+    def find_board(self, image, W, H=None, return_levels=False):
         self._open()
         W, H = _board(W, H)
         image = _image(image, self.shape, self.dtype)
         corners = np.zeros((H, W, 2), dtype=np.float64)
         found = C.c_int(0)
-        f = self._L.mrcal_amd_chessboard_detector_find_board
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        if not f(self.handle, _ptr(image), W, H, C.addressof(found), _ptr(corners)):
+        if self.pyramid_levels == 0 and not return_levels:
+            f = self._L.mrcal_amd_chessboard_detector_find_board
+            f.restype, f.argtypes = C.c_bool, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+            if not f(self.handle, _ptr(image), W, H, C.addressof(found), _ptr(corners)):
+                raise Exception("find_chessboard_corners() failed:" + self._api._last_error())
+            self.detection_level, self._last_level = (0 if found.value else None), 0
+            return corners if found.value else None
+        levels = np.zeros((H, W), dtype=np.int32)
+        detection_level = C.c_int(-1)
+        f = self._L.mrcal_amd_chessboard_detector_find_board_pyramid
+        f.restype, f.argtypes = C.c_bool, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if not f(self.handle, _ptr(image), W, H, _ptr(corners), _ptr(levels), C.addressof(detection_level), C.addressof(found)):
             raise Exception("find_chessboard_corners() failed:" + self._api._last_error())
-        return corners if found.value else None
+        self.detection_level = detection_level.value if found.value else None
+        self._last_level = detection_level.value if found.value else 0
+        # (the candidates response() speaks of are the last level's; their number is not handed out by this call)
+        self._N = None
+        if not return_levels:
+            return corners if found.value else None
+        return (corners, levels) if found.value else (None, None)
+
+    def level_shape(self, level):
+        """(H,W) of a level of the pyramid"""
+        return self.shape[0] >> level, self.shape[1] >> level
+
+    def level_image(self, level):
+        self._open()
+        if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or not 0 <= level <= self.pyramid_levels:
+            raise Exception(f"find_chessboard_corners(): this detector has the levels 0..{self.pyramid_levels}, and level {level} was asked for")
+        out = np.zeros(self.level_shape(int(level)), dtype=self.dtype)
+        f = self._L.mrcal_amd_chessboard_detector_read_level
+        f.restype, f.argtypes = C.c_bool, [C.c_void_p, C.c_int, C.c_void_p]
+        if not f(self.handle, int(level), _ptr(out)):
+            raise Exception("find_chessboard_corners() failed:" + self._api._last_error())
+        return out
+
+    def pyramid_milliseconds(self):
+        self._open()
+        decimate, descent = C.c_float(0), C.c_float(0)
+        per_level = np.zeros((self.pyramid_levels + 1,), dtype=np.float32)
+        f = self._L.mrcal_amd_chessboard_detector_pyramid_milliseconds
+        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*4
+        if not f(self.handle, C.addressof(decimate), C.addressof(descent), _ptr(per_level)):
+            raise Exception("find_chessboard_corners() failed:" + self._api._last_error())
+        return dict(decimate=float(decimate.value), descent=float(descent.value), per_level=[float(x) for x in per_level])
 
     def response(self):
         self._open()
-        R = np.zeros(self.shape, dtype=np.int32)
+        R = np.zeros(self.level_shape(self._last_level), dtype=np.int32)
         xy = np.zeros((self.max_candidates, 2), dtype=np.int32)
         Rmax = C.c_int32(0)
         f = self._L.mrcal_amd_chessboard_detector_read_response
         f.restype, f.argtypes = C.c_bool, [C.c_void_p]*4
         if not f(self.handle, _ptr(R), C.addressof(Rmax), _ptr(xy)):
             raise Exception("find_chessboard_corners() failed:" + self._api._last_error())
+        if self._N is None:
+            return R, int(Rmax.value), None
         return R, int(Rmax.value), xy[:self._N].copy()
 
     def stage_milliseconds(self):
@@ -202,7 +277,8 @@ around its start), with NaN coordinates. The N = 1 case of ChessboardDetector.ca
         return d.candidates(image)
 
 
-def find_chessboard_corners(image, W, H=None, *, threshold_256=51, nms_radius=7, max_candidates=4096):
+def find_chessboard_corners(image, W, H=None, *, threshold_256=51, nms_radius=7, max_candidates=4096, pyramid_levels=0,
+                            return_levels=False):
     """The W x H corners of the calibration board in a grey image: an (H,W,2) float64 array, or None
 
 image: (height,width) uint8 or uint16; colour images are refused. W, H: the corners a row and a column of the board
@@ -214,13 +290,21 @@ A corner: a local maximum (window 2 nms_radius + 1) of the integer ChESS respons
 image, above threshold_256/256 of the largest response, refined in double by the fixed point of cv2.cornerSubPix (an
 11 x 11 Gaussian window on the original image). At most max_candidates candidates are looked at. The definition, to the
 bit: include/mrcal_amd.h, "chessboard corners". The image kernels run on the GPU (csrc/chessboard.hip; no CPU
-fallback); the lattice among the candidates is found on the host. The one-shot form of ChessboardDetector.find_board()."""
+fallback); the lattice among the candidates is found on the host. The one-shot form of ChessboardDetector.find_board().
+
+pyramid_levels = n > 0 (0..8; every level keeps 32 pixels a side): for corners blurred over several pixels and boards
+whose squares cover hundreds of pixels. The image is halved n times (2 x 2 means), the board is looked for from the
+coarsest level down, and each of its corners is then refined level by level towards the image for as long as the
+refinement agrees with where it started within 0.3 px ("chessboard corners", p1-p3). The corners are always in pixels
+of the image. return_levels: (corners, levels) or (None, None); levels (H,W) int32: the level each corner's position
+was taken at, what compute_chessboard_corners() writes as the level whose weight is 2^-level. All 0 without a pyramid."""
     image = _image(image)
     _params(threshold_256, nms_radius, max_candidates)
+    _pyramid_levels(pyramid_levels, image.shape)
     _board(W, H)
     with ChessboardDetector(image.shape, image.dtype, threshold_256=threshold_256, nms_radius=nms_radius,
-                            max_candidates=max_candidates) as d:
-        return d.find_board(image, W, H)
+                            max_candidates=max_candidates, pyramid_levels=pyramid_levels) as d:
+        return d.find_board(image, W, H, return_levels=return_levels)
 
 
 def chessboard_grid(q, W, H=None, *, response=None, status=None):
@@ -331,12 +415,15 @@ def _detect_into_vnl(W, H, globs_per_camera, detector_params):
                 key = (image.shape, image.dtype)
                 if key not in detectors:
                     detectors[key] = ChessboardDetector(image.shape, image.dtype, **detector_params)
-                corners = detectors[key].find_board(image, W, H)
+                d = detectors[key]
+                if d.pyramid_levels == 0: corners = d.find_board(image, W, H)
+                else:                     corners, levels = d.find_board(image, W, H, return_levels=True)
                 if corners is None:
                     yield f"{filename} - - -\n"
                 else:
-                    for x, y in corners.reshape(-1, 2):
-                        yield f"{filename} {float(x)!r} {float(y)!r} 0\n"        # (repr: the float64 comes back to the bit)
+                    if d.pyramid_levels == 0: levels = np.zeros(corners.shape[:2], dtype=np.int32)
+                    for (x, y), level in zip(corners.reshape(-1, 2), levels.ravel()):
+                        yield f"{filename} {float(x)!r} {float(y)!r} {int(level)}\n"        # (repr: the float64 comes back to the bit)
     finally:
         for d in detectors.values():
             d.close()
@@ -369,7 +456,8 @@ an image without a whole board), atomically: to a temporary file that is renamed
 exist already; otherwise the number is not used: the images go through one device one after the other. The reference's
 refusal of W != H ("mrgingham currently accepts ONLY square grids") does NOT apply: this detector finds rectangular
 boards. Binary PGM images (P5, 8 and 16 bit) are read natively; other formats through PIL where it is installed.
-detector_params: threshold_256, nms_radius, max_candidates of find_chessboard_corners().
+detector_params: threshold_256, nms_radius, max_candidates, pyramid_levels of find_chessboard_corners(), each as a
+keyword of its own or all in one dict, detector_params={'pyramid_levels': 3}. With pyramid_levels > 0 the level column holds the level each corner was refined at, which comes back as the weight 2^-level.
 
 Returns (observations (N,H,W,3) of (x, y, weight), indices_frame_camera (N,2) int32, contiguous and sorted, the N
 paths). Reference: mrcal/calibration.py, compute_chessboard_corners()"""
@@ -377,6 +465,9 @@ paths). Reference: mrcal/calibration.py, compute_chessboard_corners()"""
         raise Exception(f"weight_column_kind must be one of ('level','weight',None); got '{weight_column_kind}'")
     if Npoint_observations_per_board_min is None:
         Npoint_observations_per_board_min = 2*min(W, H)
+    if isinstance(detector_params.get("detector_params"), dict):
+        # (the detector's keywords given as ONE dict, detector_params={'pyramid_levels': 3}, or each on its own)
+        detector_params = dict(detector_params.pop("detector_params"), **detector_params)
 
     globs_per_camera = [os.path.normpath(g) for g in globs_per_camera]
     Ncameras = len(globs_per_camera)
@@ -397,7 +488,9 @@ paths). Reference: mrcal/calibration.py, compute_chessboard_corners()"""
             raise Exception("I was asked to use an existing cache file, but it couldn't be read. jobs<0, so I do not recompute")
         if weight_column_kind == 'weight':
             raise Exception("Need to run the detector, so I will get a column of decimation levels, but weight_column_kind == 'weight'")
-        _params(**dict(dict(threshold_256=51, nms_radius=7, max_candidates=4096), **detector_params))
+        checked = dict(dict(threshold_256=51, nms_radius=7, max_candidates=4096, pyramid_levels=0), **detector_params)
+        _pyramid_levels(checked.pop("pyramid_levels"))
+        _params(**checked)
         sys.stderr.write("Computing chessboard corners with find_chessboard_corners() of the images matching:\n   {}\n".format(' '.join(globs_per_camera)))
         if corners_cache_vnl is not None:
             # (in the cache's own directory, so that the rename is one)

@@ -18,7 +18,14 @@
 //                          are not stored
 //   cb_refine_kernel<T>    a wavefront a candidate; the 121 window points two to a lane (k and k + 64), the five sums
 //                          added in that order in the lane and then across the lanes by a butterfly (xor 32 .. 1),
-//                          which leaves every lane the same bits; all 20 iterations inside the launch
+//                          which leaves every lane the same bits; all 20 iterations inside the launch. With DESCENT
+//                          (p3 of the definition) a wavefront is a corner of the board that was found: the start is
+//                          the float up(q) of the corner's position a level above, and the corner moves to this level
+//                          when the refinement agrees with its start within CB_DESCENT_AGREEMENT
+//   cb_decimate_kernel<T>  level l+1 of the pyramid from level l (p1). Where a row of level l is whole 16-byte words a
+//                          lane loads one word of each of two rows (16 or 8 pixels a row) and stores 8 bytes of outputs:
+//                          every pixel read once, every output written once, consecutive lanes consecutive words.
+//                          Otherwise (a row length that leaves the words unaligned) a lane an output pixel
 // Integer bookkeeping, the compaction of point_cloud.hip; no floating-point atomics, no scratch.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -238,14 +245,25 @@ __device__ __forceinline__ double cb_wave_sum(double v)
     return v;
 }
 
-template<class T>
+// DESCENT false: the candidates of part d, from their integer pixels xy; q and status are written.
+// DESCENT true: the max_candidates corners of the board, from the float up(q) of those whose level is to_level + 1 (the
+// others are left alone); q and level are updated where the corner moves to to_level (p3). total, xy, status: not read
+template<class T, bool DESCENT>
 __global__ __launch_bounds__(CB_THREADS)
 void cb_refine_kernel(int W, int H, unsigned max_candidates, const T* __restrict__ I, const uint32_t* __restrict__ total,
-                      const int32_t* __restrict__ xy, double* __restrict__ q, int32_t* __restrict__ status)
+                      const int32_t* __restrict__ xy, double* __restrict__ q, int32_t* __restrict__ status,
+                      int32_t* __restrict__ level, int to_level)
 {
     const unsigned c = blockIdx.x*(CB_THREADS/64) + (threadIdx.x >> 6);
-    const unsigned n = *total < max_candidates ? *total : max_candidates;
-    if(c >= n) return;                                  // (the whole wavefront)
+    if(DESCENT)
+    {
+        if(c >= max_candidates || level[c] != to_level + 1) return;     // (the whole wavefront)
+    }
+    else
+    {
+        const unsigned n = *total < max_candidates ? *total : max_candidates;
+        if(c >= n) return;                              // (the whole wavefront)
+    }
     const int lane = threadIdx.x & 63;
     constexpr int SIDE = 2*CB_WINDOW + 1, POINTS = SIDE*SIDE;
     double wi[2], wj[2], ww[2];
@@ -257,7 +275,8 @@ void cb_refine_kernel(int W, int H, unsigned max_candidates, const T* __restrict
         wi[h] = (double)i; wj[h] = (double)j;
         ww[h] = k < POINTS ? exp(-(wi[h]/CB_WINDOW)*(wi[h]/CB_WINDOW))*exp(-(wj[h]/CB_WINDOW)*(wj[h]/CB_WINDOW)) : 0.0;
     }
-    const double startx = (double)xy[2*c], starty = (double)xy[2*c + 1];
+    const double startx = DESCENT ? 2.0*q[2*c]     + 0.5 : (double)xy[2*c];
+    const double starty = DESCENT ? 2.0*q[2*c + 1] + 0.5 : (double)xy[2*c + 1];
     double qx = startx, qy = starty;
     int st = CB_STATUS_OK;
     for(int it=0; it<CB_REFINE_ITERATIONS; it++)
@@ -283,12 +302,64 @@ void cb_refine_kernel(int W, int H, unsigned max_candidates, const T* __restrict
         if(!(fabs(qx - startx) <= 3.5 && fabs(qy - starty) <= 3.5)) { st = CB_STATUS_LEFT; break; }
         if(dx*dx + dy*dy < 1e-5*1e-5) break;
     }
-    if(lane == 0)
+    if(DESCENT)
+    {
+        // (every lane holds the same qx, qy and st)
+        const bool moves = st == CB_STATUS_OK && fmax(fabs(qx - startx), fabs(qy - starty)) <= CB_DESCENT_AGREEMENT;
+        if(lane == 0 && moves) { q[2*c] = qx; q[2*c + 1] = qy; level[c] = to_level; }
+    }
+    else if(lane == 0)
     {
         q[2*c]     = st == CB_STATUS_OK ? qx : (double)NAN;
         q[2*c + 1] = st == CB_STATUS_OK ? qy : (double)NAN;
         status[c]  = st;
     }
+}
+
+__device__ __forceinline__ uint32_t cb_quad(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return (a + b + c + d + 2u) >> 2; }
+
+// two rows' words -> the word of outputs: 4 pixels of uint8 each, or 2 of uint16
+template<class T>
+__device__ __forceinline__ uint32_t cb_decimate_words(uint32_t t0, uint32_t t1, uint32_t b0, uint32_t b1);
+template<>
+__device__ __forceinline__ uint32_t cb_decimate_words<uint8_t>(uint32_t t0, uint32_t t1, uint32_t b0, uint32_t b1)
+{
+    return  cb_quad(t0 & 255u, (t0 >> 8) & 255u, b0 & 255u, (b0 >> 8) & 255u)
+         | (cb_quad((t0 >> 16) & 255u, t0 >> 24, (b0 >> 16) & 255u, b0 >> 24) << 8)
+         | (cb_quad(t1 & 255u, (t1 >> 8) & 255u, b1 & 255u, (b1 >> 8) & 255u) << 16)
+         | (cb_quad((t1 >> 16) & 255u, t1 >> 24, (b1 >> 16) & 255u, b1 >> 24) << 24);
+}
+template<>
+__device__ __forceinline__ uint32_t cb_decimate_words<uint16_t>(uint32_t t0, uint32_t t1, uint32_t b0, uint32_t b1)
+{
+    return cb_quad(t0 & 65535u, t0 >> 16, b0 & 65535u, b0 >> 16) | (cb_quad(t1 & 65535u, t1 >> 16, b1 & 65535u, b1 >> 16) << 16);
+}
+
+// in: (H_in, W_in) with W_in sizeof(T) a multiple of 16; out: (H_out, W_in/2). words_per_row = W_in sizeof(T)/16
+template<class T>
+__global__ __launch_bounds__(CB_THREADS)
+void cb_decimate_wide_kernel(unsigned words_per_row, unsigned H_out, const uint4* __restrict__ in, uint2* __restrict__ out)
+{
+    const size_t k = (size_t)blockIdx.x*CB_THREADS + threadIdx.x;
+    if(k >= (size_t)words_per_row*H_out) return;
+    const size_t y = k/words_per_row, w = k - y*words_per_row;
+    const uint4 t = in[(2*y)*words_per_row + w], b = in[(2*y + 1)*words_per_row + w];
+    uint2 o;
+    o.x = cb_decimate_words<T>(t.x, t.y, b.x, b.y);
+    o.y = cb_decimate_words<T>(t.z, t.w, b.z, b.w);
+    out[k] = o;
+}
+
+// any row length: a lane an output pixel
+template<class T>
+__global__ __launch_bounds__(CB_THREADS)
+void cb_decimate_kernel(int W_in, int W_out, int H_out, const T* __restrict__ in, T* __restrict__ out)
+{
+    const size_t k = (size_t)blockIdx.x*CB_THREADS + threadIdx.x;
+    if(k >= (size_t)W_out*H_out) return;
+    const size_t y = k/W_out, x = k - y*W_out;
+    const T* t = in + (2*y)*W_in + 2*x;
+    out[k] = (T)cb_quad(t[0], t[1], t[W_in], t[W_in + 1]);
 }
 
 bool cb_have_device()
@@ -308,15 +379,25 @@ struct mrcal_amd_chessboard_detector
 {
     DeviceBuffers  mem;
     uint8_t*       pool = NULL;
-    ChessboardPlan plan;
+    ChessboardPyramidPlan pyramid;      // pyramid.level[0] is the plan of a detector without a pyramid
     // the last call
     int            N = -1;              // candidates kept
     bool           overflow = false;
     float          grid_ms = 0.f;
+    int            level = 0;           // the level that was looked at last: what N, q, the response and the stages are of
     std::vector<double>  q;
     std::vector<int32_t> response, status;
     hipEvent_t     event[5] = { NULL, NULL, NULL, NULL, NULL };    // around the upload, after the response, the candidates, the refinement
-    ~mrcal_amd_chessboard_detector() { for(hipEvent_t e : event) if(e != NULL) (void)hipEventDestroy(e); }
+    // ... with a pyramid. event[0], event[1] are around the start of the level looked at last then
+    bool           pyramid_ran = false;
+    float          level_ms[CB_MAX_LEVELS + 1] = {};               // the host's clock around each level tried: a..e and the read-back
+    hipEvent_t     pyramid_event[6] = { NULL, NULL, NULL, NULL, NULL, NULL };  // around the upload, the decimation, the descent
+    bool           descended = false;
+    ~mrcal_amd_chessboard_detector()
+    {
+        for(hipEvent_t e : event)         if(e != NULL) (void)hipEventDestroy(e);
+        for(hipEvent_t e : pyramid_event) if(e != NULL) (void)hipEventDestroy(e);
+    }
 };
 
 static bool cb_given(const mrcal_amd_chessboard_detector* d)
@@ -326,14 +407,14 @@ static bool cb_given(const mrcal_amd_chessboard_detector* d)
     return false;
 }
 
-// parts a..d of the image on the host, into the detector's own arrays
-static bool cb_run(mrcal_amd_chessboard_detector* d, const void* image)
+// parts a..d of a level, into the detector's own arrays. image: the host's, uploaded first (level 0, and what a
+// detector without a pyramid does); NULL: the level's image is on the device already
+static bool cb_run_level(mrcal_amd_chessboard_detector* d, int level, const void* image)
 {
     d->N = -1;
     d->grid_ms = 0.f;
-    if(image == NULL) { set_error("find_chessboard_corners(): the image is NULL"); return false; }
-    if(!cb_have_device()) return false;
-    const ChessboardPlan& p = d->plan;
+    d->level = level;
+    const ChessboardPlan& p = d->pyramid.level[level];
     uint8_t*  d_image = d->pool + p.image;
     int32_t*  R       = (int32_t*)(d->pool + p.response);
     uint64_t* words   = (uint64_t*)(d->pool + p.words);
@@ -346,8 +427,17 @@ static bool cb_run(mrcal_amd_chessboard_detector* d, const void* image)
     const dim3 tiles(p.tiles_x*p.tiles_y), block(CB_THREADS);
 
     HIP_TRY(hipEventRecord(d->event[0], NULL), return false);
-    HIP_TRY(hipMemcpyAsync(d_image, image, (size_t)p.W*p.H*p.bytes_per_pixel, hipMemcpyHostToDevice, NULL), (void)hipDeviceSynchronize(); return false);
+    if(image != NULL)
+        HIP_TRY(hipMemcpyAsync(d_image, image, (size_t)p.W*p.H*p.bytes_per_pixel, hipMemcpyHostToDevice, NULL), (void)hipDeviceSynchronize(); return false);
     HIP_TRY(hipEventRecord(d->event[1], NULL), (void)hipDeviceSynchronize(); return false);
+    if(d->pyramid.levels > 0)
+    {
+        // the levels share the mask words, and the words of a chunk past a level's own are never written by it: what
+        // another level left there would be counted
+        const size_t used = (size_t)p.words_per_row*(size_t)p.H, all = (size_t)p.chunks*CB_CHUNK_WORDS;
+        if(all > used)
+            HIP_TRY(hipMemsetAsync(words + used, 0, (all - used)*sizeof(uint64_t), NULL), (void)hipDeviceSynchronize(); return false);
+    }
     HIP_TRY(hipMemsetAsync(Rmax, 0, sizeof(int32_t), NULL), (void)hipDeviceSynchronize(); return false);
     if(p.bytes_per_pixel == 1) hipLaunchKernelGGL(cb_response_kernel<uint8_t>,  tiles, block, 0, NULL, p.W, p.H, p.tiles_x, (const uint8_t*)d_image,  R, Rmax);
     else                       hipLaunchKernelGGL(cb_response_kernel<uint16_t>, tiles, block, 0, NULL, p.W, p.H, p.tiles_x, (const uint16_t*)d_image, R, Rmax);
@@ -360,8 +450,8 @@ static bool cb_run(mrcal_amd_chessboard_detector* d, const void* image)
     hipLaunchKernelGGL(cb_scatter_kernel, dim3(p.chunks), block, 0, NULL, p.W, p.words_per_row, (unsigned)p.max_candidates, words, bases, R, xy, cr);
     HIP_TRY(hipGetLastError(), (void)hipDeviceSynchronize(); return false);
     HIP_TRY(hipEventRecord(d->event[3], NULL), (void)hipDeviceSynchronize(); return false);
-    if(p.bytes_per_pixel == 1) hipLaunchKernelGGL(cb_refine_kernel<uint8_t>,  dim3(p.refine_groups), block, 0, NULL, p.W, p.H, (unsigned)p.max_candidates, (const uint8_t*)d_image,  bases + p.chunks, xy, q, status);
-    else                       hipLaunchKernelGGL(cb_refine_kernel<uint16_t>, dim3(p.refine_groups), block, 0, NULL, p.W, p.H, (unsigned)p.max_candidates, (const uint16_t*)d_image, bases + p.chunks, xy, q, status);
+    if(p.bytes_per_pixel == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(cb_refine_kernel<uint8_t,  false>), dim3(p.refine_groups), block, 0, NULL, p.W, p.H, (unsigned)p.max_candidates, (const uint8_t*)d_image,  bases + p.chunks, xy, q, status, (int32_t*)NULL, 0);
+    else                       hipLaunchKernelGGL(HIP_KERNEL_NAME(cb_refine_kernel<uint16_t, false>), dim3(p.refine_groups), block, 0, NULL, p.W, p.H, (unsigned)p.max_candidates, (const uint16_t*)d_image, bases + p.chunks, xy, q, status, (int32_t*)NULL, 0);
     HIP_TRY(hipGetLastError(), (void)hipDeviceSynchronize(); return false);
     HIP_TRY(hipEventRecord(d->event[4], NULL), (void)hipDeviceSynchronize(); return false);
 
@@ -382,19 +472,129 @@ static bool cb_run(mrcal_amd_chessboard_detector* d, const void* image)
     return true;
 }
 
-extern "C" {
+// level 0 alone: what a detector without a pyramid does, whatever levels this one has
+static bool cb_run(mrcal_amd_chessboard_detector* d, const void* image)
+{
+    d->N = -1;
+    d->pyramid_ran = false;
+    if(image == NULL) { set_error("find_chessboard_corners(): the image is NULL"); return false; }
+    if(!cb_have_device()) return false;
+    return cb_run_level(d, 0, image);
+}
 
-mrcal_amd_chessboard_detector_t*
-mrcal_amd_chessboard_detector_create(int width, int height, int bytes_per_pixel,
-                                     const mrcal_amd_chessboard_params_t* params, size_t free_device_bytes)
+// p1: the levels 1..n from the level-0 image on the device
+static bool cb_decimate(mrcal_amd_chessboard_detector* d)
+{
+    const ChessboardPyramidPlan& pp = d->pyramid;
+    for(int l=1; l<=pp.levels; l++)
+    {
+        const ChessboardPlan& from = pp.level[l - 1];
+        const ChessboardPlan& to   = pp.level[l];
+        const uint8_t* in  = d->pool + from.image;
+        uint8_t*       out = d->pool + to.image;
+        const dim3 groups(pp.decimate_groups[l]), block(CB_THREADS);
+        const bool u8 = to.bytes_per_pixel == 1;
+        if(pp.decimate_wide[l])
+        {
+            const unsigned words_per_row = (unsigned)((size_t)from.W*from.bytes_per_pixel/CB_DECIMATE_BYTES);
+            if(u8) hipLaunchKernelGGL(cb_decimate_wide_kernel<uint8_t>,  groups, block, 0, NULL, words_per_row, (unsigned)to.H, (const uint4*)in, (uint2*)out);
+            else   hipLaunchKernelGGL(cb_decimate_wide_kernel<uint16_t>, groups, block, 0, NULL, words_per_row, (unsigned)to.H, (const uint4*)in, (uint2*)out);
+        }
+        else
+        {
+            if(u8) hipLaunchKernelGGL(cb_decimate_kernel<uint8_t>,  groups, block, 0, NULL, from.W, to.W, to.H, (const uint8_t*)in,  (uint8_t*)out);
+            else   hipLaunchKernelGGL(cb_decimate_kernel<uint16_t>, groups, block, 0, NULL, from.W, to.W, to.H, (const uint16_t*)in, (uint16_t*)out);
+        }
+        HIP_TRY(hipGetLastError(), (void)hipDeviceSynchronize(); return false);
+    }
+    return true;
+}
+
+// p2 and p3. corners (board_height, board_width, 2) and levels are written when *found
+static bool cb_find_board_pyramid(mrcal_amd_chessboard_detector* d, const void* image, int board_width, int board_height,
+                                  double* corners, int32_t* levels, int* detection_level, int* found)
+{
+    d->N = -1;
+    d->pyramid_ran = false;
+    d->descended = false;
+    if(image == NULL) { set_error("find_chessboard_corners(): the image is NULL"); return false; }
+    if(!cb_have_device()) return false;
+    const ChessboardPyramidPlan& pp = d->pyramid;
+    const ChessboardPlan& p0 = pp.level[0];
+    for(float& ms : d->level_ms) ms = 0.f;
+    *found = 0;
+    *detection_level = -1;
+    // (made at the first call of this kind: a detector that is never asked for levels has none of them)
+    for(hipEvent_t& e : d->pyramid_event)
+        if(e == NULL) HIP_TRY(hipEventCreate(&e), return false);
+
+    HIP_TRY(hipEventRecord(d->pyramid_event[0], NULL), return false);
+    HIP_TRY(hipMemcpyAsync(d->pool + p0.image, image, (size_t)p0.W*p0.H*p0.bytes_per_pixel, hipMemcpyHostToDevice, NULL), (void)hipDeviceSynchronize(); return false);
+    HIP_TRY(hipEventRecord(d->pyramid_event[1], NULL), (void)hipDeviceSynchronize(); return false);
+    HIP_TRY(hipEventRecord(d->pyramid_event[2], NULL), (void)hipDeviceSynchronize(); return false);
+    if(!cb_decimate(d)) return false;
+    HIP_TRY(hipEventRecord(d->pyramid_event[3], NULL), (void)hipDeviceSynchronize(); return false);
+
+    const int n = board_width*board_height;
+    int L = pp.levels;
+    for(; L >= 0; L--)
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        if(!cb_run_level(d, L, NULL)) return false;
+        const auto t1 = std::chrono::steady_clock::now();
+        const bool here = chessboard_grid(d->N, d->q.data(), d->response.data(), d->status.data(), board_width, board_height, corners);
+        const auto t2 = std::chrono::steady_clock::now();
+        d->grid_ms     = std::chrono::duration<float, std::milli>(t2 - t1).count();
+        d->level_ms[L] = std::chrono::duration<float, std::milli>(t2 - t0).count();
+        if(here) break;
+    }
+    d->pyramid_ran = true;
+    if(L < 0) return true;                              // (no board at any level: no error. Level 0 was looked at last)
+    *found = 1;
+    *detection_level = L;
+    for(int c=0; c<n; c++) levels[c] = L;
+    if(L == 0) return true;
+
+    // the board's corners are candidates of this level: there are no more of them than max_candidates
+    if(n > p0.max_candidates) { set_error("find_chessboard_corners(): internal error: a board of %d corners among %d candidates", n, p0.max_candidates); return false; }
+    double*  dq     = (double*)(d->pool + pp.descent_q);
+    int32_t* dlevel = (int32_t*)(d->pool + pp.descent_level);
+    HIP_TRY(hipEventRecord(d->pyramid_event[4], NULL), return false);
+    HIP_TRY(hipMemcpyAsync(dq,     corners, (size_t)n*2*sizeof(double), hipMemcpyHostToDevice, NULL), (void)hipDeviceSynchronize(); return false);
+    HIP_TRY(hipMemcpyAsync(dlevel, levels,  (size_t)n*sizeof(int32_t),  hipMemcpyHostToDevice, NULL), (void)hipDeviceSynchronize(); return false);
+    const dim3 groups(((unsigned)n + CB_THREADS/64 - 1)/(CB_THREADS/64)), block(CB_THREADS);
+    for(int l=L-1; l>=0; l--)
+    {
+        const ChessboardPlan& p = pp.level[l];
+        const uint8_t* I = d->pool + p.image;
+        if(p.bytes_per_pixel == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(cb_refine_kernel<uint8_t,  true>), groups, block, 0, NULL, p.W, p.H, (unsigned)n, (const uint8_t*)I,  (const uint32_t*)NULL, (const int32_t*)NULL, dq, (int32_t*)NULL, dlevel, l);
+        else                       hipLaunchKernelGGL(HIP_KERNEL_NAME(cb_refine_kernel<uint16_t, true>), groups, block, 0, NULL, p.W, p.H, (unsigned)n, (const uint16_t*)I, (const uint32_t*)NULL, (const int32_t*)NULL, dq, (int32_t*)NULL, dlevel, l);
+        HIP_TRY(hipGetLastError(), (void)hipDeviceSynchronize(); return false);
+    }
+    HIP_TRY(hipEventRecord(d->pyramid_event[5], NULL), (void)hipDeviceSynchronize(); return false);
+    // (the copies wait for the launches)
+    HIP_TRY(hipMemcpy(corners, dq,     (size_t)n*2*sizeof(double), hipMemcpyDeviceToHost), (void)hipDeviceSynchronize(); return false);
+    HIP_TRY(hipMemcpy(levels,  dlevel, (size_t)n*sizeof(int32_t),  hipMemcpyDeviceToHost), (void)hipDeviceSynchronize(); return false);
+    d->descended = true;
+    // the last accepted position, carried to level 0: up(q) = 2 q + 0.5, once a level
+    for(int c=0; c<n; c++)
+    {
+        if(levels[c] < 0 || levels[c] > L) { set_error("find_chessboard_corners(): internal error: corner %d at level %d", c, levels[c]); return false; }
+        for(int l=0; l<levels[c]; l++) { corners[2*c] = 2.0*corners[2*c] + 0.5; corners[2*c + 1] = 2.0*corners[2*c + 1] + 0.5; }
+    }
+    return true;
+}
+
+static mrcal_amd_chessboard_detector* cb_create(int width, int height, int bytes_per_pixel, const mrcal_amd_chessboard_params_t* params,
+                                                int pyramid_levels, size_t free_device_bytes)
 {
     last_error_string().clear();
     if(params == NULL) { set_error("find_chessboard_corners(): the parameters are NULL"); return NULL; }
     std::string why;
-    ChessboardPlan plan;
+    ChessboardPyramidPlan plan;
     // (the refusals that need no device first)
-    if(!chessboard_plan(&plan, &why, width, height, bytes_per_pixel, params->threshold_256, params->nms_radius, params->max_candidates,
-                        free_device_bytes != 0 ? free_device_bytes : SIZE_MAX))
+    if(!chessboard_pyramid_plan(&plan, &why, width, height, bytes_per_pixel, params->threshold_256, params->nms_radius, params->max_candidates,
+                                pyramid_levels, free_device_bytes != 0 ? free_device_bytes : SIZE_MAX))
     {
         set_error("%s", why.c_str());
         return NULL;
@@ -404,20 +604,37 @@ mrcal_amd_chessboard_detector_create(int width, int height, int bytes_per_pixel,
     {
         size_t free_bytes = 0, total_bytes = 0;
         HIP_TRY(hipMemGetInfo(&free_bytes, &total_bytes), return NULL);
-        if(!chessboard_plan(&plan, &why, width, height, bytes_per_pixel, params->threshold_256, params->nms_radius, params->max_candidates, free_bytes))
+        if(!chessboard_pyramid_plan(&plan, &why, width, height, bytes_per_pixel, params->threshold_256, params->nms_radius, params->max_candidates,
+                                    pyramid_levels, free_bytes))
         {
             set_error("%s", why.c_str());
             return NULL;
         }
     }
     mrcal_amd_chessboard_detector* d = new mrcal_amd_chessboard_detector;
-    d->plan = plan;
+    d->pyramid = plan;
     if(!d->mem.alloc(&d->pool, plan.bytes)) { delete d; return NULL; }
     // (the words past the image's are never written: no bit of them may be set)
-    HIP_TRY(hipMemset(d->pool + plan.words, 0, plan.bases - plan.words), delete d; return NULL);
+    HIP_TRY(hipMemset(d->pool + plan.level[0].words, 0, plan.level[0].bases - plan.level[0].words), delete d; return NULL);
     for(int i = 0; i < 5; i++)
         HIP_TRY(hipEventCreate(&d->event[i]), delete d; return NULL);
     return d;
+}
+
+extern "C" {
+
+mrcal_amd_chessboard_detector_t*
+mrcal_amd_chessboard_detector_create(int width, int height, int bytes_per_pixel,
+                                     const mrcal_amd_chessboard_params_t* params, size_t free_device_bytes)
+{
+    return cb_create(width, height, bytes_per_pixel, params, 0, free_device_bytes);
+}
+
+mrcal_amd_chessboard_detector_t*
+mrcal_amd_chessboard_detector_create_pyramid(int width, int height, int bytes_per_pixel,
+                                             const mrcal_amd_chessboard_params_t* params, int pyramid_levels, size_t free_device_bytes)
+{
+    return cb_create(width, height, bytes_per_pixel, params, pyramid_levels, free_device_bytes);
 }
 
 bool mrcal_amd_chessboard_detector_candidates(mrcal_amd_chessboard_detector_t* d, const void* image,
@@ -457,7 +674,7 @@ bool mrcal_amd_chessboard_detector_read_response(mrcal_amd_chessboard_detector_t
     last_error_string().clear();
     if(!cb_given(d)) return false;
     if(d->N < 0) { set_error("find_chessboard_corners(): no image has been looked at yet"); return false; }
-    const ChessboardPlan& p = d->plan;
+    const ChessboardPlan& p = d->pyramid.level[d->level];       // (of the level looked at last: level 0 without a pyramid)
     if(response != NULL)     HIP_TRY(hipMemcpy(response, d->pool + p.response, (size_t)p.W*p.H*sizeof(int32_t), hipMemcpyDeviceToHost), return false);
     if(response_max != NULL) HIP_TRY(hipMemcpy(response_max, d->pool + p.response_max, sizeof(int32_t), hipMemcpyDeviceToHost), return false);
     if(candidate_xy != NULL && d->N > 0) HIP_TRY(hipMemcpy(candidate_xy, d->pool + p.xy, (size_t)d->N*2*sizeof(int32_t), hipMemcpyDeviceToHost), return false);
@@ -471,7 +688,51 @@ bool mrcal_amd_chessboard_detector_stage_milliseconds(mrcal_amd_chessboard_detec
     if(d->N < 0) { set_error("find_chessboard_corners(): no image has been looked at yet"); return false; }
     for(int i = 0; i < 4; i++)
         HIP_TRY(hipEventElapsedTime(&milliseconds[i], d->event[i], d->event[i + 1]), return false);
+    // (with a pyramid the image was uploaded once, before the levels)
+    if(d->pyramid_ran) HIP_TRY(hipEventElapsedTime(&milliseconds[0], d->pyramid_event[0], d->pyramid_event[1]), return false);
     milliseconds[4] = d->grid_ms;
+    return true;
+}
+
+bool mrcal_amd_chessboard_detector_find_board_pyramid(mrcal_amd_chessboard_detector_t* d, const void* image,
+                                                      int board_width, int board_height, double* corners, int32_t* levels,
+                                                      int* detection_level, int* found)
+{
+    last_error_string().clear();
+    if(!cb_given(d)) return false;
+    if(found == NULL || corners == NULL || levels == NULL || detection_level == NULL) { set_error("find_chessboard_corners(): an argument is NULL"); return false; }
+    std::string why;
+    if(!chessboard_board_ok(&why, board_width, board_height)) { set_error("%s", why.c_str()); return false; }
+    return cb_find_board_pyramid(d, image, board_width, board_height, corners, levels, detection_level, found);
+}
+
+bool mrcal_amd_chessboard_detector_read_level(mrcal_amd_chessboard_detector_t* d, int level, void* image_out)
+{
+    last_error_string().clear();
+    if(!cb_given(d)) return false;
+    if(image_out == NULL) { set_error("find_chessboard_corners(): an argument is NULL"); return false; }
+    if(d->N < 0) { set_error("find_chessboard_corners(): no image has been looked at yet"); return false; }
+    // (the levels above 0 are made by _find_board_pyramid() alone)
+    if(level < 0 || level > (d->pyramid_ran ? d->pyramid.levels : 0))
+    {
+        set_error("find_chessboard_corners(): the last call made the levels 0..%d, and level %d was asked for", d->pyramid_ran ? d->pyramid.levels : 0, level);
+        return false;
+    }
+    const ChessboardPlan& p = d->pyramid.level[level];
+    HIP_TRY(hipMemcpy(image_out, d->pool + p.image, (size_t)p.W*p.H*p.bytes_per_pixel, hipMemcpyDeviceToHost), return false);
+    return true;
+}
+
+bool mrcal_amd_chessboard_detector_pyramid_milliseconds(mrcal_amd_chessboard_detector_t* d, float* decimate, float* descent, float* per_level)
+{
+    last_error_string().clear();
+    if(!cb_given(d)) return false;
+    if(decimate == NULL || descent == NULL || per_level == NULL) { set_error("find_chessboard_corners(): an argument is NULL"); return false; }
+    if(d->N < 0 || !d->pyramid_ran) { set_error("find_chessboard_corners(): no image has been looked at through the pyramid yet"); return false; }
+    HIP_TRY(hipEventElapsedTime(decimate, d->pyramid_event[2], d->pyramid_event[3]), return false);
+    *descent = 0.f;
+    if(d->descended) HIP_TRY(hipEventElapsedTime(descent, d->pyramid_event[4], d->pyramid_event[5]), return false);
+    for(int l=0; l<=d->pyramid.levels; l++) per_level[l] = d->level_ms[l];
     return true;
 }
 

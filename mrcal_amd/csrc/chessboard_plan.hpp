@@ -1,7 +1,9 @@
 // What chessboard.hip works out on the host before it touches the device: the arguments that are refused and the
 // messages, where the image, the response, the mask words, the bases, the maximum and the candidate records lie in the
 // ONE pooled allocation a detector owns, and the launch geometry of the five kernels. Plain structs in and out, no HIP
-// type or call. tests/hostcheck/chessboard_grid_check.cpp runs it under the host sanitizers.
+// type or call. tests/hostcheck/chessboard_grid_check.cpp runs it under the host sanitizers. With an image pyramid
+// (chessboard_pyramid_plan()): the geometry of every level, where the level images lie behind the level-0 pool, and the
+// refusals of pyramid_levels; tests/hostcheck/chessboard_pyramid_plan_check.cpp walks that.
 //
 // What a corner is: include/mrcal_amd.h, "chessboard corners".
 #pragma once
@@ -29,6 +31,9 @@ namespace mrcal_amd {
 #define CB_STATUS_OK 0
 #define CB_STATUS_SINGULAR 1
 #define CB_STATUS_LEFT 2
+#define CB_MAX_LEVELS 8                 // pyramid_levels is 0..8
+#define CB_DESCENT_AGREEMENT 0.3        // tau of p3, in pixels of the level a corner descends to
+#define CB_DECIMATE_BYTES 16            // of each of two rows a lane of the wide cb_decimate_kernel loads
 
 static_assert(CB_THREADS == 4*CB_TX && CB_TY % 4 == 0, "a wavefront is a row of the tile, four rows at a time");
 static_assert(CB_MAX_PIXELS < (1L << 31), "a pixel index is an int32");
@@ -120,6 +125,87 @@ inline bool chessboard_board_ok(std::string* error, int board_width, int board_h
     snprintf(buf, sizeof(buf), "find_chessboard_corners(): a board has 3..256 corners a side, got %d x %d", board_width, board_height);
     *error = buf;
     return false;
+}
+
+// ------------------------------------------------------------------------------------------------------ the pyramid
+// Level l has (W >> l) x (H >> l) pixels. level[0] IS chessboard_plan()'s plan, field for field. level[l], l >= 1, is
+// the plan of an image of that level's size whose response, words, bases, maximum and candidate records lie where level
+// 0's do (they are smaller, and one level is looked at at a time) and whose image lies behind level 0's pool.
+struct ChessboardPyramidPlan
+{
+    int            levels = 0;                          // pyramid_levels: levels 0..levels exist
+    ChessboardPlan level[CB_MAX_LEVELS + 1];
+    // cb_decimate_kernel making level l (l >= 1) from level l - 1
+    bool           decimate_wide[CB_MAX_LEVELS + 1] = {};   // rows of level l - 1 are whole 16-byte words: a lane takes a word of two rows
+    unsigned       decimate_groups[CB_MAX_LEVELS + 1] = {}; // workgroups of CB_THREADS: a lane a word pair (wide) or an output pixel
+    size_t         descent_q = 0;                       // double [max_candidates][2]: the board's corners, each in the pixels of its level
+    size_t         descent_level = 0;                   // int32 [max_candidates]
+    size_t         bytes = 0;                           // of the pool
+};
+
+// the largest pyramid_levels an image of W x H pixels allows: every level has CB_MIN_SIDE pixels a side
+inline int chessboard_max_pyramid_levels(int W, int H)
+{
+    int n = 0;
+    while(n < CB_MAX_LEVELS && (W >> (n + 1)) >= CB_MIN_SIDE && (H >> (n + 1)) >= CB_MIN_SIDE) n++;
+    return n;
+}
+
+inline bool chessboard_pyramid_plan(ChessboardPyramidPlan* plan, std::string* error, int W, int H, int bytes_per_pixel,
+                                    int threshold_256, int nms_radius, int max_candidates, int pyramid_levels, size_t free_bytes)
+{
+    *plan = ChessboardPyramidPlan();
+    ChessboardPyramidPlan p;
+    // (the refusals of one level first, in their order; the memory is looked at below, for the whole pool)
+    if(!chessboard_plan(&p.level[0], error, W, H, bytes_per_pixel, threshold_256, nms_radius, max_candidates, SIZE_MAX)) return false;
+    char buf[256];
+    if(pyramid_levels < 0 || pyramid_levels > CB_MAX_LEVELS)
+    {
+        snprintf(buf, sizeof(buf), "find_chessboard_corners(): pyramid_levels must be in 0..%d, got %d", CB_MAX_LEVELS, pyramid_levels);
+        *error = buf;
+        return false;
+    }
+    const int most = chessboard_max_pyramid_levels(W, H);
+    if(pyramid_levels > most)
+    {
+        snprintf(buf, sizeof(buf), "find_chessboard_corners(): an image of %d x %d pixels is too small for pyramid_levels = %d: "
+                 "level %d would have %d x %d pixels, at least %d x %d; at most pyramid_levels = %d",
+                 W, H, pyramid_levels, most + 1, W >> (most + 1), H >> (most + 1), CB_MIN_SIDE, CB_MIN_SIDE, most);
+        *error = buf;
+        return false;
+    }
+    p.levels = pyramid_levels;
+    p.bytes  = p.level[0].bytes;
+    for(int l=1; l<=pyramid_levels; l++)
+    {
+        ChessboardPlan& q = p.level[l];
+        if(!chessboard_plan(&q, error, W >> l, H >> l, bytes_per_pixel, threshold_256, nms_radius, max_candidates, SIZE_MAX)) return false;
+        const ChessboardPlan& z = p.level[0];
+        q.response = z.response; q.words = z.words; q.bases = z.bases; q.response_max = z.response_max;
+        q.xy = z.xy; q.candidate_response = z.candidate_response; q.q = z.q; q.status = z.status;
+        q.image = p.bytes;
+        p.bytes += cb_aligned((size_t)q.W*(size_t)q.H*(size_t)bytes_per_pixel);
+        q.bytes = p.bytes;
+        const size_t row_bytes = (size_t)p.level[l - 1].W*(size_t)bytes_per_pixel;
+        p.decimate_wide[l] = row_bytes % CB_DECIMATE_BYTES == 0;
+        const size_t lanes = p.decimate_wide[l] ? row_bytes/CB_DECIMATE_BYTES*(size_t)q.H : (size_t)q.W*(size_t)q.H;
+        p.decimate_groups[l] = (unsigned)((lanes + CB_THREADS - 1)/CB_THREADS);
+    }
+    if(pyramid_levels > 0)
+    {
+        p.descent_q     = p.bytes;
+        p.descent_level = p.descent_q     + cb_aligned((size_t)max_candidates*2*sizeof(double));
+        p.bytes         = p.descent_level + cb_aligned((size_t)max_candidates*sizeof(int32_t));
+    }
+    if(p.bytes > free_bytes)
+    {
+        snprintf(buf, sizeof(buf), "find_chessboard_corners(): %d x %d pixels need %zu bytes of device memory; %zu are free",
+                 W, H, p.bytes, free_bytes);
+        *error = buf;
+        return false;
+    }
+    *plan = p;
+    return true;
 }
 
 } // namespace mrcal_amd
