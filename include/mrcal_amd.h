@@ -882,6 +882,72 @@ bool   mrcal_amd_projection_diff_evaluate(mrcal_amd_projection_diff_t* pd,
 double mrcal_amd_projection_diff_time_fit(mrcal_amd_projection_diff_t* pd, bool on);
 void   mrcal_amd_projection_diff_destroy(mrcal_amd_projection_diff_t* pd);
 
+/* ---- lens-model fit: mrcal-convert-lensmodel --sampled ----------------------
+   Reference: mrcal-convert-lensmodel:725-792 (the sampled problem), mrcal.c:4900-5176 (a point observation's rows),
+   :5655-5901 (the regularization rows), :6607-6612 (the rms).
+   N points p_i (N,3), fixed, in the from-camera's coordinates (do_optimize_frames = false), observed at q_i (N,2) with
+   weights w_i (N; NULL: all 1). The unknowns b are the intrinsics of ONE parametric lens model - all of them, or
+   without the core (fx,fy,cx,cy) when optimize_core is false: they then start at index 4 - and, with
+   optimize_extrinsics, the pose rt_cam_ref (T below; the identity otherwise). What is minimised is the reference's
+       F(b) = x.x,   x = ( w_i (project(T p_i) - q_i)   two rows a point;
+                           s_j k_j                       a row each distortion term k_j: s_j = 0.1, but 0.5 for the
+                                                         three terms of the denominator of OPENCV8 and OPENCV12;
+                           s_c (c_xy - (size_xy - 1)/2)  two rows, s_c = 1/width for BOTH, only with optimize_core )
+   the last two kinds only with apply_regularization (mrcal.optimize() has it on by default); no unity_cam01 row. A
+   point with w_i <= 0 or with a non-finite w_i, p_i or q_i takes no part: its two rows are 0, as the reference's
+   are for an outlier, and they still count in Nmeasurements = 2 N + the regularization rows. The reference's scales
+   are constants here: mrcal.c computes the number of non-regularization measurements beside them (:5697) but the
+   scales do not use it, and this version of the reference gives a point observation no range row (:4990-5003).
+       rms_reproj_error__pixels = sqrt(F/Nmeasurements)      the reference's definition, regularization rows and all
+   The iteration, from a start b: damped Gauss-Newton on H = J^T J, g = J^T x,
+       (H + lambda diag(H)) d = -g,   lambda = 1 at the start of a stage
+   (a variable nothing depends on stays put). The trial b + d is kept only if F does not rise; lambda then follows
+   Nielsen's rule from the gain ratio, and is multiplied by 2, 4, 8 ... after rejections in a row. A stage ends
+     0 converged   F <= sum w_i^2 (64 eps)^2 (|q_i|^2 + 1): a perfect fit as far as doubles can tell; or g = 0; or a step
+                   with lambda <= 1 that was kept gained, or one about to be tried is promised by the quadratic
+                   model, no more than 1e-12 F
+     1 bound       max_evaluations evaluations of F were made in this stage, the one at its start included
+                   (0: the default, 200). The best point seen is returned; with max_evaluations = 1 that is the start
+     2 too few     fewer pixel rows of points that take part than unknowns. The cost is NaN
+     3 stalled     lambda passed 1e10 without a step that lowers F, or F or g is not finite at the start (a NaN in
+                   a seed): no descent to be had. The best point seen is returned
+   A trial: stage 1 fits the intrinsics alone with T the identity; stage 2, with optimize_extrinsics, continues from
+   the result of stage 1 with the six pose variables added, started at rt_seed (NULL: 0) - the reference's two calls
+   of mrcal.optimize(). What is reported is the last stage's state and status, and the evaluations of both stages.
+   A stage with no unknowns (no distortion terms, no core) is skipped.
+   All Ntrials trials run in ONE launch, a workgroup each (csrc/lensfit.hip), from intrinsics_seed (Ntrials,
+   Nintrinsics) and rt_seed (Ntrials,6): every sum in a fixed order, so a trial has the same bits on every call and
+   whatever the other trials of the call. Results per trial: intrinsics (Ntrials,Nintrinsics), rt (Ntrials,6), cost,
+   rms, Nevaluations, status (Ntrials each; any may be NULL). *ibest: the trial with the lowest rms among those that
+   are not status 2 and have a finite rms, the first of equals; -1 if there is none.
+   false (mrcal_amd_last_error()): a splined model (it is fitted by mrcal_optimize()), an unknown model, fewer pixel
+   rows than unknowns, nothing to fit, sizes out of range. Host pointers throughout; the object keeps its device
+   buffers and stream between calls. _last_ms(): the device time of the last fit's launch, from events (< 0: none) */
+#define MRCAL_AMD_LENSFIT_CONVERGED      0
+#define MRCAL_AMD_LENSFIT_BOUND          1
+#define MRCAL_AMD_LENSFIT_TOO_FEW_POINTS 2
+#define MRCAL_AMD_LENSFIT_STALLED        3
+typedef struct mrcal_amd_lensfit mrcal_amd_lensfit_t;
+mrcal_amd_lensfit_t* mrcal_amd_lensfit_create(void);
+bool   mrcal_amd_lensfit_fit(mrcal_amd_lensfit_t* lf,
+                             const double* p /*N,3*/, const double* q /*N,2*/, const double* w /*N or NULL*/, int N,
+                             const mrcal_lensmodel_t* lensmodel, const int imagersize[2],
+                             const double* intrinsics_seed /*Ntrials,Nintrinsics*/, const double* rt_seed /*Ntrials,6 or NULL*/,
+                             int Ntrials,
+                             bool optimize_core, bool optimize_extrinsics, bool apply_regularization, int max_evaluations,
+                             double* intrinsics, double* rt, double* cost, double* rms, int* Nevaluations, int* status,
+                             int* ibest);
+double mrcal_amd_lensfit_last_ms(const mrcal_amd_lensfit_t* lf);
+/* What _fit() would decide for these arguments, without touching a device (csrc/lensfit_plan.hpp): plan_out[14] =
+   PROJ, NDIST (the kernel's instantiation: the row of the lens table), Nintrinsics, the first intrinsic that is an
+   unknown (0 or 4), stages, the unknowns of stage 1 and of stage 2 (0: no such stage), the sums a workgroup keeps,
+   threads, doubles in a staged row, rows in a chunk, LDS bytes, Nmeasurements, the LDS bytes a workgroup may take.
+   false: _fit() would refuse, mrcal_amd_last_error() says why */
+#define MRCAL_AMD_LENSFIT_PLAN_N 14
+bool   mrcal_amd_lensfit_plan(int* plan_out, const mrcal_lensmodel_t* lensmodel, int N, int Ntrials, const int imagersize[2],
+                              bool optimize_core, bool optimize_extrinsics, bool apply_regularization);
+void   mrcal_amd_lensfit_destroy(mrcal_amd_lensfit_t* lf);
+
 /* ---- triangulation: mrcal.triangulate_*() ----------------------------------
    Reference: triangulation.h / triangulation.cc (mrcal_triangulate_geometric, _lindstrom, _leecivera_l1, _linf,
    _mid2, _wmid2), broadcast by mrcal/triangulation.py. The batch forms ON THE GPU, one lane per pair

@@ -85,7 +85,8 @@ from .equalization import equalize_clahe, equalize_stretch, ImageEqualizer
 from .image_transforms import (scale_focal__best_pinhole_fit, pinhole_model_for_reprojection, image_transformation_map,
                                transform_image)
 from .utils import (sample_imager, sample_imager_unproject, write_point_cloud_as_ply, mapping_file_framenocameraindex,
-                    measurements_board, residuals_board, measurements_point, residuals_point)
+                    measurements_board, residuals_board, measurements_point, residuals_point,
+                    hypothesis_board_corner_positions)
 from .chessboard import (find_chessboard_corners, chessboard_corner_candidates, ChessboardDetector, chessboard_grid,
                          compute_chessboard_corners, load_image_gray)
 
@@ -99,6 +100,7 @@ from .cameramodel import cameramodel, CameramodelParseException
 from .calibration import (ref_calibration_object, align_procrustes_points_Rt01, traverse_sensor_links,
                           estimate_monocular_calobject_poses_Rt_tocam, estimate_joint_frame_poses, seed_stereographic)
 from . import calibration
+from .lensmodel_conversion import fit_lensmodel, fit_lensmodel_plan, convert_lensmodel, LensFitter
 from .valid_region import (RegionalStatistics, valid_intrinsics_regions, is_within_valid_intrinsics_region,
                            valid_intrinsics_mask, imagergrid_using)
 

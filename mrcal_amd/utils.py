@@ -138,6 +138,44 @@ Host code. Reference: mrcal.mapping_file_framenocameraindex() (mrcal/utils.py)""
     return mapping
 
 
+def hypothesis_board_corner_positions(icam_intrinsics=None, idx_inliers=None, **optimization_inputs):
+    """The 3D chessboard corners a solve's state puts in front of its cameras, in each observing camera's coordinates:
+    the board's geometry (with its warp) through rt_ref_frame and rt_cam_ref as
+    indices_frame_camintrinsics_camextrinsics pairs them. Returns four arrays:
+      (Nobservations,Nheight,Nwidth,3)  all observations
+      (Nobservations of camera icam_intrinsics,Nheight,Nwidth,3)   (icam_intrinsics None: the same as the first)
+      (N,3) the inliers among the second, (N,3) the outliers
+    idx_inliers (Nobservations,Nheight,Nwidth) booleans: which corners count as inliers, instead of weight > 0 (to pick
+    the inliers common to two solves). Host code. Reference: mrcal.hypothesis_board_corner_positions()"""
+    from .calibration import ref_calibration_object
+    from .poseutils import Rt_from_rt, compose_Rt, identity_Rt, transform_point_Rt
+    observations_board = optimization_inputs.get('observations_board')
+    if observations_board is None:
+        raise Exception("No board observations available")
+    observations_board = np.asarray(observations_board)
+    ifce = np.asarray(optimization_inputs['indices_frame_camintrinsics_camextrinsics'])
+    Nh, Nw = observations_board.shape[-3:-1]
+    # (Nh,Nw,3)
+    full_object = ref_calibration_object(Nw, Nh, optimization_inputs['calibration_object_spacing'],
+                                         calobject_warp=optimization_inputs.get('calobject_warp'))
+    Rt_ref_frame = Rt_from_rt(optimization_inputs['rt_ref_frame'])[ifce[:, 0]]
+    rt_cam_ref = optimization_inputs.get('rt_cam_ref')
+    rt_cam_ref = np.zeros((0, 6)) if rt_cam_ref is None else np.asarray(rt_cam_ref, dtype=float).reshape(-1, 6)
+    Rt_cam_ref = np.concatenate((identity_Rt()[None], Rt_from_rt(rt_cam_ref)), axis=0)[ifce[:, 2] + 1]
+    Rt_cam_frame = compose_Rt(Rt_cam_ref, Rt_ref_frame)
+    p_cam = transform_point_Rt(Rt_cam_frame[:, None, None, :, :], full_object)
+    if idx_inliers is None:
+        idx_inliers = observations_board[..., 2] > 0
+    idx_inliers  = np.array(idx_inliers, dtype=bool)
+    idx_outliers = ~idx_inliers
+    if icam_intrinsics is None:
+        return p_cam, p_cam, p_cam[idx_inliers], p_cam[idx_outliers]
+    idx_observations = ifce[:, 1] == icam_intrinsics
+    idx_inliers [~idx_observations] = False
+    idx_outliers[~idx_observations] = False
+    return p_cam, p_cam[idx_observations], p_cam[idx_inliers], p_cam[idx_outliers]
+
+
 def _all_measurements(optimization_inputs):
     from . import optimizer_callback
     return optimizer_callback(**optimization_inputs, no_jacobian=True, no_factorization=True)[1]
