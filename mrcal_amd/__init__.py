@@ -107,37 +107,25 @@ from .valid_region import (RegionalStatistics, valid_intrinsics_regions, is_with
 
 def gpu_available():
     """True if a HIP device is visible to libmrcal_amd.so"""
-    import ctypes
-    f = _lib.lib.mrcal_amd_device_count
-    f.restype = ctypes.c_int
-    return f() > 0
+    return _lib.lib.mrcal_amd_device_count() > 0
 
 
 def device_buffers_live():
     """how many device (and pinned host) buffers the library's objects hold at this moment"""
-    import ctypes
-    f = _lib.lib.mrcal_amd_device_buffers_live
-    f.restype, f.argtypes = ctypes.c_long, []
-    return f()
+    return _lib.lib.mrcal_amd_device_buffers_live()
 
 
 def set_optimize_jacobian_stream(stream):
     """optimize() returns no Jacobian and its problem does not outlive the call, so by default its steps do not
     stream the CSR values of J to HBM (the same results to the bit: include/mrcal_amd.h, round 6). True: they do,
     as the benchmark's metric defines a step. Returns the previous setting"""
-    import ctypes
-    f = _lib.lib.mrcal_amd_set_optimize_jacobian_stream
-    f.restype, f.argtypes = ctypes.c_int, [ctypes.c_int]
-    return bool(f(1 if stream else 0))
+    return bool(_lib.lib.mrcal_amd_set_optimize_jacobian_stream(1 if stream else 0))
 
 
 def set_test_hook(name, value):
     """For the tests (include/mrcal_amd.h, mrcal_amd_set_test_hook): force a path of the big camera block's
     factorization that a solve takes by itself only when a later point outgrows what its first point needed.
     Returns the previous value"""
-    import ctypes
-    f = _lib.lib.mrcal_amd_set_test_hook
-    f.restype, f.argtypes = ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]
-    r = f(name.encode(), int(value))
+    r = _lib.lib.mrcal_amd_set_test_hook(name.encode(), int(value))
     if r < 0: raise ValueError(f"unknown test hook {name!r}")
     return r

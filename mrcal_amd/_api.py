@@ -387,8 +387,6 @@ class Api:
             return c_tri
         # one mrcal_unproject() call per camera
         f = self.clib.mrcal_unproject
-        f.restype  = C.c_bool
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         px = np.zeros((N,3))
         for icam in np.unique(idx_tri[:,1]):
             sel_ = np.nonzero(idx_tri[:,1] == icam)[0]
@@ -603,8 +601,6 @@ class Api:
         dq_dv = np.empty((N,2,3))  if get_gradients else None
         dq_di = np.empty((N,2,Ni)) if get_gradients else None
         f = self.clib.mrcal_project
-        f.restype  = C.c_bool
-        f.argtypes = [C.c_void_p]*4 + [C.c_int, C.c_void_p, C.c_void_p]
         for im in range(models.shape[0]):
             sel = slice(None) if which is None else np.nonzero(which == im)[0]
             vi = np.ascontiguousarray(vb[sel]); n = vi.shape[0]
@@ -647,8 +643,6 @@ class Api:
             intr = np.ascontiguousarray(intrinsics_data, dtype=np.float64)
             vv = np.empty(qq.shape[:-1] + (3,))
             g = self.clib.mrcal_unproject
-            g.restype  = C.c_bool
-            g.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
             if not g(_ptr(vv), _ptr(qq), qq.size // 2, C.byref(m), _ptr(intr)):
                 raise RuntimeError("mrcal_unproject() failed!" + self._last_error())
             if normalize: vv /= np.linalg.norm(vv, axis=-1, keepdims=True)
@@ -659,8 +653,6 @@ class Api:
         dv_dq = np.empty((N,3,2))  if get_gradients else None
         dv_di = np.empty((N,3,Ni)) if get_gradients else None
         f = self.clib.mrcal_amd_unproject
-        f.restype  = C.c_bool
-        f.argtypes = [C.c_void_p]*4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_bool]
         for im in range(models.shape[0]):
             sel = slice(None) if which is None else np.nonzero(which == im)[0]
             qi = np.ascontiguousarray(qb[sel]); n = qi.shape[0]
@@ -685,9 +677,7 @@ class Api:
 
     def _last_error(self):
         if self.lib.has_symbol("mrcal_amd_last_error"):
-            f = self.clib.mrcal_amd_last_error
-            f.restype = C.c_char_p
-            s = f()
+            s = self.clib.mrcal_amd_last_error()
             if s:
                 return " " + s.decode()
         return ""

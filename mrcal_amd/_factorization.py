@@ -25,7 +25,6 @@ sequence mrcal's projection uncertainty runs (mrcal/model_analysis.py:837-843),
 works unchanged. Also here, because the J the factorization was made from is
 resident on the device: _Jt_x() and _A_Jt_J_At() (mrcal-genpywrap.py:477-731).
 """
-import ctypes as C
 import numpy as np
 
 
@@ -36,7 +35,6 @@ class CHOLMOD_factorization:
         equations: what optimizer_callback() returns. None if JtJ is singular"""
         from . import _lib
         L = _lib.lib
-        cls._declare(L)
         h = L.mrcal_amd_factorization_create_from_problem(problem.handle)
         if not h:
             return None
@@ -56,7 +54,6 @@ class CHOLMOD_factorization:
             raise RuntimeError("J must be a scipy.sparse.csr_matrix")
         L = _lib.lib
         self._L = L
-        self._declare(L)
         Nmeas, Nstate = J.shape
         P = np.ascontiguousarray(J.indptr,  dtype=np.int32)
         I = np.ascontiguousarray(J.indices, dtype=np.int32)
@@ -68,38 +65,7 @@ class CHOLMOD_factorization:
         self._h = L.mrcal_amd_factorization_create(
             Nmeas, Nstate, P.ctypes.data, I.ctypes.data, X.ctypes.data, *[int(v) for v in _partition])
         if not self._h:
-            f = L.mrcal_amd_last_error
-            f.restype = C.c_char_p
-            raise RuntimeError("CHOLMOD_factorization: " + (f() or b"failed").decode())
-
-    @staticmethod
-    def _declare(L):
-        if getattr(L, "_mrcal_amd_factorization_declared", False):
-            return
-        vp = C.c_void_p
-        L.mrcal_amd_factorization_create.restype  = vp
-        L.mrcal_amd_factorization_create.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]
-        L.mrcal_amd_factorization_create_from_problem.restype  = vp
-        L.mrcal_amd_factorization_create_from_problem.argtypes = [vp]
-        L.mrcal_amd_factorization_Nstate.restype, L.mrcal_amd_factorization_Nstate.argtypes = C.c_int, [vp]
-        L.mrcal_amd_factorization_Nmeasurements.restype, L.mrcal_amd_factorization_Nmeasurements.argtypes = C.c_int, [vp]
-        L.mrcal_amd_factorization_destroy.restype  = None
-        L.mrcal_amd_factorization_destroy.argtypes = [vp]
-        L.mrcal_amd_factorization_solve.restype  = C.c_bool
-        L.mrcal_amd_factorization_solve.argtypes = [vp, vp, C.c_int, vp]
-        L.mrcal_amd_factorization_rcond.restype  = C.c_double
-        L.mrcal_amd_factorization_rcond.argtypes = [vp]
-        L.mrcal_amd_factorization_solve_sys.restype  = C.c_bool
-        L.mrcal_amd_factorization_solve_sys.argtypes = [vp, C.c_int, vp, C.c_int, vp]
-        L.mrcal_amd_factorization_Jt_x.restype  = C.c_bool
-        L.mrcal_amd_factorization_Jt_x.argtypes = [vp, vp, vp]
-        L.mrcal_amd_factorization_A_Jt_J_At.restype  = C.c_bool
-        L.mrcal_amd_factorization_A_Jt_J_At.argtypes = [vp, vp, C.c_int, C.c_int, vp]
-        L.mrcal_amd_csr_Jt_x.restype  = C.c_bool
-        L.mrcal_amd_csr_Jt_x.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp]
-        L.mrcal_amd_csr_A_Jt_J_At.restype  = C.c_bool
-        L.mrcal_amd_csr_A_Jt_J_At.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp]
-        L._mrcal_amd_factorization_declared = True
+            raise RuntimeError("CHOLMOD_factorization: " + (L.mrcal_amd_last_error() or b"failed").decode())
 
     # CHOLMOD's system codes (cholmod_core.h), which mrcal_amd_factorization_solve_sys() takes
     _SYS = dict(A=0, LDLt=1, LD=2, DLt=3, L=4, Lt=5, D=6, P=7, Pt=8)
@@ -172,9 +138,7 @@ class CHOLMOD_factorization:
 
 
 def _last_error(L):
-    f = L.mrcal_amd_last_error
-    f.restype = C.c_char_p
-    return (f() or b"").decode()
+    return (L.mrcal_amd_last_error() or b"").decode()
 
 
 def _csr_args(Jp, Ji, Jx):
@@ -189,7 +153,6 @@ def _Jt_x(Jp, Ji, Jx, xt, out=None):
     number of columns). On the GPU"""
     from . import _lib
     L = _lib.lib
-    CHOLMOD_factorization._declare(L)
     if out is None:
         raise RuntimeError("The output array MUST be passed-in because there's no way to know its shape beforehand")
     Jp, Ji, Jx = _csr_args(Jp, Ji, Jx)
@@ -209,7 +172,6 @@ def _A_Jt_J_At(A, Jp, Ji, Jx, Nleading_rows_J=-1, out=None):
     over the Nleading_rows_J leading rows of the CSR J. A: (Nx,Nstate). On the GPU"""
     from . import _lib
     L = _lib.lib
-    CHOLMOD_factorization._declare(L)
     if Nleading_rows_J <= 0:
         raise RuntimeError("Nleading_rows_J must be passed, and must be > 0")
     Jp, Ji, Jx = _csr_args(Jp, Ji, Jx)

@@ -26,7 +26,9 @@ import tempfile
 
 import numpy as np
 
+from . import _handle
 from ._cabi import _ptr
+from ._handle import Handle, _failed
 from .utils import mapping_file_framenocameraindex
 
 _CB_MIN_SIDE = 32
@@ -37,11 +39,7 @@ _CB_MAX_LEVELS = 8
 _CB_DTYPES = {np.dtype(np.uint8): 1, np.dtype(np.uint16): 2}
 _CB_STAGES = ("upload", "response", "candidates", "refine", "grid")
 STATUS_OK, STATUS_SINGULAR, STATUS_LEFT_WINDOW = 0, 1, 2
-
-
-def _libs():
-    from . import _lib, _api
-    return _lib, _api
+_WHAT = "find_chessboard_corners()"        # what a failed call of the detector says it was
 
 
 class _Params(C.Structure):
@@ -114,7 +112,7 @@ def _board(W, H):
     return int(W), int(H)
 
 
-class ChessboardDetector:
+class ChessboardDetector(Handle):
     """find_chessboard_corners() resident: the device buffers for one shape and dtype of image are made once and every
 call reuses them.
 
@@ -137,8 +135,9 @@ call reuses them.
                                 per_level: the host's clock around each level tried, 0 for the others)
       .close(); a context manager"""
 
+    _destroy = "mrcal_amd_chessboard_detector_destroy"
+
     def __init__(self, shape, dtype=np.uint8, *, threshold_256=51, nms_radius=7, max_candidates=4096, pyramid_levels=0):
-        self.handle = None
         self.overflow, self._N = False, 0
         self.detection_level, self._last_level = None, 0
         self.shape = _shape(shape)
@@ -146,24 +145,12 @@ call reuses them.
         p = _params(threshold_256, nms_radius, max_candidates)
         self.pyramid_levels = _pyramid_levels(pyramid_levels, self.shape)
         self.max_candidates = p.max_candidates
-        lib, api = _libs()
-        self._L, self._api = lib.lib, api
         if self.pyramid_levels == 0:
-            f = self._L.mrcal_amd_chessboard_detector_create
-            f.restype, f.argtypes = C.c_void_p, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
-            self.handle = f(self.shape[1], self.shape[0], _CB_DTYPES[self.dtype], C.addressof(p), 0)
+            self._create(_WHAT, "mrcal_amd_chessboard_detector_create", self.shape[1], self.shape[0], _CB_DTYPES[self.dtype],
+                         C.addressof(p), 0)
         else:
-            f = self._L.mrcal_amd_chessboard_detector_create_pyramid
-            f.restype, f.argtypes = C.c_void_p, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t]
-            self.handle = f(self.shape[1], self.shape[0], _CB_DTYPES[self.dtype], C.addressof(p), self.pyramid_levels, 0)
-        if not self.handle:
-            self.handle = None
-            raise Exception("find_chessboard_corners() failed:" + api._last_error())
-        self._L.mrcal_amd_chessboard_detector_destroy.restype, self._L.mrcal_amd_chessboard_detector_destroy.argtypes = None, [C.c_void_p]
-
-    def _open(self):
-        if self.handle is None:
-            raise Exception("this ChessboardDetector has been closed")
+            self._create(_WHAT, "mrcal_amd_chessboard_detector_create_pyramid", self.shape[1], self.shape[0],
+                         _CB_DTYPES[self.dtype], C.addressof(p), self.pyramid_levels, 0)
 
     def candidates(self, image):
         self._open()
@@ -171,10 +158,8 @@ call reuses them.
         q = np.zeros((self.max_candidates, 2), dtype=np.float64)
         response, status = (np.zeros((self.max_candidates,), dtype=np.int32) for _ in range(2))
         N, overflow = C.c_int(0), C.c_int(0)
-        f = self._L.mrcal_amd_chessboard_detector_candidates
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*7
-        if not f(self.handle, _ptr(image), C.addressof(N), C.addressof(overflow), _ptr(q), _ptr(response), _ptr(status)):
-            raise Exception("find_chessboard_corners() failed:" + self._api._last_error())
+        self._call(_WHAT, "mrcal_amd_chessboard_detector_candidates", _ptr(image), C.addressof(N), C.addressof(overflow),
+                   _ptr(q), _ptr(response), _ptr(status))
         self.overflow, self._N = bool(overflow.value), N.value
         self.detection_level, self._last_level = None, 0
         return q[:N.value].copy(), response[:N.value].copy(), status[:N.value].copy()
@@ -186,18 +171,13 @@ call reuses them.
         corners = np.zeros((H, W, 2), dtype=np.float64)
         found = C.c_int(0)
         if self.pyramid_levels == 0 and not return_levels:
-            f = self._L.mrcal_amd_chessboard_detector_find_board
-            f.restype, f.argtypes = C.c_bool, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-            if not f(self.handle, _ptr(image), W, H, C.addressof(found), _ptr(corners)):
-                raise Exception("find_chessboard_corners() failed:" + self._api._last_error())
+            self._call(_WHAT, "mrcal_amd_chessboard_detector_find_board", _ptr(image), W, H, C.addressof(found), _ptr(corners))
             self.detection_level, self._last_level = (0 if found.value else None), 0
             return corners if found.value else None
         levels = np.zeros((H, W), dtype=np.int32)
         detection_level = C.c_int(-1)
-        f = self._L.mrcal_amd_chessboard_detector_find_board_pyramid
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        if not f(self.handle, _ptr(image), W, H, _ptr(corners), _ptr(levels), C.addressof(detection_level), C.addressof(found)):
-            raise Exception("find_chessboard_corners() failed:" + self._api._last_error())
+        self._call(_WHAT, "mrcal_amd_chessboard_detector_find_board_pyramid", _ptr(image), W, H, _ptr(corners), _ptr(levels),
+                   C.addressof(detection_level), C.addressof(found))
         self.detection_level = detection_level.value if found.value else None
         self._last_level = detection_level.value if found.value else 0
         # (the candidates response() speaks of are the last level's; their number is not handed out by this call)
@@ -215,20 +195,15 @@ call reuses them.
         if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or not 0 <= level <= self.pyramid_levels:
             raise Exception(f"find_chessboard_corners(): this detector has the levels 0..{self.pyramid_levels}, and level {level} was asked for")
         out = np.zeros(self.level_shape(int(level)), dtype=self.dtype)
-        f = self._L.mrcal_amd_chessboard_detector_read_level
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p, C.c_int, C.c_void_p]
-        if not f(self.handle, int(level), _ptr(out)):
-            raise Exception("find_chessboard_corners() failed:" + self._api._last_error())
+        self._call(_WHAT, "mrcal_amd_chessboard_detector_read_level", int(level), _ptr(out))
         return out
 
     def pyramid_milliseconds(self):
         self._open()
         decimate, descent = C.c_float(0), C.c_float(0)
         per_level = np.zeros((self.pyramid_levels + 1,), dtype=np.float32)
-        f = self._L.mrcal_amd_chessboard_detector_pyramid_milliseconds
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*4
-        if not f(self.handle, C.addressof(decimate), C.addressof(descent), _ptr(per_level)):
-            raise Exception("find_chessboard_corners() failed:" + self._api._last_error())
+        self._call(_WHAT, "mrcal_amd_chessboard_detector_pyramid_milliseconds", C.addressof(decimate), C.addressof(descent),
+                   _ptr(per_level))
         return dict(decimate=float(decimate.value), descent=float(descent.value), per_level=[float(x) for x in per_level])
 
     def response(self):
@@ -236,10 +211,7 @@ call reuses them.
         R = np.zeros(self.level_shape(self._last_level), dtype=np.int32)
         xy = np.zeros((self.max_candidates, 2), dtype=np.int32)
         Rmax = C.c_int32(0)
-        f = self._L.mrcal_amd_chessboard_detector_read_response
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*4
-        if not f(self.handle, _ptr(R), C.addressof(Rmax), _ptr(xy)):
-            raise Exception("find_chessboard_corners() failed:" + self._api._last_error())
+        self._call(_WHAT, "mrcal_amd_chessboard_detector_read_response", _ptr(R), C.addressof(Rmax), _ptr(xy))
         if self._N is None:
             return R, int(Rmax.value), None
         return R, int(Rmax.value), xy[:self._N].copy()
@@ -247,21 +219,8 @@ call reuses them.
     def stage_milliseconds(self):
         self._open()
         ms = np.zeros((len(_CB_STAGES),), dtype=np.float32)
-        f = self._L.mrcal_amd_chessboard_detector_stage_milliseconds
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2
-        if not f(self.handle, _ptr(ms)):
-            raise Exception("find_chessboard_corners() failed:" + self._api._last_error())
+        self._call(_WHAT, "mrcal_amd_chessboard_detector_stage_milliseconds", _ptr(ms))
         return dict(zip(_CB_STAGES, (float(x) for x in ms)))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._L.mrcal_amd_chessboard_detector_destroy(self.handle)
-            self.handle = None
-    def __del__(self):
-        try:    self.close()
-        except Exception: pass
-    def __enter__(self): return self
-    def __exit__(self, *a): self.close()
 
 
 def chessboard_corner_candidates(image, *, threshold_256=51, nms_radius=7, max_candidates=4096):
@@ -316,13 +275,11 @@ def chessboard_grid(q, W, H=None, *, response=None, status=None):
     N = q.shape[0]
     if response is not None: response = np.ascontiguousarray(response, dtype=np.int32).reshape(N)
     if status   is not None: status   = np.ascontiguousarray(status,   dtype=np.int32).reshape(N)
-    lib, api = _libs()
+    lib, _ = _handle._libs()
     corners = np.zeros((H, W, 2), dtype=np.float64)
     found = C.c_int(0)
-    f = lib.lib.mrcal_amd_chessboard_grid
-    f.restype, f.argtypes = C.c_bool, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    if not f(N, _ptr(q), _ptr(response), _ptr(status), W, H, C.addressof(found), _ptr(corners)):
-        raise Exception("chessboard_grid() failed:" + api._last_error())
+    if not lib.lib.mrcal_amd_chessboard_grid(N, _ptr(q), _ptr(response), _ptr(status), W, H, C.addressof(found), _ptr(corners)):
+        raise _failed("chessboard_grid()")
     return corners if found.value else None
 
 

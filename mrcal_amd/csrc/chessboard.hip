@@ -37,6 +37,7 @@
 #include "../../include/mrcal_amd.h"
 #include "host_state.hpp"
 #include "device_memory.hpp"
+#include "resident_common.hpp"
 #include "chessboard_plan.hpp"
 #include "chessboard_grid.hpp"
 
@@ -362,13 +363,6 @@ void cb_decimate_kernel(int W_in, int W_out, int H_out, const T* __restrict__ in
     out[k] = (T)cb_quad(t[0], t[1], t[W_in], t[W_in + 1]);
 }
 
-bool cb_have_device()
-{
-    if(mrcal_amd_device_count() > 0) return true;
-    set_error("no HIP device is visible: libmrcal_amd has no CPU fallback");
-    return false;
-}
-
 } // namespace
 
 } // namespace mrcal_amd
@@ -387,17 +381,12 @@ struct mrcal_amd_chessboard_detector
     int            level = 0;           // the level that was looked at last: what N, q, the response and the stages are of
     std::vector<double>  q;
     std::vector<int32_t> response, status;
-    hipEvent_t     event[5] = { NULL, NULL, NULL, NULL, NULL };    // around the upload, after the response, the candidates, the refinement
-    // ... with a pyramid. event[0], event[1] are around the start of the level looked at last then
+    StageEvents<5> events;             // around the upload, after the response, the candidates, the refinement
+    // ... with a pyramid. events 0 and 1 are around the start of the level looked at last then
     bool           pyramid_ran = false;
     float          level_ms[CB_MAX_LEVELS + 1] = {};               // the host's clock around each level tried: a..e and the read-back
-    hipEvent_t     pyramid_event[6] = { NULL, NULL, NULL, NULL, NULL, NULL };  // around the upload, the decimation, the descent
+    StageEvents<6> pyramid_events;     // around the upload, the decimation, the descent
     bool           descended = false;
-    ~mrcal_amd_chessboard_detector()
-    {
-        for(hipEvent_t e : event)         if(e != NULL) (void)hipEventDestroy(e);
-        for(hipEvent_t e : pyramid_event) if(e != NULL) (void)hipEventDestroy(e);
-    }
 };
 
 static bool cb_given(const mrcal_amd_chessboard_detector* d)
@@ -426,10 +415,10 @@ static bool cb_run_level(mrcal_amd_chessboard_detector* d, int level, const void
     int32_t*  status  = (int32_t*)(d->pool + p.status);
     const dim3 tiles(p.tiles_x*p.tiles_y), block(CB_THREADS);
 
-    HIP_TRY(hipEventRecord(d->event[0], NULL), return false);
+    if(!d->events.record(0)) return false;
     if(image != NULL)
         HIP_TRY(hipMemcpyAsync(d_image, image, (size_t)p.W*p.H*p.bytes_per_pixel, hipMemcpyHostToDevice, NULL), (void)hipDeviceSynchronize(); return false);
-    HIP_TRY(hipEventRecord(d->event[1], NULL), (void)hipDeviceSynchronize(); return false);
+    if(!d->events.record(1)) { (void)hipDeviceSynchronize(); return false; }
     if(d->pyramid.levels > 0)
     {
         // the levels share the mask words, and the words of a chunk past a level's own are never written by it: what
@@ -442,18 +431,18 @@ static bool cb_run_level(mrcal_amd_chessboard_detector* d, int level, const void
     if(p.bytes_per_pixel == 1) hipLaunchKernelGGL(cb_response_kernel<uint8_t>,  tiles, block, 0, NULL, p.W, p.H, p.tiles_x, (const uint8_t*)d_image,  R, Rmax);
     else                       hipLaunchKernelGGL(cb_response_kernel<uint16_t>, tiles, block, 0, NULL, p.W, p.H, p.tiles_x, (const uint16_t*)d_image, R, Rmax);
     HIP_TRY(hipGetLastError(), (void)hipDeviceSynchronize(); return false);
-    HIP_TRY(hipEventRecord(d->event[2], NULL), (void)hipDeviceSynchronize(); return false);
+    if(!d->events.record(2)) { (void)hipDeviceSynchronize(); return false; }
     hipLaunchKernelGGL(cb_candidates_kernel, tiles, block, 0, NULL, p.W, p.H, p.tiles_x, p.nms_radius, p.threshold_256, R, Rmax, words);
     HIP_TRY(hipGetLastError(), (void)hipDeviceSynchronize(); return false);
     hipLaunchKernelGGL(cb_scan_kernel, dim3(1), dim3(CB_SCAN_THREADS), 0, NULL, p.chunks, p.scan_per_thread, words, bases);
     HIP_TRY(hipGetLastError(), (void)hipDeviceSynchronize(); return false);
     hipLaunchKernelGGL(cb_scatter_kernel, dim3(p.chunks), block, 0, NULL, p.W, p.words_per_row, (unsigned)p.max_candidates, words, bases, R, xy, cr);
     HIP_TRY(hipGetLastError(), (void)hipDeviceSynchronize(); return false);
-    HIP_TRY(hipEventRecord(d->event[3], NULL), (void)hipDeviceSynchronize(); return false);
+    if(!d->events.record(3)) { (void)hipDeviceSynchronize(); return false; }
     if(p.bytes_per_pixel == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(cb_refine_kernel<uint8_t,  false>), dim3(p.refine_groups), block, 0, NULL, p.W, p.H, (unsigned)p.max_candidates, (const uint8_t*)d_image,  bases + p.chunks, xy, q, status, (int32_t*)NULL, 0);
     else                       hipLaunchKernelGGL(HIP_KERNEL_NAME(cb_refine_kernel<uint16_t, false>), dim3(p.refine_groups), block, 0, NULL, p.W, p.H, (unsigned)p.max_candidates, (const uint16_t*)d_image, bases + p.chunks, xy, q, status, (int32_t*)NULL, 0);
     HIP_TRY(hipGetLastError(), (void)hipDeviceSynchronize(); return false);
-    HIP_TRY(hipEventRecord(d->event[4], NULL), (void)hipDeviceSynchronize(); return false);
+    if(!d->events.record(4)) { (void)hipDeviceSynchronize(); return false; }
 
     uint32_t total = 0;
     // (the copy waits for the launches)
@@ -478,7 +467,7 @@ static bool cb_run(mrcal_amd_chessboard_detector* d, const void* image)
     d->N = -1;
     d->pyramid_ran = false;
     if(image == NULL) { set_error("find_chessboard_corners(): the image is NULL"); return false; }
-    if(!cb_have_device()) return false;
+    if(!have_device()) return false;
     return cb_run_level(d, 0, image);
 }
 
@@ -518,22 +507,21 @@ static bool cb_find_board_pyramid(mrcal_amd_chessboard_detector* d, const void* 
     d->pyramid_ran = false;
     d->descended = false;
     if(image == NULL) { set_error("find_chessboard_corners(): the image is NULL"); return false; }
-    if(!cb_have_device()) return false;
+    if(!have_device()) return false;
     const ChessboardPyramidPlan& pp = d->pyramid;
     const ChessboardPlan& p0 = pp.level[0];
     for(float& ms : d->level_ms) ms = 0.f;
     *found = 0;
     *detection_level = -1;
     // (made at the first call of this kind: a detector that is never asked for levels has none of them)
-    for(hipEvent_t& e : d->pyramid_event)
-        if(e == NULL) HIP_TRY(hipEventCreate(&e), return false);
+    if(!d->pyramid_events.create()) return false;
 
-    HIP_TRY(hipEventRecord(d->pyramid_event[0], NULL), return false);
+    if(!d->pyramid_events.record(0)) return false;
     HIP_TRY(hipMemcpyAsync(d->pool + p0.image, image, (size_t)p0.W*p0.H*p0.bytes_per_pixel, hipMemcpyHostToDevice, NULL), (void)hipDeviceSynchronize(); return false);
-    HIP_TRY(hipEventRecord(d->pyramid_event[1], NULL), (void)hipDeviceSynchronize(); return false);
-    HIP_TRY(hipEventRecord(d->pyramid_event[2], NULL), (void)hipDeviceSynchronize(); return false);
+    if(!d->pyramid_events.record(1)) { (void)hipDeviceSynchronize(); return false; }
+    if(!d->pyramid_events.record(2)) { (void)hipDeviceSynchronize(); return false; }
     if(!cb_decimate(d)) return false;
-    HIP_TRY(hipEventRecord(d->pyramid_event[3], NULL), (void)hipDeviceSynchronize(); return false);
+    if(!d->pyramid_events.record(3)) { (void)hipDeviceSynchronize(); return false; }
 
     const int n = board_width*board_height;
     int L = pp.levels;
@@ -559,7 +547,7 @@ static bool cb_find_board_pyramid(mrcal_amd_chessboard_detector* d, const void* 
     if(n > p0.max_candidates) { set_error("find_chessboard_corners(): internal error: a board of %d corners among %d candidates", n, p0.max_candidates); return false; }
     double*  dq     = (double*)(d->pool + pp.descent_q);
     int32_t* dlevel = (int32_t*)(d->pool + pp.descent_level);
-    HIP_TRY(hipEventRecord(d->pyramid_event[4], NULL), return false);
+    if(!d->pyramid_events.record(4)) return false;
     HIP_TRY(hipMemcpyAsync(dq,     corners, (size_t)n*2*sizeof(double), hipMemcpyHostToDevice, NULL), (void)hipDeviceSynchronize(); return false);
     HIP_TRY(hipMemcpyAsync(dlevel, levels,  (size_t)n*sizeof(int32_t),  hipMemcpyHostToDevice, NULL), (void)hipDeviceSynchronize(); return false);
     const dim3 groups(((unsigned)n + CB_THREADS/64 - 1)/(CB_THREADS/64)), block(CB_THREADS);
@@ -571,7 +559,7 @@ static bool cb_find_board_pyramid(mrcal_amd_chessboard_detector* d, const void* 
         else                       hipLaunchKernelGGL(HIP_KERNEL_NAME(cb_refine_kernel<uint16_t, true>), groups, block, 0, NULL, p.W, p.H, (unsigned)n, (const uint16_t*)I, (const uint32_t*)NULL, (const int32_t*)NULL, dq, (int32_t*)NULL, dlevel, l);
         HIP_TRY(hipGetLastError(), (void)hipDeviceSynchronize(); return false);
     }
-    HIP_TRY(hipEventRecord(d->pyramid_event[5], NULL), (void)hipDeviceSynchronize(); return false);
+    if(!d->pyramid_events.record(5)) { (void)hipDeviceSynchronize(); return false; }
     // (the copies wait for the launches)
     HIP_TRY(hipMemcpy(corners, dq,     (size_t)n*2*sizeof(double), hipMemcpyDeviceToHost), (void)hipDeviceSynchronize(); return false);
     HIP_TRY(hipMemcpy(levels,  dlevel, (size_t)n*sizeof(int32_t),  hipMemcpyDeviceToHost), (void)hipDeviceSynchronize(); return false);
@@ -599,7 +587,7 @@ static mrcal_amd_chessboard_detector* cb_create(int width, int height, int bytes
         set_error("%s", why.c_str());
         return NULL;
     }
-    if(!cb_have_device()) return NULL;
+    if(!have_device()) return NULL;
     if(free_device_bytes == 0)
     {
         size_t free_bytes = 0, total_bytes = 0;
@@ -616,8 +604,7 @@ static mrcal_amd_chessboard_detector* cb_create(int width, int height, int bytes
     if(!d->mem.alloc(&d->pool, plan.bytes)) { delete d; return NULL; }
     // (the words past the image's are never written: no bit of them may be set)
     HIP_TRY(hipMemset(d->pool + plan.level[0].words, 0, plan.level[0].bases - plan.level[0].words), delete d; return NULL);
-    for(int i = 0; i < 5; i++)
-        HIP_TRY(hipEventCreate(&d->event[i]), delete d; return NULL);
+    if(!d->events.create()) { delete d; return NULL; }
     return d;
 }
 
@@ -687,9 +674,9 @@ bool mrcal_amd_chessboard_detector_stage_milliseconds(mrcal_amd_chessboard_detec
     if(!cb_given(d)) return false;
     if(d->N < 0) { set_error("find_chessboard_corners(): no image has been looked at yet"); return false; }
     for(int i = 0; i < 4; i++)
-        HIP_TRY(hipEventElapsedTime(&milliseconds[i], d->event[i], d->event[i + 1]), return false);
+        if(!d->events.elapsed(&milliseconds[i], i, i + 1)) return false;
     // (with a pyramid the image was uploaded once, before the levels)
-    if(d->pyramid_ran) HIP_TRY(hipEventElapsedTime(&milliseconds[0], d->pyramid_event[0], d->pyramid_event[1]), return false);
+    if(d->pyramid_ran && !d->pyramid_events.elapsed(&milliseconds[0], 0, 1)) return false;
     milliseconds[4] = d->grid_ms;
     return true;
 }
@@ -729,9 +716,9 @@ bool mrcal_amd_chessboard_detector_pyramid_milliseconds(mrcal_amd_chessboard_det
     if(!cb_given(d)) return false;
     if(decimate == NULL || descent == NULL || per_level == NULL) { set_error("find_chessboard_corners(): an argument is NULL"); return false; }
     if(d->N < 0 || !d->pyramid_ran) { set_error("find_chessboard_corners(): no image has been looked at through the pyramid yet"); return false; }
-    HIP_TRY(hipEventElapsedTime(decimate, d->pyramid_event[2], d->pyramid_event[3]), return false);
+    if(!d->pyramid_events.elapsed(decimate, 2, 3)) return false;
     *descent = 0.f;
-    if(d->descended) HIP_TRY(hipEventElapsedTime(descent, d->pyramid_event[4], d->pyramid_event[5]), return false);
+    if(d->descended && !d->pyramid_events.elapsed(descent, 4, 5)) return false;
     for(int l=0; l<=d->pyramid.levels; l++) per_level[l] = d->level_ms[l];
     return true;
 }

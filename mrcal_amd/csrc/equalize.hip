@@ -352,22 +352,15 @@ void stretch_map_kernel(size_t N, const T* __restrict__ image, const uint32_t* _
     }
 }
 
-bool equalize_have_device()
-{
-    if(mrcal_amd_device_count() > 0) return true;
-    set_error("no HIP device is visible: libmrcal_amd has no CPU fallback");
-    return false;
-}
-
 template<class T>
 void launch_clahe(const EqualizePlan& p, const ClaheArgs& a, const void* d_in, void* d_out, uint32_t* hist, void* lut,
-                  hipEvent_t const* event)
+                  EqualizeStageEvents* event)
 {
     hipLaunchKernelGGL((clahe_hist_kernel<T>), dim3(p.hist_grid), dim3(EQUALIZE_THREADS), 0, NULL, a, p.bands, (const T*)d_in, hist);
-    if(event != NULL) (void)hipEventRecord(event[1], NULL);
+    (void)record(event, 1);
     if constexpr(sizeof(T) == 1) hipLaunchKernelGGL((clahe_lut_kernel<T,   64,  4>), dim3(p.lut_grid), dim3(64),   0, NULL, a, hist, (T*)lut);
     else                         hipLaunchKernelGGL((clahe_lut_kernel<T, 1024, 64>), dim3(p.lut_grid), dim3(1024), 0, NULL, a, hist, (T*)lut);
-    if(event != NULL) (void)hipEventRecord(event[2], NULL);
+    (void)record(event, 2);
     const dim3 grid(p.apply_grid);
     if(p.luts_in_lds)
         hipLaunchKernelGGL((clahe_apply_kernel<T, true>), grid, dim3(EQUALIZE_THREADS), (size_t)p.tiles_x*p.tiles_y*256, NULL,
@@ -378,11 +371,11 @@ void launch_clahe(const EqualizePlan& p, const ClaheArgs& a, const void* d_in, v
 }
 
 template<class T>
-void launch_stretch(const EqualizePlan& p, const void* d_in, void* d_out, uint32_t* minmax, hipEvent_t const* event)
+void launch_stretch(const EqualizePlan& p, const void* d_in, void* d_out, uint32_t* minmax, EqualizeStageEvents* event)
 {
     const size_t N = (size_t)p.W*(size_t)p.H;
     hipLaunchKernelGGL((stretch_minmax_kernel<T>), dim3(p.minmax_grid), dim3(EQUALIZE_THREADS), 0, NULL, N, (const T*)d_in, minmax);
-    if(event != NULL) { (void)hipEventRecord(event[1], NULL); (void)hipEventRecord(event[2], NULL); }
+    (void)record(event, 1); (void)record(event, 2);
     hipLaunchKernelGGL((stretch_map_kernel<T>), dim3(p.map_grid), dim3(EQUALIZE_THREADS), 0, NULL, N, (const T*)d_in, minmax, (uint8_t*)d_out);
 }
 
@@ -399,9 +392,8 @@ EqualizeParams equalize_params_of(const mrcal_amd_equalize_params_t* params)
     return p;
 }
 
-bool equalize_device(const EqualizePlan& p, const void* d_in, void* d_out, uint8_t* pool, void* const* stage_events)
+bool equalize_device(const EqualizePlan& p, const void* d_in, void* d_out, uint8_t* pool, EqualizeStageEvents* event)
 {
-    hipEvent_t const* event = (hipEvent_t const*)stage_events;
     if(p.method != EQUALIZE_METHOD_CLAHE && p.method != EQUALIZE_METHOD_STRETCH)
     { set_error("equalize(): internal error: no method to run"); return false; }
     if((((uintptr_t)d_in | (uintptr_t)d_out) & 15) != 0) { set_error("equalize(): the images on the device must be aligned to 16 bytes"); return false; }
@@ -412,7 +404,7 @@ bool equalize_device(const EqualizePlan& p, const void* d_in, void* d_out, uint8
         a.lut_scale = p.lut_scale; a.inv_tw = p.inv_tw; a.inv_th = p.inv_th;
         uint32_t* hist = (uint32_t*)(pool + p.hist);
         HIP_TRY(hipMemsetAsync(hist, 0, p.hist_bytes, NULL), return false);
-        if(event != NULL) HIP_TRY(hipEventRecord(event[0], NULL), return false);
+        if(!record(event, 0)) return false;
         if(p.dtype == EQUALIZE_DTYPE_UINT8) launch_clahe<uint8_t> (p, a, d_in, d_out, hist, pool + p.lut, event);
         else                                launch_clahe<uint16_t>(p, a, d_in, d_out, hist, pool + p.lut, event);
     }
@@ -421,11 +413,11 @@ bool equalize_device(const EqualizePlan& p, const void* d_in, void* d_out, uint8
         uint32_t* minmax = (uint32_t*)(pool + p.minmax);
         HIP_TRY(hipMemsetAsync(minmax,     0xFF, sizeof(uint32_t), NULL), return false);
         HIP_TRY(hipMemsetAsync(minmax + 1, 0,    sizeof(uint32_t), NULL), return false);
-        if(event != NULL) HIP_TRY(hipEventRecord(event[0], NULL), return false);
+        if(!record(event, 0)) return false;
         if(p.dtype == EQUALIZE_DTYPE_UINT8) launch_stretch<uint8_t> (p, d_in, d_out, minmax, event);
         else                                launch_stretch<uint16_t>(p, d_in, d_out, minmax, event);
     }
-    if(event != NULL) HIP_TRY(hipEventRecord(event[3], NULL), return false);
+    if(!record(event, 3)) return false;
     HIP_TRY(hipGetLastError(), return false);
     return true;
 }
@@ -459,9 +451,7 @@ struct mrcal_amd_equalizer
     DeviceBuffers mem;
     uint8_t*      pool = NULL;
     EqualizePlan  plan;
-    hipEvent_t    event[4] = { NULL, NULL, NULL, NULL };
-    bool          timed = false;
-    ~mrcal_amd_equalizer() { for(hipEvent_t e : event) if(e != NULL) (void)hipEventDestroy(e); }
+    EqualizeStageEvents events;
 };
 
 static bool equalizer_given(const mrcal_amd_equalizer* e)
@@ -481,7 +471,7 @@ mrcal_amd_equalizer_t* mrcal_amd_equalizer_create(int width, int height, int dty
     std::string why;
     if(!equalize_params_ok(&why, width, height, dtype, p)) { set_error("%s", why.c_str()); return NULL; }
     if(p.method == EQUALIZE_METHOD_NONE) { set_error("equalize(): an equalizer needs a method: MRCAL_AMD_EQUALIZE_CLAHE or _STRETCH"); return NULL; }
-    if(!equalize_have_device()) return NULL;
+    if(!have_device()) return NULL;
     size_t free_bytes = 0, total_bytes = 0;
     HIP_TRY(hipMemGetInfo(&free_bytes, &total_bytes), return NULL);
     EqualizePlan plan;
@@ -490,8 +480,7 @@ mrcal_amd_equalizer_t* mrcal_amd_equalizer_create(int width, int height, int dty
     mrcal_amd_equalizer* e = new mrcal_amd_equalizer;
     e->plan = plan;
     if(!e->mem.alloc(&e->pool, plan.bytes)) { delete e; return NULL; }
-    for(int i = 0; i < 4; i++)
-        HIP_TRY(hipEventCreate(&e->event[i]), delete e; return NULL);
+    if(!e->events.create()) { delete e; return NULL; }
     return e;
 }
 
@@ -500,15 +489,15 @@ bool mrcal_amd_equalizer_apply(mrcal_amd_equalizer_t* e, const void* in, void* o
     last_error_string().clear();
     if(!equalizer_given(e)) return false;
     if(in == NULL || out == NULL) { set_error("equalize(): an image is NULL"); return false; }
-    if(!equalize_have_device()) return false;
+    if(!have_device()) return false;
     const EqualizePlan& p = e->plan;
     const size_t N = (size_t)p.W*(size_t)p.H;
-    e->timed = false;
+    e->events.timed = false;
     HIP_TRY(hipMemcpy(e->pool + p.image, in, N*equalize_pixel_bytes(p.dtype), hipMemcpyHostToDevice), return false);
-    if(!equalize_device(p, e->pool + p.image, e->pool + p.result, e->pool, (void* const*)e->event)) return false;
+    if(!equalize_device(p, e->pool + p.image, e->pool + p.result, e->pool, &e->events)) return false;
     // (the copy waits for the launches)
     HIP_TRY(hipMemcpy(out, e->pool + p.result, N*equalize_pixel_bytes(p.dtype_out), hipMemcpyDeviceToHost), return false);
-    e->timed = true;
+    e->events.timed = true;
     return true;
 }
 
@@ -516,9 +505,9 @@ bool mrcal_amd_equalizer_stage_milliseconds(mrcal_amd_equalizer_t* e, float* mil
 {
     last_error_string().clear();
     if(!equalizer_given(e)) return false;
-    if(!e->timed) { set_error("equalize(): no image has been equalized yet"); return false; }
+    if(!e->events.timed) { set_error("equalize(): no image has been equalized yet"); return false; }
     for(int i = 0; i < 3; i++)
-        HIP_TRY(hipEventElapsedTime(&milliseconds[i], e->event[i], e->event[i+1]), return false);
+        if(!e->events.elapsed(&milliseconds[i], i, i+1)) return false;
     // (stretch has no such stage: what lies between its two events is no work)
     if(e->plan.method == EQUALIZE_METHOD_STRETCH) milliseconds[1] = 0.f;
     return true;

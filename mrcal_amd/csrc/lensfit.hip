@@ -29,6 +29,7 @@
 #include "lens_dispatch.hpp"
 #include "device_math.hpp"
 #include "device_memory.hpp"
+#include "resident_common.hpp"
 #include "lensfit_plan.hpp"
 #include "../../include/mrcal_amd.h"
 
@@ -421,14 +422,12 @@ struct mrcal_amd_lensfit
     double* d_rt   = NULL;      // [Ntrials][6]
     double* d_res  = NULL;      // [Ntrials][LF_RES_N]
     hipStream_t   stream = NULL;
-    hipEvent_t    ev0 = NULL, ev1 = NULL;
+    StageEvents<2> events;      // around the fit's launch
     float         fit_ms = -1.0f;
     DeviceBuffers mem;
     ~mrcal_amd_lensfit()
     {
         mem.free_all();
-        if(ev0) hipEventDestroy(ev0);
-        if(ev1) hipEventDestroy(ev1);
         if(stream) hipStreamDestroy(stream);
     }
 };
@@ -438,17 +437,10 @@ extern "C" {
 mrcal_amd_lensfit_t* mrcal_amd_lensfit_create(void)
 {
     last_error_string().clear();
-    if(mrcal_amd_device_count() <= 0)
-    {
-        set_error("no HIP device is visible: libmrcal_amd has no CPU fallback");
-        return NULL;
-    }
+    if(!have_device()) return NULL;
     mrcal_amd_lensfit* lf = new mrcal_amd_lensfit();
-    bool ok = true;
-    HIP_TRY(hipStreamCreateWithFlags(&lf->stream, hipStreamNonBlocking), ok = false);
-    if(ok) HIP_TRY(hipEventCreate(&lf->ev0), ok = false);
-    if(ok) HIP_TRY(hipEventCreate(&lf->ev1), ok = false);
-    if(!ok) { delete lf; return NULL; }
+    HIP_TRY(hipStreamCreateWithFlags(&lf->stream, hipStreamNonBlocking), delete lf; return NULL);
+    if(!lf->events.create()) { delete lf; return NULL; }
     return lf;
 }
 
@@ -539,7 +531,7 @@ bool mrcal_amd_lensfit_fit(mrcal_amd_lensfit_t* lf,
     }
     a.cfg = lens_config_of(*lensmodel);
 
-    HIP_TRY(hipEventRecord(lf->ev0, st), return false);
+    if(!lf->events.record(0, st)) return false;
     for_parametric_lens((int)lensmodel->type, [&](auto k)
     {
         using K = decltype(k);
@@ -547,11 +539,11 @@ bool mrcal_amd_lensfit_fit(mrcal_amd_lensfit_t* lf,
                            a, lf->d_p, lf->d_q, lf->d_w, lf->d_seed, lf->d_rt, lf->d_res);
     });
     HIP_TRY(hipGetLastError(), return false);
-    HIP_TRY(hipEventRecord(lf->ev1, st), return false);
+    if(!lf->events.record(1, st)) return false;
     std::vector<double> res((size_t)Ntrials*LF_RES_N);
     HIP_TRY(hipMemcpyAsync(res.data(), lf->d_res, res.size()*sizeof(double), hipMemcpyDeviceToHost, st), return false);
     HIP_TRY(hipStreamSynchronize(st), return false);
-    HIP_TRY(hipEventElapsedTime(&lf->fit_ms, lf->ev0, lf->ev1), return false);
+    if(!lf->events.elapsed(&lf->fit_ms, 0, 1)) return false;
 
     // the best trial: the lowest rms among those that did not fail, the first of equals
     int best = -1;

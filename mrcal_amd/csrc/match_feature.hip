@@ -34,6 +34,7 @@
 #include "../../include/mrcal_amd.h"
 #include "host_state.hpp"
 #include "device_memory.hpp"
+#include "resident_common.hpp"
 #include "remap.hpp"
 #include "equalize.hpp"
 #include "match_plan.hpp"
@@ -438,13 +439,6 @@ bool launch_correlate_t(int method, const MfArgs& a, int Ngroups, size_t lds, co
     return false;
 }
 
-bool mf_have_device()
-{
-    if(mrcal_amd_device_count() > 0) return true;
-    set_error("no HIP device is visible: libmrcal_amd has no CPU fallback");
-    return false;
-}
-
 } // namespace
 
 } // namespace mrcal_amd
@@ -481,7 +475,7 @@ mrcal_amd_feature_matcher_create(const void* image0, int width0, int height0,
     last_error_string().clear();
     std::string why;
     if(!match_sizes_ok(&why, 0, 1, 1, 0, width0, height0, width1, height1, dtype)) { set_error("%s", why.c_str()); return NULL; }
-    if(!mf_have_device()) return NULL;
+    if(!have_device()) return NULL;
     mrcal_amd_feature_matcher* m = new mrcal_amd_feature_matcher;
     m->dtype = dtype;
     m->W[0] = width0; m->H[0] = height0; m->W[1] = width1; m->H[1] = height1;
@@ -510,7 +504,7 @@ mrcal_amd_feature_matcher_create_equalized(const void* image0, int width0, int h
        !equalize_params_ok(&why, width0, height0, dtype, equalization) ||
        !equalize_params_ok(&why, width1, height1, dtype, equalization))
     { set_error("%s", why.c_str()); return NULL; }
-    if(!mf_have_device()) return NULL;
+    if(!have_device()) return NULL;
     mrcal_amd_feature_matcher* m = new mrcal_amd_feature_matcher;
     m->W[0] = width0; m->H[0] = height0; m->W[1] = width1; m->H[1] = height1;
     const void* host[2] = { image0, image1 };
@@ -549,7 +543,7 @@ bool mrcal_amd_feature_matcher_match(mrcal_amd_feature_matcher_t* m, int N, cons
                    m->W[0], m->H[0], m->W[1], m->H[1], m->dtype))
     { set_error("%s", why.c_str()); return false; }
     if(N == 0) return true;
-    if(!mf_have_device()) return false;
+    if(!have_device()) return false;
 
     const int    tw = template_width, th = template_height;
     const size_t Npixels = (size_t)tw*th;

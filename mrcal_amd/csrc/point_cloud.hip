@@ -25,6 +25,7 @@
 #include "../../include/mrcal_amd.h"
 #include "host_state.hpp"
 #include "device_memory.hpp"
+#include "resident_common.hpp"
 #include "stereo_range_device.hpp"
 #include "point_cloud_plan.hpp"
 #include "point_cloud.hpp"
@@ -217,13 +218,6 @@ void cloud_scatter_kernel(CloudArgs a, const uint16_t* __restrict__ disparity, c
     }
 }
 
-bool cloud_have_device()
-{
-    if(mrcal_amd_device_count() > 0) return true;
-    set_error("no HIP device is visible: libmrcal_amd has no CPU fallback");
-    return false;
-}
-
 } // namespace
 
 } // namespace mrcal_amd
@@ -246,9 +240,7 @@ struct mrcal_amd_point_cloud
     // the last cloud
     int           N = -1;
     size_t        point_bytes = 0, color_bytes = 0;     // of a record's point, of its colour
-    hipEvent_t    event[5] = { NULL, NULL, NULL, NULL, NULL };  // around the mask, after the scan, around the scatter
-    bool          timed = false;
-    ~mrcal_amd_point_cloud() { for(hipEvent_t e : event) if(e != NULL) (void)hipEventDestroy(e); }
+    StageEvents<5> events;              // around the mask, after the scan, around the scatter
 };
 
 static bool cloud_given(const mrcal_amd_point_cloud* c)
@@ -279,7 +271,7 @@ bool point_cloud_compute_device(mrcal_amd_point_cloud_t* c, const uint16_t* d_di
                                 const mrcal_amd_point_cloud_params_t* params, int* N, const void* d_color_image)
 {
     c->N = -1;
-    c->timed = false;
+    c->events.timed = false;
     const mrcal_amd_point_cloud_params_t& rq = *params;
     const int channels = rq.image == NULL ? 0 : rq.image_channels != 0 ? rq.image_channels : -1;     // (an image of 0 channels is none, and refused)
     const int channel_bytes = rq.image_dtype == MRCAL_AMD_IMAGE_UINT8 ? 1 : rq.image_dtype == MRCAL_AMD_IMAGE_UINT16 ? 2 : 0;
@@ -320,13 +312,13 @@ bool point_cloud_compute_device(mrcal_amd_point_cloud_t* c, const uint16_t* d_di
     uint64_t* words  = (uint64_t*)(c->pool + plan.words);
     uint32_t* counts = (uint32_t*)(c->pool + plan.counts);
     uint32_t* bases  = (uint32_t*)(c->pool + plan.bases);
-    HIP_TRY(hipEventRecord(c->event[0], NULL), return false);
+    if(!c->events.record(0)) return false;
     hipLaunchKernelGGL(cloud_mask_kernel, dim3(plan.groups), dim3(CLOUD_THREADS), 0, NULL, a, d_disparity, c->map, words, counts);
     HIP_TRY(hipGetLastError(), return false);
-    HIP_TRY(hipEventRecord(c->event[1], NULL), return false);
+    if(!c->events.record(1)) return false;
     hipLaunchKernelGGL(cloud_scan_kernel, dim3(1), dim3(CLOUD_SCAN_THREADS), 0, NULL, plan.groups, plan.scan_per_thread, counts, bases);
     HIP_TRY(hipGetLastError(), return false);
-    HIP_TRY(hipEventRecord(c->event[2], NULL), return false);
+    if(!c->events.record(2)) return false;
     uint32_t total = 0;
     // (the copy waits for the launches)
     HIP_TRY(hipMemcpy(&total, bases + plan.groups, sizeof(total), hipMemcpyDeviceToHost), (void)hipDeviceSynchronize(); return false);
@@ -348,17 +340,17 @@ bool point_cloud_compute_device(mrcal_amd_point_cloud_t* c, const uint16_t* d_di
     a.capacity = (unsigned)c->capacity;
     if(total > 0)
     {
-        HIP_TRY(hipEventRecord(c->event[3], NULL), return false);
+        if(!c->events.record(3)) return false;
         if(rq.points_float32) cloud_launch_scatter<float> (c, a, d_disparity, d_image, channels, rq.image_dtype);
         else                  cloud_launch_scatter<double>(c, a, d_disparity, d_image, channels, rq.image_dtype);
         HIP_TRY(hipGetLastError(), (void)hipDeviceSynchronize(); return false);
-        HIP_TRY(hipEventRecord(c->event[4], NULL), (void)hipDeviceSynchronize(); return false);
+        if(!c->events.record(4)) { (void)hipDeviceSynchronize(); return false; }
     }
     HIP_TRY(hipStreamSynchronize(NULL), return false);
     c->N = (int)total;
     c->point_bytes = 3*(rq.points_float32 ? sizeof(float) : sizeof(double));
     c->color_bytes = (size_t)channels*channel_bytes;
-    c->timed = true;
+    c->events.timed = true;
     *N = c->N;
     return true;
 }
@@ -382,7 +374,7 @@ mrcal_amd_point_cloud_create(const mrcal_lensmodel_type_t rectification_model_ty
     // (the refusals that need no device first)
     if(!cloud_plan(&plan, &why, width, height, SIZE_MAX)) { set_error("%s", why.c_str()); return NULL; }
     if(((uintptr_t)device_map0 & 15) != 0) { set_error("stereo_point_cloud(): the map on the device must be aligned to 16 bytes"); return NULL; }
-    if(!cloud_have_device()) return NULL;
+    if(!have_device()) return NULL;
     size_t free_bytes = 0, total_bytes = 0;
     HIP_TRY(hipMemGetInfo(&free_bytes, &total_bytes), return NULL);
     if(!cloud_plan(&plan, &why, width, height, free_bytes)) { set_error("%s", why.c_str()); return NULL; }
@@ -395,15 +387,14 @@ mrcal_amd_point_cloud_create(const mrcal_lensmodel_type_t rectification_model_ty
     c->range_args.latlon   = rectification_model_type == MRCAL_LENSMODEL_LATLON;
     c->map = device_map0;
     if(!c->mem.alloc(&c->pool, plan.bytes)) { delete c; return NULL; }
-    for(int i = 0; i < 5; i++)
-        HIP_TRY(hipEventCreate(&c->event[i]), delete c; return NULL);
+    if(!c->events.create()) { delete c; return NULL; }
     return c;
 }
 
 bool mrcal_amd_point_cloud_set_map(mrcal_amd_point_cloud_t* c, const float* map0)
 {
     last_error_string().clear();
-    if(!cloud_given(c) || !cloud_have_device()) return false;
+    if(!cloud_given(c) || !have_device()) return false;
     if(map0 == NULL) { set_error("stereo_point_cloud(): the map is NULL"); return false; }
     const size_t n = (size_t)2*c->plan.W*c->plan.H;
     if(c->own_map == NULL && !c->mem.alloc(&c->own_map, n)) return false;
@@ -418,7 +409,7 @@ bool mrcal_amd_point_cloud_compute(mrcal_amd_point_cloud_t* c, const uint16_t* d
     last_error_string().clear();
     if(!cloud_given(c)) return false;
     if(disparity_scaled == NULL || params == NULL || N == NULL) { set_error("stereo_point_cloud(): an argument is NULL"); return false; }
-    if(!cloud_have_device()) return false;
+    if(!have_device()) return false;
     c->N = -1;
     uint16_t* d_disparity = (uint16_t*)(c->pool + c->plan.disparity);
     HIP_TRY(hipMemcpy(d_disparity, disparity_scaled, (size_t)c->plan.W*c->plan.H*sizeof(uint16_t), hipMemcpyHostToDevice), return false);
@@ -443,12 +434,10 @@ bool mrcal_amd_point_cloud_stage_milliseconds(mrcal_amd_point_cloud_t* c, float*
 {
     last_error_string().clear();
     if(!cloud_given(c)) return false;
-    if(!c->timed) { set_error("stereo_point_cloud(): no cloud has been computed yet"); return false; }
-    HIP_TRY(hipEventElapsedTime(&milliseconds[0], c->event[0], c->event[1]), return false);
-    HIP_TRY(hipEventElapsedTime(&milliseconds[1], c->event[1], c->event[2]), return false);
+    if(!c->events.timed) { set_error("stereo_point_cloud(): no cloud has been computed yet"); return false; }
+    if(!c->events.elapsed(&milliseconds[0], 0, 1) || !c->events.elapsed(&milliseconds[1], 1, 2)) return false;
     milliseconds[2] = 0.f;              // (an empty cloud: nothing was scattered)
-    if(c->N > 0) HIP_TRY(hipEventElapsedTime(&milliseconds[2], c->event[3], c->event[4]), return false);
-    return true;
+    return c->N == 0 || c->events.elapsed(&milliseconds[2], 3, 4);
 }
 
 void mrcal_amd_point_cloud_destroy(mrcal_amd_point_cloud_t* c) { delete c; }

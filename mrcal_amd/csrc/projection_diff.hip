@@ -37,6 +37,7 @@
 #include "lens_dispatch.hpp"
 #include "device_math.hpp"
 #include "device_memory.hpp"
+#include "resident_common.hpp"
 #include "noise_propagation.hpp"
 #include "../../include/mrcal_amd.h"
 
@@ -424,12 +425,6 @@ hipError_t launch_fit(int Nfits, int M, int N, bool atinfinity, const double foc
     return hipGetLastError();
 }
 
-bool have_device()
-{
-    if(mrcal_amd_device_count() > 0) return true;
-    set_error("no HIP device is visible: libmrcal_amd has no CPU fallback");
-    return false;
-}
 bool fit_sizes_ok(int M, int N)
 {
     if(M >= 1 && N >= 1 && (int64_t)M*N <= (int64_t)INT32_MAX/4) return true;
@@ -460,15 +455,13 @@ struct mrcal_amd_projection_diff
     double* d_res     = NULL;   // [Nfits][FIT_RES_N]
     double* d_Rt      = NULL;   // [Nfits][12]
     hipStream_t   stream = NULL;
-    hipEvent_t    ev0 = NULL, ev1 = NULL;       // around the fit's launch, if asked for
+    StageEvents<2> events;                      // around the fit's launch, if asked for
     bool          time_fit = false;
     float         fit_ms = -1.0f;
     DeviceBuffers mem;
     ~mrcal_amd_projection_diff()
     {
         mem.free_all();
-        if(ev0) hipEventDestroy(ev0);
-        if(ev1) hipEventDestroy(ev1);
         if(stream) hipStreamDestroy(stream);
     }
 };
@@ -602,19 +595,18 @@ bool mrcal_amd_projection_diff_evaluate(mrcal_amd_projection_diff_t* pd,
     {
         if(pd->time_fit)
         {
-            if(pd->ev0 == NULL) HIP_TRY(hipEventCreate(&pd->ev0), return false);
-            if(pd->ev1 == NULL) HIP_TRY(hipEventCreate(&pd->ev1), return false);
-            HIP_TRY(hipEventRecord(pd->ev0, st), return false);
+            // (made when first asked for)
+            if(!pd->events.create() || !pd->events.record(0, st)) return false;
         }
         HIP_TRY(launch_fit(Nfits, Nd, N, atinfinity, focus_center, focus_radius, pd->d_q0, pd->d_p, pd->d_v + (size_t)N*3, (size_t)N*3,
                            weighted ? pd->d_w : NULL, DN, pd->d_res, pd->d_Rt, st), return false);
-        if(pd->time_fit) HIP_TRY(hipEventRecord(pd->ev1, st), return false);
+        if(pd->time_fit && !pd->events.record(1, st)) return false;
         // the verdicts before anything else is queued: too few points is the caller's exception
         std::vector<double> res((size_t)Nfits*FIT_RES_N);
         HIP_TRY(hipMemcpyAsync(res.data(), pd->d_res, res.size()*sizeof(double), hipMemcpyDeviceToHost, st), return false);
         HIP_TRY(hipMemcpyAsync(Rt10, pd->d_Rt, (size_t)Nfits*12*sizeof(double), hipMemcpyDeviceToHost, st), return false);
         HIP_TRY(hipStreamSynchronize(st), return false);
-        if(pd->time_fit) HIP_TRY(hipEventElapsedTime(&pd->fit_ms, pd->ev0, pd->ev1), return false);
+        if(pd->time_fit && !pd->events.elapsed(&pd->fit_ms, 0, 1)) return false;
         bool too_few = false;
         for(int f = 0; f < Nfits; f++)
         {

@@ -27,6 +27,7 @@
 #include "kernels.hpp"
 #include "host_state.hpp"
 #include "device_memory.hpp"
+#include "resident_common.hpp"
 #include "stereo_geometry.hpp"
 #include "remap.hpp"
 #include "stereo_sgm.hpp"
@@ -549,13 +550,6 @@ bool range_arguments(RangeArgs* a, mrcal_lensmodel_type_t t, const double* fxycx
     a->baseline = baseline;
     a->latlon   = t == MRCAL_LENSMODEL_LATLON;
     return true;
-}
-
-bool have_device()
-{
-    if(mrcal_amd_device_count() > 0) return true;
-    set_error("no HIP device is visible: libmrcal_amd has no CPU fallback");
-    return false;
 }
 
 // dense (H,W) uint16 host array -> (H,W) double host array

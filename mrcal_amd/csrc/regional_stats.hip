@@ -26,6 +26,7 @@
 #include "noise_propagation.hpp"
 #include "regional_stats_plan.hpp"
 #include "regional_stats.hpp"
+#include "resident_common.hpp"
 #include "../../include/mrcal_amd.h"
 
 using namespace mrcal_amd;
@@ -282,11 +283,9 @@ mrcal_amd_regional_statistics_create(mrcal_amd_problem_t* P, int gridn_width, in
         return NULL;
 
     hipStream_t st = P->stream;
-    hipEvent_t ev0 = NULL, ev1 = NULL;
-    HIP_TRY(hipEventCreate(&ev0), return NULL);
-    HIP_TRY(hipEventCreate(&ev1), hipEventDestroy(ev0); return NULL);
-    bool ok = true;
-    HIP_TRY(hipEventRecord(ev0, st), ok = false);
+    StageEvents<2> events;          // around the binning
+    if(!events.create()) return NULL;
+    bool ok = events.record(0, st);
     if(ok) HIP_TRY(hipMemsetAsync(d_hist, 0, (size_t)plan.hist_ints*sizeof(int), st), ok = false);
     if(ok)
     {
@@ -300,17 +299,15 @@ mrcal_amd_regional_statistics_create(mrcal_amd_problem_t* P, int gridn_width, in
                            P->op[P->icur].x, s->d_mean, s->d_stdev, s->d_count);
         HIP_TRY(hipGetLastError(), ok = false);
     }
-    if(ok) HIP_TRY(hipEventRecord(ev1, st), ok = false);
+    ok = ok && events.record(1, st);
     // (also on failure: nothing queued may still be using the temporaries)
     HIP_TRY(hipStreamSynchronize(st), ok = false);
     if(ok)
     {
         float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1), ok = false);
+        ok = events.elapsed(&ms, 0, 1);
         s->binning_ms = ms;
     }
-    hipEventDestroy(ev0);
-    hipEventDestroy(ev1);
     return ok ? s.release() : NULL;
 }
 

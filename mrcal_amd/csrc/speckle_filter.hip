@@ -248,19 +248,12 @@ void speckle_apply_kernel(size_t N, int new_value, int max_speckle_size, const i
     if(root >= 0 && count[root] <= max_speckle_size) image[pixel] = (int16_t)new_value;
 }
 
-bool speckle_have_device()
-{
-    if(mrcal_amd_device_count() > 0) return true;
-    set_error("no HIP device is visible: libmrcal_amd has no CPU fallback");
-    return false;
-}
-
 } // namespace
 
-bool speckle_filter_device(const SpeckleGrids& g, const SpeckleParams& p, int16_t* image, void* workspace, void* const* pass_events)
+bool speckle_filter_device(const SpeckleGrids& g, const SpeckleParams& p, int16_t* image, void* workspace, SpecklePassEvents* pass_events)
 {
     // (recorded only for the stand-alone filter, which reports its passes one by one)
-#define SPECKLE_PASS_DONE(i) do { if(pass_events != NULL) HIP_TRY(hipEventRecord((hipEvent_t)pass_events[i], NULL), return false); } while(0)
+#define SPECKLE_PASS_DONE(i) do { if(!record(pass_events, i)) return false; } while(0)
     const size_t N = (size_t)g.W*(size_t)g.H;
     int32_t* label = (int32_t*)workspace;
     int32_t* count = (int32_t*)((uint8_t*)workspace + speckle_count_offset(N));
@@ -292,9 +285,7 @@ struct mrcal_amd_speckle_filter
     DeviceBuffers mem;
     uint8_t*      pool = NULL;
     SpecklePlan   plan;
-    hipEvent_t    event[5] = { NULL, NULL, NULL, NULL, NULL };      // before the first pass, and after each of the four
-    bool          timed = false;
-    ~mrcal_amd_speckle_filter() { for(hipEvent_t e : event) if(e != NULL) (void)hipEventDestroy(e); }
+    SpecklePassEvents events;       // before the first pass, and after each of the four
 };
 
 static bool speckle_given(const mrcal_amd_speckle_filter* f)
@@ -311,7 +302,7 @@ mrcal_amd_speckle_filter_t* mrcal_amd_speckle_filter_create(int width, int heigh
     last_error_string().clear();
     std::string why;
     if(!speckle_params_ok(&why, width, height, 0, 0, 0)) { set_error("%s", why.c_str()); return NULL; }
-    if(!speckle_have_device()) return NULL;
+    if(!have_device()) return NULL;
     size_t free_bytes = 0, total_bytes = 0;
     HIP_TRY(hipMemGetInfo(&free_bytes, &total_bytes), return NULL);
     SpecklePlan plan;
@@ -320,8 +311,7 @@ mrcal_amd_speckle_filter_t* mrcal_amd_speckle_filter_create(int width, int heigh
     mrcal_amd_speckle_filter* f = new mrcal_amd_speckle_filter;
     f->plan = plan;
     if(!f->mem.alloc(&f->pool, plan.bytes)) { delete f; return NULL; }
-    for(int i = 0; i < 5; i++)
-        HIP_TRY(hipEventCreate(&f->event[i]), delete f; return NULL);
+    if(!f->events.create()) { delete f; return NULL; }
     return f;
 }
 
@@ -334,17 +324,17 @@ bool mrcal_amd_speckle_filter_apply(mrcal_amd_speckle_filter_t* f, const int16_t
     std::string why;
     if(!speckle_params_ok(&why, g.W, g.H, new_value, max_speckle_size, max_diff)) { set_error("%s", why.c_str()); return false; }
     if(in == NULL || out == NULL) { set_error("filter_speckles(): an image is NULL"); return false; }
-    if(!speckle_have_device()) return false;
+    if(!have_device()) return false;
     const size_t bytes = (size_t)g.W*(size_t)g.H*sizeof(int16_t);
     int16_t* d_image = (int16_t*)(f->pool + f->plan.image);
-    f->timed = false;
+    f->events.timed = false;
     HIP_TRY(hipMemcpy(d_image, in, bytes, hipMemcpyHostToDevice), return false);
     if(!speckle_filter_device(g, speckle_params(new_value, max_speckle_size, max_diff), d_image, f->pool + f->plan.label,
-                              (void* const*)f->event))
+                              &f->events))
         return false;
     // (the copy waits for the launches)
     HIP_TRY(hipMemcpy(out, d_image, bytes, hipMemcpyDeviceToHost), return false);
-    f->timed = true;
+    f->events.timed = true;
     return true;
 }
 
@@ -352,18 +342,17 @@ bool mrcal_amd_speckle_filter_milliseconds(mrcal_amd_speckle_filter_t* f, float*
 {
     last_error_string().clear();
     if(!speckle_given(f)) return false;
-    if(!f->timed) { set_error("filter_speckles(): no image has been filtered yet"); return false; }
-    HIP_TRY(hipEventElapsedTime(milliseconds, f->event[0], f->event[4]), return false);
-    return true;
+    if(!f->events.timed) { set_error("filter_speckles(): no image has been filtered yet"); return false; }
+    return f->events.elapsed(milliseconds, 0, 4);
 }
 
 bool mrcal_amd_speckle_filter_pass_milliseconds(mrcal_amd_speckle_filter_t* f, float* milliseconds)
 {
     last_error_string().clear();
     if(!speckle_given(f)) return false;
-    if(!f->timed) { set_error("filter_speckles(): no image has been filtered yet"); return false; }
+    if(!f->events.timed) { set_error("filter_speckles(): no image has been filtered yet"); return false; }
     for(int i = 0; i < 4; i++)
-        HIP_TRY(hipEventElapsedTime(&milliseconds[i], f->event[i], f->event[i+1]), return false);
+        if(!f->events.elapsed(&milliseconds[i], i, i+1)) return false;
     return true;
 }
 

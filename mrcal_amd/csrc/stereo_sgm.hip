@@ -386,13 +386,6 @@ void sgm_check_kernel(SgmArgs a, int disp12_max_diff, const uint8_t* __restrict_
 ////////////////////////////////////////////////////////////////////////////////
 // host
 ////////////////////////////////////////////////////////////////////////////////
-bool sgm_have_device()
-{
-    if(mrcal_amd_device_count() > 0) return true;
-    set_error("no HIP device is visible: libmrcal_amd has no CPU fallback");
-    return false;
-}
-
 template<int NPL>
 void sgm_launch_path(const SgmPlan& plan, const SgmArgs& a, int dx, int dy, int first,
                      const uint64_t* census0, const uint64_t* census1, uint16_t* S)
@@ -433,13 +426,11 @@ struct mrcal_amd_stereo_sgm
     uint8_t*      pool = NULL;
     SgmPlan       plan;
     SgmParams     params;
-    hipEvent_t    stage[6] = { NULL, NULL, NULL, NULL, NULL, NULL };    // before the census, and after each stage; the last: after the speckle filter
-    bool          timed = false;
+    StageEvents<6> stage;           // before the census, and after each stage; the last: after the speckle filter
     // the speckle filter (speckle_filter.hip), on request only: its labels and counts lie in S, which is dead by then
     bool          speckle_on = false;
     SpeckleParams speckle = { 0, 0, 0 };
     SpeckleGrids  speckle_grids;
-    ~mrcal_amd_stereo_sgm() { for(hipEvent_t e : stage) if(e != NULL) (void)hipEventDestroy(e); }
 };
 
 static bool sgm_given(const mrcal_amd_stereo_sgm* m)
@@ -453,7 +444,10 @@ namespace mrcal_amd {
 
 void* sgm_device_image(mrcal_amd_stereo_sgm* m, int i) { return m->pool + m->plan.image[i]; }
 
-bool sgm_match_device(mrcal_amd_stereo_sgm* m, int16_t* disparity)
+// The launch sequence of a match, queued in the NULL stream: census, paths, selection, left-right check and, on
+// request, the speckle filter; the disparity image stays on the device. events: the matcher's own, or NULL: nothing is
+// recorded
+static bool sgm_enqueue(mrcal_amd_stereo_sgm* m, StageEvents<6>* events, int16_t** d_disparity_out)
 {
     const SgmPlan& plan = m->plan;
     SgmArgs a;
@@ -463,9 +457,9 @@ bool sgm_match_device(mrcal_amd_stereo_sgm* m, int16_t* disparity)
     uint8_t*  index_left  = m->pool + plan.index_left;
     uint8_t*  index_right = m->pool + plan.index_right;
     int16_t*  d_disparity = (int16_t*)(m->pool + plan.disparity);
-    m->timed = false;
+    m->stage.timed = false;
 
-    HIP_TRY(hipEventRecord(m->stage[0], NULL), return false);
+    if(!record(events, 0)) return false;
     const dim3 census_grid(plan.census_grid[0], plan.census_grid[1]), census_block(SGM_CENSUS_TILE_X, 4);
     for(int i = 0; i < 2; i++)
     {
@@ -475,7 +469,7 @@ bool sgm_match_device(mrcal_amd_stereo_sgm* m, int16_t* disparity)
             hipLaunchKernelGGL(sgm_census_kernel<uint16_t>, census_grid, census_block, 0, NULL, plan.W, plan.H, (const uint16_t*)(m->pool + plan.image[i]), census[i]);
     }
     HIP_TRY(hipGetLastError(), return false);
-    HIP_TRY(hipEventRecord(m->stage[1], NULL), return false);
+    if(!record(events, 1)) return false;
     for(int r = 0; r < m->params.paths; r++)
     {
 #define SGM_CALL(NPL) sgm_launch_path<NPL>(plan, a, SGM_DIRECTIONS[r][0], SGM_DIRECTIONS[r][1], r == 0, census[0], census[1], S)
@@ -483,62 +477,41 @@ bool sgm_match_device(mrcal_amd_stereo_sgm* m, int16_t* disparity)
 #undef SGM_CALL
     }
     HIP_TRY(hipGetLastError(), return false);
-    HIP_TRY(hipEventRecord(m->stage[2], NULL), return false);
+    if(!record(events, 2)) return false;
 #define SGM_CALL(NPL) sgm_launch_select<NPL>(plan, a, m->params.uniqueness_ratio, S, index_left, index_right, d_disparity)
     SGM_PER_LANE(plan.per_lane, SGM_CALL)
 #undef SGM_CALL
     HIP_TRY(hipGetLastError(), return false);
-    HIP_TRY(hipEventRecord(m->stage[3], NULL), return false);
+    if(!record(events, 3)) return false;
     hipLaunchKernelGGL(sgm_check_kernel, dim3(plan.check_grid), dim3(SGM_CHECK_THREADS), 0, NULL,
                        a, m->params.disp12_max_diff, index_left, index_right, d_disparity);
     HIP_TRY(hipGetLastError(), return false);
-    HIP_TRY(hipEventRecord(m->stage[4], NULL), return false);
+    if(!record(events, 4)) return false;
     if(m->speckle_on)
     {
         // S is 2 D >= 32 bytes a pixel and nothing reads it after the selection: the filter's 8 bytes a pixel go there
         if(!speckle_filter_device(m->speckle_grids, m->speckle, d_disparity, S)) return false;
-        HIP_TRY(hipEventRecord(m->stage[5], NULL), return false);
+        if(!record(events, 5)) return false;
     }
-    // (the copy waits for the launches)
-    HIP_TRY(hipMemcpy(disparity, d_disparity, (size_t)plan.W*plan.H*sizeof(int16_t), hipMemcpyDeviceToHost), return false);
-    m->timed = true;
+    *d_disparity_out = d_disparity;
     return true;
 }
 
-// sgm_match_device() without the copy to the host, launch for launch: that function and its path stay as they were
+bool sgm_match_device(mrcal_amd_stereo_sgm* m, int16_t* disparity)
+{
+    int16_t* d_disparity;
+    if(!sgm_enqueue(m, &m->stage, &d_disparity)) return false;
+    // (the copy waits for the launches)
+    HIP_TRY(hipMemcpy(disparity, d_disparity, (size_t)m->plan.W*m->plan.H*sizeof(int16_t), hipMemcpyDeviceToHost), return false);
+    m->stage.timed = true;
+    return true;
+}
+
+// ... without the copy to the host, and without the events: the stages of this path are not reported
 bool sgm_match_device_resident(mrcal_amd_stereo_sgm* m, const int16_t** d_disparity_out)
 {
-    const SgmPlan& plan = m->plan;
-    SgmArgs a;
-    a.W = plan.W; a.H = plan.H; a.D = plan.D; a.dmin = m->params.disparity_min; a.P1 = m->params.P1; a.P2 = m->params.P2;
-    uint64_t* census[2] = { (uint64_t*)(m->pool + plan.census[0]), (uint64_t*)(m->pool + plan.census[1]) };
-    uint16_t* S           = (uint16_t*)(m->pool + plan.S);
-    uint8_t*  index_left  = m->pool + plan.index_left;
-    uint8_t*  index_right = m->pool + plan.index_right;
-    int16_t*  d_disparity = (int16_t*)(m->pool + plan.disparity);
-    m->timed = false;           // (no event is recorded: the stages of this path are not reported)
-
-    const dim3 census_grid(plan.census_grid[0], plan.census_grid[1]), census_block(SGM_CENSUS_TILE_X, 4);
-    for(int i = 0; i < 2; i++)
-    {
-        if(plan.dtype == MRCAL_AMD_IMAGE_UINT8)
-            hipLaunchKernelGGL(sgm_census_kernel<uint8_t>,  census_grid, census_block, 0, NULL, plan.W, plan.H, (const uint8_t*)(m->pool + plan.image[i]),  census[i]);
-        else
-            hipLaunchKernelGGL(sgm_census_kernel<uint16_t>, census_grid, census_block, 0, NULL, plan.W, plan.H, (const uint16_t*)(m->pool + plan.image[i]), census[i]);
-    }
-    for(int r = 0; r < m->params.paths; r++)
-    {
-#define SGM_CALL(NPL) sgm_launch_path<NPL>(plan, a, SGM_DIRECTIONS[r][0], SGM_DIRECTIONS[r][1], r == 0, census[0], census[1], S)
-        SGM_PER_LANE(plan.per_lane, SGM_CALL)
-#undef SGM_CALL
-    }
-#define SGM_CALL(NPL) sgm_launch_select<NPL>(plan, a, m->params.uniqueness_ratio, S, index_left, index_right, d_disparity)
-    SGM_PER_LANE(plan.per_lane, SGM_CALL)
-#undef SGM_CALL
-    hipLaunchKernelGGL(sgm_check_kernel, dim3(plan.check_grid), dim3(SGM_CHECK_THREADS), 0, NULL,
-                       a, m->params.disp12_max_diff, index_left, index_right, d_disparity);
-    HIP_TRY(hipGetLastError(), return false);
-    if(m->speckle_on && !speckle_filter_device(m->speckle_grids, m->speckle, d_disparity, S)) return false;
+    int16_t* d_disparity;
+    if(!sgm_enqueue(m, NULL, &d_disparity)) return false;
     *d_disparity_out = d_disparity;
     return true;
 }
@@ -558,7 +531,7 @@ mrcal_amd_stereo_sgm_create(int width, int height, int dtype, const mrcal_amd_st
     p.uniqueness_ratio = params->uniqueness_ratio; p.disp12_max_diff = params->disp12_max_diff;
     std::string why;
     if(!sgm_params_ok(&why, width, height, dtype, p)) { set_error("%s", why.c_str()); return NULL; }
-    if(!sgm_have_device()) return NULL;
+    if(!have_device()) return NULL;
     size_t free_bytes = 0, total_bytes = 0;
     HIP_TRY(hipMemGetInfo(&free_bytes, &total_bytes), return NULL);
     SgmPlan plan;
@@ -567,15 +540,14 @@ mrcal_amd_stereo_sgm_create(int width, int height, int dtype, const mrcal_amd_st
     mrcal_amd_stereo_sgm* m = new mrcal_amd_stereo_sgm;
     m->plan = plan; m->params = p;
     if(!m->mem.alloc(&m->pool, plan.bytes)) { delete m; return NULL; }
-    for(int i = 0; i < 6; i++)
-        HIP_TRY(hipEventCreate(&m->stage[i]), delete m; return NULL);
+    if(!m->stage.create()) { delete m; return NULL; }
     return m;
 }
 
 bool mrcal_amd_stereo_sgm_match(mrcal_amd_stereo_sgm_t* m, const void* image0, const void* image1, int16_t* disparity)
 {
     last_error_string().clear();
-    if(!sgm_given(m) || !sgm_have_device()) return false;
+    if(!sgm_given(m) || !have_device()) return false;
     const size_t n = (size_t)m->plan.W*m->plan.H*sgm_pixel_bytes(m->plan.dtype);
     HIP_TRY(hipMemcpy(sgm_device_image(m, 0), image0, n, hipMemcpyHostToDevice), return false);
     HIP_TRY(hipMemcpy(sgm_device_image(m, 1), image1, n, hipMemcpyHostToDevice), return false);
@@ -586,9 +558,9 @@ bool mrcal_amd_stereo_sgm_stage_milliseconds(mrcal_amd_stereo_sgm_t* m, float* m
 {
     last_error_string().clear();
     if(!sgm_given(m)) return false;
-    if(!m->timed) { set_error("stereo_matching_sgm(): no match has been made yet"); return false; }
+    if(!m->stage.timed) { set_error("stereo_matching_sgm(): no match has been made yet"); return false; }
     for(int i = 0; i < 4; i++)
-        HIP_TRY(hipEventElapsedTime(&milliseconds[i], m->stage[i], m->stage[i+1]), return false);
+        if(!m->stage.elapsed(&milliseconds[i], i, i+1)) return false;
     return true;
 }
 
@@ -606,7 +578,7 @@ bool mrcal_amd_stereo_sgm_set_speckle_filter(mrcal_amd_stereo_sgm_t* m, int wind
     m->speckle = p;
     m->speckle_on = window_size > 0;
     if(m->speckle_on) m->speckle_grids = speckle_grids(m->plan.W, m->plan.H);
-    m->timed = false;
+    m->stage.timed = false;
     return true;
 }
 
@@ -614,11 +586,9 @@ bool mrcal_amd_stereo_sgm_speckle_milliseconds(mrcal_amd_stereo_sgm_t* m, float*
 {
     last_error_string().clear();
     if(!sgm_given(m)) return false;
-    if(!m->timed) { set_error("stereo_matching_sgm(): no match has been made yet"); return false; }
+    if(!m->stage.timed) { set_error("stereo_matching_sgm(): no match has been made yet"); return false; }
     *milliseconds = 0.f;
-    if(m->speckle_on)
-        HIP_TRY(hipEventElapsedTime(milliseconds, m->stage[4], m->stage[5]), return false);
-    return true;
+    return !m->speckle_on || m->stage.elapsed(milliseconds, 4, 5);
 }
 
 void mrcal_amd_stereo_sgm_destroy(mrcal_amd_stereo_sgm_t* m) { delete m; }

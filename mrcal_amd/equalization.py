@@ -20,6 +20,7 @@ import ctypes as C
 import numpy as np
 
 from ._cabi import _ptr
+from ._handle import Handle
 
 
 EQUALIZE_NONE, EQUALIZE_CLAHE, EQUALIZE_STRETCH = 0, 1, 2
@@ -32,11 +33,6 @@ _MAX_TILES = 4096
 class _EqualizeParams(C.Structure):
     """mrcal_amd_equalize_params_t"""
     _fields_ = [("method", C.c_int), ("clip_limit", C.c_double), ("tiles_x", C.c_int), ("tiles_y", C.c_int)]
-
-
-def _libs():
-    from . import _lib, _api
-    return _lib, _api
 
 
 def _method(method, none_allowed):
@@ -121,7 +117,7 @@ def equalization_params(equalization, clahe_clip_limit, clahe_tiles, images=()):
     return _EqualizeParams(method, clip_limit, tiles_x, tiles_y), dtype
 
 
-class ImageEqualizer:
+class ImageEqualizer(Handle):
     """equalize_clahe() and equalize_stretch(), resident: the device buffers for one image size and type are made once,
 and every apply() reuses them.
 
@@ -130,61 +126,36 @@ and every apply() reuses them.
       .stage_milliseconds()         how long the histograms, the LUTs and the interpolation of the last apply() took on
                                     the device, without the copies ('stretch': the extremes, 0, the map)"""
 
+    _destroy = "mrcal_amd_equalizer_destroy"
+
     def __init__(self, shape, dtype, method='clahe', *, clip_limit=8.0, tiles=(8, 8)):
-        self.handle = None
         self.shape, self.dtype = _shape(shape), _dtype(dtype)
         m = _method(method, False)
         clip_limit, tiles_x, tiles_y = _clahe_arguments(clip_limit, tiles)
         if m == EQUALIZE_CLAHE:
             _tiles_fit(self.shape, tiles_x, tiles_y)
         self.dtype_out = np.dtype(np.uint8) if m == EQUALIZE_STRETCH else self.dtype
-        lib, api = _libs()
-        self._L, self._api = lib.lib, api
         p = _EqualizeParams(m, clip_limit, tiles_x, tiles_y)
-        f = self._L.mrcal_amd_equalizer_create
-        f.restype, f.argtypes = C.c_void_p, [C.c_int]*3 + [C.c_void_p]
-        self.handle = f(self.shape[1], self.shape[0], _DTYPES[self.dtype], C.addressof(p))
-        if not self.handle:
-            self.handle = None
-            raise Exception("equalize() failed:" + api._last_error())
-        self._L.mrcal_amd_equalizer_destroy.restype, self._L.mrcal_amd_equalizer_destroy.argtypes = None, [C.c_void_p]
+        self._create("equalize()", "mrcal_amd_equalizer_create", self.shape[1], self.shape[0], _DTYPES[self.dtype], C.addressof(p))
 
     def apply(self, image, out=None):
-        if self.handle is None:
-            raise Exception("this ImageEqualizer has been closed")
+        self._open()
         _image(image, "image", self.shape, self.dtype)
         _out(out, self.shape, self.dtype_out)
         a = np.ascontiguousarray(image)
         dense = out is not None and out.flags.c_contiguous and out is not image and not np.shares_memory(out, a)
         o = out if dense else np.zeros(self.shape, dtype=self.dtype_out)
-        f = self._L.mrcal_amd_equalizer_apply
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*3
-        if not f(self.handle, _ptr(a), _ptr(o)):
-            raise Exception("equalize() failed:" + self._api._last_error())
+        self._call("equalize()", "mrcal_amd_equalizer_apply", _ptr(a), _ptr(o))
         if out is None:
             return o
         if o is not out: out[...] = o
         return out
 
     def stage_milliseconds(self):
-        if self.handle is None:
-            raise Exception("this ImageEqualizer has been closed")
+        self._open()
         ms = np.zeros((3,), dtype=np.float32)
-        f = self._L.mrcal_amd_equalizer_stage_milliseconds
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2
-        if not f(self.handle, _ptr(ms)):
-            raise Exception("equalize() failed:" + self._api._last_error())
+        self._call("equalize()", "mrcal_amd_equalizer_stage_milliseconds", _ptr(ms))
         return dict(zip(("histogram", "lut", "apply"), (float(x) for x in ms)))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._L.mrcal_amd_equalizer_destroy(self.handle)
-            self.handle = None
-    def __del__(self):
-        try:    self.close()
-        except Exception: pass
-    def __enter__(self): return self
-    def __exit__(self, *a): self.close()
 
 
 def _out(out, shape, dtype):

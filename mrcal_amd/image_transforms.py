@@ -29,7 +29,6 @@ def _unproject_host(q, lensmodel, intrinsics_data):
     intrinsics_data = np.ascontiguousarray(intrinsics_data, dtype=np.float64)
     v = np.zeros(q.shape[:-1] + (3,))
     f = _lib.lib.mrcal_unproject
-    f.restype, f.argtypes = C.c_bool, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     if not f(_ptr(v), _ptr(q), q.size//2, C.byref(m), _ptr(intrinsics_data)):
         raise Exception("mrcal_unproject() failed:" + _api._last_error())
     return v
@@ -155,8 +154,6 @@ Reference: mrcal.image_transformation_map()"""
     A, t = np.ascontiguousarray(A, dtype=np.float64), np.ascontiguousarray(t, dtype=np.float64)
     mapxy = np.zeros((H_to, W_to, 2), dtype=np.float32)
     f = _lib.lib.mrcal_amd_image_transformation_map
-    f.restype  = C.c_bool
-    f.argtypes = [C.c_void_p]*8 + [C.c_double, C.c_void_p, C.c_int]
     if not f(_ptr(mapxy), C.addressof(m_from), _ptr(intrinsics_from), C.addressof(m_to), _ptr(intrinsics_to),
              C.addressof(imagersize_to), _ptr(A), _ptr(t), d, _ptr(region), Nregion):
         raise Exception("image_transformation_map() failed:" + _api._last_error())
@@ -186,8 +183,6 @@ to 1/32 pixel first, and that is not imitated. Reference: mrcal.transform_image(
     o, ret = _output_array(out, (H, W) if channels == 1 else (H, W, 3), a.dtype, border == 5)
     m = np.ascontiguousarray(mapxy)
     f = _lib.lib.mrcal_amd_transform_image
-    f.restype  = C.c_bool
-    f.argtypes = [C.c_void_p]*2 + [C.c_int]*4 + [C.c_void_p] + [C.c_int]*4 + [C.c_void_p]
     if not f(_ptr(o), _ptr(a), w, h, channels, dtype, _ptr(m), W, H, interp, border, _ptr(bv)):
         raise Exception("transform_image() failed:" + _api._last_error())
     if ret is not o: ret[...] = o

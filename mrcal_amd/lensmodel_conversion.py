@@ -12,28 +12,12 @@ import re
 
 import numpy as np
 
+from . import _handle
 from ._cabi import _ptr
+from ._handle import Handle, _failed
 
 STATUS_CONVERGED, STATUS_BOUND, STATUS_TOO_FEW_POINTS, STATUS_STALLED = 0, 1, 2, 3
 STATUS_NAMES = ("converged", "bound on evaluations reached", "too few points", "stalled")
-
-
-def _declare(L):
-    if getattr(L, "_mrcal_amd_lensfit_declared", False):
-        return
-    vp = C.c_void_p
-    L.mrcal_amd_lensfit_create.restype   = vp
-    L.mrcal_amd_lensfit_create.argtypes  = []
-    L.mrcal_amd_lensfit_fit.restype      = C.c_bool
-    L.mrcal_amd_lensfit_fit.argtypes     = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int,
-                                            C.c_bool, C.c_bool, C.c_bool, C.c_int] + [vp]*7
-    L.mrcal_amd_lensfit_last_ms.restype  = C.c_double
-    L.mrcal_amd_lensfit_last_ms.argtypes = [vp]
-    L.mrcal_amd_lensfit_plan.restype     = C.c_bool
-    L.mrcal_amd_lensfit_plan.argtypes    = [vp, vp, C.c_int, C.c_int, vp, C.c_bool, C.c_bool, C.c_bool]
-    L.mrcal_amd_lensfit_destroy.restype  = None
-    L.mrcal_amd_lensfit_destroy.argtypes = [vp]
-    L._mrcal_amd_lensfit_declared = True
 
 
 PLAN_FIELDS = ("proj", "ndist", "Nintrinsics", "ivar0", "Nstages", "NP1", "NP2", "Nsums", "threads", "row_doubles",
@@ -45,26 +29,22 @@ def fit_lensmodel_plan(lensmodel, N, *, Ntrials=1, imagersize=(2, 2), optimize_c
     """What fit_lensmodel() decides on the host for these arguments (csrc/lensfit_plan.hpp), as a dict of PLAN_FIELDS:
     the kernel's instantiation, the unknowns of each stage, threads, the chunk of rows, LDS. Raises what
     fit_lensmodel() would refuse with. No device is touched"""
-    from . import _lib, _api
-    _declare(_lib.lib)
+    _lib, _ = _handle._libs()
     m = _lib.lensmodel(lensmodel)
     out = np.zeros(len(PLAN_FIELDS), dtype=np.int32)
     size = np.ascontiguousarray(np.asarray(imagersize).reshape(2), dtype=np.int32)
     if not _lib.lib.mrcal_amd_lensfit_plan(_ptr(out), C.byref(m), int(N), int(Ntrials), _ptr(size), bool(optimize_core),
                                            bool(optimize_extrinsics), bool(do_apply_regularization)):
-        raise Exception("fit_lensmodel() failed:" + _api._last_error())
+        raise _failed("fit_lensmodel()")
     return dict(zip(PLAN_FIELDS, (int(v) for v in out)))
 
 
-class LensFitter:
+class LensFitter(Handle):
     """The resident form (mrcal_amd_lensfit_*): keeps its device buffers and stream between fits"""
+    _destroy = "mrcal_amd_lensfit_destroy"
+
     def __init__(self):
-        from . import _lib, _api
-        self._lib, self._L, self._api = _lib, _lib.lib, _api
-        _declare(self._L)
-        self.handle = self._L.mrcal_amd_lensfit_create()
-        if not self.handle:
-            raise Exception("fit_lensmodel() failed:" + _api._last_error())
+        self._create("fit_lensmodel()", "mrcal_amd_lensfit_create")
 
     def fit(self, p, q, lensmodel, intrinsics_seed, *, imagersize, weights=None, rt_seed=None, optimize_core=True,
             optimize_extrinsics=False, do_apply_regularization=True, max_evaluations=None):
@@ -79,8 +59,8 @@ class LensFitter:
             weights = np.ascontiguousarray(weights, dtype=np.float64)
             if weights.shape != (N,):
                 raise Exception(f"weights must have shape ({N},), got {weights.shape}")
-        m = self._lib.lensmodel(lensmodel)
-        Ni = self._L.mrcal_lensmodel_num_params(C.byref(m))
+        m = _handle._libs()[0].lensmodel(lensmodel)
+        Ni = self._function("mrcal_lensmodel_num_params")(C.byref(m))
         seed = np.ascontiguousarray(intrinsics_seed, dtype=np.float64)
         one = seed.ndim == 1
         if one: seed = seed.reshape(1, -1)
@@ -96,29 +76,16 @@ class LensFitter:
         cost, rms = np.zeros(Nt), np.zeros(Nt)
         Nevaluations, status = np.zeros(Nt, dtype=np.int32), np.full(Nt, -1, dtype=np.int32)
         ibest = C.c_int(-1)
-        ok = self._L.mrcal_amd_lensfit_fit(self.handle, _ptr(p), _ptr(q), _ptr(weights), N, C.byref(m), _ptr(size),
-                                           _ptr(seed), _ptr(rt_seed), Nt,
-                                           bool(optimize_core), bool(optimize_extrinsics), bool(do_apply_regularization),
-                                           0 if max_evaluations is None else int(max_evaluations),
-                                           _ptr(intrinsics), _ptr(rt), _ptr(cost), _ptr(rms), _ptr(Nevaluations), _ptr(status),
-                                           C.byref(ibest))
-        if not ok:
-            raise Exception("fit_lensmodel() failed:" + self._api._last_error())
+        self._call("fit_lensmodel()", "mrcal_amd_lensfit_fit", _ptr(p), _ptr(q), _ptr(weights), N, C.byref(m), _ptr(size),
+                   _ptr(seed), _ptr(rt_seed), Nt,
+                   bool(optimize_core), bool(optimize_extrinsics), bool(do_apply_regularization),
+                   0 if max_evaluations is None else int(max_evaluations),
+                   _ptr(intrinsics), _ptr(rt), _ptr(cost), _ptr(rms), _ptr(Nevaluations), _ptr(status), C.byref(ibest))
         return dict(intrinsics=intrinsics, rt_cam_ref=rt, cost=cost, rms_reproj_error__pixels=rms,
                     Nevaluations=Nevaluations, status=status, ibest=ibest.value)
 
     def last_ms(self):
-        return self._L.mrcal_amd_lensfit_last_ms(self.handle)
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._L.mrcal_amd_lensfit_destroy(self.handle)
-            self.handle = None
-    def __del__(self):
-        try:    self.close()
-        except Exception: pass
-    def __enter__(self): return self
-    def __exit__(self, *a): self.close()
+        return self._function("mrcal_amd_lensfit_last_ms")(self.handle)
 
 
 def fit_lensmodel(p, q, lensmodel, intrinsics_seed, *, imagersize, weights=None, rt_seed=None, optimize_core=True,

@@ -20,7 +20,9 @@ import re
 import sys
 import numpy as np
 
+from . import _handle
 from ._cabi import _ptr
+from ._handle import Handle, _failed
 
 _known_methods = ('mean-pcam', 'cross-reprojection-ccp', 'cross-reprojection-rrp-Jfp')
 _methods       = {'cross-reprojection-ccp': 0, 'cross-reprojection-rrp-Jfp': 1}
@@ -91,53 +93,33 @@ def _inputs_of(model, method):
     return optimization_inputs, icam_intrinsics
 
 
-def _declare(L):
-    if getattr(L, "_mrcal_amd_uncertainty_declared", False):
-        return
-    vp = C.c_void_p
-    L.mrcal_amd_uncertainty_create.restype  = vp
-    L.mrcal_amd_uncertainty_create.argtypes = [vp, C.c_int, C.c_int, C.c_double]
-    L.mrcal_amd_uncertainty_evaluate.restype  = C.c_bool
-    L.mrcal_amd_uncertainty_evaluate.argtypes = [vp, vp, C.c_int, C.c_bool, C.c_int, vp]
-    L.mrcal_amd_uncertainty_observed_pixel_uncertainty.restype  = C.c_double
-    L.mrcal_amd_uncertainty_observed_pixel_uncertainty.argtypes = [vp]
-    L.mrcal_amd_uncertainty_destroy.restype  = None
-    L.mrcal_amd_uncertainty_destroy.argtypes = [vp]
-    L._mrcal_amd_uncertainty_declared = True
-
-
-class ProjectionUncertainty:
+class ProjectionUncertainty(Handle):
     """The projection uncertainty of one calibrated camera, kept resident: the k x k matrix C of
     Var(q) = sigma^2 G(p) C G(p)^T is computed once, on the GPU, from the solve the model stores
     (model.optimization_inputs(), model.icam_intrinsics(); never the model's current pose). evaluate() then costs a
     projection with gradients and a k x k quadratic form a point. One context serves atinfinity both ways"""
 
+    _destroy = "mrcal_amd_uncertainty_destroy"
+
     def __init__(self, model, *, method='cross-reprojection-ccp', observed_pixel_uncertainty=None):
         optimization_inputs, icam_intrinsics = _inputs_of(model, method)
-        from . import _lib, _api
         from .resident import Problem
-        self._L = _lib.lib
-        self._api = _api
-        _declare(self._L)
         self.method = method
-        self.handle = None
         sigma = -1.0 if observed_pixel_uncertainty is None else float(observed_pixel_uncertainty)
         if observed_pixel_uncertainty is not None and not sigma > 0.0:
             raise Exception(f"observed_pixel_uncertainty must be > 0, got {observed_pixel_uncertainty}")
         with Problem(**optimization_inputs) as problem:
             # (the regularization rows of J and K are read off the problem's Jacobian: it must be streamed)
             problem.set_jacobian_stream(True)
-            self.handle = self._L.mrcal_amd_uncertainty_create(problem.handle, int(icam_intrinsics), _methods[method], sigma)
-        if not self.handle:
-            raise Exception("projection uncertainty failed:" + _api._last_error())
-        self.observed_pixel_uncertainty = float(self._L.mrcal_amd_uncertainty_observed_pixel_uncertainty(self.handle))
+            self._create("projection uncertainty", "mrcal_amd_uncertainty_create", problem.handle, int(icam_intrinsics),
+                         _methods[method], sigma)
+        self.observed_pixel_uncertainty = float(self._function("mrcal_amd_uncertainty_observed_pixel_uncertainty")(self.handle))
 
     def evaluate(self, p_cam, *, atinfinity=False, what='covariance'):
         """Var(q) (..., 2,2) for what='covariance', else the standard deviation (...): the worst direction's or the
         RMS of the two. p_cam (..., 3) in the camera frame"""
         _check_what(what)
-        if self.handle is None:
-            raise Exception("this ProjectionUncertainty has been closed")
+        self._open()
         p = np.asarray(p_cam, dtype=np.float64)
         if p.shape[-1:] != (3,):
             raise Exception(f"p_cam must have shape (..., 3), got {p.shape}")
@@ -145,22 +127,12 @@ class ProjectionUncertainty:
         pf = np.ascontiguousarray(p.reshape(-1, 3))
         N = pf.shape[0]
         out = np.empty((N, 4) if what == 'covariance' else (N,), dtype=np.float64)
-        if N > 0 and not self._L.mrcal_amd_uncertainty_evaluate(self.handle, _ptr(pf), N, bool(atinfinity),
-                                                                _whats[what], _ptr(out)):
-            raise Exception("projection uncertainty failed:" + self._api._last_error())
+        if N > 0:
+            self._call("projection uncertainty", "mrcal_amd_uncertainty_evaluate", _ptr(pf), N, bool(atinfinity), _whats[what],
+                       _ptr(out))
         if what == 'covariance':
             return out.reshape(lead + (2, 2))
         return out.reshape(lead) if lead else out[0]
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._L.mrcal_amd_uncertainty_destroy(self.handle)
-            self.handle = None
-    def __del__(self):
-        try:    self.close()
-        except Exception: pass
-    def __enter__(self): return self
-    def __exit__(self, *a): self.close()
 
 
 def projection_uncertainty(p_cam, model, *, method='cross-reprojection-ccp', atinfinity=False, what='covariance',
@@ -174,23 +146,6 @@ def projection_uncertainty(p_cam, model, *, method='cross-reprojection-ccp', ati
 
 # ---------------------------------------------------------------------------------------------------------------------
 # projection differences
-
-def _declare_diff(L):
-    if getattr(L, "_mrcal_amd_projection_diff_declared", False):
-        return
-    vp = C.c_void_p
-    L.mrcal_amd_implied_rt10.restype  = C.c_bool
-    L.mrcal_amd_implied_rt10.argtypes = [vp]*9 + [C.c_int, C.c_int, C.c_bool, vp, C.c_double]
-    L.mrcal_amd_projection_diff_create.restype  = vp
-    L.mrcal_amd_projection_diff_create.argtypes = [C.c_int, vp, vp, vp, C.c_int]
-    L.mrcal_amd_projection_diff_evaluate.restype  = C.c_bool
-    L.mrcal_amd_projection_diff_evaluate.argtypes = [vp, vp, C.c_int, C.c_bool, vp, C.c_bool, vp, C.c_double] + [vp]*8
-    L.mrcal_amd_projection_diff_time_fit.restype  = C.c_double
-    L.mrcal_amd_projection_diff_time_fit.argtypes = [vp, C.c_bool]
-    L.mrcal_amd_projection_diff_destroy.restype  = None
-    L.mrcal_amd_projection_diff_destroy.argtypes = [vp]
-    L._mrcal_amd_projection_diff_declared = True
-
 
 def _Rt_from_fit(rt, atinfinity):
     """(..., 4,3) from the fitted (..., 6): at infinity the fit is a rotation, and row 3 is 0"""
@@ -227,9 +182,7 @@ def _implied_rt10(q0, p0, v1, weights, atinfinity, focus_center, focus_radius):
         weights = np.ascontiguousarray(weights.reshape(M, N))
     fc = np.ascontiguousarray(np.asarray(focus_center, dtype=float).reshape(2))
 
-    from . import _lib, _api
-    L = _lib.lib
-    _declare_diff(L)
+    L = _handle._libs()[0].lib
     rt = np.zeros(6)
     cost = C.c_double(0.0)
     Nevaluations, Nused, status = C.c_int(0), C.c_int(0), C.c_int(-1)
@@ -239,7 +192,7 @@ def _implied_rt10(q0, p0, v1, weights, atinfinity, focus_center, focus_radius):
     if not ok:
         if status.value == 2:
             raise Exception("Focus region contained too few points")
-        raise Exception("implied_Rt10__from_unprojections() failed:" + _api._last_error())
+        raise _failed("implied_Rt10__from_unprojections()")
     return rt, dict(cost=cost.value, Nevaluations=Nevaluations.value, Nused=Nused.value, status=status.value)
 
 
@@ -259,13 +212,12 @@ def _is_noncentral(lensmodel):
     return re.match("LENSMODEL_CAHVORE_", lensmodel) is not None
 
 
-class _DiffContext:
+class _DiffContext(Handle):
     """The gridded unprojections of two or more models, resident (mrcal_amd_projection_diff_*)"""
+    _destroy = "mrcal_amd_projection_diff_destroy"
+
     def __init__(self, lensmodels, intrinsics_data, q0):
-        from . import _lib, _api
-        self._L, self._api = _lib.lib, _api
-        _declare_diff(self._L)
-        self.handle = None
+        _lib, _ = _handle._libs()
         self.Nmodels = len(lensmodels)
         self.grid = q0.shape[:-1]
         self.N = int(np.prod(self.grid))
@@ -273,14 +225,12 @@ class _DiffContext:
         arr = (type(ms[0])*self.Nmodels)(*ms)
         intr = [np.ascontiguousarray(i, dtype=np.float64) for i in intrinsics_data]
         for name, m, i in zip(lensmodels, ms, intr):
-            Ni = self._L.mrcal_lensmodel_num_params(C.byref(m))
+            Ni = _lib.lib.mrcal_lensmodel_num_params(C.byref(m))
             if i.shape != (Ni,):
                 raise Exception(f"{name} takes {Ni} intrinsics, got an array of shape {i.shape}")
         ptrs = (C.c_void_p*self.Nmodels)(*[i.ctypes.data for i in intr])
         q = np.ascontiguousarray(q0.reshape(self.N, 2), dtype=np.float64)
-        self.handle = self._L.mrcal_amd_projection_diff_create(self.Nmodels, arr, ptrs, _ptr(q), self.N)
-        if not self.handle:
-            raise Exception("projection_diff() failed:" + _api._last_error())
+        self._create("projection_diff()", "mrcal_amd_projection_diff_create", self.Nmodels, arr, ptrs, _ptr(q), self.N)
 
     def evaluate(self, distance, atinfinity, uncertainties, Rt10, focus_center, focus_radius):
         """(difflen (Nd,Nh,Nw), diff (Nfits,Nd,Nh,Nw,2), Rt10 (Nfits,4,3), report). Rt10 None: the fit"""
@@ -297,13 +247,14 @@ class _DiffContext:
         if fit and uncertainties is not None:
             us = (C.c_void_p*self.Nmodels)(*[u.handle for u in uncertainties])
         fc = np.ascontiguousarray(np.asarray(focus_center, dtype=float).reshape(2))
-        ok = self._L.mrcal_amd_projection_diff_evaluate(self.handle, _ptr(d), Nd, bool(atinfinity), us, fit, _ptr(fc),
-                                                        float(focus_radius), _ptr(Rt), _ptr(rt), _ptr(cost),
-                                                        _ptr(Nevaluations), _ptr(Nused), _ptr(status), _ptr(difflen), _ptr(diff))
-        if not ok:
+        try:
+            self._call("projection_diff()", "mrcal_amd_projection_diff_evaluate", _ptr(d), Nd, bool(atinfinity), us, fit, _ptr(fc),
+                       float(focus_radius), _ptr(Rt), _ptr(rt), _ptr(cost), _ptr(Nevaluations), _ptr(Nused), _ptr(status),
+                       _ptr(difflen), _ptr(diff))
+        except Exception:
             if fit and (status == 2).any():
-                raise Exception("Focus region contained too few points")
-            raise Exception("projection_diff() failed:" + self._api._last_error())
+                raise Exception("Focus region contained too few points") from None
+            raise
         if fit:
             # (the same conversion as implied_Rt10__from_unprojections(): the same bits; the device's own R differs from
             #  it by rounding)
@@ -311,17 +262,7 @@ class _DiffContext:
         return difflen, diff, Rt, dict(rt=rt, cost=cost, Nevaluations=Nevaluations, Nused=Nused, status=status)
 
     def time_fit(self, on=True):
-        return self._L.mrcal_amd_projection_diff_time_fit(self.handle, bool(on))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._L.mrcal_amd_projection_diff_destroy(self.handle)
-            self.handle = None
-    def __del__(self):
-        try:    self.close()
-        except Exception: pass
-    def __enter__(self): return self
-    def __exit__(self, *a): self.close()
+        return self._function("mrcal_amd_projection_diff_time_fit")(self.handle, bool(on))
 
 
 def projection_diff(models, *, implied_Rt10=None, gridn_width=60, gridn_height=None, intrinsics_only=False, distance=None,

@@ -257,41 +257,6 @@ class _DeviceArray:
                                              data=(int(ptr), False), version=2)
 
 
-def _declare_sharded(L):
-    if getattr(L, "_mrcal_amd_sharded_declared", False):
-        return
-    vp = C.c_void_p
-    L.mrcal_amd_problem_shard_info.restype  = C.c_int
-    L.mrcal_amd_problem_shard_info.argtypes = [vp, C.POINTER(C.c_int), C.c_int]
-    L.mrcal_amd_problem_sharded_reset.restype  = C.c_bool
-    L.mrcal_amd_problem_sharded_reset.argtypes = [vp, C.c_int, C.c_int, C.c_double]
-    L.mrcal_amd_problem_sharded_enqueue.restype  = C.c_bool
-    L.mrcal_amd_problem_sharded_enqueue.argtypes = [vp, C.c_int, C.c_int]
-    L.mrcal_amd_problem_sharded_comm_buffer.restype  = vp
-    L.mrcal_amd_problem_sharded_comm_buffer.argtypes = [vp, C.c_int, C.POINTER(C.c_int64)]
-    L.mrcal_amd_problem_sharded_snapshot.restype  = C.c_bool
-    L.mrcal_amd_problem_sharded_snapshot.argtypes = [vp, C.c_int]
-    L.mrcal_amd_problem_sharded_wait.restype  = C.c_bool
-    L.mrcal_amd_problem_sharded_wait.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
-    L.mrcal_amd_problem_sharded_finish.restype  = C.c_bool
-    L.mrcal_amd_problem_sharded_finish.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]
-    L.mrcal_amd_problem_current.restype, L.mrcal_amd_problem_current.argtypes = C.c_int, [vp]
-    for name, args in (("outlier_stats", [vp, C.c_int, C.c_double, vp, vp]),
-                       ("mark_outliers", [vp, C.c_int, C.c_double, vp])):
-        f = getattr(L, f"mrcal_amd_problem_phase_{name}")
-        f.restype, f.argtypes = C.c_bool, args
-    L.mrcal_amd_comm_unique_id.restype,  L.mrcal_amd_comm_unique_id.argtypes  = C.c_bool, [vp]
-    L.mrcal_amd_comm_create.restype,     L.mrcal_amd_comm_create.argtypes     = vp, [vp, C.c_int, C.c_int]
-    L.mrcal_amd_comm_create_host.restype, L.mrcal_amd_comm_create_host.argtypes = vp, [C.c_char_p, C.c_int, C.c_int]
-    L.mrcal_amd_comm_destroy.restype,    L.mrcal_amd_comm_destroy.argtypes    = None, [vp]
-    L.mrcal_amd_comm_Ncollectives.restype, L.mrcal_amd_comm_Ncollectives.argtypes = C.c_long, [vp]
-    L.mrcal_amd_comm_Ndoubles.restype, L.mrcal_amd_comm_Ndoubles.argtypes = C.c_longlong, [vp]
-    L.mrcal_amd_comm_world_observed.restype, L.mrcal_amd_comm_world_observed.argtypes = C.c_int, [vp]
-    L.mrcal_amd_problem_attach_comm.restype,  L.mrcal_amd_problem_attach_comm.argtypes  = C.c_bool, [vp, vp]
-    L.mrcal_amd_problem_gather_state.restype, L.mrcal_amd_problem_gather_state.argtypes = C.c_bool, [vp]
-    L._mrcal_amd_sharded_declared = True
-
-
 class GpuShard:
     """The shard interface over libmrcal_amd.so's sharded-step API, for a driver
     that does the collectives itself (ShardedDogleg)"""
@@ -300,7 +265,6 @@ class GpuShard:
         self.torch = torch
         self.p     = problem
         self.L = L = problem._lib
-        _declare_sharded(L)
         info = (C.c_int*12)()
         # (called unconditionally: under `python -O` an assert - and the call inside it - is not there)
         nfilled = L.mrcal_amd_problem_shard_info(problem.handle, info, len(info))
@@ -429,7 +393,6 @@ class ShardedProblem:
             dist.all_reduce(t, group=group)
             self.Nnz_global = int(t.item())
         self._lib = L = self.problem._lib
-        _declare_sharded(L)
         self._comm_handle = None
         self.dogleg = None
         self.Ncorners = p.Nobservations_board*max(p.width_n,0)*max(p.height_n,0)

@@ -46,18 +46,15 @@ rectified_system() refuses too).
 import ctypes as C
 import numpy as np
 
+from . import _handle
 from ._cabi import _ptr
+from ._handle import Handle, _failed
 from .poseutils import compose_Rt
 from .equalization import equalization_params, _EqualizeParams
 
 
 class _Point2(C.Structure):
     _fields_ = [("x", C.c_double), ("y", C.c_double)]
-
-
-def _libs():
-    from . import _lib, _api
-    return _lib, _api
 
 
 def _rectification_model_type(lib, rectification_model):
@@ -72,7 +69,7 @@ A value > 0 is used as given. A value < 0 scales the resolution model0 has at th
 rectified view: -1 keeps it, -0.5 halves it. For LENSMODEL_LATLON and LENSMODEL_LONLAT the result is then adjusted so
 that the field of view is a whole number of pixels; for LENSMODEL_PINHOLE it is the resolution at the centre.
 Reference: mrcal.rectified_resolution(), mrcal_rectified_resolution()"""
-    lib, api = _libs()
+    lib, api = _handle._libs()
     lensmodel, intrinsics = model0.intrinsics()
     m = lib.lensmodel(lensmodel)
     intrinsics = np.ascontiguousarray(intrinsics, dtype=np.float64)
@@ -81,11 +78,9 @@ Reference: mrcal.rectified_resolution(), mrcal_rectified_resolution()"""
         raise Exception(f"R_cam0_rect0 must have shape (3,3), got {R.shape}")
     az, el = C.c_double(pixels_per_deg_az), C.c_double(pixels_per_deg_el)
     fov, center = _Point2(az_fov_deg, el_fov_deg), _Point2(az0_deg, el0_deg)
-    f = lib.lib.mrcal_rectified_resolution
-    f.restype, f.argtypes = C.c_bool, [C.c_void_p]*7 + [C.c_int]
-    if not f(C.addressof(az), C.addressof(el), C.addressof(m), _ptr(intrinsics), C.addressof(fov), C.addressof(center),
-             _ptr(R), _rectification_model_type(lib, rectification_model)):
-        raise Exception("mrcal_rectified_resolution() failed:" + api._last_error())
+    if not lib.lib.mrcal_rectified_resolution(C.addressof(az), C.addressof(el), C.addressof(m), _ptr(intrinsics), C.addressof(fov),
+                                              C.addressof(center), _ptr(R), _rectification_model_type(lib, rectification_model)):
+        raise _failed("mrcal_rectified_resolution()")
     return az.value, el.value
 
 
@@ -102,7 +97,7 @@ return_metadata: also a dict with az_fov_deg, el_fov_deg, az0_deg, el0_deg, pixe
 baseline as they ended up. Runs on the host: no GPU is needed.
 Reference: mrcal.rectified_system(), mrcal_rectified_system2()"""
     from .cameramodel import cameramodel
-    lib, api = _libs()
+    lib, api = _handle._libs()
     if len(models) != 2:
         raise Exception("I need exactly 2 camera models")
     for m in models:
@@ -122,14 +117,12 @@ Reference: mrcal.rectified_system(), mrcal_rectified_system2()"""
     az, el = C.c_double(pixels_per_deg_az), C.c_double(pixels_per_deg_el)
     autodetect = az0_deg is None
     fov, center = _Point2(az_fov_deg, el_fov_deg), _Point2(0. if autodetect else az0_deg, el0_deg)
-    f = lib.lib.mrcal_rectified_system2
-    f.restype  = C.c_bool
-    f.argtypes = [C.c_void_p]*8 + [C.c_double] + [C.c_void_p]*4 + [C.c_int] + [C.c_bool]*4
-    if not f(C.addressof(imagersize), _ptr(fxycxy), _ptr(rt_rect0_ref), C.addressof(baseline),
-             C.addressof(az), C.addressof(el), C.addressof(fov), C.addressof(center),
-             float(az_edge_margin_deg), C.addressof(m), _ptr(intrinsics), _ptr(rt0), _ptr(rt1),
-             _rectification_model_type(lib, rectification_model), autodetect, False, False, False):
-        raise Exception("mrcal_rectified_system2() failed:" + api._last_error())
+    if not lib.lib.mrcal_rectified_system2(
+            C.addressof(imagersize), _ptr(fxycxy), _ptr(rt_rect0_ref), C.addressof(baseline),
+            C.addressof(az), C.addressof(el), C.addressof(fov), C.addressof(center),
+            float(az_edge_margin_deg), C.addressof(m), _ptr(intrinsics), _ptr(rt0), _ptr(rt1),
+            _rectification_model_type(lib, rectification_model), autodetect, False, False, False):
+        raise _failed("mrcal_rectified_system2()")
 
     # rect1 has the orientation of rect0, and its origin at camera 1: rt_rect0_rect1 = (0,0,0, baseline,0,0)
     rt_rect1_ref = rt_rect0_ref.copy()
@@ -214,7 +207,7 @@ def _output_array(out, shape, dtype, transparent):
     return (np.ascontiguousarray(out) if transparent else np.empty(shape, dtype=dtype)), out
 
 
-class Rectification:
+class Rectification(Handle):
     """The rectification of a stereo pair, resident: both maps are made on the device once and stay there.
 
     models: the two cameramodels; models_rectified: what rectified_system() returned for them.
@@ -231,13 +224,13 @@ class Rectification:
     between its upload and the remap (equalize_clahe(), equalize_stretch()), the same bits as equalizing it first.
     With 'stretch' the rectified images are uint8. None: nothing of it runs"""
 
+    _destroy = "mrcal_amd_rectification_destroy"
+
     def __init__(self, models, models_rectified):
-        self.handle = None
         _validate_models_rectified(models_rectified)
         if len(models) != 2:
             raise Exception("I need exactly 2 camera models")
-        lib, api = _libs()
-        self._L, self._api = lib.lib, api
+        lib, _ = _handle._libs()
         self._models, self._models_rectified = tuple(models), tuple(models_rectified)
         self.Naz, self.Nel = (int(x) for x in models_rectified[0].imagersize())
         args, keep = [], []
@@ -252,38 +245,23 @@ class Rectification:
         fxycxy = np.ascontiguousarray(fxycxy, dtype=np.float64)
         imagersize = (C.c_uint*2)(self.Naz, self.Nel)
         r_rect0_ref = np.ascontiguousarray(models_rectified[0].rt_cam_ref()[:3], dtype=np.float64)
-        f = self._L.mrcal_amd_rectification_create
-        f.restype, f.argtypes = C.c_void_p, [C.c_void_p]*6 + [C.c_int] + [C.c_void_p]*3 + [C.c_double]
-        self.handle = f(*args, _rectification_model_type(lib, rectification_model), _ptr(fxycxy), C.addressof(imagersize),
-                        _ptr(r_rect0_ref), _baseline(models_rectified))
-        if not self.handle:
-            self.handle = None
-            raise Exception("rectification_maps() failed:" + api._last_error())
-        self._L.mrcal_amd_rectification_destroy.restype, self._L.mrcal_amd_rectification_destroy.argtypes = None, [C.c_void_p]
-
-    def _open(self):
-        if self.handle is None:
-            raise Exception("this Rectification has been closed")
+        self._create("rectification_maps()", "mrcal_amd_rectification_create", *args,
+                     _rectification_model_type(lib, rectification_model), _ptr(fxycxy), C.addressof(imagersize),
+                     _ptr(r_rect0_ref), _baseline(models_rectified))
 
     def _equalize(self, params):
         """what the calls that follow do to their raw images; None: nothing, which a handle that was never told
         otherwise does by itself"""
         if params is None and not getattr(self, "_equalizing", False):
             return
-        f = self._L.mrcal_amd_rectification_set_equalization
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2
         p = params if params is not None else _EqualizeParams(0, 8.0, 8, 8)
-        if not f(self.handle, C.addressof(p)):
-            raise Exception("equalize() failed:" + self._api._last_error())
+        self._call("equalize()", "mrcal_amd_rectification_set_equalization", C.addressof(p))
         self._equalizing = params is not None
 
     def maps(self):
         self._open()
         maps = np.zeros((2, self.Nel, self.Naz, 2), dtype=np.float32)
-        f = self._L.mrcal_amd_rectification_maps
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2
-        if not f(self.handle, _ptr(maps)):
-            raise Exception("rectification_maps() failed:" + self._api._last_error())
+        self._call("rectification_maps()", "mrcal_amd_rectification_maps", _ptr(maps))
         return maps
 
     def rectify(self, image0, image1, out=None, *, equalization=None, clahe_clip_limit=8.0, clahe_tiles=(8, 8)):
@@ -304,11 +282,8 @@ class Rectification:
         (o0, r0), (o1, r1) = (_output_array(None if out is None else out[i], shape, a0.dtype if dtype_out is None else dtype_out, False)
                               for i in (0, 1))
         self._equalize(eq)
-        f = self._L.mrcal_amd_rectification_rectify
-        f.restype  = C.c_bool
-        f.argtypes = [C.c_void_p]*4 + [C.c_int]*2 + [C.c_void_p] + [C.c_int]*6 + [C.c_void_p]
-        if not f(self.handle, _ptr(o0), _ptr(o1), _ptr(a0), w0, h0, _ptr(a1), w1, h1, c0, t0, 1, 0, None):
-            raise Exception("rectify() failed:" + self._api._last_error())
+        self._call("rectify()", "mrcal_amd_rectification_rectify", _ptr(o0), _ptr(o1), _ptr(a0), w0, h0, _ptr(a1), w1, h1,
+                   c0, t0, 1, 0, None)
         if r0 is not o0: r0[...] = o0
         if r1 is not o1: r1[...] = o1
         return r0, r1
@@ -341,19 +316,11 @@ class Rectification:
         self._equalize(eq)
         a0, a1 = np.ascontiguousarray(image0), np.ascontiguousarray(image1)
         out = np.zeros((self.Nel, self.Naz), dtype=np.int16)
-        images = (self.handle, _ptr(a0), a0.shape[1], a0.shape[0], _ptr(a1), a1.shape[1], a1.shape[0], dtype, C.addressof(p))
+        images = (_ptr(a0), a0.shape[1], a0.shape[0], _ptr(a1), a1.shape[1], a1.shape[0], dtype, C.addressof(p))
         if speckle[0] == 0:             # (no filter: the entry point without it)
-            f = self._L.mrcal_amd_rectification_disparity
-            f.restype  = C.c_bool
-            f.argtypes = [C.c_void_p]*2 + [C.c_int]*2 + [C.c_void_p] + [C.c_int]*3 + [C.c_void_p]*2
-            ok = f(*images, _ptr(out))
+            self._call("stereo_matching_sgm()", "mrcal_amd_rectification_disparity", *images, _ptr(out))
         else:
-            f = self._L.mrcal_amd_rectification_disparity_filtered
-            f.restype  = C.c_bool
-            f.argtypes = [C.c_void_p]*2 + [C.c_int]*2 + [C.c_void_p] + [C.c_int]*3 + [C.c_void_p] + [C.c_int]*2 + [C.c_void_p]
-            ok = f(*images, *speckle, _ptr(out))
-        if not ok:
-            raise Exception("stereo_matching_sgm() failed:" + self._api._last_error())
+            self._call("stereo_matching_sgm()", "mrcal_amd_rectification_disparity_filtered", *images, *speckle, _ptr(out))
         return out
 
     def point_cloud(self, disparity, *, image0=None, disparity_scale=1, disparity_min=None, disparity_max=None,
@@ -368,11 +335,8 @@ class Rectification:
         rmin, rmax, Rt, float32 = _cloud_frame(self._models_rectified, self._models, range_min, range_max, frame, dtype)
         p, keep = _cloud_params(scale, dmin, dmax, rmin, rmax, Rt, float32, image)
         N = C.c_int(0)
-        f = self._L.mrcal_amd_rectification_point_cloud
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*4
-        if not f(self.handle, _ptr(d), C.addressof(p), C.addressof(N)):
-            raise Exception("stereo_point_cloud() failed:" + self._api._last_error())
-        return _cloud_read(self._L.mrcal_amd_rectification_point_cloud_read, self.handle, self._api, N.value, float32, image)
+        self._call("stereo_point_cloud()", "mrcal_amd_rectification_point_cloud", _ptr(d), C.addressof(p), C.addressof(N))
+        return _cloud_read(self, "mrcal_amd_rectification_point_cloud_read", N.value, float32, image)
 
     def point_cloud_of_images(self, image0, image1, *, color_image=None, frame='ref', dtype=np.float64,
                                   range_min=None, range_max=None, speckle_window_size=0, speckle_range=0,
@@ -409,37 +373,20 @@ class Rectification:
             image = (np.zeros((0,), dtype=dtype_equalized),) + tuple(image[1:])      # (what the colours are read into: 'stretch' makes uint8)
         self._equalize(eq)
         N = C.c_int(0)
-        f = self._L.mrcal_amd_rectification_point_cloud_of_images
-        f.restype  = C.c_bool
-        f.argtypes = [C.c_void_p]*2 + [C.c_int]*2 + [C.c_void_p] + [C.c_int]*3 + [C.c_void_p] + [C.c_int]*2 + [C.c_void_p]*2
-        if not f(self.handle, _ptr(a0), a0.shape[1], a0.shape[0], _ptr(a1), a1.shape[1], a1.shape[0], sgm_dtype, C.addressof(p_sgm),
-                 *speckle, C.addressof(p), C.addressof(N)):
-            raise Exception("stereo_point_cloud() failed:" + self._api._last_error())
-        return _cloud_read(self._L.mrcal_amd_rectification_point_cloud_read, self.handle, self._api, N.value, float32, image)
+        self._call("stereo_point_cloud()", "mrcal_amd_rectification_point_cloud_of_images", _ptr(a0), a0.shape[1], a0.shape[0],
+                   _ptr(a1), a1.shape[1], a1.shape[0], sgm_dtype, C.addressof(p_sgm), *speckle, C.addressof(p), C.addressof(N))
+        return _cloud_read(self, "mrcal_amd_rectification_point_cloud_read", N.value, float32, image)
 
     def point_cloud_stage_milliseconds(self):
         """how long the mask, the scan and the scatter of the last cloud took on the device"""
         self._open()
-        return _cloud_stage_milliseconds(self._L.mrcal_amd_rectification_point_cloud_stage_milliseconds, self.handle, self._api)
+        return _cloud_stage_milliseconds(self, "mrcal_amd_rectification_point_cloud_stage_milliseconds")
 
     def _range_dense(self, disparity_scaled, disparity_scale, dmin, dmax):
         d = np.ascontiguousarray(disparity_scaled, dtype=np.uint16)
         r = np.zeros(d.shape, dtype=np.float64)
-        f = self._L.mrcal_amd_rectification_range
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*3 + [C.c_uint16]*3
-        if not f(self.handle, _ptr(r), _ptr(d), int(disparity_scale), int(dmin), int(dmax)):
-            raise Exception("stereo_range() failed:" + self._api._last_error())
+        self._call("stereo_range()", "mrcal_amd_rectification_range", _ptr(r), _ptr(d), int(disparity_scale), int(dmin), int(dmax))
         return r
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._L.mrcal_amd_rectification_destroy(self.handle)
-            self.handle = None
-    def __del__(self):
-        try:    self.close()
-        except Exception: pass
-    def __enter__(self): return self
-    def __exit__(self, *a): self.close()
 
 
 def rectification_maps(models, models_rectified):
@@ -487,7 +434,7 @@ Reference: mrcal.stereo_range(), mrcal_stereo_range_dense(), mrcal_stereo_range_
 
     is_scalar = np.ndim(disparity) == 0
     disparity = np.atleast_1d(np.asarray(disparity))
-    lib, api = _libs()
+    lib, api = _handle._libs()
     rectification_model, fxycxy = models_rectified[0].intrinsics()
     fxycxy = np.ascontiguousarray(fxycxy, dtype=np.float64)
     model_type = _rectification_model_type(lib, rectification_model)
@@ -505,10 +452,9 @@ Reference: mrcal.stereo_range(), mrcal_stereo_range_dense(), mrcal_stereo_range_
         r = np.zeros((H, W), dtype=np.float64)
         image_d = _Image(W, H, W*2, d.ctypes.data)
         image_r = _Image(W, H, W*8, r.ctypes.data)
-        f = lib.lib.mrcal_stereo_range_dense
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2 + [C.c_uint16]*3 + [C.c_int, C.c_void_p, C.c_double]
-        if not f(C.addressof(image_r), C.addressof(image_d), scale, dmin, dmax, model_type, _ptr(fxycxy), baseline):
-            raise Exception("mrcal_stereo_range_dense() failed:" + api._last_error())
+        if not lib.lib.mrcal_stereo_range_dense(C.addressof(image_r), C.addressof(image_d), scale, dmin, dmax, model_type,
+                                                _ptr(fxycxy), baseline):
+            raise _failed("mrcal_stereo_range_dense()")
         return r
 
     r = _range_sparse(disparity.astype(float) / disparity_scale, qrect0, float(disparity_min), float(disparity_max),
@@ -518,7 +464,7 @@ Reference: mrcal.stereo_range(), mrcal_stereo_range_dense(), mrcal_stereo_range_
 
 def _range_sparse(disparity, qrect0, disparity_min, disparity_max, model_type, fxycxy, baseline, want_points):
     """the broadcast batch through mrcal_amd_stereo_range_sparse(): ranges (...), or the points (...,3)"""
-    lib, api = _libs()
+    lib, api = _handle._libs()
     qrect0 = np.asarray(qrect0, dtype=np.float64)
     if qrect0.ndim < 1 or qrect0.shape[-1] != 2:
         raise Exception(f"qrect0 must have shape (...,2), got {qrect0.shape}")
@@ -527,12 +473,10 @@ def _range_sparse(disparity, qrect0, disparity_min, disparity_max, model_type, f
     q = np.ascontiguousarray(np.broadcast_to(qrect0, lead + (2,)), dtype=np.float64).reshape(-1, 2)
     N = d.shape[0]
     out = np.zeros((N, 3) if want_points else (N,))
-    f = lib.lib.mrcal_amd_stereo_range_sparse
-    f.restype  = C.c_bool
-    f.argtypes = [C.c_void_p]*4 + [C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_double]
-    if not f(None if want_points else _ptr(out), _ptr(out) if want_points else None, _ptr(d), _ptr(q), N,
-             disparity_min, disparity_max, model_type, _ptr(fxycxy), baseline):
-        raise Exception("mrcal_stereo_range_sparse() failed:" + api._last_error())
+    if not lib.lib.mrcal_amd_stereo_range_sparse(None if want_points else _ptr(out), _ptr(out) if want_points else None,
+                                                 _ptr(d), _ptr(q), N, disparity_min, disparity_max, model_type, _ptr(fxycxy),
+                                                 baseline):
+        raise _failed("mrcal_stereo_range_sparse()")
     return out.reshape(lead + ((3,) if want_points else ()))
 
 
@@ -542,7 +486,7 @@ the disparity is invalid. Exactly one of disparity and ranges is given; qrect0 a
 Reference: mrcal.stereo_unproject()"""
     if (ranges is None) == (disparity is None):
         raise Exception("Exactly one of (disparity,ranges) must be non-None")
-    lib, api = _libs()
+    lib, api = _handle._libs()
     if ranges is None and qrect0 is not None:
         # one launch: the range and the unit vector it scales
         _validate_models_rectified(models_rectified)
@@ -664,7 +608,7 @@ def _template_window(q1e, template_size):
     return tmin, tmin + np.array(template_size, dtype=float) - 1
 
 
-class FeatureMatcher:
+class FeatureMatcher(Handle):
     """Template matching between two images, resident: both images are uploaded once, and every match() finds a batch
 of features of image0 in image1.
 
@@ -680,30 +624,21 @@ of features of image0 in image1.
     equalizing them first; with 'stretch' the templates are uint8. None: nothing of it runs.
     What a match is: match_feature()"""
 
+    _destroy = "mrcal_amd_feature_matcher_destroy"
+
     def __init__(self, image0, image1, *, equalization=None, clahe_clip_limit=8.0, clahe_tiles=(8, 8)):
-        self.handle = None
         (a0, w0, h0), (a1, w1, h1), dtype = _match_images(image0, image1)
         eq, dtype_equalized = (None, None) if equalization is None else \
             equalization_params(equalization, clahe_clip_limit, clahe_tiles, (image0, image1))
-        lib, api = _libs()
-        self._L, self._api = lib.lib, api
         self._dtype = a0.dtype if eq is None else dtype_equalized
         if eq is None:
-            f = self._L.mrcal_amd_feature_matcher_create
-            f.restype, f.argtypes = C.c_void_p, [C.c_void_p, C.c_int, C.c_int]*2 + [C.c_int]
-            self.handle = f(_ptr(a0), w0, h0, _ptr(a1), w1, h1, dtype)
+            self._create("match_feature()", "mrcal_amd_feature_matcher_create", _ptr(a0), w0, h0, _ptr(a1), w1, h1, dtype)
         else:
-            f = self._L.mrcal_amd_feature_matcher_create_equalized
-            f.restype, f.argtypes = C.c_void_p, [C.c_void_p, C.c_int, C.c_int]*2 + [C.c_int, C.c_void_p]
-            self.handle = f(_ptr(a0), w0, h0, _ptr(a1), w1, h1, dtype, C.addressof(eq))
-        if not self.handle:
-            self.handle = None
-            raise Exception("match_feature() failed:" + api._last_error())
-        self._L.mrcal_amd_feature_matcher_destroy.restype, self._L.mrcal_amd_feature_matcher_destroy.argtypes = None, [C.c_void_p]
+            self._create("match_feature()", "mrcal_amd_feature_matcher_create_equalized", _ptr(a0), w0, h0, _ptr(a1), w1, h1,
+                         dtype, C.addressof(eq))
 
     def match(self, q0, *, search_radius1, template_size1, q1_estimate=None, H10=None, method=None, diagnostics=False):
-        if self.handle is None:
-            raise Exception("this FeatureMatcher has been closed")
+        self._open()
         tw, th = _template_size(template_size1)
         q0, q1e, H01 = _match_features(q0, q1_estimate, H10)
         method, radius = _match_method(method), _match_radius(search_radius1)
@@ -711,40 +646,24 @@ of features of image0 in image1.
         q1, status = np.full((N, 2), np.nan), np.zeros((N,), dtype=np.int32)
         at, value = np.full((N, 2), np.nan), np.full((N,), np.nan)
         qmin, size = np.zeros((N, 2), dtype=np.int32), np.zeros((N, 2), dtype=np.int32)
-        f = self._L.mrcal_amd_feature_matcher_match
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p, C.c_int] + [C.c_void_p]*2 + [C.c_int]*4 + [C.c_void_p]*6
-        if not f(self.handle, N, _ptr(q1e), _ptr(H01), tw, th, radius, method,
-                 _ptr(q1), _ptr(status), _ptr(at), _ptr(value), _ptr(qmin), _ptr(size)):
-            raise Exception("match_feature() failed:" + self._api._last_error())
+        self._call("match_feature()", "mrcal_amd_feature_matcher_match", N, _ptr(q1e), _ptr(H01), tw, th, radius, method,
+                   _ptr(q1), _ptr(status), _ptr(at), _ptr(value), _ptr(qmin), _ptr(size))
         if not diagnostics:
             return q1, status
-        get_surface, get_template = self._L.mrcal_amd_feature_matcher_matchoutput, self._L.mrcal_amd_feature_matcher_template
-        get_surface.restype = get_template.restype = C.c_bool
-        get_surface.argtypes = get_template.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         out = []
         for i in range(N):
             d = dict()
             if status[i] not in (MATCH_OUTSIDE_IMAGE1, MATCH_OUTSIDE_IMAGE0):
                 d['matchoutput_image'] = np.zeros((size[i, 1], size[i, 0]), dtype=np.float32)
                 d['template']          = np.zeros((th, tw), dtype=self._dtype)
-                if not (get_surface(self.handle, i, _ptr(d['matchoutput_image'])) and get_template(self.handle, i, _ptr(d['template']))):
-                    raise Exception("match_feature() failed:" + self._api._last_error())
+                self._call("match_feature()", "mrcal_amd_feature_matcher_matchoutput", i, _ptr(d['matchoutput_image']))
+                self._call("match_feature()", "mrcal_amd_feature_matcher_template", i, _ptr(d['template']))
             if status[i] == MATCH_OK:
                 d['matchoutput_optimum_subpixel_at'] = at[i].copy()
                 d['matchoutput_optimum_subpixel']    = float(value[i])
                 d['qshift_image1_matchoutput']       = qmin[i] + q1e[i] - _template_window(q1e[i], (tw, th))[0]
             out.append(d)
         return q1, status, out
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._L.mrcal_amd_feature_matcher_destroy(self.handle)
-            self.handle = None
-    def __del__(self):
-        try:    self.close()
-        except Exception: pass
-    def __enter__(self): return self
-    def __exit__(self, *a): self.close()
 
 
 def match_feature(image0, image1, q0, *, search_radius1, template_size1, q1_estimate=None, H10=None, method=None,
@@ -895,7 +814,7 @@ def _sgm_images(image0, image1, shape=None, dtype=None):
     return np.ascontiguousarray(image0), np.ascontiguousarray(image1)
 
 
-class StereoMatcherSGM:
+class StereoMatcherSGM(Handle):
     """Dense stereo matching, resident: every device buffer a match of one image size needs is made once, and every
 match() reuses them.
 
@@ -907,8 +826,9 @@ match() reuses them.
       .speckle_milliseconds()            ... and the speckle filter (0 without it)
     What a disparity image is: stereo_matching_sgm()"""
 
+    _destroy = "mrcal_amd_stereo_sgm_destroy"
+
     def __init__(self, shape, dtype, *, speckle_window_size=0, speckle_range=0, **params):
-        self.handle = None
         self._speckle = _speckle_keywords(speckle_window_size, speckle_range)
         self._params = _sgm_params(**params)
         self._dtype = _sgm_dtype(dtype)
@@ -917,64 +837,35 @@ match() reuses them.
         if len(shape) != 2 or shape[0] <= 0 or shape[1] <= 0:
             raise Exception(f"stereo_matching_sgm(): shape must be (H,W), got {shape}")
         self.shape = shape
-        lib, api = _libs()
-        self._L, self._api = lib.lib, api
-        f = self._L.mrcal_amd_stereo_sgm_create
-        f.restype, f.argtypes = C.c_void_p, [C.c_int]*3 + [C.c_void_p]
-        self.handle = f(shape[1], shape[0], _SGM_DTYPES[self._dtype], C.addressof(self._params))
-        if not self.handle:
-            self.handle = None
-            raise Exception("stereo_matching_sgm() failed:" + api._last_error())
-        self._L.mrcal_amd_stereo_sgm_destroy.restype, self._L.mrcal_amd_stereo_sgm_destroy.argtypes = None, [C.c_void_p]
+        self._create("stereo_matching_sgm()", "mrcal_amd_stereo_sgm_create", shape[1], shape[0], _SGM_DTYPES[self._dtype],
+                     C.addressof(self._params))
         if self._speckle[0] > 0:        # (0: nothing of the filter is touched)
-            f = self._L.mrcal_amd_stereo_sgm_set_speckle_filter
-            f.restype, f.argtypes = C.c_bool, [C.c_void_p, C.c_int, C.c_int]
-            if not f(self.handle, *self._speckle):
+            try:
+                self._call("stereo_matching_sgm()", "mrcal_amd_stereo_sgm_set_speckle_filter", *self._speckle)
+            except Exception:
                 self.close()
-                raise Exception("stereo_matching_sgm() failed:" + api._last_error())
+                raise
 
     def match(self, image0, image1, out=None):
-        if self.handle is None:
-            raise Exception("this StereoMatcherSGM has been closed")
+        self._open()
         a0, a1 = _sgm_images(image0, image1, self.shape, self._dtype)
         o, r = _output_array(out, self.shape, np.int16, False)
-        f = self._L.mrcal_amd_stereo_sgm_match
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*4
-        if not f(self.handle, _ptr(a0), _ptr(a1), _ptr(o)):
-            raise Exception("stereo_matching_sgm() failed:" + self._api._last_error())
+        self._call("stereo_matching_sgm()", "mrcal_amd_stereo_sgm_match", _ptr(a0), _ptr(a1), _ptr(o))
         if r is not o: r[...] = o
         return r
 
     def stage_milliseconds(self):
-        if self.handle is None:
-            raise Exception("this StereoMatcherSGM has been closed")
+        self._open()
         ms = np.zeros((4,), dtype=np.float32)
-        f = self._L.mrcal_amd_stereo_sgm_stage_milliseconds
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2
-        if not f(self.handle, _ptr(ms)):
-            raise Exception("stereo_matching_sgm() failed:" + self._api._last_error())
+        self._call("stereo_matching_sgm()", "mrcal_amd_stereo_sgm_stage_milliseconds", _ptr(ms))
         return dict(zip(("census", "paths", "select", "check"), (float(x) for x in ms)))
 
     def speckle_milliseconds(self):
         """how long the speckle filter of the last match() took on the device; 0 without it"""
-        if self.handle is None:
-            raise Exception("this StereoMatcherSGM has been closed")
+        self._open()
         ms = C.c_float(0)
-        f = self._L.mrcal_amd_stereo_sgm_speckle_milliseconds
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2
-        if not f(self.handle, C.addressof(ms)):
-            raise Exception("stereo_matching_sgm() failed:" + self._api._last_error())
+        self._call("stereo_matching_sgm()", "mrcal_amd_stereo_sgm_speckle_milliseconds", C.addressof(ms))
         return float(ms.value)
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._L.mrcal_amd_stereo_sgm_destroy(self.handle)
-            self.handle = None
-    def __del__(self):
-        try:    self.close()
-        except Exception: pass
-    def __enter__(self): return self
-    def __exit__(self, *a): self.close()
 
 
 def stereo_matching_sgm(image0, image1, *, disparity_min=0, disparity_max, P1=10, P2=120, paths=8, uniqueness_ratio=10,
@@ -1072,7 +963,7 @@ def _speckle_out(out, shape):
         raise Exception(f"filter_speckles(): 'out' must be a numpy array of shape {shape} and dtype int16")
 
 
-class SpeckleFilter:
+class SpeckleFilter(Handle):
     """filter_speckles(), resident: the device buffers for one image size are made once, and every filter() reuses them.
 
     shape: (H,W) of the disparity images.
@@ -1083,64 +974,35 @@ class SpeckleFilter:
                                          roots and sizes, the result
     What the filter is: filter_speckles()"""
 
+    _destroy = "mrcal_amd_speckle_filter_destroy"
+
     def __init__(self, shape):
-        self.handle = None
         self.shape = _speckle_shape(shape)
-        lib, api = _libs()
-        self._L, self._api = lib.lib, api
-        f = self._L.mrcal_amd_speckle_filter_create
-        f.restype, f.argtypes = C.c_void_p, [C.c_int]*2
-        self.handle = f(self.shape[1], self.shape[0])
-        if not self.handle:
-            self.handle = None
-            raise Exception("filter_speckles() failed:" + api._last_error())
-        self._L.mrcal_amd_speckle_filter_destroy.restype, self._L.mrcal_amd_speckle_filter_destroy.argtypes = None, [C.c_void_p]
+        self._create("filter_speckles()", "mrcal_amd_speckle_filter_create", self.shape[1], self.shape[0])
 
     def filter(self, disparity, *, new_value, max_speckle_size, max_diff, out=None):
-        if self.handle is None:
-            raise Exception("this SpeckleFilter has been closed")
+        self._open()
         _speckle_image(disparity, self.shape)
         params = _speckle_params(new_value, max_speckle_size, max_diff)
         _speckle_out(out, self.shape)
         a = np.ascontiguousarray(disparity)
         # (the library takes in == out: a dense `out` is filled straight away, disparity itself included)
         o, r = _output_array(out, self.shape, np.int16, False)
-        f = self._L.mrcal_amd_speckle_filter_apply
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*3 + [C.c_int]*3
-        if not f(self.handle, _ptr(a), _ptr(o), *params):
-            raise Exception("filter_speckles() failed:" + self._api._last_error())
+        self._call("filter_speckles()", "mrcal_amd_speckle_filter_apply", _ptr(a), _ptr(o), *params)
         if r is not o: r[...] = o
         return r
 
     def milliseconds(self):
-        if self.handle is None:
-            raise Exception("this SpeckleFilter has been closed")
+        self._open()
         ms = C.c_float(0)
-        f = self._L.mrcal_amd_speckle_filter_milliseconds
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2
-        if not f(self.handle, C.addressof(ms)):
-            raise Exception("filter_speckles() failed:" + self._api._last_error())
+        self._call("filter_speckles()", "mrcal_amd_speckle_filter_milliseconds", C.addressof(ms))
         return float(ms.value)
 
     def pass_milliseconds(self):
-        if self.handle is None:
-            raise Exception("this SpeckleFilter has been closed")
+        self._open()
         ms = np.zeros((4,), dtype=np.float32)
-        f = self._L.mrcal_amd_speckle_filter_pass_milliseconds
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2
-        if not f(self.handle, _ptr(ms)):
-            raise Exception("filter_speckles() failed:" + self._api._last_error())
+        self._call("filter_speckles()", "mrcal_amd_speckle_filter_pass_milliseconds", _ptr(ms))
         return dict(zip(("label", "merge", "count", "apply"), (float(x) for x in ms)))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._L.mrcal_amd_speckle_filter_destroy(self.handle)
-            self.handle = None
-    def __del__(self):
-        try:    self.close()
-        except Exception: pass
-    def __enter__(self): return self
-    def __exit__(self, *a): self.close()
 
 
 def filter_speckles(disparity, *, new_value, max_speckle_size, max_diff, out=None):
@@ -1260,25 +1122,22 @@ def _cloud_params(scale, dmin, dmax, rmin, rmax, Rt, float32, image):
     return p, (Rt, image)
 
 
-def _cloud_read(read, handle, api, N, float32, image):
+def _cloud_read(owner, read, N, float32, image):
+    """owner: the Rectification or StereoPointCloud that made the cloud; read: the name of its read function"""
     points = np.zeros((N, 3), dtype=np.float32 if float32 else np.float64)
     index  = np.zeros((N,), dtype=np.int32)
     color  = None if image is None else np.zeros((N,) if image[3] == 1 else (N, 3), dtype=image[0].dtype)
-    read.restype, read.argtypes = C.c_bool, [C.c_void_p]*4
-    if not read(handle, _ptr(points), _ptr(color), _ptr(index)):
-        raise Exception("stereo_point_cloud() failed:" + api._last_error())
+    owner._call("stereo_point_cloud()", read, _ptr(points), _ptr(color), _ptr(index))
     return points, color, index
 
 
-def _cloud_stage_milliseconds(f, handle, api):
+def _cloud_stage_milliseconds(owner, name):
     ms = np.zeros((3,), dtype=np.float32)
-    f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2
-    if not f(handle, _ptr(ms)):
-        raise Exception("stereo_point_cloud() failed:" + api._last_error())
+    owner._call("stereo_point_cloud()", name, _ptr(ms))
     return dict(zip(("mask", "scan", "scatter"), (float(x) for x in ms)))
 
 
-class StereoPointCloud:
+class StereoPointCloud(Handle):
     """stereo_point_cloud() without the camera models, resident: the device buffers for one size of disparity image are
 made once, and every point_cloud() reuses them; the output buffers grow when a cloud outgrows them.
 
@@ -1288,8 +1147,9 @@ made once, and every point_cloud() reuses them; the output buffers grow when a c
       .stage_milliseconds()     how long the mask, the scan and the scatter of the last cloud took on the device
     What a cloud is: stereo_point_cloud(). A Rectification has its own: Rectification.point_cloud()"""
 
+    _destroy = "mrcal_amd_point_cloud_destroy"
+
     def __init__(self, models_rectified, *, map0=None):
-        self.handle = None
         _validate_models_rectified(models_rectified)
         self._models_rectified = tuple(models_rectified)
         self.Naz, self.Nel = (int(x) for x in models_rectified[0].imagersize())
@@ -1299,31 +1159,23 @@ made once, and every point_cloud() reuses them; the output buffers grow when a c
             map0 = np.ascontiguousarray(map0)
         if self.Nel*self.Naz > _CLOUD_MAX_PIXELS:
             raise Exception(f"stereo_point_cloud(): a disparity image of {self.Naz} x {self.Nel} pixels cannot be made a cloud of: at most {_CLOUD_MAX_PIXELS} pixels")
-        lib, api = _libs()
-        self._L, self._api = lib.lib, api
+        lib, _ = _handle._libs()
         rectification_model, fxycxy = models_rectified[0].intrinsics()
         fxycxy = np.ascontiguousarray(fxycxy, dtype=np.float64)
-        f = self._L.mrcal_amd_point_cloud_create
-        f.restype, f.argtypes = C.c_void_p, [C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p]
-        self.handle = f(_rectification_model_type(lib, rectification_model), _ptr(fxycxy), _baseline(models_rectified),
-                        self.Naz, self.Nel, None)
-        if not self.handle:
-            self.handle = None
-            raise Exception("stereo_point_cloud() failed:" + api._last_error())
-        self._L.mrcal_amd_point_cloud_destroy.restype, self._L.mrcal_amd_point_cloud_destroy.argtypes = None, [C.c_void_p]
+        self._create("stereo_point_cloud()", "mrcal_amd_point_cloud_create", _rectification_model_type(lib, rectification_model),
+                     _ptr(fxycxy), _baseline(models_rectified), self.Naz, self.Nel, None)
         self._has_map = map0 is not None
         if self._has_map:
-            f = self._L.mrcal_amd_point_cloud_set_map
-            f.restype, f.argtypes = C.c_bool, [C.c_void_p]*2
-            if not f(self.handle, _ptr(map0)):
+            try:
+                self._call("stereo_point_cloud()", "mrcal_amd_point_cloud_set_map", _ptr(map0))
+            except Exception:
                 self.close()
-                raise Exception("stereo_point_cloud() failed:" + api._last_error())
+                raise
 
     def point_cloud(self, disparity, *, image0=None, disparity_scale=1, disparity_min=None, disparity_max=None,
                     disparity_scaled_min=None, disparity_scaled_max=None, range_min=None, range_max=None,
                     frame='ref', dtype=np.float64):
-        if self.handle is None:
-            raise Exception("this StereoPointCloud has been closed")
+        self._open()
         if frame == 'cam0':
             raise Exception("stereo_point_cloud(): frame='cam0' needs 'models'")
         if image0 is not None:
@@ -1335,26 +1187,12 @@ made once, and every point_cloud() reuses them; the output buffers grow when a c
         rmin, rmax, Rt, float32 = _cloud_frame(self._models_rectified, None, range_min, range_max, frame, dtype)
         p, keep = _cloud_params(scale, dmin, dmax, rmin, rmax, Rt, float32, image0)
         N = C.c_int(0)
-        f = self._L.mrcal_amd_point_cloud_compute
-        f.restype, f.argtypes = C.c_bool, [C.c_void_p]*4
-        if not f(self.handle, _ptr(d), C.addressof(p), C.addressof(N)):
-            raise Exception("stereo_point_cloud() failed:" + self._api._last_error())
-        return _cloud_read(self._L.mrcal_amd_point_cloud_read, self.handle, self._api, N.value, float32, image0)
+        self._call("stereo_point_cloud()", "mrcal_amd_point_cloud_compute", _ptr(d), C.addressof(p), C.addressof(N))
+        return _cloud_read(self, "mrcal_amd_point_cloud_read", N.value, float32, image0)
 
     def stage_milliseconds(self):
-        if self.handle is None:
-            raise Exception("this StereoPointCloud has been closed")
-        return _cloud_stage_milliseconds(self._L.mrcal_amd_point_cloud_stage_milliseconds, self.handle, self._api)
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._L.mrcal_amd_point_cloud_destroy(self.handle)
-            self.handle = None
-    def __del__(self):
-        try:    self.close()
-        except Exception: pass
-    def __enter__(self): return self
-    def __exit__(self, *a): self.close()
+        self._open()
+        return _cloud_stage_milliseconds(self, "mrcal_amd_point_cloud_stage_milliseconds")
 
 
 def stereo_point_cloud(disparity, models_rectified, *, models=None, image0=None, disparity_scale=1, disparity_min=None,

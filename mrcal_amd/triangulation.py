@@ -22,7 +22,9 @@ observation-time and the calibration-time noise on the GPU: include/mrcal_amd.h,
 import ctypes as C
 import numpy as np
 
+from . import _handle
 from ._cabi import _ptr, Lensmodel
+from ._handle import Handle, _failed
 from .poseutils import rotate_point_R
 
 
@@ -54,7 +56,6 @@ def _flat(a, lead, tail):
 
 def _run(name, v0, v1, pose, pose_shape, get_gradients, out):
     """the broadcast batch through mrcal_amd_triangulate_<name>(). pose_shape: (3,) for t01, (4,3) for Rt01"""
-    from . import _lib, _api
     v0, v1, pose = (np.asarray(a, dtype=np.float64) for a in (v0, v1, pose))
     npose = len(pose_shape)
     if v0.ndim < 1 or v0.shape[-1] != 3 or v1.ndim < 1 or v1.shape[-1] != 3:
@@ -72,10 +73,9 @@ def _run(name, v0, v1, pose, pose_shape, get_gradients, out):
     a, b, c = _flat(v0, lead, (3,)), _flat(v1, lead, (3,)), _flat(pose, lead, pose_shape)
     N = a.shape[0]
     res = [np.empty((N,) + s[len(lead):]) for s in shapes]
-    f = getattr(_lib.lib, "mrcal_amd_triangulate_" + name)
-    f.restype, f.argtypes = C.c_bool, [C.c_int] + [C.c_void_p]*7
+    f = getattr(_handle._libs()[0].lib, "mrcal_amd_triangulate_" + name)
     if not f(N, _ptr(a), _ptr(b), _ptr(c), *[_ptr(r) for r in res], *([None]*(4 - len(res)))):
-        raise Exception(f"triangulate_{name}() failed:" + _api._last_error())
+        raise _failed(f"triangulate_{name}()")
     res = [r.reshape(s) for r, s in zip(res, shapes)]
     if out is not None:
         for o, r in zip(outs, res): o[...] = r
@@ -158,21 +158,6 @@ def _compute_Var_q_triangulation(sigma, stdev_cross_camera_correlation):
     return var_q
 
 
-def _declare(L):
-    if getattr(L, "_mrcal_amd_triangulation_declared", False):
-        return
-    vp = C.c_void_p
-    L.mrcal_amd_triangulation_create.restype  = vp
-    L.mrcal_amd_triangulation_create.argtypes = [vp, C.c_int, vp]
-    L.mrcal_amd_triangulation_evaluate.restype  = C.c_bool
-    L.mrcal_amd_triangulation_evaluate.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_bool, vp, vp, vp]
-    L.mrcal_amd_triangulation_observed_pixel_uncertainty.restype  = C.c_double
-    L.mrcal_amd_triangulation_observed_pixel_uncertainty.argtypes = [vp]
-    L.mrcal_amd_triangulation_destroy.restype  = None
-    L.mrcal_amd_triangulation_destroy.argtypes = [vp]
-    L._mrcal_amd_triangulation_declared = True
-
-
 def _models_array(models):
     if not isinstance(models, np.ndarray):
         models = np.array(models, dtype=object)
@@ -207,15 +192,16 @@ _LINDSTROM_NOISE = ("Triangulation gradients not supported (yet?) with method=tr
                     "It has slightly different inputs and slightly different gradients")
 
 
-class Triangulation:
+class Triangulation(Handle):
     """triangulate() on a set of camera models, kept resident: the models' intrinsics and poses go to the device once,
     and with calibration = True so do the calibration's problem, the factorization of its normal equations and the
     estimate of its pixel noise (the models must then come out of ONE calibration and not have been moved since, as
     for mrcal.triangulate()). models: an iterable of any shape (...,2) of cameramodels: the pairs triangulate() uses
     when it is given none"""
 
+    _destroy = "mrcal_amd_triangulation_destroy"
+
     def __init__(self, models, *, calibration=False, _optimization_inputs=None):
-        self.handle = None
         self._pairs = _models_array(models)
         flat = self._pairs.ravel()
         self._index, self._models = {}, []
@@ -225,9 +211,7 @@ class Triangulation:
                 self._models.append(m)
         # (_optimization_inputs: triangulate() has made the checks already)
         optimization_inputs = (_optimization_inputs or _check_calibration(flat)) if calibration else None
-        from . import _lib, _api
-        self._L, self._api = _lib.lib, _api
-        _declare(self._L)
+        _lib, _ = _handle._libs()
         self.calibration = bool(calibration)
         cams = (_Camera*len(self._models))()
         keep = []
@@ -247,20 +231,17 @@ class Triangulation:
             with Problem(**optimization_inputs) as problem:
                 # (the regularization rows are read off the problem's Jacobian: it must be streamed)
                 problem.set_jacobian_stream(True)
-                self.handle = self._L.mrcal_amd_triangulation_create(problem.handle, len(self._models), C.addressof(cams))
+                self._create("triangulate()", "mrcal_amd_triangulation_create", problem.handle, len(self._models), C.addressof(cams))
         else:
-            self.handle = self._L.mrcal_amd_triangulation_create(None, len(self._models), C.addressof(cams))
-        if not self.handle:
-            raise Exception("triangulate() failed:" + _api._last_error())
-        est = float(self._L.mrcal_amd_triangulation_observed_pixel_uncertainty(self.handle))
+            self._create("triangulate()", "mrcal_amd_triangulation_create", None, len(self._models), C.addressof(cams))
+        est = float(self._function("mrcal_amd_triangulation_observed_pixel_uncertainty")(self.handle))
         self.observed_pixel_uncertainty = est if est > 0 else None
 
     def triangulate(self, q, models=None, *, q_calibration_stdev=None, q_observation_stdev=None,
                     q_observation_stdev_correlation=0, method=triangulate_leecivera_mid2, stabilize_coords=True):
         """mrcal.triangulate() on this context's cameras. models: the pairs (...,2), each one of the context's models;
         None: those the context was made with"""
-        if self.handle is None:
-            raise Exception("this Triangulation has been closed")
+        self._open()
         if q_observation_stdev is not None and q_observation_stdev < 0:
             raise Exception("q_observation_stdev MUST be None or >= 0")
         pairs = self._pairs if models is None else _models_array(models)
@@ -285,11 +266,10 @@ class Triangulation:
         p       = np.zeros((N,3))
         var_obs = np.zeros((N,3,3))   if with_obs else None
         var_cal = np.zeros((3*N,3*N)) if with_cal else None
-        if N > 0 and not self._L.mrcal_amd_triangulation_evaluate(
-                self.handle, N, _ptr(qf), _ptr(icam), imethod,
-                float(q_calibration_stdev) if with_cal else 0.0, float(q_observation_stdev) if with_obs else 0.0,
-                float(q_observation_stdev_correlation), bool(stabilize_coords), _ptr(p), _ptr(var_obs), _ptr(var_cal)):
-            raise Exception("triangulate() failed:" + self._api._last_error())
+        if N > 0:
+            self._call("triangulate()", "mrcal_amd_triangulation_evaluate", N, _ptr(qf), _ptr(icam), imethod,
+                       float(q_calibration_stdev) if with_cal else 0.0, float(q_observation_stdev) if with_obs else 0.0,
+                       float(q_observation_stdev_correlation), bool(stabilize_coords), _ptr(p), _ptr(var_obs), _ptr(var_cal))
 
         p = p.reshape(lead + (3,))
         if q_calibration_stdev is None and q_observation_stdev is None:
@@ -307,16 +287,6 @@ class Triangulation:
         if with_obs:
             for i in range(N): flat[3*i:3*i+3, 3*i:3*i+3] += var_obs[i]
         return p, Var_p_calibration, Var_p_observation, Var_p_joint
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._L.mrcal_amd_triangulation_destroy(self.handle)
-            self.handle = None
-    def __del__(self):
-        try:    self.close()
-        except Exception: pass
-    def __enter__(self): return self
-    def __exit__(self, *a): self.close()
 
 
 def triangulate(q, models, *, q_calibration_stdev=None, q_observation_stdev=None, q_observation_stdev_correlation=0,

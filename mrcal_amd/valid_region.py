@@ -18,42 +18,9 @@ import sys
 
 import numpy as np
 
+from . import _handle
 from ._cabi import _ptr
-
-
-def _declare(L):
-    if getattr(L, "_mrcal_amd_valid_region_declared", False):
-        return
-    vp = C.c_void_p
-    ip = C.POINTER(C.c_int)
-    L.mrcal_amd_regional_statistics_create.restype  = vp
-    L.mrcal_amd_regional_statistics_create.argtypes = [vp, C.c_int, C.c_int]
-    L.mrcal_amd_regional_statistics_grid.restype  = C.c_bool
-    L.mrcal_amd_regional_statistics_grid.argtypes = [vp, C.c_int, ip, ip]
-    L.mrcal_amd_regional_statistics_get.restype  = C.c_bool
-    L.mrcal_amd_regional_statistics_get.argtypes = [vp, C.c_int, vp, vp, vp]
-    L.mrcal_amd_regional_statistics_binning_ms.restype  = C.c_double
-    L.mrcal_amd_regional_statistics_binning_ms.argtypes = [vp]
-    L.mrcal_amd_regional_statistics_destroy.restype  = None
-    L.mrcal_amd_regional_statistics_destroy.argtypes = [vp]
-    L.mrcal_amd_valid_region_mask.restype  = C.c_bool
-    L.mrcal_amd_valid_region_mask.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
-                                              C.c_double, C.c_double, C.c_double, C.c_double, vp, vp]
-    L.mrcal_amd_region_outline.restype  = C.c_int
-    L.mrcal_amd_region_outline.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, C.POINTER(C.c_int64)]
-    L.mrcal_amd_valid_region_lds_vertices.restype  = C.c_int
-    L.mrcal_amd_valid_region_lds_vertices.argtypes = []
-    L.mrcal_amd_valid_region_contains.restype  = C.c_bool
-    L.mrcal_amd_valid_region_contains.argtypes = [vp, vp, C.c_int64, vp, C.c_int]
-    L.mrcal_amd_valid_region_image.restype  = C.c_bool
-    L.mrcal_amd_valid_region_image.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int]
-    L._mrcal_amd_valid_region_declared = True
-
-
-def _lib():
-    from . import _lib as lib, _api
-    _declare(lib.lib)
-    return lib, _api
+from ._handle import Handle, _failed
 
 
 def _grid_height(gridn_width, gridn_height, imagersize):
@@ -71,22 +38,21 @@ def imagergrid_using(imagersize, gridn_width, gridn_height=None):
     return '($1*{}):($2*{}):3'.format(float(W - 1)/(gridn_width - 1), float(H - 1)/(gridn_height - 1))
 
 
-class RegionalStatistics:
+class RegionalStatistics(Handle):
     """mean, standard deviation and count of the board residuals in every cell of a grid over the imager, for ALL the
     cameras of a solve, binned in one pass on the GPU and kept there. optimization_inputs: of the solve (at its
     optimum: x is evaluated there). gridn_height=None: int(round(H/W*gridn_width)) for each camera's own imager.
     problem: a resident mrcal_amd.resident.Problem to bin at its current state instead of making one"""
 
+    _destroy = "mrcal_amd_regional_statistics_destroy"
+
     def __init__(self, optimization_inputs, gridn_width=20, gridn_height=None, *, problem=None):
-        lib, api = _lib()
-        self._L, self._api = lib.lib, api
-        self.handle = None
         gw = int(gridn_width)
         gh = -1 if gridn_height is None else int(gridn_height)
         if gridn_height is not None and gh < 2:
             raise Exception(f"regional statistics: gridn_height must be >= 2: got {gridn_height}")
         if problem is not None:
-            self.handle = self._L.mrcal_amd_regional_statistics_create(problem.handle, gw, gh)
+            self._create("regional statistics", "mrcal_amd_regional_statistics_create", problem.handle, gw, gh)
         else:
             from .cameramodel import _is_poison
             from .resident import Problem
@@ -95,45 +61,28 @@ class RegionalStatistics:
             if ob is None or np.size(ob) == 0:
                 raise Exception("regional statistics: the problem has no board observations, and only those are binned")
             with Problem(**inputs) as p:
-                self.handle = self._L.mrcal_amd_regional_statistics_create(p.handle, gw, gh)
-        if not self.handle:
-            raise Exception("regional statistics failed:" + api._last_error())
+                self._create("regional statistics", "mrcal_amd_regional_statistics_create", p.handle, gw, gh)
         self.gridn_width = gw
-
-    def _check(self):
-        if self.handle is None:
-            raise Exception("this RegionalStatistics has been closed")
 
     def grid_of_camera(self, icam_intrinsics):
         """(gridn_width, gridn_height) of one camera"""
-        self._check()
+        self._open()
         gw, gh = C.c_int(0), C.c_int(0)
-        if not self._L.mrcal_amd_regional_statistics_grid(self.handle, int(icam_intrinsics), C.byref(gw), C.byref(gh)):
-            raise Exception("regional statistics failed:" + self._api._last_error())
+        self._call("regional statistics", "mrcal_amd_regional_statistics_grid", int(icam_intrinsics), C.byref(gw), C.byref(gh))
         return gw.value, gh.value
 
     def of_camera(self, icam_intrinsics):
         """(mean, stdev, count) of one camera, each (gridn_height,gridn_width); count is int32"""
         gw, gh = self.grid_of_camera(icam_intrinsics)
         mean, stdev, count = np.empty((gh, gw)), np.empty((gh, gw)), np.empty((gh, gw), dtype=np.int32)
-        if not self._L.mrcal_amd_regional_statistics_get(self.handle, int(icam_intrinsics), _ptr(mean), _ptr(stdev), _ptr(count)):
-            raise Exception("regional statistics failed:" + self._api._last_error())
+        self._call("regional statistics", "mrcal_amd_regional_statistics_get", int(icam_intrinsics), _ptr(mean), _ptr(stdev),
+                   _ptr(count))
         return mean, stdev, count
 
     def binning_ms(self):
         """device time of the binning launches"""
-        self._check()
-        return float(self._L.mrcal_amd_regional_statistics_binning_ms(self.handle))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._L.mrcal_amd_regional_statistics_destroy(self.handle)
-            self.handle = None
-    def __del__(self):
-        try:    self.close()
-        except Exception: pass
-    def __enter__(self): return self
-    def __exit__(self, *a): self.close()
+        self._open()
+        return float(self._function("mrcal_amd_regional_statistics_binning_ms")(self.handle))
 
 
 def _model_inputs(model):
@@ -156,7 +105,7 @@ def region_outline(mask):
     """The outline of the largest 8-connected region of a mask (H,W): its vertices (N,2) int32 as (x,y) = (column,
     row), clockwise on the screen from the topmost-leftmost cell, not closed; and twice its shoelace area. The
     definition: include/mrcal_amd.h. Host code"""
-    lib, _ = _lib()
+    lib, _ = _handle._libs()
     m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
     if m.ndim != 2 or m.size == 0:
         raise Exception(f"the mask must have shape (H,W), got {m.shape}")
@@ -194,7 +143,7 @@ def compute_valid_intrinsics_region(model, threshold_uncertainty, threshold_mean
                                     distance, gridn_width=30, gridn_height=None, *,
                                     uncertainty=None, statistics=None, return_details=False):
     from .model_analysis import ProjectionUncertainty
-    lib, api = _lib()
+    lib, api = _handle._libs()
     W, H = (int(v) for v in model.imagersize())
     gridn_width  = int(gridn_width)
     gridn_height = _grid_height(gridn_width, gridn_height, (W, H))
@@ -207,8 +156,8 @@ def compute_valid_intrinsics_region(model, threshold_uncertainty, threshold_mean
     try:
         s = RegionalStatistics(optimization_inputs, gridn_width, gridn_height) if own_s else statistics
         u = ProjectionUncertainty(model) if own_u else uncertainty
-        if u.handle is None: raise Exception("this ProjectionUncertainty has been closed")
-        s._check()
+        u._open()
+        s._open()
         m = lib.lensmodel(lensmodel)
         intr = np.ascontiguousarray(intrinsics, dtype=np.float64)
         mask = np.zeros((gridn_height, gridn_width), dtype=np.uint8)
@@ -217,7 +166,7 @@ def compute_valid_intrinsics_region(model, threshold_uncertainty, threshold_mean
                                                    gridn_width, gridn_height, float(distance),
                                                    float(threshold_uncertainty), float(threshold_mean), float(threshold_stdev),
                                                    float(threshold_count), _ptr(mask), _ptr(unc)):
-            raise Exception("valid-intrinsics region failed:" + api._last_error())
+            raise _failed("valid-intrinsics region")
         contour = contour_of_mask(mask, (W, H))
         if not return_details:
             return contour
@@ -293,7 +242,7 @@ def is_within_valid_intrinsics_region(q, model):
     qf = np.ascontiguousarray(q.reshape(-1, 2))
     out = np.zeros((qf.shape[0],), dtype=np.uint8)
     if r.shape[0] > 0 and qf.shape[0] > 0:
-        lib, api = _lib()
+        lib, api = _handle._libs()
         if not lib.lib.mrcal_amd_valid_region_contains(_ptr(out), _ptr(qf), qf.shape[0], _ptr(r), r.shape[0]):
             raise Exception("is_within_valid_intrinsics_region() failed:" + api._last_error())
     return out.astype(bool).reshape(lead)
@@ -308,7 +257,7 @@ def valid_intrinsics_mask(model):
     W, H = (int(v) for v in model.imagersize())
     out = np.zeros((H, W), dtype=np.uint8)
     if r.shape[0] > 0:
-        lib, api = _lib()
+        lib, api = _handle._libs()
         if not lib.lib.mrcal_amd_valid_region_image(_ptr(out), W, H, _ptr(r), r.shape[0]):
             raise Exception("valid_intrinsics_mask() failed:" + api._last_error())
     return out

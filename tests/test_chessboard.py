@@ -325,7 +325,7 @@ def test_images_are_read(amd, tmp_path):
 
 def test_refusals_before_any_device_work(amd, monkeypatch):
     def no_device(*a, **k): raise AssertionError("device work before the refusal")
-    monkeypatch.setattr(amd.chessboard, "_libs", no_device)
+    monkeypatch.setattr(amd._handle, "_libs", no_device)
     u8 = np.zeros((48, 64), dtype=np.uint8)
     find, candidates, Detector = amd.find_chessboard_corners, amd.chessboard_corner_candidates, amd.ChessboardDetector
     for bad in (np.zeros((48, 64, 3), dtype=np.uint8), np.zeros((48,), dtype=np.uint8), [[0]*64]*48):
@@ -514,6 +514,8 @@ def test_the_renders_equal_the_checker_and_find_the_board(amd):
         config = CONFIGS[k]
         image, truth, q_c, response_c, status_c, overflow_c, R_c = render(k)
         with amd.ChessboardDetector(image.shape, image.dtype) as d:
+            with pytest.raises(Exception, match="no image has been looked at yet"):
+                d.stage_milliseconds()
             q, response, status = d.candidates(image)
             assert np.array_equal(d.response()[0], R_c) and np.array_equal(response, response_c) and np.array_equal(status, status_c)
             assert np.abs(q - q_c).max() < 1e-4

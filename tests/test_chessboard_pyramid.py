@@ -69,7 +69,7 @@ def worst_error(result, truth):
 # ------------------------------------------------------------------------------------------------ without a GPU ---
 def test_levels_and_refusals_before_any_device_work(amd, monkeypatch):
     def no_device(*a, **k): raise AssertionError("device work before the refusal")
-    monkeypatch.setattr(amd.chessboard, "_libs", no_device)
+    monkeypatch.setattr(amd._handle, "_libs", no_device)
     find, Detector = amd.find_chessboard_corners, amd.ChessboardDetector
     # the sizes of the levels: an odd last row or column is dropped at every step
     d = Detector.__new__(Detector)
@@ -258,6 +258,8 @@ SWEEP_IDS = [f"sigma{sigma:g}-{square}px" for sigma, square in pc.SWEEP]
 def compare_with_the_checker(amd, image, result):
     """-> (corners compared, corners left out of the level comparison)"""
     with amd.ChessboardDetector(image.shape, image.dtype, pyramid_levels=LEVELS) as d:
+        with pytest.raises(Exception, match="no image has been looked at through the pyramid yet"):
+            d.pyramid_milliseconds()
         corners, levels = d.find_board(image, *pc.BOARD, return_levels=True)
         assert (corners is not None) == (result is not None)
         if result is None:

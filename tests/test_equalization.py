@@ -164,8 +164,7 @@ def test_what_the_definition_implies(dtype):
 
 def test_refusals_before_any_device_work(amd, monkeypatch):
     def no_device(*a, **k): raise AssertionError("device work before the refusal")
-    monkeypatch.setattr(amd.equalization, "_libs", no_device)
-    monkeypatch.setattr(amd.stereo, "_libs", no_device)
+    monkeypatch.setattr(amd._handle, "_libs", no_device)
     a = np.zeros((20, 30), dtype=np.uint8)
     bgr = np.zeros((20, 30, 3), dtype=np.uint8)
     fake = amd.Rectification.__new__(amd.Rectification)
@@ -325,6 +324,8 @@ def test_the_resident_equalizer(amd):
         image, other = crop(shape, dtype), np.ascontiguousarray(crop(shape, dtype)[::-1, ::-1]//2)
         with amd.ImageEqualizer(shape, dtype, 'clahe', clip_limit=2, tiles=(8, 8)) as e:
             assert amd.device_buffers_live() == live0 + 1               # ONE pooled allocation
+            with pytest.raises(Exception, match="no image has been equalized yet"):
+                e.stage_milliseconds()
             for im in (image, other, image):                            # (nothing of the call before is left)
                 assert_same(e.apply(im), amd.equalize_clahe(im, clip_limit=2))
                 assert_same(e.apply(im), chk.equalize_clahe(im, 2, (8, 8)))

@@ -136,12 +136,10 @@ def test_run_steps_continues(amd):
 def test_sharded_enqueue_needs_sharded_reset(amd):
     """After a solve() the control block is initialized, but the step's layout is the single GPU's: the caller-driven
     step must not run on it until sharded_reset() has said that the caller does the sums"""
-    from mrcal_amd.parallel import _declare_sharded
     from mrcal_amd.resident import Problem
     with Problem(**_problem(amd._api)) as p:
         p.solve()
         L = p._lib
-        _declare_sharded(L)
         assert not L.mrcal_amd_problem_sharded_enqueue(p.handle, 0, 0)
         assert "sharded_reset() first" in p._api._last_error()
         assert L.mrcal_amd_problem_sharded_reset(p.handle, 1, 0, 0.0)

@@ -118,7 +118,7 @@ def test_refusals_before_any_device_work(amd, monkeypatch):
     models = [amd.cameramodel(intrinsics=('LENSMODEL_PINHOLE', np.array((500., 500., 31.5, 23.5))), imagersize=(64, 48),
                               rt_cam_ref=np.array((0., 0., 0., -x, 0., 0.))) for x in (0., BASELINE)]
     def no_device(*a, **k): raise AssertionError("device work before the refusal")
-    monkeypatch.setattr(amd.stereo, "_libs", no_device)
+    monkeypatch.setattr(amd._handle, "_libs", no_device)
     d = np.full((20, 30), 160, dtype=np.int16)
     image = np.zeros((48, 64), dtype=np.uint8)
     cloud = amd.stereo_point_cloud
@@ -337,6 +337,8 @@ def test_equals_the_checker(amd, shape, rectification_model):
     kw  = dict(disparity_scale=SCALE, disparity_scaled_min=DMIN, disparity_scaled_max=DMAX)
     live0 = amd.device_buffers_live()
     with amd.StereoPointCloud(models_rectified, map0=map0) as cloud:
+        with pytest.raises(Exception, match="no cloud has been computed yet"):
+            cloud.stage_milliseconds()
         for ipattern, (name, disparity) in enumerate(patterns(H, W, 17)):
             before = disparity.copy()
             want = chk.point_cloud(disparity, rectification_model, fxycxy, BASELINE, Rt_out_rect0=Rt, **kw)

@@ -111,7 +111,7 @@ def test_the_filter_on_the_checkers_own_sgm_output(noisy_half):
 
 def test_refusals_before_any_device_work(amd, monkeypatch):
     def no_device(*a, **k): raise AssertionError("device work before the refusal")
-    monkeypatch.setattr(amd.stereo, "_libs", no_device)
+    monkeypatch.setattr(amd._handle, "_libs", no_device)
     a = np.zeros((20, 30), dtype=np.int16)
     kw = dict(new_value=-16, max_speckle_size=10, max_diff=16)
     flt = amd.filter_speckles
@@ -310,6 +310,9 @@ def test_the_resident_filter(amd):
               dict(new_value=NEW_VALUE, max_speckle_size=0, max_diff=16), kw]
     with amd.SpeckleFilter((H0, W0)) as f:
         assert amd.device_buffers_live() == live0 + 1                   # ONE pooled allocation
+        for milliseconds in (f.milliseconds, f.pass_milliseconds):
+            with pytest.raises(Exception, match="no image has been filtered yet"):
+                milliseconds()
         for k in others:
             assert_same(f.filter(img, **k), amd.filter_speckles(img, **k))
             assert_same(f.filter(img, **k), chk.filter_speckles(img, k["new_value"], k["max_speckle_size"], k["max_diff"]))
@@ -341,6 +344,8 @@ def test_the_filter_inside_the_matcher(amd, noisy_half, disparity_min):
     assert amd.device_buffers_live() == live0
     with amd.StereoMatcherSGM(image0.shape, image0.dtype, speckle_window_size=50, speckle_range=1, **kw) as matcher:
         live1 = amd.device_buffers_live()
+        with pytest.raises(Exception, match="no match has been made yet"):
+            matcher.speckle_milliseconds()
         assert_same(matcher.match(image0, image1), expected)
         assert_same(matcher.match(image0, image1), expected)            # (S, lent to the filter, is made anew)
         assert amd.device_buffers_live() == live1                       # the filter allocates nothing

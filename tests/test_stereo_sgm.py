@@ -124,7 +124,7 @@ def test_checker_on_a_slanted_plane(image):
 
 def test_refusals_before_any_device_work(amd, monkeypatch):
     def no_device(*a, **k): raise AssertionError("device work before the refusal")
-    monkeypatch.setattr(amd.stereo, "_libs", no_device)
+    monkeypatch.setattr(amd._handle, "_libs", no_device)
     a = np.zeros((20, 30), dtype=np.uint8)
     sgm = amd.stereo_matching_sgm
     with pytest.raises(TypeError, match="disparity_max"):
@@ -293,6 +293,8 @@ def test_the_resident_matcher(amd, image):
     assert_same(amd.stereo_matching_sgm(*pairs[0], **kw), one_shot[0])         # the same bits twice
     with amd.StereoMatcherSGM((33, 70), np.uint8, **kw) as matcher:
         assert amd.device_buffers_live() > live0
+        with pytest.raises(Exception, match="no match has been made yet"):
+            matcher.stage_milliseconds()
         for (a, b), expected in zip(pairs, one_shot):
             assert_same(matcher.match(a, b), expected)
         assert_same(matcher.match(*pairs[0]), one_shot[0])                      # nothing of the pairs before is left

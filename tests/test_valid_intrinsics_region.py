@@ -338,8 +338,7 @@ def test_points_off_the_pixel_grid_and_the_edge_cases(amd):
     assert amd.valid_intrinsics_mask(empty).shape == (48, 64) and not amd.valid_intrinsics_mask(empty).any()
     assert amd.is_within_valid_intrinsics_region(np.zeros((0, 2)), m).shape == (0,)
     # more vertices than are kept in LDS: a saw-toothed band
-    from mrcal_amd.valid_region import _lib
-    limit = _lib()[0].lib.mrcal_amd_valid_region_lds_vertices()
+    limit = amd._lib.lib.mrcal_amd_valid_region_lds_vertices()
     assert limit == 4096
     n = limit + 50
     top = [(2*i, 10 + 6*(i % 2)) for i in range(n)]
