@@ -40,6 +40,7 @@
 #include "resident_common.hpp"
 #include "chessboard_plan.hpp"
 #include "chessboard_grid.hpp"
+#include "wave_sum.hpp"
 
 namespace mrcal_amd {
 
@@ -240,12 +241,6 @@ __device__ __forceinline__ double cb_sample(const T* __restrict__ I, int W, int 
     return top*(1.0 - fy) + bottom*fy;
 }
 
-__device__ __forceinline__ double cb_wave_sum(double v)
-{
-    for(int off=32; off>0; off>>=1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // DESCENT false: the candidates of part d, from their integer pixels xy; q and status are written.
 // DESCENT true: the max_candidates corners of the board, from the float up(q) of those whose level is to_level + 1 (the
 // others are left alone); q and level are updated where the corner moves to to_level (p3). total, xy, status: not read
@@ -295,7 +290,7 @@ void cb_refine_kernel(int W, int H, unsigned max_candidates, const T* __restrict
             bx += gxx*wi[h] + gxy*wj[h];
             by += gxy*wi[h] + gyy*wj[h];
         }
-        a = cb_wave_sum(a); b = cb_wave_sum(b); cc = cb_wave_sum(cc); bx = cb_wave_sum(bx); by = cb_wave_sum(by);
+        a = wave_sum(a); b = wave_sum(b); cc = wave_sum(cc); bx = wave_sum(bx); by = wave_sum(by);
         const double det = a*cc - b*b, trace = a + cc;
         if(!(det > 1e-10*trace*trace)) { st = CB_STATUS_SINGULAR; break; }
         const double dx = (cc*bx - b*by)/det, dy = (a*by - b*bx)/det;

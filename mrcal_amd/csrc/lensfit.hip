@@ -28,6 +28,7 @@
 #include "lens_models.hpp"
 #include "lens_dispatch.hpp"
 #include "device_math.hpp"
+#include "damped_newton.hpp"
 #include "device_memory.hpp"
 #include "resident_common.hpp"
 #include "lensfit_plan.hpp"
@@ -73,7 +74,9 @@ struct LfState
     double intr[LF_NI_MAX], rt[6];          // the best point so far
     double tintr[LF_NI_MAX], trt[6];        // the trial the threads evaluate
     double R[9], dR[27];                    // of trt
-    double F, lambda, nu, pred, floor;
+    double F;
+    Damping damp;
+    double pred, floor;
     double g[LF_NP_MAX], H[LF_NH_MAX];      // at the best point: the upper triangle row by row
     double L[LF_NP_MAX][LF_NP_MAX], d[LF_NP_MAX];
     double tot[LF_NE_MAX];                  // the sums of the evaluation just made
@@ -135,87 +138,43 @@ void lf_control(LfState& S, const LfArgs& a, int NP, bool pose, int eval)
         {
             const int c = cdist + j;
             const double s = a.reg_distortion[j];
-            S.H[c*NP - c*(c - 1)/2] += s*s;
+            S.H[packed_diagonal(c, NP)] += s*s;
             S.g[c] += s*(s*S.tintr[4 + j]);
         }
         if(a.reg_center != 0.0)
             for(int k = 0; k < 2; k++)
             {
                 const int c = 2 + k;
-                S.H[c*NP - c*(c - 1)/2] += a.reg_center*a.reg_center;
+                S.H[packed_diagonal(c, NP)] += a.reg_center*a.reg_center;
                 S.g[c] += a.reg_center*(a.reg_center*(S.tintr[2 + k] - a.center_target[k]));
             }
         S.F = Fn;
         double gmax = 0.0;
         bool gfinite = true;
         for(int k = 0; k < NP; k++) { gmax = fmax(gmax, fabs(S.g[k])); gfinite = gfinite && isfinite(S.g[k]); }
-        const double lambda_used = S.lambda;
-        if(eval > 0)
-        {
-            // Nielsen's update from the gain ratio (projection_diff.hip)
-            const double gain = S.pred > 0.0 ? dF/S.pred : 1.0, q = 2.0*gain - 1.0;
-            S.lambda = fmax(S.lambda*fmax(1.0/3.0, 1.0 - q*q*q), LF_LAMBDA_MIN);
-            S.nu = 2.0;
-        }
+        const double lambda_used = S.damp.lambda;
+        if(eval > 0) S.damp.accepted(dF, S.pred, LF_LAMBDA_MIN);
         if(!isfinite(Fn) || !gfinite)              { done = true; status = LENSFIT_STALLED; S.failed = 1; }
         else if(Fn <= S.floor || gmax == 0.0)      done = true;
         else if(eval > 0 && dF <= LF_FTOL*Fn && lambda_used <= LF_LAMBDA_GN) done = true;
     }
-    else
-    {
-        S.lambda *= S.nu; S.nu *= 2.0;
-    }
+    else S.damp.rejected();
     if(!done && eval + 1 >= a.max_evals) { done = true; status = LENSFIT_BOUND; }
 
     while(!done)
     {
-        if(!(S.lambda <= LF_LAMBDA_MAX)) { done = true; status = LENSFIT_STALLED; break; }
-        // L L^T = H + lambda diag(H); a variable nothing depends on stays put
-        double (*L)[LF_NP_MAX] = S.L;
-        double* d = S.d;
-        bool ok = true;
-        int ih = 0;
-        for(int i = 0; i < NP; i++)
-            for(int j = i; j < NP; j++, ih++)
-                L[j][i] = (i == j) ? (S.H[ih] == 0.0 ? 1.0 : S.H[ih]*(1.0 + S.lambda)) : S.H[ih];
-        for(int j = 0; j < NP && ok; j++)
-        {
-            double s = L[j][j];
-            for(int k = 0; k < j; k++) s -= L[j][k]*L[j][k];
-            if(!(s > 0.0) || !isfinite(s)) { ok = false; break; }
-            const double ljj = sqrt(s), iljj = 1.0/ljj;
-            L[j][j] = ljj;
-            for(int i = j + 1; i < NP; i++)
-            {
-                double v = L[i][j];
-                for(int k = 0; k < j; k++) v -= L[i][k]*L[j][k];
-                L[i][j] = v*iljj;
-            }
-        }
+        if(!(S.damp.lambda <= LF_LAMBDA_MAX)) { done = true; status = LENSFIT_STALLED; break; }
+        double pred;
+        bool ok = damped_step<true>(S.L, S.d, &pred, S.H, S.g, NP, S.damp.lambda);
         if(ok)
         {
-            for(int i = 0; i < NP; i++)
-            {
-                double v = -S.g[i];
-                for(int k = 0; k < i; k++) v -= L[i][k]*d[k];
-                d[i] = v/L[i][i];
-            }
-            for(int i = NP - 1; i >= 0; i--)
-            {
-                double v = d[i];
-                for(int k = i + 1; k < NP; k++) v -= L[k][i]*d[k];
-                d[i] = v/L[i][i];
-            }
-            // the decrease of F = x.x the quadratic model promises: d^T (lambda diag(H) d - g)
-            double pred = 0.0;
-            ih = 0;
-            for(int k = 0; k < NP; ih += NP - k, k++) pred += d[k]*(S.lambda*S.H[ih]*d[k] - S.g[k]);
+            // F = x.x: what the step promises, as it stands
             S.pred = pred;
-            for(int k = 0; k < NP; k++) ok = ok && isfinite(d[k]);
-            if(ok && pred <= LF_FTOL*S.F && S.lambda <= LF_LAMBDA_GN) { done = true; break; }
+            for(int k = 0; k < NP; k++) ok = ok && isfinite(S.d[k]);
+            if(ok && pred <= LF_FTOL*S.F && S.damp.lambda <= LF_LAMBDA_GN) { done = true; break; }
         }
         if(ok) break;
-        S.lambda *= S.nu; S.nu *= 2.0;
+        S.damp.rejected();
     }
     if(!done)
     {
@@ -286,8 +245,7 @@ void lensfit_kernel(LfArgs a, const double* __restrict__ pg, const double* __res
             for(int k = 0; k < NI; k++) S.tintr[k] = S.intr[k];
             for(int k = 0; k < 6;  k++) S.trt[k]   = S.rt[k];
             R_from_r_with_grad(S.R, S.dR, S.trt);
-            S.lambda = LF_LAMBDA0;
-            S.nu     = 2.0;
+            S.damp   = { LF_LAMBDA0, 2.0 };
             S.pred   = 0.0;
             if(S.failed) S.done = 1;
             else if(2*S.nused < NP) { S.done = 1; S.status = LENSFIT_TOO_FEW_POINTS; S.failed = 1; S.F = NAN; }

@@ -36,6 +36,8 @@
 #include "lens_models.hpp"
 #include "lens_dispatch.hpp"
 #include "device_math.hpp"
+#include "damped_newton.hpp"
+#include "wave_sum.hpp"
 #include "device_memory.hpp"
 #include "resident_common.hpp"
 #include "noise_propagation.hpp"
@@ -53,7 +55,7 @@ constexpr double FIT_C               = (5.0*M_PI/180.0)*(5.0*M_PI/180.0);
 constexpr double FIT_LAMBDA0         = 1e-3;
 constexpr double FIT_LAMBDA_MIN      = 1e-15;
 constexpr double FIT_LAMBDA_MAX      = 1e10;      // beyond it a step is < 1e-10 of the Gauss-Newton step: no descent to be had
-                                                  // (lambda doubles, quadruples, ... after rejections: 8 in a row get there from 1e-3)
+                                                  // (lambda doubles, quadruples, ... after rejections: 9 in a row get there from 1e-3)
 constexpr double FIT_FTOL            = 1e-12;     // an accepted step that gains less than this part of F ends the fit
 // 1 - v1.p/|p| is computed from unit vectors: the dot product and the division leave it good to an ulp or so of 1, and
 // x_i/w_i = 2 (1 - cos) to 2..3 eps. A cost at or below 1/2 sum (3 eps w_i)^2 is a perfect fit as far as doubles can
@@ -79,7 +81,9 @@ struct FitArgs
 
 struct FitState
 {
-    double rt[6], F, g[6], H[21], lambda, nu, pred, floor;
+    double rt[6], F, g[6], H[21];
+    Damping damp;
+    double pred, floor;
     double R[9], dR[27], t[6];      // the trial the threads evaluate: t[0..2] r, t[3..5] the translation
     double L[6][6], d[6];           // thread 0's factorization (in LDS: indexed by loop counters, it would spill)
     int    done, status, nevals, nused;
@@ -123,9 +127,7 @@ void fit_sum(double* tot, double* acc, double (*s_red)[FIT_NSUMS_MAX])
 #pragma unroll
     for(int k = 0; k < NS; k++)
     {
-        double s = acc[k];
-#pragma unroll
-        for(int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+        const double s = wave_sum(acc[k]);
         if(lane == 0) s_red[wave][k] = s;
     }
     __syncthreads();
@@ -140,7 +142,7 @@ void fit_sum(double* tot, double* acc, double (*s_red)[FIT_NSUMS_MAX])
 }
 
 // Thread 0, after evaluation number eval (0: the start) gave tot = (F, g, H) at S.t: keep the trial or not, lambda,
-// termination, the next trial. NP x NP Cholesky of H (1 + lambda) on the diagonal
+// termination, the next trial. The step itself: damped_newton.hpp
 template<int NP>
 __device__
 void fit_control(FitState& S, const double* tot, int eval)
@@ -156,72 +158,27 @@ void fit_control(FitState& S, const double* tot, int eval)
         for(int k = 0; k < NP; k++) { S.rt[k] = S.t[k]; S.g[k] = tot[1 + k]; gmax = fmax(gmax, fabs(S.g[k])); }
         for(int k = 0; k < NH; k++) S.H[k] = tot[1 + NP + k];
         S.F = Fn;
-        if(eval > 0)
-        {
-            // Nielsen's update from the gain ratio: lambda falls to a third after a step as good as predicted, and
-            // hardly at all after one that barely paid. (Dividing and multiplying by 10 had the fit reject every
-            // other trial in the flat valley of the Huber weights: 400 evaluations were not enough there)
-            const double gain = S.pred > 0.0 ? dF/S.pred : 1.0, q = 2.0*gain - 1.0;
-            S.lambda = fmax(S.lambda*fmax(1.0/3.0, 1.0 - q*q*q), FIT_LAMBDA_MIN);
-            S.nu = 2.0;
-        }
+        if(eval > 0) S.damp.accepted(dF, S.pred, FIT_LAMBDA_MIN);
         bool gfinite = true;
         for(int k = 0; k < NP; k++) gfinite = gfinite && isfinite(S.g[k]);
         if(Fn <= S.floor || (gfinite && gmax == 0.0) || (eval > 0 && dF <= FIT_FTOL*Fn)) done = true;
     }
-    else
-    {
-        S.lambda *= S.nu; S.nu *= 2.0;
-    }
+    else S.damp.rejected();
     if(!done && eval + 1 >= FIT_MAX_EVALUATIONS) { done = true; status = FIT_STATUS_BOUND; }
 
     while(!done)
     {
-        if(!(S.lambda <= FIT_LAMBDA_MAX)) { done = true; status = FIT_STATUS_STALLED; break; }
-        // L L^T = H + lambda diag(H), upper triangle of H row by row; a variable nothing depends on stays put
-        double (*L)[6] = S.L;
-        double* d = S.d;
-        bool ok = true;
-        int ih = 0;
-        for(int i = 0; i < NP; i++)
-            for(int j = i; j < NP; j++, ih++)
-                L[j][i] = (i == j) ? (S.H[ih] == 0.0 ? 1.0 : S.H[ih]*(1.0 + S.lambda)) : S.H[ih];
-        for(int j = 0; j < NP && ok; j++)
-        {
-            double s = L[j][j];
-            for(int k = 0; k < j; k++) s -= L[j][k]*L[j][k];
-            if(!(s > 0.0) || !isfinite(s)) { ok = false; break; }
-            L[j][j] = sqrt(s);
-            for(int i = j + 1; i < NP; i++)
-            {
-                double v = L[i][j];
-                for(int k = 0; k < j; k++) v -= L[i][k]*L[j][k];
-                L[i][j] = v/L[j][j];
-            }
-        }
+        if(!(S.damp.lambda <= FIT_LAMBDA_MAX)) { done = true; status = FIT_STATUS_STALLED; break; }
+        double pred;
+        bool ok = damped_step<false>(S.L, S.d, &pred, S.H, S.g, NP, S.damp.lambda);
         if(ok)
         {
-            for(int i = 0; i < NP; i++)
-            {
-                double v = -S.g[i];
-                for(int k = 0; k < i; k++) v -= L[i][k]*d[k];
-                d[i] = v/L[i][i];
-            }
-            for(int i = NP - 1; i >= 0; i--)
-            {
-                double v = d[i];
-                for(int k = i + 1; k < NP; k++) v -= L[k][i]*d[k];
-                d[i] = v/L[i][i];
-            }
-            // the decrease the quadratic model promises: 1/2 d^T (lambda diag(H) d - g)
-            double pred = 0.0;
-            ih = 0;
-            for(int k = 0; k < NP; ih += NP - k, k++) pred += d[k]*(S.lambda*S.H[ih]*d[k] - S.g[k]);
+            // F = 1/2 sum: half of what the step promises for x.x
             S.pred = 0.5*pred;
-            for(int k = 0; k < NP; k++) { S.t[k] = S.rt[k] + d[k]; ok = ok && isfinite(S.t[k]); }
+            for(int k = 0; k < NP; k++) { S.t[k] = S.rt[k] + S.d[k]; ok = ok && isfinite(S.t[k]); }
         }
         if(ok) break;
-        S.lambda *= S.nu; S.nu *= 2.0;
+        S.damp.rejected();
     }
     if(!done) R_from_r_with_grad(S.R, S.dR, S.t);
     S.done   = done ? 1 : 0;
@@ -263,8 +220,7 @@ void pd_fit_kernel(FitArgs a, const double* __restrict__ q0, const double* __res
         {
             S.nused  = (int)s_tot[0];
             S.floor  = 0.5*FIT_NOISE*FIT_NOISE*s_tot[1];
-            S.lambda = FIT_LAMBDA0;
-            S.nu     = 2.0;
+            S.damp   = { FIT_LAMBDA0, 2.0 };
             S.pred   = 0.0;
             S.F      = 0.0;
             S.nevals = 0;

@@ -38,6 +38,7 @@
 #include "lens_models.hpp"
 #include "lens_dispatch.hpp"
 #include "device_math.hpp"
+#include "wave_sum.hpp"
 #include "../../include/mrcal_amd.h"
 
 using namespace mrcal_amd;
@@ -202,14 +203,7 @@ void pu_points_kernel(PUArgs a, const double* __restrict__ C, const double* __re
                 h1 += ge1*c;
             }
         }
-        double v00 = h0*g0, v01 = h0*g1, v11 = h1*g1;
-#pragma unroll
-        for(int off = 32; off >= 1; off >>= 1)
-        {
-            v00 += __shfl_xor(v00, off);
-            v01 += __shfl_xor(v01, off);
-            v11 += __shfl_xor(v11, off);
-        }
+        const double v00 = wave_sum(h0*g0), v01 = wave_sum(h0*g1), v11 = wave_sum(h1*g1);
         if(lane == 0)
         {
             const double sg = a.sigma;

@@ -27,6 +27,7 @@
 #include "regional_stats_plan.hpp"
 #include "regional_stats.hpp"
 #include "resident_common.hpp"
+#include "wave_sum.hpp"
 #include "../../include/mrcal_amd.h"
 
 using namespace mrcal_amd;
@@ -173,13 +174,6 @@ void rs_rank_kernel(int Ncorners, int HW, int Ncells, int Nentries_max, const Bo
     }
 }
 
-__device__ inline double rs_wave_sum(double v)
-{
-#pragma unroll
-    for(int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 __global__ __launch_bounds__(256)
 void rs_reduce_kernel(int Ncells, int Nmeas, const int* __restrict__ start, const int* __restrict__ sorted, const double* __restrict__ x,
                       double* __restrict__ mean, double* __restrict__ stdev, int* __restrict__ count)
@@ -196,7 +190,7 @@ void rs_reduce_kernel(int Ncells, int Nmeas, const int* __restrict__ start, cons
             const int i = sorted[e0 + (v >> 1)] + (v & 1);
             s += (i >= 0 && i < Nmeas) ? x[i] : 0.0;
         }
-        m = rs_wave_sum(s)/(double)n;
+        m = wave_sum(s)/(double)n;
         double s2 = 0.0;
         for(int v = lane; v < n; v += 64)
         {
@@ -205,7 +199,7 @@ void rs_reduce_kernel(int Ncells, int Nmeas, const int* __restrict__ start, cons
             const double dd = d*d;
             s2 += dd;
         }
-        sd = sqrt(rs_wave_sum(s2)/(double)n);
+        sd = sqrt(wave_sum(s2)/(double)n);
     }
     if(lane == 0) { mean[cell] = m; stdev[cell] = sd; count[cell] = n; }
 }

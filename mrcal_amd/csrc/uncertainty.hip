@@ -34,6 +34,7 @@
 #include "layout.hpp"
 #include "host_state.hpp"
 #include "problem_object.hpp"
+#include "wave_sum.hpp"
 #include "../../include/mrcal_amd.h"
 
 using namespace mrcal_amd;
@@ -128,13 +129,6 @@ __device__ __forceinline__ int row_mode(const DrtDims& d, const RowMap& m)
     return DRT_NONE;
 }
 
-// the sum over the wavefront, every lane ends up with it; the order of the additions is fixed
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-    for(int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // one wavefront per board observation: rows [rows_per_obs*obs, +rows_per_obs)
 __global__ __launch_bounds__(64)
 void drt_board_rows_kernel(DrtDims d, int Nobs, int rows_per_obs,
@@ -219,7 +213,7 @@ void drt_board_rows_kernel(DrtDims d, int Nobs, int rows_per_obs,
 #pragma unroll
     for(int i = 0; i < 69; i++)
     {
-        const double v = wave_sum_f64(acc[i]);
+        const double v = wave_sum(acc[i]);
         if(lane == 0) out->s[i] = v;
     }
     if(lane == 0)

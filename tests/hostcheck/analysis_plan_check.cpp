@@ -3,9 +3,8 @@
 // and without the core and the extrinsics, and the grouping of pixel pairs by camera. Not a product path, and nothing
 // loads it into Python.
 //
-//   hipcc -std=c++17 -O1 -g -x hip --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined \
-//         tests/hostcheck/analysis_plan_check.cpp -fsanitize=address,undefined -o tests/hostcheck/analysis_plan_check
-//   tests/hostcheck/analysis_plan_check        (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
+//   built by tests/hostbuild.py, build_program("analysis_plan_check"): a row of its PROGRAMS. No arguments
+//   (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>

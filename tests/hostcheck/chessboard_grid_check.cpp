@@ -6,8 +6,8 @@
 // and 30 points of clutter: found in the order of the definition; a corner removed, only clutter: not found; a corner
 // duplicated 0.4 of a step away: not taken. Not a product path, and nothing loads it into Python.
 //
-//   hipcc -std=c++17 -O1 -g -x c++ -fsanitize=address,undefined -fno-gpu-sanitize tests/hostcheck/chessboard_grid_check.cpp mrcal_amd/csrc/chessboard_grid.cpp -o tests/hostcheck/chessboard_grid_check
-//   tests/hostcheck/chessboard_grid_check         (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
+//   built by tests/hostbuild.py, build_program("chessboard_grid_check"): a row of its PROGRAMS. No arguments
+//   (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>

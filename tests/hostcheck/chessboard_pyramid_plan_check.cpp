@@ -5,8 +5,8 @@
 // that a level's shared parts fit where level 0's are, the decimation's launch geometry, and what just fits the free
 // device memory. Not a product path, and nothing loads it into Python.
 //
-//   hipcc -std=c++17 -O1 -g -x c++ -fsanitize=address,undefined -fno-gpu-sanitize tests/hostcheck/chessboard_pyramid_plan_check.cpp -o tests/hostcheck/chessboard_pyramid_plan_check
-//   tests/hostcheck/chessboard_pyramid_plan_check         (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
+//   built by tests/hostbuild.py, build_program("chessboard_pyramid_plan_check"): a row of its PROGRAMS. No arguments
+//   (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>

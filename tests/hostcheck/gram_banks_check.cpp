@@ -16,9 +16,8 @@
 //     allocation of the smallest board
 // Not a product path, and nothing loads it into Python.
 //
-//   hipcc -std=c++17 -O1 -g -x c++ -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -fsanitize=address,undefined -fno-gpu-sanitize \
-//         tests/hostcheck/gram_banks_check.cpp -o tests/hostcheck/gram_banks_check
-//   tests/hostcheck/gram_banks_check     (prints the table, then "ok"; a sanitizer report or a failed check ends it with a non-zero status)
+//   built by tests/hostbuild.py, build_program("gram_banks_check"): a row of its PROGRAMS. No arguments
+//   (prints the table, then "ok"; a sanitizer report or a failed check ends it with a non-zero status)
 #include <stdio.h>
 #include <stdlib.h>
 #include <set>

@@ -9,9 +9,8 @@
 //     (Tt T)[i][j] exactly; every entry of a stored block has exactly one home; an undeclared position is nobody's.
 // Not a product path, and nothing loads it into Python.
 //
-//   hipcc -std=c++17 -O1 -g -x c++ -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -fsanitize=address,undefined -fno-gpu-sanitize \
-//         tests/hostcheck/gram_packing_check.cpp -o tests/hostcheck/gram_packing_check
-//   tests/hostcheck/gram_packing_check         (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
+//   built by tests/hostbuild.py, build_program("gram_packing_check"): a row of its PROGRAMS. No arguments
+//   (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>

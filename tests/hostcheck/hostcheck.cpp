@@ -4,7 +4,7 @@
 // compile against the reference's own mrcal_project() (oracle/_ref).
 // This is not a product path: nothing in mrcal_amd/ loads it.
 //
-//   hipcc -O2 -std=c++17 -fPIC -shared -o libhostcheck.so hostcheck.cpp      (host code only)
+//   built by tests/hostbuild.py, build_library("hostcheck")      (host code only)
 #include <string.h>
 #include "../../mrcal_amd/csrc/lens_models.hpp"
 

@@ -3,9 +3,8 @@
 // instantiation, the unknowns of each stage, the sums, threads, the chunk of rows, LDS within the limit - the
 // regularization scales, the measurement counts, and every refusal. Not a product path, and nothing loads it into Python.
 //
-//   hipcc -std=c++17 -O1 -g -x c++ -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -fsanitize=address,undefined -fno-gpu-sanitize \
-//         tests/hostcheck/lensfit_plan_check.cpp -o tests/hostcheck/lensfit_plan_check
-//   tests/hostcheck/lensfit_plan_check         (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
+//   built by tests/hostbuild.py, build_program("lensfit_plan_check"): a row of its PROGRAMS. No arguments
+//   (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>

@@ -3,8 +3,8 @@
 // image, the two "outside" statuses, the sizes that are refused, the template map against the plain expression, and the
 // offsets into the pooled surface buffer for 1, 2 and 65 features. Not a product path, and nothing loads it into Python.
 //
-//   hipcc -std=c++17 -O1 -g -x c++ -fsanitize=address,undefined -fno-gpu-sanitize tests/hostcheck/match_plan_check.cpp -o tests/hostcheck/match_plan_check
-//   tests/hostcheck/match_plan_check           (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
+//   built by tests/hostbuild.py, build_program("match_plan_check"): a row of its PROGRAMS. No arguments
+//   (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>

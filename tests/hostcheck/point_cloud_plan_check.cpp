@@ -4,8 +4,8 @@
 // scan of the counts fits its one workgroup at the largest size, how the output buffers grow, and what just fits the
 // free device memory and what does not. Not a product path, and nothing loads it into Python.
 //
-//   hipcc -std=c++17 -O1 -g -x c++ -fsanitize=address,undefined -fno-gpu-sanitize tests/hostcheck/point_cloud_plan_check.cpp -o tests/hostcheck/point_cloud_plan_check
-//   tests/hostcheck/point_cloud_plan_check         (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
+//   built by tests/hostbuild.py, build_program("point_cloud_plan_check"): a row of its PROGRAMS. No arguments
+//   (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>

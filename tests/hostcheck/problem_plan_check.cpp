@@ -2,9 +2,8 @@
 // problems of tests/test_problem_plan.py - case A whole, its shards, with triangulated points, and the three refusals.
 // Not a product path, and nothing loads it into Python.
 //
-//   hipcc -std=c++17 -O1 -g -x hip --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined \
-//         mrcal_amd/csrc/problem_plan.cpp tests/hostcheck/problem_plan_check.cpp -fsanitize=address,undefined -o tests/hostcheck/problem_plan_check
-//   tests/hostcheck/problem_plan_check        (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
+//   built by tests/hostbuild.py, build_program("problem_plan_check"): a row of its PROGRAMS. No arguments
+//   (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>

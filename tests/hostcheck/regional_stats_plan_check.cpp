@@ -1,5 +1,5 @@
 // Drives csrc/regional_stats_plan.hpp as a stand-alone program (built with ASan + UBSan by
-// tests/test_valid_intrinsics_region.py). Prints "ok" and returns 0 if every check holds.
+// tests/hostbuild.py, a row of its PROGRAMS). Prints "ok" and returns 0 if every check holds.
 #include <stdio.h>
 #include <stdlib.h>
 #include <math.h>

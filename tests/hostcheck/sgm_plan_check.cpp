@@ -4,8 +4,8 @@
 // of 4 paths or a workgroup of 16 pixels is just full or just not, and the refusal of a problem that does not fit
 // the free device memory. Not a product path, and nothing loads it into Python.
 //
-//   hipcc -std=c++17 -O1 -g -x c++ -fsanitize=address,undefined -fno-gpu-sanitize tests/hostcheck/sgm_plan_check.cpp -o tests/hostcheck/sgm_plan_check
-//   tests/hostcheck/sgm_plan_check             (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
+//   built by tests/hostbuild.py, build_program("sgm_plan_check"): a row of its PROGRAMS. No arguments
+//   (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>

@@ -4,8 +4,8 @@
 // or just not, what the matcher's two keywords become, and the refusal of an image that does not fit the free device
 // memory. Not a product path, and nothing loads it into Python.
 //
-//   hipcc -std=c++17 -O1 -g -x c++ -fsanitize=address,undefined -fno-gpu-sanitize tests/hostcheck/speckle_plan_check.cpp -o tests/hostcheck/speckle_plan_check
-//   tests/hostcheck/speckle_plan_check         (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
+//   built by tests/hostbuild.py, build_program("speckle_plan_check"): a row of its PROGRAMS. No arguments
+//   (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>

@@ -1,5 +1,5 @@
 // Drives csrc/region_outline.cpp as a stand-alone program (built with ASan + UBSan by
-// tests/test_valid_intrinsics_region.py). Reads masks from the file named on the command line, one a line:
+// tests/hostbuild.py for tests/test_valid_region_host.py). Reads masks from the file named on the command line, one a line:
 //   w h c c c ...      (w*h cells, 0 or 1, row-major)
 // and prints for each:  nvertices area2 x y x y ...   through the C entry point, with a capacity one short of what is
 // needed first, to see that nothing is written beyond it.

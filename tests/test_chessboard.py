@@ -18,12 +18,11 @@ What was measured, and is asserted below:
 import functools
 import io
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import hostbuild
 import chessboard_checker as chk
 
 # measured once (the docstring above); the assertions use them as written here
@@ -43,16 +42,7 @@ CONFIGS = (dict(square=30., angle=0.,   perspective=(0., 0.),      k1=0.,   nois
 def test_host_code_under_the_host_sanitizers():
     """csrc/chessboard_plan.hpp and csrc/chessboard_grid.cpp driven by a stand-alone program with its own main, built
     with ASan and UBSan"""
-    here, csrc = os.path.join(ROOT, "tests", "hostcheck"), os.path.join(ROOT, "mrcal_amd", "csrc")
-    exe, src = os.path.join(here, "chessboard_grid_check"), os.path.join(here, "chessboard_grid_check.cpp")
-    grid = os.path.join(csrc, "chessboard_grid.cpp")
-    deps = [src, grid, os.path.join(csrc, "chessboard_grid.hpp"), os.path.join(csrc, "chessboard_plan.hpp")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        # (host code only: -x c++, and no sanitizer for any GPU code)
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-g", "-x", "c++", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
-                               "-fno-sanitize-recover=undefined", src, grid, "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
+    hostbuild.assert_prints_ok("chessboard_grid_check")
 
 
 def board_points(W, H, step, degrees, perspective, k1, jitter, rng):

@@ -25,13 +25,11 @@ What was measured with the checker alone (pyramid_levels = 3, tau = 0.3 px), and
     the sweep
   no step of the sweep lies within 1e-6 px of tau"""
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import hostbuild
 import chessboard_checker as chk
 import chessboard_pyramid_checker as pc
 
@@ -119,15 +117,7 @@ def test_levels_and_refusals_before_any_device_work(amd, monkeypatch):
 def test_pyramid_plan_under_the_host_sanitizers():
     """csrc/chessboard_plan.hpp's pyramid plan driven by a stand-alone program with its own main, built with ASan and
     UBSan: the level geometry, the refusals, and pyramid_levels = 0 giving the plan there was, field for field"""
-    here, csrc = os.path.join(ROOT, "tests", "hostcheck"), os.path.join(ROOT, "mrcal_amd", "csrc")
-    exe, src = os.path.join(here, "chessboard_pyramid_plan_check"), os.path.join(here, "chessboard_pyramid_plan_check.cpp")
-    deps = [src, os.path.join(csrc, "chessboard_plan.hpp")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        # (host code only: -x c++, and no sanitizer for any GPU code)
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-g", "-x", "c++", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
-                               "-fno-sanitize-recover=undefined", src, "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
+    hostbuild.assert_prints_ok("chessboard_pyramid_plan_check")
 
 
 def test_decimation_of_the_checker():

@@ -9,12 +9,12 @@ On the GPU: EQUALITY with the checker, every pixel, no tolerance, and bit equali
 composed one. cv2 is no part of this project: nothing here is held to it."""
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN_DIR, ROOT
+from conftest import GOLDEN_DIR
+import hostbuild
 import equalize_checker as chk
 
 
@@ -258,15 +258,7 @@ def test_refusals_before_any_device_work(amd, monkeypatch):
 
 def test_equalize_plan_under_the_host_sanitizers():
     """csrc/equalize_plan.hpp driven by a stand-alone program with its own main, built with ASan and UBSan"""
-    here = os.path.join(ROOT, "tests", "hostcheck")
-    exe, src = os.path.join(here, "equalize_plan_check"), os.path.join(here, "equalize_plan_check.cpp")
-    deps = [src, os.path.join(ROOT, "mrcal_amd", "csrc", "equalize_plan.hpp")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        # (host code only: -x c++, and no sanitizer for any GPU code)
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-g", "-x", "c++", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
-                               "-fno-sanitize-recover=undefined", src, "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
+    hostbuild.assert_prints_ok("equalize_plan_check")
 
 
 # --------------------------------------------------------------------------------------------------- on the GPU ---

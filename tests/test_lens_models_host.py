@@ -11,27 +11,20 @@ device_math.hpp), built for the HOST as a test-only library
 
 No GPU needed: this is what pins the projection math in the CPU suite."""
 import ctypes as C
-import os
-import subprocess
 import numpy as np
 import pytest
 
-from conftest import ROOT, relative_error
+from conftest import relative_error
+import hostbuild
 from mrcal_amd._cabi import Lensmodel
 
-HERE = os.path.join(ROOT, "tests", "hostcheck")
 PROJ = dict(OPENCV=0, STEREOGRAPHIC=1, LONLAT=2, LATLON=3, CAHVOR=4, CAHVORE=5)
 REL_TOL = 1e-6
 
 
 @pytest.fixture(scope="module")
 def hostlib():
-    so, src = os.path.join(HERE, "libhostcheck.so"), os.path.join(HERE, "hostcheck.cpp")
-    deps = [src] + [os.path.join(ROOT, "mrcal_amd", "csrc", f) for f in ("lens_models.hpp", "device_math.hpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-fPIC", "-shared",
-                               "-Wno-unused-function", "-o", so, src])
-    L = C.CDLL(so)
+    L = C.CDLL(hostbuild.build_library("hostcheck"))
     vp = C.c_void_p
     L.hostcheck_project.restype  = C.c_int
     L.hostcheck_project.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, C.c_double]

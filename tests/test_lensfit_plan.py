@@ -2,12 +2,9 @@
 sanitizers (tests/hostcheck/lensfit_plan_check.cpp), and through the library's mrcal_amd_lensfit_plan() - the same
 function, as fit_lensmodel() calls it: for every row of the lens table, with and without the core and the pose, the
 instantiation, the unknowns, the threads, the chunk and an LDS size within the limit the plan states; every refusal."""
-import os
-import subprocess
-
 import pytest
 
-from conftest import ROOT
+import hostbuild
 
 # for_parametric_lens(), restated: (model, PROJ, NDIST). PROJ_*: csrc/lens_models.hpp
 PROJ_OPENCV, PROJ_STEREOGRAPHIC, PROJ_LONLAT, PROJ_LATLON, PROJ_CAHVOR, PROJ_CAHVORE = range(6)
@@ -21,16 +18,7 @@ SPLINED = "LENSMODEL_SPLINED_STEREOGRAPHIC_order=3_Nx=8_Ny=6_fov_x_deg=80"
 
 def test_lensfit_plan_under_the_host_sanitizers():
     """csrc/lensfit_plan.hpp driven by a stand-alone program with its own main, built with ASan and UBSan"""
-    here = os.path.join(ROOT, "tests", "hostcheck")
-    exe, src = os.path.join(here, "lensfit_plan_check"), os.path.join(here, "lensfit_plan_check.cpp")
-    deps = [src] + [os.path.join(ROOT, "mrcal_amd", "csrc", f) for f in ("lensfit_plan.hpp", "lens_dispatch.hpp", "lens_models.hpp")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        # (host code only: -x c++ - lens_dispatch.hpp reaches the HIP headers for its __host__ __device__ - and no sanitizer for any GPU code)
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-g", "-x", "c++", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-                               "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-sanitize-recover=undefined", "-Wno-unused-result",
-                               src, "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
+    hostbuild.assert_prints_ok("lensfit_plan_check")
 
 
 @pytest.mark.parametrize("lensmodel,proj,ndist", TABLE)

@@ -6,12 +6,12 @@ Without a GPU: apply_homography(), the checker against a brute-force loop and ag
 the match surface against the checker (tests/match_feature_checker.py: numpy with exact integer sums, no cv2), the
 template to the bit, the peak and the subpixel step, batches, and two cameras looking at a textured plane."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN_DIR, ROOT
+from conftest import GOLDEN_DIR
+import hostbuild
 import match_feature_checker as chk
 
 # the reference's test: some made-up homography with scaling, rotating, skewing and translating
@@ -145,15 +145,7 @@ def test_refusals_before_any_device_work(amd, image, monkeypatch):
 
 def test_match_plan_under_the_host_sanitizers():
     """csrc/match_plan.hpp driven by a stand-alone program with its own main, built with ASan and UBSan"""
-    here = os.path.join(ROOT, "tests", "hostcheck")
-    exe, src = os.path.join(here, "match_plan_check"), os.path.join(here, "match_plan_check.cpp")
-    deps = [src, os.path.join(ROOT, "mrcal_amd", "csrc", "match_plan.hpp")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        # (host code only: -x c++, and no sanitizer for any GPU code)
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-g", "-x", "c++", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
-                               "-fno-sanitize-recover=undefined", src, "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
+    hostbuild.assert_prints_ok("match_plan_check")
 
 
 # --------------------------------------------------------------------------------------------------- on the GPU ---

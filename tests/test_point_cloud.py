@@ -6,12 +6,12 @@ The checker (point_cloud_checker.py) restates the definition in numpy and again 
 held to it entry for entry; points to 1e-12 relative of (range + |t|), the bound the range kernels are held to against
 numpy (test_stereo.py), and for frame = 'rect0' to the BITS of the existing stereo_unproject()."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN_DIR, ROOT
+from conftest import GOLDEN_DIR
+import hostbuild
 import point_cloud_checker as chk
 
 MODELS = ("LENSMODEL_LATLON", "LENSMODEL_PINHOLE")
@@ -216,15 +216,7 @@ def test_refusals_before_any_device_work(amd, monkeypatch):
 
 def test_point_cloud_plan_under_the_host_sanitizers():
     """csrc/point_cloud_plan.hpp driven by a stand-alone program with its own main, built with ASan and UBSan"""
-    here = os.path.join(ROOT, "tests", "hostcheck")
-    exe, src = os.path.join(here, "point_cloud_plan_check"), os.path.join(here, "point_cloud_plan_check.cpp")
-    deps = [src, os.path.join(ROOT, "mrcal_amd", "csrc", "point_cloud_plan.hpp")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        # (host code only: -x c++, and no sanitizer for any GPU code)
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-g", "-x", "c++", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
-                               "-fno-sanitize-recover=undefined", src, "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
+    hostbuild.assert_prints_ok("point_cloud_plan_check")
 
 
 # ------------------------------------------------------------------------------------------------ the PLY writer ---

@@ -7,12 +7,12 @@ host sanitizers. On the GPU: EQUALITY with the checker, every pixel, no toleranc
 which a tile is just full or just not, structured images whose regions span every tile, the resident object, and the
 filter as the last stage of stereo_matching_sgm(), StereoMatcherSGM and Rectification.disparity()."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN_DIR, ROOT
+from conftest import GOLDEN_DIR
+import hostbuild
 import speckle_checker as chk
 import stereo_sgm_checker as sgm_chk
 
@@ -176,15 +176,7 @@ def test_refusals_before_any_device_work(amd, monkeypatch):
 
 def test_speckle_plan_under_the_host_sanitizers():
     """csrc/speckle_plan.hpp driven by a stand-alone program with its own main, built with ASan and UBSan"""
-    here = os.path.join(ROOT, "tests", "hostcheck")
-    exe, src = os.path.join(here, "speckle_plan_check"), os.path.join(here, "speckle_plan_check.cpp")
-    deps = [src, os.path.join(ROOT, "mrcal_amd", "csrc", "speckle_plan.hpp")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        # (host code only: -x c++, and no sanitizer for any GPU code)
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-g", "-x", "c++", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
-                               "-fno-sanitize-recover=undefined", src, "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
+    hostbuild.assert_prints_ok("speckle_plan_check")
 
 
 # --------------------------------------------------------------------------------------------------- on the GPU ---

@@ -7,10 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import os
-import subprocess
-
-from conftest import GOLDEN_DIR, ROOT
+from conftest import GOLDEN_DIR
+import hostbuild
 import rectification_checker as chk
 
 MODELS = ("LENSMODEL_LATLON", "LENSMODEL_PINHOLE")
@@ -37,13 +35,7 @@ def angle_deg(a, b):
 @pytest.fixture(scope="module")
 def hostlib():
     """csrc/stereo_geometry.cpp built for the host, by itself"""
-    here = os.path.join(ROOT, "tests", "hostcheck")
-    so, src = os.path.join(here, "libstereo_check.so"), os.path.join(here, "stereo_check.cpp")
-    deps = [src] + [os.path.join(ROOT, "mrcal_amd", "csrc", f) for f in ("stereo_geometry.cpp", "stereo_geometry.hpp", "lens_models.hpp", "lens_dispatch.hpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=on",
-                               "-Wno-unused-function", "-o", so, src])
-    return C.CDLL(so)
+    return C.CDLL(hostbuild.build_library("stereo_check"))
 
 
 # -------------------------------------------------------------------------------------------------------------------

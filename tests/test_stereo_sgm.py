@@ -6,12 +6,12 @@ per-disparity loops, its accuracy on a slanted plane, every refusal before any d
 pixel, over the sizes, disparity ranges and parameters at which a kernel takes another path; ties, the floor of a
 negative subpixel numerator, uint16, the resident object, and image pair -> rectification -> disparity -> range."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN_DIR, ROOT
+from conftest import GOLDEN_DIR
+import hostbuild
 import stereo_sgm_checker as chk
 
 
@@ -191,15 +191,7 @@ def test_rectification_disparity_refuses_before_any_device_work(amd):
 
 def test_sgm_plan_under_the_host_sanitizers():
     """csrc/sgm_plan.hpp driven by a stand-alone program with its own main, built with ASan and UBSan"""
-    here = os.path.join(ROOT, "tests", "hostcheck")
-    exe, src = os.path.join(here, "sgm_plan_check"), os.path.join(here, "sgm_plan_check.cpp")
-    deps = [src, os.path.join(ROOT, "mrcal_amd", "csrc", "sgm_plan.hpp")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        # (host code only: -x c++, and no sanitizer for any GPU code)
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-g", "-x", "c++", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
-                               "-fno-sanitize-recover=undefined", src, "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
+    hostbuild.assert_prints_ok("sgm_plan_check")
 
 
 # --------------------------------------------------------------------------------------------------- on the GPU ---

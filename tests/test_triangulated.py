@@ -13,7 +13,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from conftest import relative_error, ROOT
+from conftest import relative_error
+import hostbuild
 from mrcal_amd._cabi import Lensmodel
 from mrcal_amd.synthetic import copy_inputs
 
@@ -198,14 +199,7 @@ def test_project_unproject_broadcast_over_models(amd_api):
 def test_pair_residual_matches_reference_cpu(ref_api):
     """the pair residual and its derivatives (host build of triangulation.hpp)
     against the rows the reference's callback produces. No GPU"""
-    import subprocess, os
-    from test_lens_models_host import HERE
-    so = os.path.join(HERE, "libhostcheck.so")
-    src = os.path.join(HERE, "hostcheck.cpp")
-    deps = [src] + [os.path.join(ROOT, "mrcal_amd", "csrc", f) for f in ("lens_models.hpp", "device_math.hpp", "triangulation.hpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-function", "-o", so, src])
-    L = C.CDLL(so)
+    L = C.CDLL(hostbuild.build_library("hostcheck"))
     L.hostcheck_tri_pair_error.restype  = C.c_double
     L.hostcheck_tri_pair_error.argtypes = [C.c_void_p]*3 + [C.c_void_p]*4
 
@@ -292,9 +286,7 @@ def test_pair_residual_rounding_envelope_cpu(ref_api):
     K eps/|x| (x) and K eps/x^2 relative (J) of the 60-digit evaluation of the
     same formula. No GPU"""
     import mp_triangulated as M
-    from test_lens_models_host import HERE
-    import os
-    L = C.CDLL(os.path.join(HERE, "libhostcheck.so"))
+    L = C.CDLL(hostbuild.build_library("hostcheck"))
     L.hostcheck_tri_pair_error.restype  = C.c_double
     L.hostcheck_tri_pair_error.argtypes = [C.c_void_p]*3 + [C.c_void_p]*4
     oi, _ = sfm_problem("LENSMODEL_OPENCV4", Ncam=4, Npoints=3000, seed=6, noise=0.3)

@@ -15,13 +15,11 @@ Without a GPU: the header built for the host (tests/hostcheck/triangulation_chec
 which must also give the host build's p to the bit."""
 import ctypes as C
 import os
-import subprocess
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import hostbuild
 
-HERE    = os.path.join(ROOT, "tests", "hostcheck")
 METHODS = dict(geometric=0, lindstrom=1, leecivera_l1=2, leecivera_linf=3, leecivera_mid2=4, leecivera_wmid2=5)
 SIZES   = (1, 63, 64, 65, 257)
 TOL     = 1e-6
@@ -103,12 +101,7 @@ def ref_triangulate(ref_api, method, pairs):
 
 @pytest.fixture(scope="module")
 def hostlib():
-    so, src = os.path.join(HERE, "libtriangulation_check.so"), os.path.join(HERE, "triangulation_check.cpp")
-    deps = [src] + [os.path.join(ROOT, "mrcal_amd", "csrc", f) for f in ("triangulation_math.hpp", "device_math.hpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=on",
-                               "-Wno-unused-function", "-o", so, src])
-    L = C.CDLL(so)
+    L = C.CDLL(hostbuild.build_library("triangulation_check"))
     L.tricheck_eval.restype,          L.tricheck_eval.argtypes          = C.c_int, [C.c_int]*3 + [C.c_void_p]*7
     L.tricheck_eval_double.restype,   L.tricheck_eval_double.argtypes   = C.c_int, [C.c_int]*2 + [C.c_void_p]*4
     L.tricheck_is_convergent.restype, L.tricheck_is_convergent.argtypes = None, [C.c_int] + [C.c_void_p]*4
@@ -349,7 +342,7 @@ def test_device_buffers_are_given_back(amd, cases):
 
 from mrcal_amd.synthetic import make_calibration_problem, copy_inputs, intrinsics_for, IMAGERSIZE
 
-GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
+from conftest import GOLDEN_DIR
 COV_TOL    = 1e-6       # of the matrix's largest entry
 
 

@@ -3,33 +3,16 @@ with ASan and UBSan, on the CPU: the work lists of the regional statistics (csrc
 of a mask (csrc/region_outline.cpp; the definition: include/mrcal_amd.h, "valid-intrinsics region"). The outline is held
 vertex for vertex to the border follower of valid_region_checker.py, and to the properties that define it. No GPU here:
 the GPU tests are in test_valid_intrinsics_region.py."""
-import os
 import subprocess
 
 import numpy as np
 
-from conftest import ROOT
+import hostbuild
 import valid_region_checker as chk
 
 
-# ---------------------------------------------------------------------------------------------------- host: builds
-def build_hostcheck(name, extra_sources=(), deps=()):
-    """a stand-alone program with its own main, built with ASan and UBSan (host code only: -x c++)"""
-    here = os.path.join(ROOT, "tests", "hostcheck")
-    exe, src = os.path.join(here, name), os.path.join(here, name + ".cpp")
-    deps = [src] + list(extra_sources) + list(deps)
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        sources = [src] + list(extra_sources)
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-g", "-x", "c++", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
-                               "-fno-sanitize-recover=undefined", *sources, "-o", exe])
-    return exe
-
-
 def test_regional_stats_plan_under_the_host_sanitizers():
-    csrc = os.path.join(ROOT, "mrcal_amd", "csrc")
-    exe = build_hostcheck("regional_stats_plan_check", deps=[os.path.join(csrc, "regional_stats_plan.hpp")])
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
+    hostbuild.assert_prints_ok("regional_stats_plan_check")
 
 
 # --------------------------------------------------------------------------------------------------- host: outline
@@ -106,9 +89,7 @@ def test_outline_against_the_checker_and_its_properties(amd, tmp_path):
     from mrcal_amd.valid_region import region_outline, contour_of_mask
     masks = named_masks()
     # the stand-alone program, under the sanitizers
-    csrc = os.path.join(ROOT, "mrcal_amd", "csrc")
-    exe = build_hostcheck("valid_region_check", extra_sources=[os.path.join(csrc, "region_outline.cpp")],
-                          deps=[os.path.join(csrc, "region_outline.hpp")])
+    exe = hostbuild.build_program("valid_region_check")
     path = tmp_path / "masks.txt"
     with open(path, "w") as f:
         for m in masks.values():
