@@ -27,6 +27,7 @@
 // The assembly of the block normal equations (from the per-observation Grams; rows outside the Grams; a caller's bare matrix)
 // (round 6: one of the translation units solver_kernels.hip was cut into; solver_device.hpp has what they share)
 #include "solver_device.hpp"
+#include "cycle_stamps.hpp"
 #include "assembly_splined.hpp"
 #include "solver_kernel_decls.hpp"
 
@@ -71,13 +72,9 @@ void assemble_frame_block(const DeviceProblem& P, const NormalDims& nd, const Op
     double* __restrict__ Ls   = gf + 6;
     double* __restrict__ rinv = Ls + 36;
     const int t = threadIdx.x;
-#ifdef ASM_TS
-    long long ats[16]; int nats = 0;
-#define ATS() do { if(t == 0 && nats < 16) ats[nats++] = clock64(); } while(0)
-#else
-#define ATS()
-#endif
-    ATS();
+    StampSlots<ASM_TS, 16> ats_slots;                       // (a mark per pass of the loads' loop: an array, thread 0's)
+    CycleStamps<ASM_TS, 16, true> ats(ats_slots, t == 0);
+    ats.mark();
     const int e0 = 6*f;   // frame blocks come first in E
     double* __restrict__ Bt = O.Bt;
     double* __restrict__ D  = O.D;
@@ -156,11 +153,11 @@ void assemble_frame_block(const DeviceProblem& P, const NormalDims& nd, const Op
                         if(kind == FRAMEPOS_D_MIRROR) Df[k*6 + a] = acc;
                     }
                 }
-                ATS();
+                ats.mark();
             }
         }
         __syncthreads();
-        ATS();
+        ats.mark();
         for(int i = t; i < 6*nd.Nc; i += blockDim.x) Bt[(size_t)e0*nd.Nc + i] = Btf[i];
         if(t < 36)      D[(size_t)f*36 + t]     = Df[t];
         else if(t < 42) g[nd.E_state0 + e0 + (t-36)] = gf[t-36];
@@ -209,9 +206,9 @@ void assemble_frame_block(const DeviceProblem& P, const NormalDims& nd, const Op
             for(int j=0;j<6;j++) Ls[i*6+j] = (j <= i) ? M[i][j] : 0.0;
         if(!ok) atomicExch(F.status, 1);
     }
-    ATS();
+    ats.mark();
     __syncthreads();
-    ATS();
+    ats.mark();
     if(t < 36) F.LD[(size_t)f*36 + t] = Ls[t];
     double Lr[6][6], ri[6];             // (the strict lower triangle is all the substitution reads)
 #pragma unroll
@@ -236,12 +233,16 @@ void assemble_frame_block(const DeviceProblem& P, const NormalDims& nd, const Op
         if(c < nd.Nc) { for(int i=0;i<6;i++) F.Wt[(size_t)(e0+i)*nd.Nc + c] = w[i]; }
         else          { for(int i=0;i<6;i++) F.y[e0+i] = w[i]; }
     }
-    ATS();
-#ifdef ASM_TS
-    if(t == 0 && (f == 0 || f == 300 || f == 999))
-        printf("asm ts f=%d n=%d (zero | loads + adds | sync | bt-write+factor | sync | fsub): %lld %lld %lld %lld %lld %lld\n", f, nats,
-               ats[1]-ats[0], ats[2]-ats[1], ats[3]-ats[2], ats[4]-ats[3], ats[5]-ats[4], ats[6]-ats[5]);
-#endif
+    ats.mark();
+    // (marks: start, the end of every pass of the loads' loop, the barrier behind it, thread 0's factorization, the
+    //  barrier behind it, the substitution. The names are those of mode 1 with ONE pass, as at the metric's size -
+    //  eight cameras, a Gram of two positions a thread at the most; each further pass is a mark more and the names
+    //  move up by as many. Mode 2 has no pass)
+    if constexpr(ASM_TS)
+    {
+        if(stamps_reporter(f, P.Nframes, t == 0))
+            ats.report("asm_frame", "zero_loads_adds sync bt_write_factor factor_sync fsub", f, P.Nframes);
+    }
 }
 
 // S-S part: observations that see the same (intrinsics, extrinsics) pair add to
@@ -258,9 +259,8 @@ void reduce_pair_chunk(const DeviceProblem& P, const AssemblyPlan& plan,
     const PairOp* __restrict__ ops = plan.pair_table + (size_t)plan.chunk_pair[ichunk]*npos;
     double* __restrict__ out = plan.chunk_part + (size_t)ichunk*npos;
     const int nobs = c1 - c0;
-#ifdef ASM_TS
-    const long long cts0 = clock64();
-#endif
+    CycleStamps<ASM_TS, 3> cts;
+    cts.mark();
     // one position per thread (a workgroup per 256 positions of the chunk: two position per thread and half
     // as many workgroups needed 112 registers, and at four waves per SIMD the launch no longer fit the chip
     // at once), 16 observations of it in flight together
@@ -289,9 +289,14 @@ void reduce_pair_chunk(const DeviceProblem& P, const AssemblyPlan& plan,
         for(int u = 0; u < 16; u++) acc += (u0 + u < nobs) ? vv[u] : 0.0;
     }
     if(pos < npos) out[pos] = acc;
-#ifdef ASM_TS
-    if(threadIdx.x == 0 && islice == 0 && (ichunk == 0 || ichunk == plan.Nchunks-1)) printf("asm ts chunk %d of %d (nobs %d) dur=%lld\n", ichunk, plan.Nchunks, nobs, clock64()-cts0);
-#endif
+    if constexpr(ASM_TS)
+    {
+        if(stamps_reporter(ichunk, plan.Nchunks, threadIdx.x == 0 && islice == 0))
+        {
+            cts.mark(); cts.count(2, nobs);
+            cts.report("asm_chunk", "dur nobs", ichunk, plan.Nchunks);
+        }
+    }
 }
 
 

@@ -1,6 +1,7 @@
 // The splined models' assembly: local Grams on the matrix cores, staged triangles, the gathers, the compaction's plan
 // (round 6: one of the translation units solver_kernels.hip was cut into; solver_device.hpp has what they share)
 #include "solver_device.hpp"
+#include "cycle_stamps.hpp"
 #include "assembly_splined.hpp"
 #include "solver_kernel_decls.hpp"
 
@@ -192,14 +193,10 @@ void assemble_splined_kernel(DeviceProblem P, NormalDims nd, OpRef R, AssemblyPl
     const int Ncs = P.Ncore_state;
     if(t < 42) FD[t] = 0.0;
     if(t < 6*SPL_NDENSE) FB[t] = 0.0;
-    // (-DSPL_TS: cycles per phase, printed by three of the workgroups)
-#ifdef SPL_TS
-    long long ts_bbox = 0, ts_zero = 0, ts_scatter = 0, ts_gram = 0, ts_out = 0, ts0 = clock64(), ts1;
-    const long long tw0 = wall_clock64(), tc0 = ts0;
-#define SPL_TICK(what) { ts1 = clock64(); what += ts1 - ts0; ts0 = ts1; }
-#else
-#define SPL_TICK(what)
-#endif
+    // (-DSPL_TS: cycles per phase, and the workgroup's place in time: the chip-wide clock at its start and end)
+    CycleStamps<SPL_TS, 8> ts;
+    enum { TS_BBOX, TS_ZERO, TS_SCATTER, TS_GRAM, TS_OUT, TS_REST, TS_WALL0, TS_WALL1 };
+    ts.count(TS_WALL0, ts.wall());
 
     for(int o = o0; o < o1; o++)
     {
@@ -229,7 +226,7 @@ void assemble_splined_kernel(DeviceProblem P, NormalDims nd, OpRef R, AssemblyPl
             nsy = max(1, (owy - order + T - 1)/T);
         }
         const int nsub = nsx*nsy;
-        SPL_TICK(ts_bbox)
+        ts.lap(TS_BBOX);
         if(nsub > SPL_MAXSUB || (nsub > 1 && NPTS > (int)sizeof(own)))
         {
             if(xy0 == 0)
@@ -370,7 +367,7 @@ void assemble_splined_kernel(DeviceProblem P, NormalDims nd, OpRef R, AssemblyPl
                 const double xv = x[r0 + 2*(((nsub == 1) ? c0 : 0) + max(0, min(tq, ((nsub == 1) ? nr : NPTS) - 1))) + xy];
                 for(int i = tq; i < nr4*(LD/2); i += blockDim.x) ((double2*)Jd)[i] = make_double2(0.0, 0.0);
                 spl_lds_barrier();
-                SPL_TICK(ts_zero)
+                ts.lap(TS_ZERO);
                 for(int e0 = 0; e0 < ne; e0 += 2*EB*256)
                 {
                     if(e0 + EB*256 < ne)   ask(e0 + EB*256, v1, ci1, ii1);
@@ -391,7 +388,7 @@ void assemble_splined_kernel(DeviceProblem P, NormalDims nd, OpRef R, AssemblyPl
                         if(row >= 0 && row < nr) Jd[row*LD + lx] = (i == tq) ? xv : x[r0 + 2*i + xy];
                     }
                 spl_lds_barrier();
-                SPL_TICK(ts_scatter)
+                ts.lap(TS_SCATTER);
                 int r16g = r16, kqg = kq;
                 asm volatile("" : "+v"(r16g), "+v"(kqg));
                 switch(na)
@@ -406,7 +403,7 @@ void assemble_splined_kernel(DeviceProblem P, NormalDims nd, OpRef R, AssemblyPl
                 case 7: spl_gram_mfma<7, first>(Jd, LD, nr4 >> 2, r16g, kqg, 16*Ia, 16*Ib, nb, acc); break;
                 default:spl_gram_mfma<8, first>(Jd, LD, nr4 >> 2, r16g, kqg, 16*Ia, 16*Ib, nb, acc); break;
                 }
-                SPL_TICK(ts_gram)
+                ts.lap(TS_GRAM);
                 // out: the whole lower triangle is staged - the camera-block rows and the x row for the gather - with
                 // stores nobody here waits for; the six frame rows and the x row also go to F, for the second half of this
                 // (the lane's coordinates made opaque here: left alone, the compiler computes the 36 store addresses once,
@@ -483,7 +480,7 @@ void assemble_splined_kernel(DeviceProblem P, NormalDims nd, OpRef R, AssemblyPl
                 }
             if(nsub > 1) __syncthreads();
             // (F is written again after the next pass's barriers)
-            SPL_TICK(ts_out)
+            ts.lap(TS_OUT);
         }
         }   // isub
         // the observation's core and extrinsics columns of Bt: one addition each, nothing read back (an atomic one, as
@@ -518,13 +515,15 @@ void assemble_splined_kernel(DeviceProblem P, NormalDims nd, OpRef R, AssemblyPl
             if(vv != 0.0) atomicAdd(&O.D[(size_t)f*36 + ia*6 + ib], vv);
         }
     }
-#ifdef SPL_TS
-    if((f == 0 || f == 400 || f == 799) && (t == 0 || t == 255))
-        printf("splined assembly f %d t %d: bbox %lld zero %lld scatter %lld gram %lld out %lld cycles\n", f, t, ts_bbox, ts_zero, ts_scatter, ts_gram, ts_out);
-    // (the workgroup's place in time: the constant 100 MHz clock at its start and end, and its own cycles)
-    if((f % 100 == 0 || f == 255 || f == 256 || f == 511 || f == 512 || f == 799) && t == 0)
-        printf("splined assembly f %d: wall %lld .. %lld (x10 ns), %lld cycles\n", f, tw0, wall_clock64(), clock64() - tc0);
-#endif
+    if constexpr(SPL_TS)
+    {
+        // workgroup (a frame's surface) of the workgroups, first and last thread
+        if(stamps_reporter((int)blockIdx.x, (int)gridDim.x, t == 0 || t == (int)blockDim.x - 1))
+        {
+            ts.lap(TS_REST); ts.count(TS_WALL1, ts.wall());
+            ts.report("spl_frame", "bbox zero scatter gram out rest wall0 wall1", (int)blockIdx.x, (int)gridDim.x, t, (int)blockDim.x);
+        }
+    }
 }
 
 #define SPLG_BATCH 3      // passes whose loads are in flight together (4: 104 registers with the sub-boxes' loop, and two of these
@@ -566,9 +565,9 @@ void assemble_splined_gather_kernel(DeviceProblem P, NormalDims nd, OpRef R, Ass
     __syncthreads();
     const bool xrow = (r == nd.Nc);
     const int  sr   = xrow ? -1 : (S_to_state(nd, r));     // state index of the row
-#ifdef SPLG_TS
-    long long gts0 = clock64(), gts_match = 0, gtq; int gn_match = 0, gn_batch = 0;
-#endif
+    // (-DSPLG_TS) laps: the matches' loads and sums, and everything else up to the barrier; the matches, the batches
+    CycleStamps<SPLG_TS, 4> gts;
+    enum { GTS_OTHER, GTS_MATCH, GTS_NMATCH, GTS_NBATCH };
     if(wave < nwaves)
     {
         double* __restrict__ acc = accs + wave*stride;
@@ -620,14 +619,10 @@ void assemble_splined_gather_kernel(DeviceProblem P, NormalDims nd, OpRef R, Ass
                 }
             }
             unsigned long long mm = __ballot(lr0 >= 0 || lr1 >= 0);
-#ifdef SPLG_TS
-            gn_match += __popcll(mm); gtq = clock64();
-#endif
+            gts.count(GTS_NMATCH, __popcll(mm)); gts.lap(GTS_OTHER);
             while(mm)
             {
-#ifdef SPLG_TS
-                gn_batch++;
-#endif
+                gts.count(GTS_NBATCH, 1);
                 // up to SPLG_BATCH observations: every load first, then the sums in order
                 double v[SPLG_BATCH][2][2], vc[SPLG_BATCH][2];
                 int    cs[SPLG_BATCH][2], csc[SPLG_BATCH], Kk[SPLG_BATCH];
@@ -715,9 +710,7 @@ void assemble_splined_gather_kernel(DeviceProblem P, NormalDims nd, OpRef R, Ass
                         }
                     }
             }
-#ifdef SPLG_TS
-            gts_match += clock64() - gtq;
-#endif
+            gts.lap(GTS_MATCH);
             };
             // (the first sub-box - almost always the only one - exactly as before there were any)
             passes_of(0, h0);
@@ -732,10 +725,16 @@ void assemble_splined_gather_kernel(DeviceProblem P, NormalDims nd, OpRef R, Ass
 #endif
         }
     }
-#ifdef SPLG_TS
-    if(lane == 0 && (wave == 0 || wave == 5) && window > 0 && (blk % 149 == 0))
-        printf("gather row %d wave %d: %lld cycles to the barrier, %lld of them in %d matches (%d batches)\n", blk, wave, clock64() - gts0, gts_match, gn_match, gn_batch);
-#endif
+    if constexpr(SPLG_TS)
+    {
+        // row of this launch's rows, wave of the waves; other + match: to the barrier. (Every launch of this kernel: the
+        //  knots' rows, the only ones that reported before, come here for spline orders past the knots' own kernel only)
+        if(stamps_reporter((int)blockIdx.x, (int)gridDim.x, lane == 0) && stamps_reporter(wave, nwaves))
+        {
+            gts.lap(GTS_OTHER);
+            gts.report("spl_gather", "other match nmatch nbatch", (int)blockIdx.x, (int)gridDim.x, wave, nwaves);
+        }
+    }
     __syncthreads();
     // the waves' copies, in wave order
     for(int c = t; c < stride; c += blockDim.x)

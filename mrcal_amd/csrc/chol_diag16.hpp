@@ -3,6 +3,7 @@
 // (the launch-per-panel Cholesky, whose 64 x 64 diagonal blocks are four of these)
 #pragma once
 #include "solver_device.hpp"
+#include "cycle_stamps.hpp"
 
 namespace mrcal_amd {
 
@@ -55,13 +56,13 @@ static inline bool chol_fits_lds(int n) { return n <= 200 && chol_lds_bytes(n) <
 template<class DstL>
 __device__ __forceinline__
 bool chol_factor_diag16(const int lane, const int jb, const double* __restrict__ rowL,
-                        double* __restrict__ X, double* __restrict__ cbuf, DstL dstL)
+                        double* __restrict__ X, double* __restrict__ cbuf, DstL dstL,
+                        const int iblock = 0, const int nblocks = 1 /* which call of the caller's this is: who reports (-DDIAG16_TS) */)
 {
     const int  r16  = lane & 15;
     const bool mine = lane < 16 && r16 < jb;
-#ifdef DIAG16_TS
-    const long long dts_in = clock64();
-#endif
+    CycleStamps<DIAG16_TS, 19> dts;
+    dts.mark();
     double row[CHOL_PB];
     {
         // unconditional loads, then select: no branches
@@ -111,30 +112,20 @@ bool chol_factor_diag16(const int lane, const int jb, const double* __restrict__
             for(int c = j + 1; c < CHOL_PB; c++) row[c] = fma(-lp[(j-1) & 1], Lc[(j-1) & 1][c], row[c]);
         }
     };
-#ifdef DIAG16_TS
-    long long dts[17];
-#define CHOL_COL(j) dts[j] = clock64(); __builtin_amdgcn_sched_barrier(0); column(IC(j));
-#else
     // A scheduling barrier between the columns: left alone, the compiler's scheduler treats the sixteen unrolled
     // columns as one block and interleaves them (sinking LDS reads to their uses, hoisting multiply-adds): 6160
     // cycles per call. With the columns kept apart, in the order written: see tools/exp/diag16_bench.hip
+    // (dts: empty but in the measurement build -DDIAG16_TS, which stamps every column)
 #ifndef CHOL_NO_COLUMN_BARRIER
-#define CHOL_COL(j) __builtin_amdgcn_sched_barrier(0); column(IC(j));
+#define CHOL_COL(j) dts.mark(); __builtin_amdgcn_sched_barrier(0); column(IC(j));
 #else
-#define CHOL_COL(j) column(IC(j));
-#endif
+#define CHOL_COL(j) dts.mark(); column(IC(j));
 #endif
     CHOL_COL(0)  CHOL_COL(1)  CHOL_COL(2)  CHOL_COL(3)  CHOL_COL(4)  CHOL_COL(5)  CHOL_COL(6)  CHOL_COL(7)
     CHOL_COL(8)  CHOL_COL(9)  CHOL_COL(10) CHOL_COL(11) CHOL_COL(12) CHOL_COL(13) CHOL_COL(14) CHOL_COL(15)
 #undef CHOL_COL
 #undef IC
-#ifdef DIAG16_TS
-    dts[16] = clock64();
-    if(lane == 0 && blockIdx.x == 0 && rowL != NULL && dts[0] % 997 == 0)
-        printf("diag16 entry to column 0: %lld; per column: %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld\n",
-               dts[0]-dts_in, dts[1]-dts[0], dts[2]-dts[1], dts[3]-dts[2], dts[4]-dts[3], dts[5]-dts[4], dts[6]-dts[5], dts[7]-dts[6], dts[8]-dts[7],
-               dts[9]-dts[8], dts[10]-dts[9], dts[11]-dts[10], dts[12]-dts[11], dts[13]-dts[12], dts[14]-dts[13], dts[15]-dts[14], dts[16]-dts[15]);
-#endif
+    dts.mark();
     // L through dstL (lanes 0..15), X into its block (lanes 16..31): one store per column for the whole wave
     {
         const bool isid = (lane >= 16 && lane < 32);
@@ -146,9 +137,12 @@ bool chol_factor_diag16(const int lane, const int jb, const double* __restrict__
             *dst = row[c];
         }
     }
-#ifdef DIAG16_TS
-    { const long long dts_out = clock64(); if(lane == 0 && blockIdx.x == 0 && dts_in % 997 == 0) printf("diag16 whole call %lld cycles\n", dts_out - dts_in); }
-#endif
+    dts.mark();
+    if constexpr(DIAG16_TS)
+    {
+        if(stamps_reporter(iblock, nblocks, lane == 0 && blockIdx.x == 0))
+            dts.report("diag16", "entry c0 c1 c2 c3 c4 c5 c6 c7 c8 c9 c10 c11 c12 c13 c14 c15 store", iblock, nblocks);
+    }
     return bad;
 }
 

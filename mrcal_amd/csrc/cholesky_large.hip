@@ -97,9 +97,11 @@ void lchol_diag_block(int n, double* __restrict__ M, int j0,
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const int r16 = lane & 15, kq = lane >> 4;
     const int nb = min(NB, n - j0);
-#ifdef LCH_TS
-    long long ts[6]; ts[0] = clock64();
-#endif
+    // (-DLCH_TS) marks: issue of the loads, pre-update, factorization, store; within the factorization, by laps: the
+    // diagonal blocks, (b), (c) and the barriers
+    CycleStamps<LCH_TS, 9> ts;
+    enum { TS_DIAG16 = 5, TS_B, TS_C, TS_BARRIERS };
+    ts.mark();
     if(t == 0) notpd = 0;
     // the block, padded with the identity (so that a short last panel factors too); with Xprev, this block's rows
     // of the previous panel and Xprev too (rows 64.. of A are free until the factorization starts: the identity is
@@ -134,9 +136,7 @@ void lchol_diag_block(int n, double* __restrict__ M, int j0,
             else              A[(NB + i)*LD + j] = (i == j) ? 1.0 : 0.0;
         }
     }
-#ifdef LCH_TS
-    ts[1] = clock64();
-#endif
+    ts.mark();
     if(Xprev != NULL)
     {
         double* __restrict__ Xp = A + NB*LD;
@@ -178,28 +178,21 @@ void lchol_diag_block(int n, double* __restrict__ M, int j0,
     }
     else __syncthreads();
 
-#ifdef LCH_TS
-    ts[2] = clock64();
-#endif
+    ts.mark();
     auto diag = [&](int base) __attribute__((always_inline))
     {
         double* __restrict__ rowL = &A[(base + r16)*LD + base];
         double* __restrict__ sink = cb + 128 + lane;
         // (the entries right of the diagonal are stored too, as zeros: nothing reads them)
         const bool bad = chol_factor_diag16(lane, CHOL_PB, rowL, Xb, cb,
-                                            [&](int c) -> double* { return (lane < 16) ? rowL + c : sink; });
+                                            [&](int c) -> double* { return (lane < 16) ? rowL + c : sink; },
+                                            base/CHOL_PB, NB/CHOL_PB);
         if(bad && lane == 0) notpd = 1;
     };
-#ifdef LCH_TS
-    long long tsd = 0, tsb = 0, tsc = 0, tsy = 0, tq = clock64(), tq1;
-#define LCH_TICK(w) { tq1 = clock64(); w += tq1 - tq; tq = tq1; }
-#else
-#define LCH_TICK(w)
-#endif
     if(wave == 0) diag(0);
-    LCH_TICK(tsd)
+    ts.lap(TS_DIAG16);
     __syncthreads();
-    LCH_TICK(tsy)
+    ts.lap(TS_BARRIERS);
 
 #pragma unroll 1
     for(int base = 0; base < NB; base += LCH_PB)
@@ -219,9 +212,9 @@ void lchol_diag_block(int n, double* __restrict__ M, int j0,
 #pragma unroll
             for(int v = 0; v < 4; v++) A[(m0 + 16*ti + kq + 4*v)*LD + base + r16] = acc[v];
         }
-        LCH_TICK(tsb)
+        ts.lap(TS_B);
         __syncthreads();
-        LCH_TICK(tsy)
+        ts.lap(TS_BARRIERS);
         // (c) tiles (ta, tb), tb <= ta, of rows m0.. x columns m0..63; (0,0) = the next diagonal block: wave 0
         {
             const int ntr = (NR - m0)/16, ntc = (NB - m0)/16;
@@ -246,16 +239,14 @@ void lchol_diag_block(int n, double* __restrict__ M, int j0,
 #pragma unroll
                 for(int v = 0; v < 4; v++) pc[4*v*LD] = acc[v];
             }
-            LCH_TICK(tsc)
+            ts.lap(TS_C);
             if(wave == 0 && m0 < NB) diag(m0);
-            LCH_TICK(tsd)
+            ts.lap(TS_DIAG16);
         }
         __syncthreads();
-        LCH_TICK(tsy)
+        ts.lap(TS_BARRIERS);
     }
-#ifdef LCH_TS
-    ts[3] = clock64();
-#endif
+    ts.mark();
     // L back into the matrix; X[i][k] = (L^-T)[k][i] = row 64+k, column i
     for(int idx = t; idx < NB*NB; idx += LCH_THREADS)
     {
@@ -264,10 +255,13 @@ void lchol_diag_block(int n, double* __restrict__ M, int j0,
         Linv[idx] = (j <= i) ? A[(NB + j)*LD + i] : 0.0;
     }
     if(t == 0 && notpd) atomicExch(status, 1);
-#ifdef LCH_TS
-    ts[4] = clock64();
-    if((t == 0 || t == 64*5) && (j0 == 128 || j0 == 640)) printf("lchol diag j0 %d t %d: issue loads %lld, pre-update %lld, factor %lld (diag16 %lld, b %lld, c %lld, barriers %lld), store %lld cycles\n", j0, t, ts[1]-ts[0], ts[2]-ts[1], ts[3]-ts[2], tsd, tsb, tsc, tsy, ts[4]-ts[3]);
-#endif
+    ts.mark();
+    if constexpr(LCH_TS)
+    {
+        // panel of panels, and wave of waves: wave 0 has the diagonal blocks' chain, the middle one has not
+        if(stamps_reporter(j0/NB, (n + NB - 1)/NB, lane == 0) && stamps_reporter(wave, LCH_NW))
+            ts.report("lchol_diag", "loads pre_update factor store diag16 b c barriers", j0/NB, (n + NB - 1)/NB, wave, LCH_NW);
+    }
 }
 // with_finish (round 5): the end of the trial step (step2_finish: one workgroup anyway) opens this launch instead of
 // being a launch of its own in front of it - 4.8 us of pure launch on every trial step of a big camera block; what it
@@ -333,9 +327,8 @@ void lchol_update_tile(int n, double* __restrict__ M, int j0, const double* __re
     const int nbt = (n - m0 + NB - 1)/NB;
     int bi, bj;
     lch_tile_of(q, nbt, &bi, &bj, incl00);
-#ifdef LCH_TS
-    const long long tt0 = clock64();
-#endif
+    CycleStamps<LCH_TS, 2> ts;
+    ts.mark();
     const bool rhs  = (bi == nbt), diag = (bi == bj);
     const int  i0   = rhs ? n : m0 + NB*bi, c0 = m0 + NB*bj;
     const int  ni   = rhs ? 1 : min(NB, n - i0), nc = min(NB, n - c0);     // rows of M in the two blocks
@@ -414,9 +407,16 @@ void lchol_update_tile(int n, double* __restrict__ M, int j0, const double* __re
             if(i < ni && c < nc && (!diag || c <= i)) M[(size_t)(i0 + i)*n + c0 + c] = tile[u][v] + d[v];
         }
     }
-#ifdef LCH_TS
-    if(t == 0 && (j0 == 64 || j0 == 576) && (q == 0 || q == 40)) printf("lchol tile j0 %d q %d: %lld cycles\n", j0, q, clock64() - tt0);
-#endif
+    if constexpr(LCH_TS)
+    {
+        // panel of panels, tile of the panel's tiles (lch_tile_of: the triangle's, then the right-hand side's row)
+        const int ntiles = nbt*(nbt + 1)/2 - (incl00 ? 0 : 1) + nbt;
+        if(stamps_reporter(j0/NB, (n + NB - 1)/NB, t == 0) && stamps_reporter(q, ntiles))
+        {
+            ts.mark();
+            ts.report("lchol_tile", "cycles", j0/NB, (n + NB - 1)/NB, q, ntiles);
+        }
+    }
 }
 // rows r0 .. r0+63 (up to the rhs row n) of a panel:  L21 = M21 L11^-T, in place
 __device__ __forceinline__

@@ -57,13 +57,9 @@ void schur_cholesky_solve_body(int n, const int* __restrict__ skip, int keep_fac
 
     __shared__ int notpd;
     if(t == 0) notpd = 0;
-#ifdef CHOL_TS
-    long long cts[64]; int ncts = 0;
-#define CTS() do { if(t == 0 && ncts < 64) cts[ncts++] = clock64(); } while(0)
-#else
-#define CTS()
-#endif
-    CTS();
+    StampSlots<CHOL_TS, 64> cts_slots;                      // (a mark per panel and step: an array, thread 0's)
+    CycleStamps<CHOL_TS, 64, true> cts(cts_slots, t == 0);
+    cts.mark();
 
     // The lower triangle into LDS. Wave w takes rows w, w+16, ..., 64 columns per
     // lane pass, and asks for ALL of it before it stores anything: S was written
@@ -141,7 +137,8 @@ void schur_cholesky_solve_body(int n, const int* __restrict__ skip, int keep_fac
         double* __restrict__ rowL = rowptr(j0 + (mine ? r16 : 0)) + j0;
         double* __restrict__ sink = cbuf + 128 + lane;
         const bool bad = chol_factor_diag16(lane, jb, rowL, Xs + p*CHOL_PB*CHOL_XLD, cbuf,
-                                            [&](int c) -> double* { return (mine && c <= r16) ? rowL + c : sink; });
+                                            [&](int c) -> double* { return (mine && c <= r16) ? rowL + c : sink; },
+                                            p, npanels);
         if(bad && lane == 0) notpd = 1;
     };
 
@@ -152,7 +149,7 @@ void schur_cholesky_solve_body(int n, const int* __restrict__ skip, int keep_fac
     // (p = -1: nothing but the factorization of the first diagonal block, so
     // that there is ONE copy of that long inlined code, not a cold one for the
     // first block and another for the rest)
-    CTS();
+    cts.mark();
     for(int p = -1; p < npanels; p++)
     {
         const int j0 = (p < 0) ? 0 : p*CHOL_PB;
@@ -193,7 +190,7 @@ void schur_cholesky_solve_body(int n, const int* __restrict__ skip, int keep_fac
             }
         }
         if(p >= 0) __syncthreads();
-        CTS();
+        cts.mark();
 
         // (c) trailing update with MFMA: C[i][c] -= sum_k L[i][k] L[c][k], k in the
         //     panel; rows m0..n (incl. the rhs row), columns m0..n-1, c <= i.
@@ -252,7 +249,7 @@ void schur_cholesky_solve_body(int n, const int* __restrict__ skip, int keep_fac
             }
         }
         __syncthreads();
-        CTS();
+        cts.mark();
     }
     if(t == 0 && notpd) atomicExch(status, 1);
 
@@ -307,7 +304,7 @@ void schur_cholesky_solve_body(int n, const int* __restrict__ skip, int keep_fac
             z[i] -= acc;
         }
     };
-    CTS();
+    cts.mark();
     // (n = 0 - a solve without camera variables - has no panel: back_diag(-1) would read and WRITE 16 doubles in
     //  front of the triangle, i.e. this kernel's own flags in LDS; found when a change of the LDS layout made
     //  such solves report "not positive definite" at random.
@@ -315,7 +312,7 @@ void schur_cholesky_solve_body(int n, const int* __restrict__ skip, int keep_fac
     //  the sweep costs is its chain of LDS round trips, not the barrier)
     if(wave == 0 && npanels > 0) back_diag(npanels-1);
     __syncthreads();
-    CTS();
+    cts.mark();
     // (round 6) Wave 0's chain through the full panels stays in REGISTERS: d_p, which lanes 0..15 have just made, reaches
     // the sixteen dot products that update panel p-1's entries by v_readlane instead of through an LDS write and read,
     // and so do the updated entries on their way into X_{p-1}'s product. The same products and sums in the same order
@@ -365,7 +362,7 @@ void schur_cholesky_solve_body(int n, const int* __restrict__ skip, int keep_fac
         else
             for(int i = t - 64; i < j0 - CHOL_PB; i += nt - 64) back_update(i, j0, jb);
         __syncthreads();
-        CTS();
+        cts.mark();
     }
     // r <- -d ; keep the factor for later solves (uncertainty, solve_xt_JtJ_bt)
     for(int i = t; i < n; i += nt) r[i] = -z[i];
@@ -375,11 +372,10 @@ void schur_cholesky_solve_body(int n, const int* __restrict__ skip, int keep_fac
             const int i = idx / n, j = idx - i*n;
             if(j <= i) S[(size_t)i*n + j] = rowptr(i)[j];
         }
-    CTS();
+    cts.mark();
     if constexpr(FINISH != 0) { if(t == 0) step2_chol_done(sd, notpd != 0); }
-#ifdef CHOL_TS
-    if(t == 0) { printf("chol ts (load | diag0 | b,c per panel ... | backward | store):"); for(int i=1;i<ncts;i++) printf(" %lld", cts[i]-cts[i-1]); printf("\n"); }
-#endif
+    // (after the two named: b, c of every panel, the backward sweep's steps, the store)
+    if constexpr(CHOL_TS) { if(t == 0) cts.report("chol_lds", "load diag0", 0, 1); }
 }
 
 template<int FINISH>

@@ -36,6 +36,7 @@
 #include "kernels.hpp"
 #include "dogleg_choose.hpp"
 #include "kernels_shared.hpp"
+#include "cycle_stamps.hpp"
 
 namespace mrcal_amd {
 
@@ -736,13 +737,29 @@ void gram_copy_fused(double (&acc)[NM], const double* __restrict__ tile, const u
 #else
 #define ABLATE(P, bits) 0
 #endif
-#ifdef BOARD_TS
-#define TS(i) do { ts[i] = clock64(); } while(0)
-#define TSACC(i, t0) do { const long long _t = clock64(); ts[i] += _t - (t0); (t0) = _t; } while(0)
-#else
-#define TS(i)
-#define TSACC(i, t0)
-#endif
+// the board kernel's stamps (-DBOARD_TS): three marks - the wave's start, the end of its start-up, its end - and behind
+// them the laps of the four phases
+enum { BTS_PROJECTION = 3, BTS_TILE_WRITE, BTS_COPY_OUT, BTS_GRAM, BTS_N };
+
+// ten words per observation into DeviceProblem::debug_ts (all 1600 waves of a launch: more than a print can carry):
+// start, end of startup, [projection, tile write, copy-out, Gram] cycles, end, hw id, the chip-wide clock at start and end
+// (a template: the shipped DeviceProblem has no debug_ts, and the shipped kernel no call of this)
+template<class Problem, class Stamps>
+__device__ __forceinline__
+void board_stamps_store(const Problem& P, const Stamps& ts, int iobs, int lane, long long wall0)
+{
+    if(P.debug_ts == NULL || lane != 0) return;
+    long long* o = P.debug_ts + (size_t)iobs*10;
+    unsigned hwid;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+    unsigned xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    o[0] = ts.slot(0); o[1] = ts.slot(1);
+    o[2] = ts.slot(BTS_PROJECTION); o[3] = ts.slot(BTS_TILE_WRITE); o[4] = ts.slot(BTS_COPY_OUT); o[5] = ts.slot(BTS_GRAM);
+    o[6] = ts.slot(2);
+    o[7] = (long long)hwid | ((long long)(xcc & 0xf) << 32);
+    o[8] = wall0; o[9] = ts.wall();
+}
 
 // The copy-out invariants of a lane (copy_out_full) when every variable group
 // is optimized: k and the CSR -> tile column map are compile-time constants
@@ -808,11 +825,9 @@ void board_observation(const DeviceProblem& P,
     constexpr bool ROWL = ALLOPT;
 
     const int lane = threadIdx.x;
-#ifdef BOARD_TS
-    long long ts[8] = {0,0,0,0,0,0,0,0};
-    const long long wall0 = (long long)wall_clock64();      // (100 MHz, the same clock on every XCD; clock64() is per XCD)
-    TS(0);
-#endif
+    CycleStamps<BOARD_TS, BTS_N> ts;
+    const long long wall0 = ts.wall();      // (100 MHz, the same clock on every XCD; clock64() is per XCD)
+    ts.mark();
     const int NPTS = P.W*P.H;
 
     // FIRST: request everything whose address depends on the observation index
@@ -942,10 +957,7 @@ void board_observation(const DeviceProblem& P,
     __builtin_amdgcn_wave_barrier();   // obs_lds is complete (one wave: the LDS is in order)
     if(ABLATE(P, 16)) { if(obs_lds[lane] + intr[0] + warp0 + jp[0] == 12345.678) x[0] = 1.0; return; }
 
-#ifdef BOARD_TS
-    TS(1);
-    long long tcur = ts[1];
-#endif
+    ts.mark();
     for(int pt0 = 0; pt0 < NPTS; pt0 += 64)
     {
         const int  pt    = pt0 + (ROWL ? board_lane_corner(lane) : lane);
@@ -1097,7 +1109,7 @@ void board_observation(const DeviceProblem& P,
         }
 
         if(!WITH_J) continue;
-        TSACC(2, tcur);     // projection + rows
+        ts.lap(BTS_PROJECTION);     // projection + rows
 
         // The two halves of the pass (its first and its second 32 corners) go through the 64-row tile one after
         // the other. All 64 lanes write each of them, one row each: lanes 0..31 the x rows of the half's corners,
@@ -1156,7 +1168,7 @@ void board_observation(const DeviceProblem& P,
                 }
             }
             __builtin_amdgcn_wave_barrier();
-            TSACC(3, tcur);     // tile write
+            ts.lap(BTS_TILE_WRITE);
 
             // stream the half-tile out: rows row0 .. row0+nrows of the observation
             gdouble* __restrict__ out = Jv + m.i_nnz0 + (size_t)(2*(pt0 + 32*h))*k;
@@ -1175,7 +1187,7 @@ void board_observation(const DeviceProblem& P,
                     if(kfull) gram_copy_fused<false,STORE_J,ROWL,NBLK,KFULL,  KS>(acc, tile, gram_full, out, co_A0, co_A1, co_B0, co_B1, co_gofs, rs, nrows);
                     else      gram_copy_fused<false,STORE_J,ROWL,NBLK,KFULL-6,KS>(acc, tile, gram_full, out, co_A0, co_A1, co_B0, co_B1, co_gofs, rs, nrows);
                 }
-                TSACC(5, tcur);
+                ts.lap(BTS_GRAM);
                 continue;
             }
             if(STORE_J && !ABLATE(P, 1))
@@ -1215,7 +1227,7 @@ void board_observation(const DeviceProblem& P,
                 }
             }
 
-            TSACC(4, tcur);     // copy-out
+            ts.lap(BTS_COPY_OUT);
             if(WITH_GRAM && !ABLATE(P, 2))
             {
                 // G += Tt T over this half. 4 tile rows per k-step; the rows
@@ -1235,10 +1247,8 @@ void board_observation(const DeviceProblem& P,
                     gram_step_ops<NBLK>(acc, rd);
                 }
             }
-#ifdef BOARD_TS
-            { const double dep = acc[0]; asm volatile("" :: "v"(dep)); }
-#endif
-            TSACC(5, tcur);     // Gram
+            if constexpr(BOARD_TS) { const double dep = acc[0]; asm volatile("" :: "v"(dep)); }
+            ts.lap(BTS_GRAM);
         }
     }
 
@@ -1249,21 +1259,8 @@ void board_observation(const DeviceProblem& P,
         for(int mm=0;mm<NM;mm++)
             g[mm*64 + lane] = acc[mm];
     }
-#ifdef BOARD_TS
-    TS(6);
-    if(P.debug_ts != NULL && lane == 0)
-    {
-        long long* o = P.debug_ts + (size_t)iobs*10;
-        // start, end of startup, [projection, tile write, copy-out, Gram] cycles, end, hw id
-        unsigned hwid;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        o[0] = ts[0]; o[1] = ts[1]; o[2] = ts[2]; o[3] = ts[3]; o[4] = ts[4]; o[5] = ts[5]; o[6] = ts[6];
-        o[7] = (long long)hwid | ((long long)(xcc & 0xf) << 32);
-        o[8] = wall0; o[9] = (long long)wall_clock64();
-    }
-#endif
+    ts.mark();
+    if constexpr(BOARD_TS) board_stamps_store(P, ts, iobs, lane, wall0);
 }
 
 template<int PROJ, int NDIST, bool WITH_J, bool WITH_GRAM, bool ALLOPT = false, bool STORE_J = true>

@@ -1,6 +1,7 @@
 // The Schur complement onto the camera block: block elimination, the reduction, the SYRK kernels
 // (round 6: one of the translation units solver_kernels.hip was cut into; solver_device.hpp has what they share)
 #include "solver_device.hpp"
+#include "cycle_stamps.hpp"
 #include "solver_kernel_decls.hpp"
 
 namespace mrcal_amd {
@@ -390,9 +391,8 @@ void schur_syrk_mfma_kernel(NormalDims nd, const int* __restrict__ skip, int e_l
 
     syrk_d4 acc  = {0.0, 0.0, 0.0, 0.0};
     syrk_d4 accr = {0.0, 0.0, 0.0, 0.0};
-#ifdef ASM_TS
-    const long long sts0 = clock64();
-#endif
+    CycleStamps<SYRK_TS, 3> sts;
+    sts.mark();
     for(int e0 = e_begin; e0 < e_end; e0 += 4*SYRK_UNROLL)
     {
         double a[SYRK_UNROLL], b[SYRK_UNROLL], yy[SYRK_UNROLL];
@@ -429,9 +429,15 @@ void schur_syrk_mfma_kernel(NormalDims nd, const int* __restrict__ skip, int e_l
 #pragma unroll
         for(int v=0;v<4;v++) rpart[kk + 4*v] = accr[v];
     }
-#ifdef ASM_TS
-    if(lane == 0 && (px == 1 || px == 44) && (sy == 0 || sy == 40)) printf("syrk ts px=%d sy=%d block=(%d,%d) rows=%d dur=%lld\n", px, sy, blockIdx.x, blockIdx.y, e_end-e_begin, clock64()-sts0);
-#endif
+    if constexpr(SYRK_TS)
+    {
+        // tile pair of the pairs, slice of the slices
+        if(stamps_reporter(px, npairs, lane == 0) && stamps_reporter(sy, nslices))
+        {
+            sts.mark(); sts.count(2, e_end - e_begin);
+            sts.report("syrk_dense", "dur rows", px, npairs, sy, nslices);
+        }
+    }
 }
 
 // The same for big camera blocks (splined models: 76 x 76 tiles), where the
@@ -588,13 +594,11 @@ void schur_syrk_sparse_kernel(NormalDims nd, const int* __restrict__ skip, int e
     for(int q = 0; q < SYRK_STRIP; q++) acc[q] = syrk_d4{0.0, 0.0, 0.0, 0.0};
     syrk_d4 accr = {0.0, 0.0, 0.0, 0.0};
     unsigned touched = 0;       // bit q: a block of this slice touched B tile q of the strip (and the A tile)
-#ifdef SYRK_TS
-    long long sts_scan = 0, sts_blocks = 0, sts_t0 = clock64(), sts_t1; int sts_live = 0, sts_mma = 0;
-    const long long sts_begin = sts_t0, sts_wall0 = wall_clock64();
-#define SYRK_TICK(w) { sts_t1 = clock64(); w += sts_t1 - sts_t0; sts_t0 = sts_t1; }
-#else
-#define SYRK_TICK(w)
-#endif
+    // (-DSYRK_TS) laps: the scan of the occupancy bits, the blocks, what comes after them; the blocks that count and
+    // the B tiles they touch; the chip-wide clock at the start
+    CycleStamps<SYRK_TS, 6> sts;
+    enum { STS_SCAN, STS_BLOCKS, STS_REST, STS_LIVE, STS_BTILES, STS_WALL0 };
+    sts.count(STS_WALL0, sts.wall());
     if(e_begin < e_end)
     {
         auto block_of   = [&](int e) { return (e < 6*nd.Nfb) ? e/6 : nd.Nfb + (e - 6*nd.Nfb)/3; };
@@ -668,10 +672,8 @@ void schur_syrk_sparse_kernel(NormalDims nd, const int* __restrict__ skip, int e
                 if(wa & mi) m |= 16u;
             }
             unsigned long long live = __ballot((m & 16u) && (diag || (m & 15u)));
-            SYRK_TICK(sts_scan)
-#ifdef SYRK_TS
-            sts_live += __popcll(live);
-#endif
+            sts.lap(STS_SCAN);
+            sts.count(STS_LIVE, __popcll(live));
             while(live)
             {
                 // fill the ring, then spend it
@@ -685,9 +687,7 @@ void schur_syrk_sparse_kernel(NormalDims nd, const int* __restrict__ skip, int e
                         fetch(b_first + nslices*(SYRK_SPARSE_WAVES*(base + bit) + wave), mb, ring[d]);
                         nring = d + 1;
                         touched |= mb;
-#ifdef SYRK_TS
-                        sts_mma += __popc(mb & 15u);
-#endif
+                        sts.count(STS_BTILES, __popc(mb & 15u));
                     }
                 if(nring == SYRK_DEPTH)
                 {
@@ -696,11 +696,11 @@ void schur_syrk_sparse_kernel(NormalDims nd, const int* __restrict__ skip, int e
                     nring = 0;
                 }
             }
-            SYRK_TICK(sts_blocks)
+            sts.lap(STS_BLOCKS);
         }
 #pragma unroll
         for(int d = 0; d < SYRK_DEPTH; d++) if(d < nring) apply(ring[d]);
-        SYRK_TICK(sts_blocks)
+        sts.lap(STS_BLOCKS);
     }
     // the waves' sums, in wave order
     if(SYRK_SPARSE_WAVES > 1)
@@ -754,11 +754,15 @@ void schur_syrk_sparse_kernel(NormalDims nd, const int* __restrict__ skip, int e
 #pragma unroll
         for(int v=0;v<4;v++) rpart[kk + 4*v] = accr[v];
     }
-#ifdef SYRK_TS
-    if(lane == 0 && sy == 3 && (px % 97 == 0))
-        printf("syrk strip %d (tile row %d, from tile %d) slice %d: wall %lld, whole %lld cycles: scan %lld, blocks %lld (%d live, %d B tiles)\n",
-               px, bi, bj0, sy, sts_wall0, clock64() - sts_begin, sts_scan, sts_blocks, sts_live, sts_mma);
-#endif
+    if constexpr(SYRK_TS)
+    {
+        // strip of the strips, slice of the slices (the whole workgroup: scan + blocks + rest)
+        if(stamps_reporter(px, (int)gridDim.x, lane == 0) && stamps_reporter(sy, nslices))
+        {
+            sts.lap(STS_REST);
+            sts.report("syrk_sparse", "scan blocks rest live btiles wall0", px, (int)gridDim.x, sy, nslices);
+        }
+    }
 }
 
 // S, r of the point being eliminated (reduction of the SYRK's slots: this rank's

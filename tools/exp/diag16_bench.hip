@@ -1,6 +1,6 @@
 // chol_factor_diag16() alone: one wave factoring a 16 x 16 block held in LDS, N times, cycles per call.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I mrcal_amd/csrc -o /tmp/diag16_bench tools/exp/diag16_bench.hip
-#include "../../mrcal_amd/csrc/solver_kernels.hip"
+#include "../../mrcal_amd/csrc/chol_diag16.hpp"
 #include <cstdio>
 #include <cmath>
 __global__ __launch_bounds__(64)

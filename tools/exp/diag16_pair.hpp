@@ -1,5 +1,5 @@
 // EXPERIMENT, not part of the product (round 4; measured and dropped: profiles/r04_diag16_variants.txt).
-// Included by tools/exp/diag16_pair_bench.hip behind csrc/solver_kernels.hip.
+// Included by tools/exp/diag16_pair_bench.hip behind csrc/chol_diag16.hpp.
 namespace mrcal_amd {
 // The same block by TWO waves (round 4). One wave's issue rate is what chol_factor_diag16() is bound by (250 cycles a
 // column for ~30 vector instructions, of which the pivot chain - v_rsq_f64, two Newton steps, the scaling - is 12 that

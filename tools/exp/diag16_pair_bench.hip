@@ -2,7 +2,7 @@
 // (L and X = L^-T).   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I mrcal_amd/csrc -o /tmp/diag16_pair_bench tools/exp/diag16_pair_bench.hip
 __device__ double g_pair_dbg[64];
 #define CHOL_PAIR_DEBUG g_pair_dbg
-#include "../../mrcal_amd/csrc/solver_kernels.hip"
+#include "../../mrcal_amd/csrc/chol_diag16.hpp"
 #include "diag16_pair.hpp"
 #include <cstdio>
 #include <cmath>

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""three trial steps at the metric's size, for builds with -DASM_TS / -DCHOL_TS (kernel-internal cycle stamps on stdout; dev tool)"""
+"""three trial steps at the metric's size, for builds with -DASM_TS / -DSYRK_TS / -DCHOL_TS (kernel-internal cycle stamps on
+stdout, one `ts ...` line a report: pipe into tools/cycle_stamps.py; dev tool).  usage: probe_asm_ts.py [steps]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mrcal_amd
