@@ -82,6 +82,7 @@ from .stereo import (rectified_resolution, rectified_system, rectification_maps,
                      stereo_matching_sgm, StereoMatcherSGM, STEREO_SGM_DISPARITY_SCALE,
                      filter_speckles, SpeckleFilter, stereo_point_cloud, StereoPointCloud)
 from .equalization import equalize_clahe, equalize_stretch, ImageEqualizer
+from .smoothing import smooth_gaussian, smooth_weights, antialias_sigma, ImageSmoother
 from .image_transforms import (scale_focal__best_pinhole_fit, pinhole_model_for_reprojection, image_transformation_map,
                                transform_image)
 from .utils import (sample_imager, sample_imager_unproject, write_point_cloud_as_ply, mapping_file_framenocameraindex,

@@ -25,7 +25,7 @@ for a in "$@"; do
 done
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=on -Wall -Wno-unused-function -Wno-unused-value -Wno-unused-result $DEV"
-SOURCES="kernels.hip splined_kernels.hip project_kernels.hip cholesky_large.hip assembly_splined.hip schur.hip assembly.hip step.hip factorization_solve.hip cholesky_lds.hip uncertainty.hip noise_propagation.hip projection_uncertainty.hip projection_diff.hip triangulation.hip rectification.hip match_feature.hip stereo_sgm.hip speckle_filter.hip point_cloud.hip chessboard.hip equalize.hip regional_stats.hip valid_region.hip lensfit.hip
+SOURCES="kernels.hip splined_kernels.hip project_kernels.hip cholesky_large.hip assembly_splined.hip schur.hip assembly.hip step.hip factorization_solve.hip cholesky_lds.hip uncertainty.hip noise_propagation.hip projection_uncertainty.hip projection_diff.hip triangulation.hip rectification.hip match_feature.hip stereo_sgm.hip speckle_filter.hip point_cloud.hip chessboard.hip equalize.hip smooth.hip regional_stats.hip valid_region.hip lensfit.hip
          problem.cpp problem_plan.cpp solver_plan.cpp camblock_route.cpp solver.cpp cabi_layout.cpp factorization.cpp unproject.cpp comm.cpp cameramodel_io.cpp stereo_geometry.cpp chessboard_grid.cpp region_outline.cpp"
 # (at most 16 by default: a build box may report many more cores than a command is given)
 JOBS=${JOBS:-$(( $(nproc) < 16 ? $(nproc) : 16 ))}

@@ -33,6 +33,7 @@
 #include "stereo_sgm.hpp"
 #include "speckle_plan.hpp"
 #include "equalize.hpp"
+#include "smooth.hpp"
 #include "stereo_range_device.hpp"
 #include "point_cloud.hpp"
 
@@ -452,14 +453,20 @@ bool remap_device(const void* d_src, int W, int H, int C, int dtype, const float
 }
 namespace {
 
-// a raw image of the host on the device, equalized there if that is asked for (equalize.hip): *d_image, of *dtype_image
-// (stretch makes uint8 of uint16). Everything is tmp's, and queued in the NULL stream
-bool upload_equalized(DeviceBuffers& tmp, const EqualizeParams& equalization, const void* image, int W, int H, int dtype,
-                      const void** d_image, int* dtype_image)
+// a raw image of the host on the device, equalized there if that is asked for (equalize.hip) and then filtered if that
+// is (smooth.hip): *d_image, of *dtype_image (stretch makes uint8 of uint16). *d_unfiltered, if it is wanted: the image
+// as it was before the filter. Everything is tmp's, and queued in the NULL stream
+bool upload_equalized(DeviceBuffers& tmp, const EqualizeParams& equalization, const SmoothParams& antialias,
+                      const void* image, int W, int H, int dtype,
+                      const void** d_image, int* dtype_image, const void** d_unfiltered = NULL)
 {
     uint8_t* d_src = NULL;
-    return tmp.upload(&d_src, (const uint8_t*)image, (size_t)W*H*dtype_size(dtype)) &&
-           equalize_resident(tmp, tmp, equalization, d_src, W, H, dtype, d_image, dtype_image);
+    const void* d_equalized = NULL;
+    if(!(tmp.upload(&d_src, (const uint8_t*)image, (size_t)W*H*dtype_size(dtype)) &&
+         equalize_resident(tmp, tmp, equalization, d_src, W, H, dtype, &d_equalized, dtype_image)))
+        return false;
+    if(d_unfiltered != NULL) *d_unfiltered = d_equalized;
+    return smooth_resident(tmp, antialias, d_equalized, W, H, *dtype_image, d_image);
 }
 
 // the images an equalization takes: false, and why
@@ -473,18 +480,29 @@ bool equalization_arguments_ok(const EqualizeParams& equalization, int width, in
     return false;
 }
 
-// host image -> remapped host image through a map that is on the device already. equalization: of the image, on the
-// device, before the remap; out is then of the equalized type
+// the images the anti-aliasing filter takes, of the type the equalization leaves them in: false, and why
+bool antialias_arguments_ok(const SmoothParams& antialias, const EqualizeParams& equalization, int width, int height, int channels, int dtype)
+{
+    if(smooth_is_off(antialias)) return true;
+    if(channels != 1) { set_error("smooth(): an image that is filtered is grey, not of %d channels", channels); return false; }
+    std::string why;
+    if(smooth_params_ok(&why, width, height, equalize_dtype_out(equalization.method, dtype), antialias)) return true;
+    set_error("%s", why.c_str());
+    return false;
+}
+
+// host image -> remapped host image through a map that is on the device already. equalization, antialias: of the image,
+// on the device, before the remap; out is then of the equalized type
 bool remap_host_image(void* out, const void* image, int W, int H, int C, int dtype, const float* d_map, int Nout,
                       int interp, int border_mode, const double* border_value,
-                      const EqualizeParams& equalization = EqualizeParams())
+                      const EqualizeParams& equalization = EqualizeParams(), const SmoothParams& antialias = SmoothParams())
 {
     DeviceBuffers tmp;
-    if(equalization.method != EQUALIZE_METHOD_NONE)
+    if(equalization.method != EQUALIZE_METHOD_NONE || !smooth_is_off(antialias))
     {
         const void* d_image = NULL; uint8_t* d_out = NULL;
         int dtype_image = dtype;
-        if(!upload_equalized(tmp, equalization, image, W, H, dtype, &d_image, &dtype_image)) return false;
+        if(!upload_equalized(tmp, equalization, antialias, image, W, H, dtype, &d_image, &dtype_image)) return false;
         const size_t nout = (size_t)Nout*C*dtype_size(dtype_image);
         if(!(border_mode == MRCAL_AMD_BORDER_TRANSPARENT ? tmp.upload(&d_out, (const uint8_t*)out, nout) : tmp.alloc(&d_out, nout)))
             return false;
@@ -587,6 +605,8 @@ struct mrcal_amd_rectification
     double                   fxycxy[4] = { 0., 0., 0., 0. };
     // of every raw image, between its upload and the remap (equalize.hip); the method NONE: none
     EqualizeParams           equalization;
+    // ... and after that (smooth.hip); both sigmas 0: none
+    SmoothParams             antialias;
     ~mrcal_amd_rectification() { mrcal_amd_point_cloud_destroy(cloud); }
 };
 
@@ -687,8 +707,11 @@ bool mrcal_amd_rectification_rectify(mrcal_amd_rectification_t* r, void* out0, v
     if(!equalization_arguments_ok(r->equalization, width0, height0, channels, dtype) ||
        !equalization_arguments_ok(r->equalization, width1, height1, channels, dtype))
         return false;
-    return remap_host_image(out0, image0, width0, height0, channels, dtype, r->map[0], r->W*r->H, interpolation, border_mode, border_value, r->equalization)
-        && remap_host_image(out1, image1, width1, height1, channels, dtype, r->map[1], r->W*r->H, interpolation, border_mode, border_value, r->equalization);
+    if(!antialias_arguments_ok(r->antialias, r->equalization, width0, height0, channels, dtype) ||
+       !antialias_arguments_ok(r->antialias, r->equalization, width1, height1, channels, dtype))
+        return false;
+    return remap_host_image(out0, image0, width0, height0, channels, dtype, r->map[0], r->W*r->H, interpolation, border_mode, border_value, r->equalization, r->antialias)
+        && remap_host_image(out1, image1, width1, height1, channels, dtype, r->map[1], r->W*r->H, interpolation, border_mode, border_value, r->equalization, r->antialias);
 }
 
 bool mrcal_amd_rectification_set_equalization(mrcal_amd_rectification_t* r, const mrcal_amd_equalize_params_t* params)
@@ -702,6 +725,18 @@ bool mrcal_amd_rectification_set_equalization(mrcal_amd_rectification_t* r, cons
     if(!equalize_params_ok(&why, p.tiles_x > 0 ? p.tiles_x : 1, p.tiles_y > 0 ? p.tiles_y : 1, MRCAL_AMD_IMAGE_UINT8, p))
     { set_error("%s", why.c_str()); return false; }
     r->equalization = p;
+    return true;
+}
+
+bool mrcal_amd_rectification_set_antialias(mrcal_amd_rectification_t* r, const mrcal_amd_smooth_params_t* params)
+{
+    last_error_string().clear();
+    if(!rectification_given(r)) return false;
+    const SmoothParams p = smooth_params_of(params);
+    // (what can be refused without an image; the rest when one comes)
+    std::string why;
+    if(!smooth_is_off(p) && !smooth_params_ok(&why, 1, 1, MRCAL_AMD_IMAGE_UINT8, p)) { set_error("%s", why.c_str()); return false; }
+    r->antialias = p;
     return true;
 }
 
@@ -741,6 +776,9 @@ bool mrcal_amd_rectification_disparity_filtered(mrcal_amd_rectification_t* r,
     if(!equalization_arguments_ok(r->equalization, width0, height0, 1, dtype) ||
        !equalization_arguments_ok(r->equalization, width1, height1, 1, dtype))
         return false;
+    if(!antialias_arguments_ok(r->antialias, r->equalization, width0, height0, 1, dtype) ||
+       !antialias_arguments_ok(r->antialias, r->equalization, width1, height1, 1, dtype))
+        return false;
     const int dtype_matched = equalize_dtype_out(r->equalization.method, dtype);
     mrcal_amd_stereo_sgm_t* m = mrcal_amd_stereo_sgm_create(r->W, r->H, dtype_matched, params);
     if(m == NULL) return false;
@@ -754,7 +792,7 @@ bool mrcal_amd_rectification_disparity_filtered(mrcal_amd_rectification_t* r,
         for(int i = 0; i < 2 && ok; i++)
         {
             const void* d_src = NULL; int dtype_src = dtype;
-            ok = upload_equalized(tmp, r->equalization, image[i], W[i], H[i], dtype, &d_src, &dtype_src) &&
+            ok = upload_equalized(tmp, r->equalization, r->antialias, image[i], W[i], H[i], dtype, &d_src, &dtype_src) &&
                  remap_device(d_src, W[i], H[i], 1, dtype_src, r->map[i], sgm_device_image(m, i), r->W*r->H,
                               MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT, NULL);
         }
@@ -805,6 +843,9 @@ bool mrcal_amd_rectification_point_cloud_of_images(mrcal_amd_rectification_t* r,
     if(!equalization_arguments_ok(r->equalization, width0, height0, 1, dtype) ||
        !equalization_arguments_ok(r->equalization, width1, height1, 1, dtype))
         return false;
+    if(!antialias_arguments_ok(r->antialias, r->equalization, width0, height0, 1, dtype) ||
+       !antialias_arguments_ok(r->antialias, r->equalization, width1, height1, 1, dtype))
+        return false;
     const int dtype_matched = equalize_dtype_out(r->equalization.method, dtype);
     mrcal_amd_point_cloud_t* c = rectification_cloud(r);
     if(c == NULL) return false;
@@ -826,12 +867,12 @@ bool mrcal_amd_rectification_point_cloud_of_images(mrcal_amd_rectification_t* r,
         DeviceBuffers tmp;
         for(int i = 0; i < 2 && ok; i++)
         {
-            const void* d_src = NULL; int dtype_src = dtype;
-            ok = upload_equalized(tmp, r->equalization, image[i], W[i], H[i], dtype, &d_src, &dtype_src) &&
+            const void *d_src = NULL, *d_unfiltered = NULL; int dtype_src = dtype;
+            ok = upload_equalized(tmp, r->equalization, r->antialias, image[i], W[i], H[i], dtype, &d_src, &dtype_src, &d_unfiltered) &&
                  remap_device(d_src, W[i], H[i], 1, dtype_src, r->map[i], sgm_device_image(m, i), r->W*r->H,
                               MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT, NULL);
-            // colours from image0 itself: from the equalized one, where it lies
-            if(ok && i == 0 && equalized_colors) { d_color = d_src; p.image_dtype = dtype_src; }
+            // colours from image0 itself: from the equalized one, where it lies, as it was before the anti-aliasing filter
+            if(ok && i == 0 && equalized_colors) { d_color = d_unfiltered; p.image_dtype = dtype_src; }
         }
         const int16_t* d_disparity = NULL;
         // (the cloud waits for its launches, and so for these: the images and the matcher may go when this returns)
@@ -880,14 +921,25 @@ bool mrcal_amd_transform_image(void* out, const void* image, int width, int heig
                                const float* mapxy, int width_out, int height_out,
                                int interpolation, int border_mode, const double* border_value)
 {
+    return mrcal_amd_transform_image_smoothed(out, image, width, height, channels, dtype, mapxy, width_out, height_out,
+                                              interpolation, border_mode, border_value, NULL);
+}
+
+bool mrcal_amd_transform_image_smoothed(void* out, const void* image, int width, int height, int channels, int dtype,
+                                        const float* mapxy, int width_out, int height_out,
+                                        int interpolation, int border_mode, const double* border_value,
+                                        const mrcal_amd_smooth_params_t* params)
+{
     last_error_string().clear();
     if(!remap_arguments_ok(width, height, channels, dtype, width_out, height_out, interpolation, border_mode)) return false;
+    const SmoothParams antialias = smooth_params_of(params);
+    if(!antialias_arguments_ok(antialias, EqualizeParams(), width, height, channels, dtype)) return false;
     if(!have_device()) return false;
     DeviceBuffers tmp;
     float* d_map = NULL;
     if(!tmp.upload(&d_map, mapxy, (size_t)2*width_out*height_out)) return false;
     return remap_host_image(out, image, width, height, channels, dtype, d_map, width_out*height_out,
-                            interpolation, border_mode, border_value);
+                            interpolation, border_mode, border_value, EqualizeParams(), antialias);
 }
 
 bool mrcal_amd_stereo_range_sparse(double* range, double* p, const double* disparity, const mrcal_point2_t* qrect0,

@@ -160,7 +160,7 @@ Reference: mrcal.image_transformation_map()"""
     return mapxy
 
 
-def transform_image(image, mapxy, *, out=None, borderMode=None, borderValue=0, interpolation=None):
+def transform_image(image, mapxy, *, out=None, borderMode=None, borderValue=0, interpolation=None, antialias=None):
     """out[i,j] = image at the pixel mapxy[i,j] = (x,y): (H,W) or (H,W,3), like the image
 
 image: uint8, uint16 or float32, (H_in, W_in) or (H_in, W_in, 3). mapxy: float32 (H, W, 2), from
@@ -169,9 +169,13 @@ borderMode: None, 'constant' or 0: a neighbour outside the image counts as borde
 channel), and so does a pixel whose map entry is not finite; 'transparent' or 5: a pixel with any neighbour outside
 keeps what 'out' had (zeros if no 'out' is given). Integer images are rounded to nearest and saturate.
 The interpolation is exact bilinear interpolation in float32: cv2.remap(), which the reference calls, rounds the map
-to 1/32 pixel first, and that is not imitated. Reference: mrcal.transform_image()"""
+to 1/32 pixel first, and that is not imitated. Reference: mrcal.transform_image()
+antialias: None, 'auto', a sigma or (sigma_x, sigma_y): the image (grayscale, uint8 or uint16 then) is filtered on the
+device between its upload and the remap (smooth_gaussian()), the same bits as filtering it first. 'auto':
+antialias_sigma(mapxy); where that is 0, and for None, nothing of it runs"""
     from . import _lib, _api
     from .stereo import _image_arguments, _remap_modes, _border_values, _output_array
+    from .smoothing import antialias_params, antialias_sigma
     if not isinstance(image, np.ndarray): raise Exception("'image' must be a numpy array")
     if not isinstance(mapxy, np.ndarray): raise Exception("'mapxy' must be a numpy array")
     a, w, h, channels, dtype = _image_arguments(image)
@@ -182,8 +186,13 @@ to 1/32 pixel first, and that is not imitated. Reference: mrcal.transform_image(
     H, W = mapxy.shape[:2]
     o, ret = _output_array(out, (H, W) if channels == 1 else (H, W, 3), a.dtype, border == 5)
     m = np.ascontiguousarray(mapxy)
-    f = _lib.lib.mrcal_amd_transform_image
-    if not f(_ptr(o), _ptr(a), w, h, channels, dtype, _ptr(m), W, H, interp, border, _ptr(bv)):
+    smooth = antialias_params(antialias, lambda: antialias_sigma(mapxy), (image,))
+    if smooth is None:
+        ok = _lib.lib.mrcal_amd_transform_image(_ptr(o), _ptr(a), w, h, channels, dtype, _ptr(m), W, H, interp, border, _ptr(bv))
+    else:
+        ok = _lib.lib.mrcal_amd_transform_image_smoothed(_ptr(o), _ptr(a), w, h, channels, dtype, _ptr(m), W, H, interp, border,
+                                                         _ptr(bv), C.addressof(smooth))
+    if not ok:
         raise Exception("transform_image() failed:" + _api._last_error())
     if ret is not o: ret[...] = o
     return ret

@@ -51,6 +51,7 @@ from ._cabi import _ptr
 from ._handle import Handle, _failed
 from .poseutils import compose_Rt
 from .equalization import equalization_params, _EqualizeParams
+from .smoothing import antialias_params, antialias_sigma
 
 
 class _Point2(C.Structure):
@@ -222,7 +223,11 @@ class Rectification(Handle):
     rectify(), disparity() and point_cloud_of_images() take equalization = None | 'clahe' | 'stretch',
     clahe_clip_limit = 8.0, clahe_tiles = (8,8): each raw image (grayscale, uint8 or uint16) is equalized on the device
     between its upload and the remap (equalize_clahe(), equalize_stretch()), the same bits as equalizing it first.
-    With 'stretch' the rectified images are uint8. None: nothing of it runs"""
+    With 'stretch' the rectified images are uint8. None: nothing of it runs.
+    The same three take antialias = None | 'auto' | sigma | (sigma_x, sigma_y): each raw image (grayscale, uint8 or
+    uint16) is filtered on the device (smooth_gaussian()) after its upload and its equalization and before the remap,
+    the same bits as filtering it first. 'auto': antialias_sigma() of the two maps, the larger; where that is 0, and for
+    None, nothing of it runs. The colours of a point cloud are not filtered"""
 
     _destroy = "mrcal_amd_rectification_destroy"
 
@@ -258,15 +263,31 @@ class Rectification(Handle):
         self._call("equalize()", "mrcal_amd_rectification_set_equalization", C.addressof(p))
         self._equalizing = params is not None
 
+    def _antialias_auto(self):
+        """antialias_sigma() of the two maps, the larger: computed once"""
+        if getattr(self, "_antialias_auto_sigma", None) is None:
+            maps = self.maps()
+            self._antialias_auto_sigma = max(antialias_sigma(maps[0]), antialias_sigma(maps[1]))
+        return self._antialias_auto_sigma
+
+    def _antialias(self, antialias, images):
+        """what the calls that follow do to their raw images after the equalization; None: nothing, which a handle
+        that was never told otherwise does by itself"""
+        params = antialias_params(antialias, self._antialias_auto, images)
+        if params is None and not getattr(self, "_antialiasing", False):
+            return
+        self._call("smooth()", "mrcal_amd_rectification_set_antialias", None if params is None else C.addressof(params))
+        self._antialiasing = params is not None
+
     def maps(self):
         self._open()
         maps = np.zeros((2, self.Nel, self.Naz, 2), dtype=np.float32)
         self._call("rectification_maps()", "mrcal_amd_rectification_maps", _ptr(maps))
         return maps
 
-    def rectify(self, image0, image1, out=None, *, equalization=None, clahe_clip_limit=8.0, clahe_tiles=(8, 8)):
+    def rectify(self, image0, image1, out=None, *, equalization=None, clahe_clip_limit=8.0, clahe_tiles=(8, 8), antialias=None):
         """(image0 rectified, image1 rectified): linear interpolation, 0 outside the images. out: the two arrays to fill.
-        equalization: of the raw images, on the device, before the remap (grayscale, uint8 or uint16, then)"""
+        equalization, antialias: of the raw images, on the device, before the remap (grayscale, uint8 or uint16, then)"""
         self._open()
         if equalization is None:
             eq, dtype_out = None, None
@@ -282,6 +303,7 @@ class Rectification(Handle):
         (o0, r0), (o1, r1) = (_output_array(None if out is None else out[i], shape, a0.dtype if dtype_out is None else dtype_out, False)
                               for i in (0, 1))
         self._equalize(eq)
+        self._antialias(antialias, (image0, image1))
         self._call("rectify()", "mrcal_amd_rectification_rectify", _ptr(o0), _ptr(o1), _ptr(a0), w0, h0, _ptr(a1), w1, h1,
                    c0, t0, 1, 0, None)
         if r0 is not o0: r0[...] = o0
@@ -298,11 +320,11 @@ class Rectification(Handle):
                             _rectification=self)
 
     def disparity(self, image0, image1, *, speckle_window_size=0, speckle_range=0,
-                  equalization=None, clahe_clip_limit=8.0, clahe_tiles=(8, 8), **params):
+                  equalization=None, clahe_clip_limit=8.0, clahe_tiles=(8, 8), antialias=None, **params):
         """stereo_matching_sgm(*rectify(image0, image1), **params), the same bits: int16 (Nel, Naz). The rectified images
         are made and matched on the device and do not cross to the host. image0, image1: grayscale, uint8 or uint16.
         speckle_window_size > 0: the disparity image is filtered there too (filter_speckles()).
-        equalization: of the raw images, there too, before the remap"""
+        equalization, antialias: of the raw images, there too, before the remap"""
         self._open()
         speckle = _speckle_keywords(speckle_window_size, speckle_range)
         p = _sgm_params(**params)
@@ -314,6 +336,7 @@ class Rectification(Handle):
         dtype = _SGM_DTYPES[_sgm_dtype(image0.dtype)]
         eq = None if equalization is None else equalization_params(equalization, clahe_clip_limit, clahe_tiles, (image0, image1))[0]
         self._equalize(eq)
+        self._antialias(antialias, (image0, image1))
         a0, a1 = np.ascontiguousarray(image0), np.ascontiguousarray(image1)
         out = np.zeros((self.Nel, self.Naz), dtype=np.int16)
         images = (_ptr(a0), a0.shape[1], a0.shape[0], _ptr(a1), a1.shape[1], a1.shape[0], dtype, C.addressof(p))
@@ -340,7 +363,7 @@ class Rectification(Handle):
 
     def point_cloud_of_images(self, image0, image1, *, color_image=None, frame='ref', dtype=np.float64,
                                   range_min=None, range_max=None, speckle_window_size=0, speckle_range=0,
-                                  equalization=None, clahe_clip_limit=8.0, clahe_tiles=(8, 8), **sgm_params):
+                                  equalization=None, clahe_clip_limit=8.0, clahe_tiles=(8, 8), antialias=None, **sgm_params):
         """point_cloud(disparity(image0, image1, ...), image0 = color_image or image0, disparity_scale = 16,
         disparity_min = disparity_min, ...), the same bits: (points, color, index). The pair is rectified, matched, on
         request filtered, and made a cloud of on the device: neither the rectified images nor the disparities cross to the
@@ -348,7 +371,8 @@ class Rectification(Handle):
         BGR, of its imager size; None: image0. A negative disparity_min is refused: stereo_range()'s cast to uint16 has no
         meaning for negative disparities. equalization: of the raw images, on the device, before the remap; the colours
         are then those of the EQUALIZED image0 (as in the reference's mrcal-stereo), unless a color_image is given,
-        which is used as it is"""
+        which is used as it is. antialias: of the raw images, after the equalization; the colours are NOT filtered: they
+        are those of image0 as it was before the filter"""
         self._open()
         speckle = _speckle_keywords(speckle_window_size, speckle_range)
         p_sgm = _sgm_params(**sgm_params)
@@ -362,6 +386,7 @@ class Rectification(Handle):
         sgm_dtype = _SGM_DTYPES[_sgm_dtype(image0.dtype)]
         eq, dtype_equalized = (None, None) if equalization is None else \
             equalization_params(equalization, clahe_clip_limit, clahe_tiles, (image0, image1))
+        self._antialias(antialias, (image0, image1))
         a0, a1 = np.ascontiguousarray(image0), np.ascontiguousarray(image1)
         # (image0 as its own colour image: the SAME array, which the library then takes equalized, where it lies)
         image = _cloud_image(a0 if color_image is None else color_image, "image0" if color_image is None else "color_image", self._models)
