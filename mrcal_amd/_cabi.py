@@ -11,8 +11,7 @@ tier") with the reference's signatures (mrcal.h:374-853, internal.h:99-114):
                                    libmrcal_amd.so on its own.
 
 SIGNATURES has a row for every function include/mrcal_amd.h declares (tests/test_cabi_symbols.py holds the two
-together), SIGNATURES_SMOOTH one for every function of include/mrcal_amd_smooth.h (tests/test_smooth_host.py);
-MrcalLib applies them when it loads a library. Nothing else in the package sets a restype or argtypes.
+together); MrcalLib applies them when it loads a library. Nothing else in the package sets a restype or argtypes.
 
 This module is plumbing: no numerics happen here.
 """
@@ -320,6 +319,13 @@ SIGNATURES = {
     "mrcal_amd_equalizer_destroy": (None, [vp]),
     "mrcal_amd_rectification_set_equalization": (b, [vp, vp]),
     "mrcal_amd_feature_matcher_create_equalized": (vp, [vp, i, i, vp] + [i]*3 + [vp]),
+    "mrcal_amd_smoother_create": (vp, [i]*3 + [vp]),
+    "mrcal_amd_smoother_apply": (b, [vp]*3),
+    "mrcal_amd_smoother_milliseconds": (b, [vp, vp]),
+    "mrcal_amd_smoother_destroy": (None, [vp]),
+    "mrcal_amd_smooth_weights": (b, [d, ip, vp]),
+    "mrcal_amd_rectification_set_antialias": (b, [vp, vp]),
+    "mrcal_amd_transform_image_smoothed": (b, [vp, vp] + [i]*4 + [vp] + [i]*4 + [vp, vp]),
     "mrcal_amd_regional_statistics_create": (vp, [vp, i, i]),
     "mrcal_amd_regional_statistics_grid": (b, [vp, i, ip, ip]),
     "mrcal_amd_regional_statistics_get": (b, [vp, i] + [vp]*3),
@@ -330,17 +336,6 @@ SIGNATURES = {
     "mrcal_amd_valid_region_lds_vertices": (i, []),
     "mrcal_amd_valid_region_contains": (b, [vp, vp, i64, vp, i]),
     "mrcal_amd_valid_region_image": (b, [vp, i, i, vp, i]),
-}
-
-# ... and in the order of include/mrcal_amd_smooth.h
-SIGNATURES_SMOOTH = {
-    "mrcal_amd_smoother_create": (vp, [i]*3 + [vp]),
-    "mrcal_amd_smoother_apply": (b, [vp]*3),
-    "mrcal_amd_smoother_milliseconds": (b, [vp, vp]),
-    "mrcal_amd_smoother_destroy": (None, [vp]),
-    "mrcal_amd_smooth_weights": (b, [d, ip, vp]),
-    "mrcal_amd_rectification_set_antialias": (b, [vp, vp]),
-    "mrcal_amd_transform_image_smoothed": (b, [vp, vp] + [i]*4 + [vp] + [i]*4 + [vp, vp]),
 }
 
 # exported for the tests of the host-side planning code, and declared in no header: not part of the interface
@@ -361,7 +356,7 @@ class MrcalLib:
         self.path = path
         self.lib  = C.CDLL(path)
         # (a symbol the library lacks is passed over: the reference's own library has none of the mrcal_amd_* names)
-        for table in (SIGNATURES, SIGNATURES_SMOOTH, DEBUG_SIGNATURES):
+        for table in (SIGNATURES, DEBUG_SIGNATURES):
             for name, (restype, argtypes) in table.items():
                 f = getattr(self.lib, name, None)
                 if f is not None:

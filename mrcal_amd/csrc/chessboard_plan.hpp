@@ -11,6 +11,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include "image_format.hpp"
 
 namespace mrcal_amd {
 
@@ -23,7 +24,6 @@ namespace mrcal_amd {
 #define CB_CHUNK_WORDS 16               // mask words a workgroup of cb_scatter_kernel places: the unit of the scan
 #define CB_SCAN_THREADS 1024            // cb_scan_kernel is ONE workgroup of these
 #define CB_MIN_SIDE 32
-#define CB_MAX_PIXELS (1L << 28)
 #define CB_MAX_CANDIDATES 65536
 #define CB_ALIGN 256                    // of the parts of the pool, in bytes
 #define CB_WINDOW 5                     // the refinement window: offsets -5..5
@@ -36,7 +36,7 @@ namespace mrcal_amd {
 #define CB_DECIMATE_BYTES 16            // of each of two rows a lane of the wide cb_decimate_kernel loads
 
 static_assert(CB_THREADS == 4*CB_TX && CB_TY % 4 == 0, "a wavefront is a row of the tile, four rows at a time");
-static_assert(CB_MAX_PIXELS < (1L << 31), "a pixel index is an int32");
+static_assert(IMAGE_MAX_PIXELS < (1L << 31), "a pixel index is an int32");
 
 struct ChessboardPlan
 {
@@ -74,9 +74,9 @@ inline bool chessboard_plan(ChessboardPlan* plan, std::string* error, int W, int
     else if(W < CB_MIN_SIDE || H < CB_MIN_SIDE)
         snprintf(buf, sizeof(buf), "find_chessboard_corners(): an image of %d x %d pixels is too small: at least %d x %d",
                  W, H, CB_MIN_SIDE, CB_MIN_SIDE);
-    else if((long)W*(long)H > CB_MAX_PIXELS)
+    else if(!image_size_ok(W, H))
         snprintf(buf, sizeof(buf), "find_chessboard_corners(): an image of %d x %d pixels is too large: at most %ld pixels",
-                 W, H, CB_MAX_PIXELS);
+                 W, H, IMAGE_MAX_PIXELS);
     else if(threshold_256 < 0 || threshold_256 > 255)
         snprintf(buf, sizeof(buf), "find_chessboard_corners(): threshold_256 must be in 0..255, got %d", threshold_256);
     else if(nms_radius < 1 || nms_radius > CB_NMS_RADIUS_MAX)

@@ -31,8 +31,6 @@
 
 static_assert(EQUALIZE_METHOD_NONE == MRCAL_AMD_EQUALIZE_NONE && EQUALIZE_METHOD_CLAHE == MRCAL_AMD_EQUALIZE_CLAHE &&
               EQUALIZE_METHOD_STRETCH == MRCAL_AMD_EQUALIZE_STRETCH, "equalize_plan.hpp restates the header's methods");
-static_assert(EQUALIZE_DTYPE_UINT8 == MRCAL_AMD_IMAGE_UINT8 && EQUALIZE_DTYPE_UINT16 == MRCAL_AMD_IMAGE_UINT16,
-              "equalize_plan.hpp restates the header's image types");
 
 namespace mrcal_amd {
 
@@ -405,7 +403,7 @@ bool equalize_device(const EqualizePlan& p, const void* d_in, void* d_out, uint8
         uint32_t* hist = (uint32_t*)(pool + p.hist);
         HIP_TRY(hipMemsetAsync(hist, 0, p.hist_bytes, NULL), return false);
         if(!record(event, 0)) return false;
-        if(p.dtype == EQUALIZE_DTYPE_UINT8) launch_clahe<uint8_t> (p, a, d_in, d_out, hist, pool + p.lut, event);
+        if(p.dtype == IMAGE_DTYPE_UINT8) launch_clahe<uint8_t> (p, a, d_in, d_out, hist, pool + p.lut, event);
         else                                launch_clahe<uint16_t>(p, a, d_in, d_out, hist, pool + p.lut, event);
     }
     else
@@ -414,7 +412,7 @@ bool equalize_device(const EqualizePlan& p, const void* d_in, void* d_out, uint8
         HIP_TRY(hipMemsetAsync(minmax,     0xFF, sizeof(uint32_t), NULL), return false);
         HIP_TRY(hipMemsetAsync(minmax + 1, 0,    sizeof(uint32_t), NULL), return false);
         if(!record(event, 0)) return false;
-        if(p.dtype == EQUALIZE_DTYPE_UINT8) launch_stretch<uint8_t> (p, d_in, d_out, minmax, event);
+        if(p.dtype == IMAGE_DTYPE_UINT8) launch_stretch<uint8_t> (p, d_in, d_out, minmax, event);
         else                                launch_stretch<uint16_t>(p, d_in, d_out, minmax, event);
     }
     if(!record(event, 3)) return false;
@@ -436,7 +434,7 @@ bool equalize_resident(DeviceBuffers& result, DeviceBuffers& workspace, const Eq
     EqualizePlan plan; std::string why;
     if(!equalize_plan(&plan, &why, W, H, dtype, params, free_bytes, false)) { set_error("%s", why.c_str()); return false; }
     uint8_t *d_out = NULL, *pool = NULL;
-    if(!(result.alloc(&d_out, (size_t)W*H*equalize_pixel_bytes(plan.dtype_out)) && workspace.alloc(&pool, plan.bytes))) return false;
+    if(!(result.alloc(&d_out, (size_t)W*H*image_pixel_bytes(plan.dtype_out)) && workspace.alloc(&pool, plan.bytes))) return false;
     if(!equalize_device(plan, d_image, d_out, pool)) return false;
     *d_equalized = d_out; *dtype_equalized = plan.dtype_out;
     return true;
@@ -493,10 +491,10 @@ bool mrcal_amd_equalizer_apply(mrcal_amd_equalizer_t* e, const void* in, void* o
     const EqualizePlan& p = e->plan;
     const size_t N = (size_t)p.W*(size_t)p.H;
     e->events.timed = false;
-    HIP_TRY(hipMemcpy(e->pool + p.image, in, N*equalize_pixel_bytes(p.dtype), hipMemcpyHostToDevice), return false);
+    HIP_TRY(hipMemcpy(e->pool + p.image, in, N*image_pixel_bytes(p.dtype), hipMemcpyHostToDevice), return false);
     if(!equalize_device(p, e->pool + p.image, e->pool + p.result, e->pool, &e->events)) return false;
     // (the copy waits for the launches)
-    HIP_TRY(hipMemcpy(out, e->pool + p.result, N*equalize_pixel_bytes(p.dtype_out), hipMemcpyDeviceToHost), return false);
+    HIP_TRY(hipMemcpy(out, e->pool + p.result, N*image_pixel_bytes(p.dtype_out), hipMemcpyDeviceToHost), return false);
     e->events.timed = true;
     return true;
 }

@@ -1,5 +1,5 @@
 // The equalization of equalize.hip for the other translation units that have an image on the device already
-// (rectification.hip: the raw images before the remap; match_feature.hip: the two images of a matcher).
+// (rectification.hip's ImagePreparation::upload(): a raw image after its upload, for rectification.hip's remaps and match_feature.hip's matcher).
 // HOST declarations; the kernels stay where they are.
 #pragma once
 #include <stdint.h>

@@ -10,17 +10,16 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include "image_format.hpp"
 
 namespace mrcal_amd {
 
-// (the values of MRCAL_AMD_EQUALIZE_* and MRCAL_AMD_IMAGE_*, which this file does not include)
+// (the values of MRCAL_AMD_EQUALIZE_*, which this file does not include)
 #define EQUALIZE_METHOD_NONE    0
 #define EQUALIZE_METHOD_CLAHE   1
 #define EQUALIZE_METHOD_STRETCH 2
-#define EQUALIZE_DTYPE_UINT8    0
-#define EQUALIZE_DTYPE_UINT16   1
+#define EQUALIZE_DTYPE_UINT8    IMAGE_DTYPE_UINT8       // (the name equalize_plan_check.cpp asks by)
 
-#define EQUALIZE_MAX_PIXELS (1L << 28)
 #define EQUALIZE_MAX_TILES  4096        // tiles_x tiles_y: what the histograms of a uint16 image may still cost (1 GiB)
 #define EQUALIZE_ALIGN      256         // of the parts of the pool, in bytes
 #define EQUALIZE_THREADS    256         // of the histogram, apply, extremes and map kernels
@@ -64,9 +63,8 @@ struct EqualizePlan
 };
 
 inline size_t equalize_aligned(size_t n) { return (n + EQUALIZE_ALIGN - 1)/EQUALIZE_ALIGN*EQUALIZE_ALIGN; }
-inline size_t equalize_pixel_bytes(int dtype) { return dtype == EQUALIZE_DTYPE_UINT8 ? 1 : 2; }
 // stretch makes uint8 of everything; CLAHE keeps the type
-inline int equalize_dtype_out(int method, int dtype) { return method == EQUALIZE_METHOD_STRETCH ? EQUALIZE_DTYPE_UINT8 : dtype; }
+inline int equalize_dtype_out(int method, int dtype) { return method == EQUALIZE_METHOD_STRETCH ? IMAGE_DTYPE_UINT8 : dtype; }
 
 // the arguments that cannot be equalized, for whatever data: false, and why
 inline bool equalize_params_ok(std::string* error, int W, int H, int dtype, const EqualizeParams& p)
@@ -75,9 +73,9 @@ inline bool equalize_params_ok(std::string* error, int W, int H, int dtype, cons
     buf[0] = 0;
     if(!(p.method == EQUALIZE_METHOD_NONE || p.method == EQUALIZE_METHOD_CLAHE || p.method == EQUALIZE_METHOD_STRETCH))
         snprintf(buf, sizeof(buf), "equalize(): the method must be one of MRCAL_AMD_EQUALIZE_* (0..2), not %d", p.method);
-    else if(!(dtype == EQUALIZE_DTYPE_UINT8 || dtype == EQUALIZE_DTYPE_UINT16))
+    else if(!image_dtype_is_integer(dtype))
         snprintf(buf, sizeof(buf), "equalize(): images are uint8 or uint16");
-    else if(W <= 0 || H <= 0 || (long)W*H > EQUALIZE_MAX_PIXELS)
+    else if(!image_size_ok(W, H))
         snprintf(buf, sizeof(buf), "equalize(): images of %d x %d pixels cannot be equalized", W, H);
     else if(p.method == EQUALIZE_METHOD_CLAHE)
     {
@@ -114,8 +112,8 @@ inline bool equalize_plan(EqualizePlan* plan, std::string* error, int W, int H, 
     if(with_images)
     {
         q.image     = 0;
-        q.result    = equalize_aligned(N*equalize_pixel_bytes(dtype));
-        q.workspace = q.result + equalize_aligned(N*equalize_pixel_bytes(q.dtype_out));
+        q.result    = equalize_aligned(N*image_pixel_bytes(dtype));
+        q.workspace = q.result + equalize_aligned(N*image_pixel_bytes(q.dtype_out));
     }
     q.hist = q.lut = q.minmax = q.bytes = q.workspace;
     if(p.method == EQUALIZE_METHOD_CLAHE)
@@ -125,7 +123,7 @@ inline bool equalize_plan(EqualizePlan* plan, std::string* error, int W, int H, 
         q.Wpad = pad ? W + p.tiles_x - W % p.tiles_x : W;
         q.Hpad = pad ? H + p.tiles_y - H % p.tiles_y : H;
         q.tw = q.Wpad/p.tiles_x; q.th = q.Hpad/p.tiles_y;
-        q.hist_size = dtype == EQUALIZE_DTYPE_UINT8 ? 256 : 65536;
+        q.hist_size = dtype == IMAGE_DTYPE_UINT8 ? 256 : 65536;
         const int total = q.tw*q.th;                    // (<= 2^28 + what the padding adds: fits)
         q.lut_scale = (float)(q.hist_size - 1) / (float)total;
         q.inv_tw = 1.0f / (float)q.tw;
@@ -138,18 +136,18 @@ inline bool equalize_plan(EqualizePlan* plan, std::string* error, int W, int H, 
             if(q.clip < 1) q.clip = 1;
         }
         const size_t tiles = (size_t)q.tiles_x*(size_t)q.tiles_y;
-        q.luts_in_lds = dtype == EQUALIZE_DTYPE_UINT8 && tiles*256 <= EQUALIZE_LDS_LUT_BYTES;
+        q.luts_in_lds = dtype == IMAGE_DTYPE_UINT8 && tiles*256 <= EQUALIZE_LDS_LUT_BYTES;
         q.bands       = (unsigned)((q.th + EQUALIZE_BAND_ROWS - 1)/EQUALIZE_BAND_ROWS);
         q.hist_grid   = (unsigned)tiles*q.bands;
         q.lut_grid    = (unsigned)tiles;
-        q.lut_threads = dtype == EQUALIZE_DTYPE_UINT8 ? 64 : 1024;
+        q.lut_threads = dtype == IMAGE_DTYPE_UINT8 ? 64 : 1024;
         q.apply_grid_x = (unsigned)((W + EQUALIZE_THREADS*EQUALIZE_APPLY_X - 1)/(EQUALIZE_THREADS*EQUALIZE_APPLY_X));
         q.apply_grid_y = (unsigned)((H + EQUALIZE_APPLY_ROWS - 1)/EQUALIZE_APPLY_ROWS);
         q.apply_grid   = q.apply_grid_x*q.apply_grid_y;          // (<= 2^28/16 + what the edges add)
         q.hist_bytes = tiles*(size_t)q.hist_size*sizeof(uint32_t);
         q.hist  = q.workspace;
         q.lut   = q.hist + equalize_aligned(q.hist_bytes);
-        q.bytes = q.lut + equalize_aligned(tiles*(size_t)q.hist_size*equalize_pixel_bytes(dtype));
+        q.bytes = q.lut + equalize_aligned(tiles*(size_t)q.hist_size*image_pixel_bytes(dtype));
         q.minmax = q.bytes;
     }
     else if(p.method == EQUALIZE_METHOD_STRETCH)

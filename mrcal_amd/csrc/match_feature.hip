@@ -37,6 +37,7 @@
 #include "resident_common.hpp"
 #include "remap.hpp"
 #include "equalize.hpp"
+#include "image_prepare.hpp"
 #include "match_plan.hpp"
 
 namespace mrcal_amd {
@@ -472,54 +473,40 @@ mrcal_amd_feature_matcher_t*
 mrcal_amd_feature_matcher_create(const void* image0, int width0, int height0,
                                  const void* image1, int width1, int height1, int dtype)
 {
-    last_error_string().clear();
-    std::string why;
-    if(!match_sizes_ok(&why, 0, 1, 1, 0, width0, height0, width1, height1, dtype)) { set_error("%s", why.c_str()); return NULL; }
-    if(!have_device()) return NULL;
-    mrcal_amd_feature_matcher* m = new mrcal_amd_feature_matcher;
-    m->dtype = dtype;
-    m->W[0] = width0; m->H[0] = height0; m->W[1] = width1; m->H[1] = height1;
-    const void* host[2] = { image0, image1 };
-    for(int i = 0; i < 2; i++)
-    {
-        uint8_t* d = NULL;
-        if(!m->images.upload(&d, (const uint8_t*)host[i], (size_t)m->W[i]*m->H[i]*match_pixel_bytes(dtype))) { delete m; return NULL; }
-        m->image[i] = d;
-    }
-    return m;
+    return mrcal_amd_feature_matcher_create_equalized(image0, width0, height0, image1, width1, height1, dtype, NULL);
 }
 
-// _create(), both images equalized on the device after the upload (equalize.hip)
+// _create(), both images equalized on the device after the upload (equalize.hip); params NULL or the method NONE: as
+// they are
 mrcal_amd_feature_matcher_t*
 mrcal_amd_feature_matcher_create_equalized(const void* image0, int width0, int height0,
                                            const void* image1, int width1, int height1, int dtype,
                                            const mrcal_amd_equalize_params_t* params)
 {
-    const EqualizeParams equalization = equalize_params_of(params);
-    if(equalization.method == EQUALIZE_METHOD_NONE)
-        return mrcal_amd_feature_matcher_create(image0, width0, height0, image1, width1, height1, dtype);
     last_error_string().clear();
+    ImagePreparation preparation;
+    preparation.equalization = equalize_params_of(params);
     std::string why;
     if(!match_sizes_ok(&why, 0, 1, 1, 0, width0, height0, width1, height1, dtype) ||
-       !equalize_params_ok(&why, width0, height0, dtype, equalization) ||
-       !equalize_params_ok(&why, width1, height1, dtype, equalization))
+       !preparation.ok(&why, width0, height0, 1, dtype) || !preparation.ok(&why, width1, height1, 1, dtype))
     { set_error("%s", why.c_str()); return NULL; }
     if(!have_device()) return NULL;
     mrcal_amd_feature_matcher* m = new mrcal_amd_feature_matcher;
+    m->dtype = dtype;
     m->W[0] = width0; m->H[0] = height0; m->W[1] = width1; m->H[1] = height1;
     const void* host[2] = { image0, image1 };
     {
-        // the raw images, the histograms and the LUTs go when this scope ends; the equalized images are the matcher's
+        // the raw images, the histograms and the LUTs go when this scope ends; the prepared images are the matcher's
         DeviceBuffers tmp;
         for(int i = 0; i < 2; i++)
         {
-            uint8_t* d_raw = NULL; const void* d = NULL;
-            if(!(tmp.upload(&d_raw, (const uint8_t*)host[i], (size_t)m->W[i]*m->H[i]*match_pixel_bytes(dtype)) &&
-                 equalize_resident(m->images, tmp, equalization, d_raw, m->W[i], m->H[i], dtype, &d, &m->dtype)))
+            const void* d = NULL;
+            if(!preparation.upload(m->images, tmp, host[i], m->W[i], m->H[i], 1, dtype, &d, &m->dtype))
             { (void)hipDeviceSynchronize(); delete m; return NULL; }
             m->image[i] = (void*)d;
         }
-        HIP_TRY(hipStreamSynchronize(NULL), delete m; return NULL);
+        // (nothing was queued for images that are taken as they are)
+        if(!preparation.off()) HIP_TRY(hipStreamSynchronize(NULL), delete m; return NULL);
     }
     return m;
 }
@@ -572,7 +559,7 @@ bool mrcal_amd_feature_matcher_match(mrcal_amd_feature_matcher_t* m, int N, cons
     DeviceBuffers tmp;
     if(!(tmp.upload(&d_map, map) && tmp.upload(&d_features, features) && tmp.alloc(&d_sums, (size_t)N) &&
          tmp.alloc(&d_q1, (size_t)2*N) && tmp.alloc(&d_at, (size_t)2*N) && tmp.alloc(&d_sub, (size_t)N) && tmp.alloc(&d_status, (size_t)N) &&
-         m->last.alloc(&d_templates, Npixels*(size_t)N*match_pixel_bytes(m->dtype)) && m->last.alloc(&m->surfaces, plan.Nsurface)))
+         m->last.alloc(&d_templates, Npixels*(size_t)N*image_pixel_bytes(m->dtype)) && m->last.alloc(&m->surfaces, plan.Nsurface)))
     { m->last.free_all(); m->surfaces = NULL; return false; }
     m->templates = d_templates;
 
@@ -650,7 +637,7 @@ bool mrcal_amd_feature_matcher_template(mrcal_amd_feature_matcher_t* m, int i, v
 {
     last_error_string().clear();
     if(!matcher_feature_given(m, i)) return false;
-    const size_t n = (size_t)m->tw*m->th*match_pixel_bytes(m->dtype);
+    const size_t n = (size_t)m->tw*m->th*image_pixel_bytes(m->dtype);
     HIP_TRY(hipMemcpy(template_image, (const uint8_t*)m->templates + (size_t)i*n, n, hipMemcpyDeviceToHost), return false);
     return true;
 }

@@ -16,6 +16,7 @@
 #include <stdio.h>
 #include <string>
 #include <vector>
+#include "image_format.hpp"
 
 namespace mrcal_amd {
 
@@ -49,7 +50,7 @@ struct MatchPlan
     size_t lds_bytes = 0;
 };
 
-inline size_t match_pixel_bytes(int dtype) { return dtype == 0 ? 1 : dtype == 1 ? 2 : 4; }
+inline size_t match_pixel_bytes(int dtype) { return image_pixel_bytes(dtype); }   // (the name match_plan_check.cpp asks by)
 
 // LDS of a workgroup: the patch of image1 under a tile (tile + template - 1) and the template.
 // uint8 is staged as 32-bit words of four pixels; a lane reads the words tx .. tx + tpitch of a row, and the 16 lanes
@@ -69,7 +70,7 @@ inline void match_lds_layout(int* pitch, int* tpitch, size_t* bytes, int tw, int
     {
         *tpitch = tw;
         *pitch  = MATCH_TILE_X + tw - 1;
-        *bytes  = match_pixel_bytes(dtype)*(rows*(size_t)*pitch + (size_t)th*(size_t)tw);
+        *bytes  = image_pixel_bytes(dtype)*(rows*(size_t)*pitch + (size_t)th*(size_t)tw);
     }
 }
 
@@ -78,7 +79,7 @@ inline bool match_sizes_ok(std::string* error, int N, int tw, int th, int radius
 {
     char buf[256];
     buf[0] = 0;
-    if(!(dtype == 0 || dtype == 1 || dtype == 2))
+    if(!(image_dtype_is_integer(dtype) || dtype == IMAGE_DTYPE_FLOAT))
         snprintf(buf, sizeof(buf), "match_feature(): images are uint8, uint16 or float32");
     else if(N < 0 || N > (1 << 20))
         snprintf(buf, sizeof(buf), "match_feature(): %d features cannot be matched in one call (at most %d)", N, 1 << 20);

@@ -11,6 +11,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include "image_format.hpp"
 
 namespace mrcal_amd {
 
@@ -20,15 +21,15 @@ namespace mrcal_amd {
 #define CLOUD_WORDS_PER_GROUP (CLOUD_SPAN/64)                   // 64-bit mask words a workgroup: bit b of word w is pixel 64 w + b
 #define CLOUD_SCAN_THREADS 1024         // cloud_scan_kernel is ONE workgroup of these
 #define CLOUD_SCAN_MAX_PER_THREAD 256   // counts a thread of it sums serially, at most
-#define CLOUD_MAX_PIXELS (1L << 28)
+#define CLOUD_MAX_PIXELS IMAGE_MAX_PIXELS     // (the name point_cloud_plan_check.cpp asks by)
 #define CLOUD_ALIGN 256                 // of the parts of the pool, in bytes
 #define CLOUD_CAPACITY_STEP 4096        // the output buffers hold a multiple of this many records
 
 // At the largest image the count array still fits the one workgroup of the scan: a thread sums at most
 // CLOUD_SCAN_MAX_PER_THREAD counts serially, and the tree over the threads' sums does the rest. And the total, at most
 // a count a pixel, fits the uint32 it is summed in with room to spare
-static_assert(CLOUD_MAX_PIXELS/CLOUD_SPAN <= (long)CLOUD_SCAN_THREADS*CLOUD_SCAN_MAX_PER_THREAD, "the scan is one workgroup");
-static_assert(CLOUD_MAX_PIXELS < (1L << 31), "a rank is an int32");
+static_assert(IMAGE_MAX_PIXELS/CLOUD_SPAN <= (long)CLOUD_SCAN_THREADS*CLOUD_SCAN_MAX_PER_THREAD, "the scan is one workgroup");
+static_assert(IMAGE_MAX_PIXELS < (1L << 31), "a rank is an int32");
 static_assert(CLOUD_SPAN % 64 == 0 && CLOUD_THREADS % 64 == 0, "whole wavefronts, whole words");
 
 struct CloudPlan
@@ -51,10 +52,10 @@ inline bool cloud_plan(CloudPlan* plan, std::string* error, int W, int H, size_t
 {
     *plan = CloudPlan();
     char buf[256];
-    if(W <= 0 || H <= 0 || (long)W*(long)H > CLOUD_MAX_PIXELS)
+    if(!image_size_ok(W, H))
     {
         snprintf(buf, sizeof(buf), "stereo_point_cloud(): a disparity image of %d x %d pixels cannot be made a cloud of: at most %ld pixels",
-                 W, H, CLOUD_MAX_PIXELS);
+                 W, H, IMAGE_MAX_PIXELS);
         *error = buf;
         return false;
     }

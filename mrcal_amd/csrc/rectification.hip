@@ -34,6 +34,7 @@
 #include "speckle_plan.hpp"
 #include "equalize.hpp"
 #include "smooth.hpp"
+#include "image_prepare.hpp"
 #include "stereo_range_device.hpp"
 #include "point_cloud.hpp"
 
@@ -388,8 +389,6 @@ void remap_kernel(const T* __restrict__ src, int W, int H, const float* __restri
     }
 }
 
-size_t dtype_size(int dtype) { return dtype == MRCAL_AMD_IMAGE_UINT8 ? 1 : dtype == MRCAL_AMD_IMAGE_UINT16 ? 2 : 4; }
-
 template<class T, int C>
 void launch_remap_tc(const void* src, int W, int H, const float* map, void* out, int Nout, int interp, int border_mode,
                      const BorderValue& bv)
@@ -451,73 +450,54 @@ bool remap_device(const void* d_src, int W, int H, int C, int dtype, const float
     HIP_TRY(hipGetLastError(), return false);
     return true;
 }
-namespace {
 
-// a raw image of the host on the device, equalized there if that is asked for (equalize.hip) and then filtered if that
-// is (smooth.hip): *d_image, of *dtype_image (stretch makes uint8 of uint16). *d_unfiltered, if it is wanted: the image
-// as it was before the filter. Everything is tmp's, and queued in the NULL stream
-bool upload_equalized(DeviceBuffers& tmp, const EqualizeParams& equalization, const SmoothParams& antialias,
-                      const void* image, int W, int H, int dtype,
-                      const void** d_image, int* dtype_image, const void** d_unfiltered = NULL)
+static_assert(IMAGE_DTYPE_UINT8 == MRCAL_AMD_IMAGE_UINT8 && IMAGE_DTYPE_UINT16 == MRCAL_AMD_IMAGE_UINT16 &&
+              IMAGE_DTYPE_FLOAT == MRCAL_AMD_IMAGE_FLOAT, "image_format.hpp restates the header's image types");
+
+// (image_prepare.hpp: match_feature.hip prepares its two images with it too)
+bool ImagePreparation::upload(DeviceBuffers& result, DeviceBuffers& workspace, const void* host_image, int W, int H, int C, int dtype,
+                              const void** d_image, int* dtype_image, const void** d_unfiltered) const
 {
-    uint8_t* d_src = NULL;
+    const bool filtered = !smooth_is_off(antialias);
+    uint8_t* d_raw = NULL;
     const void* d_equalized = NULL;
-    if(!(tmp.upload(&d_src, (const uint8_t*)image, (size_t)W*H*dtype_size(dtype)) &&
-         equalize_resident(tmp, tmp, equalization, d_src, W, H, dtype, &d_equalized, dtype_image)))
+    if(!((off() ? result : workspace).upload(&d_raw, (const uint8_t*)host_image, (size_t)W*H*C*image_pixel_bytes(dtype)) &&
+         equalize_resident(filtered ? workspace : result, workspace, equalization, d_raw, W, H, dtype, &d_equalized, dtype_image)))
         return false;
     if(d_unfiltered != NULL) *d_unfiltered = d_equalized;
-    return smooth_resident(tmp, antialias, d_equalized, W, H, *dtype_image, d_image);
+    return smooth_resident(result, antialias, d_equalized, W, H, *dtype_image, d_image);
 }
+namespace {
 
-// the images an equalization takes: false, and why
-bool equalization_arguments_ok(const EqualizeParams& equalization, int width, int height, int channels, int dtype)
+// a pair of raw images of one type that the remap and the preparation take: false, and why
+bool pair_arguments_ok(const ImagePreparation& preparation, int width0, int height0, int width1, int height1, int channels, int dtype,
+                       int width_out, int height_out, int interpolation, int border_mode)
 {
-    if(equalization.method == EQUALIZE_METHOD_NONE) return true;
-    if(channels != 1) { set_error("equalize(): an image that is equalized is grey, not of %d channels", channels); return false; }
+    if(!remap_arguments_ok(width0, height0, channels, dtype, width_out, height_out, interpolation, border_mode) ||
+       !remap_arguments_ok(width1, height1, channels, dtype, width_out, height_out, interpolation, border_mode))
+        return false;
     std::string why;
-    if(equalize_params_ok(&why, width, height, dtype, equalization)) return true;
+    if(preparation.ok(&why, width0, height0, channels, dtype) && preparation.ok(&why, width1, height1, channels, dtype)) return true;
     set_error("%s", why.c_str());
     return false;
 }
 
-// the images the anti-aliasing filter takes, of the type the equalization leaves them in: false, and why
-bool antialias_arguments_ok(const SmoothParams& antialias, const EqualizeParams& equalization, int width, int height, int channels, int dtype)
-{
-    if(smooth_is_off(antialias)) return true;
-    if(channels != 1) { set_error("smooth(): an image that is filtered is grey, not of %d channels", channels); return false; }
-    std::string why;
-    if(smooth_params_ok(&why, width, height, equalize_dtype_out(equalization.method, dtype), antialias)) return true;
-    set_error("%s", why.c_str());
-    return false;
-}
-
-// host image -> remapped host image through a map that is on the device already. equalization, antialias: of the image,
-// on the device, before the remap; out is then of the equalized type
+// host image -> remapped host image through a map that is on the device already. preparation: of the image, on the
+// device, before the remap; out is then of the prepared type
 bool remap_host_image(void* out, const void* image, int W, int H, int C, int dtype, const float* d_map, int Nout,
-                      int interp, int border_mode, const double* border_value,
-                      const EqualizeParams& equalization = EqualizeParams(), const SmoothParams& antialias = SmoothParams())
+                      int interp, int border_mode, const double* border_value, const ImagePreparation& preparation)
 {
     DeviceBuffers tmp;
-    if(equalization.method != EQUALIZE_METHOD_NONE || !smooth_is_off(antialias))
-    {
-        const void* d_image = NULL; uint8_t* d_out = NULL;
-        int dtype_image = dtype;
-        if(!upload_equalized(tmp, equalization, antialias, image, W, H, dtype, &d_image, &dtype_image)) return false;
-        const size_t nout = (size_t)Nout*C*dtype_size(dtype_image);
-        if(!(border_mode == MRCAL_AMD_BORDER_TRANSPARENT ? tmp.upload(&d_out, (const uint8_t*)out, nout) : tmp.alloc(&d_out, nout)))
-            return false;
-        if(!remap_device(d_image, W, H, C, dtype_image, d_map, d_out, Nout, interp, border_mode, border_value)) return false;
-        HIP_TRY(hipMemcpy(out, d_out, nout, hipMemcpyDeviceToHost), (void)hipDeviceSynchronize(); return false);
-        return true;
-    }
-    uint8_t *d_src = NULL, *d_out = NULL;
-    const size_t nsrc = (size_t)W*H*C*dtype_size(dtype), nout = (size_t)Nout*C*dtype_size(dtype);
-    if(!tmp.upload(&d_src, (const uint8_t*)image, nsrc)) return false;
+    const void* d_image = NULL; uint8_t* d_out = NULL;
+    int dtype_image = dtype;
+    if(!preparation.upload(tmp, tmp, image, W, H, C, dtype, &d_image, &dtype_image)) return false;
+    const size_t nout = (size_t)Nout*C*image_pixel_bytes(dtype_image);
     // a transparent border keeps what out had
     if(!(border_mode == MRCAL_AMD_BORDER_TRANSPARENT ? tmp.upload(&d_out, (const uint8_t*)out, nout) : tmp.alloc(&d_out, nout)))
         return false;
-    if(!remap_device(d_src, W, H, C, dtype, d_map, d_out, Nout, interp, border_mode, border_value)) return false;
-    HIP_TRY(hipMemcpy(out, d_out, nout, hipMemcpyDeviceToHost), return false);
+    if(!remap_device(d_image, W, H, C, dtype_image, d_map, d_out, Nout, interp, border_mode, border_value)) return false;
+    // (the temporaries go when this returns: after a copy that failed, not before the launches have)
+    HIP_TRY(hipMemcpy(out, d_out, nout, hipMemcpyDeviceToHost), (void)hipDeviceSynchronize(); return false);
     return true;
 }
 
@@ -603,10 +583,8 @@ struct mrcal_amd_rectification
     mrcal_amd_point_cloud_t* cloud = NULL;
     mrcal_lensmodel_type_t   rectification_model_type = MRCAL_LENSMODEL_LATLON;
     double                   fxycxy[4] = { 0., 0., 0., 0. };
-    // of every raw image, between its upload and the remap (equalize.hip); the method NONE: none
-    EqualizeParams           equalization;
-    // ... and after that (smooth.hip); both sigmas 0: none
-    SmoothParams             antialias;
+    // of every raw image, between its upload and the remap: _set_equalization() and _set_antialias() fill its halves
+    ImagePreparation         preparation;
     ~mrcal_amd_rectification() { mrcal_amd_point_cloud_destroy(cloud); }
 };
 
@@ -701,17 +679,10 @@ bool mrcal_amd_rectification_rectify(mrcal_amd_rectification_t* r, void* out0, v
 {
     last_error_string().clear();
     if(!rectification_given(r) || !have_device()) return false;
-    if(!remap_arguments_ok(width0, height0, channels, dtype, r->W, r->H, interpolation, border_mode) ||
-       !remap_arguments_ok(width1, height1, channels, dtype, r->W, r->H, interpolation, border_mode))
+    if(!pair_arguments_ok(r->preparation, width0, height0, width1, height1, channels, dtype, r->W, r->H, interpolation, border_mode))
         return false;
-    if(!equalization_arguments_ok(r->equalization, width0, height0, channels, dtype) ||
-       !equalization_arguments_ok(r->equalization, width1, height1, channels, dtype))
-        return false;
-    if(!antialias_arguments_ok(r->antialias, r->equalization, width0, height0, channels, dtype) ||
-       !antialias_arguments_ok(r->antialias, r->equalization, width1, height1, channels, dtype))
-        return false;
-    return remap_host_image(out0, image0, width0, height0, channels, dtype, r->map[0], r->W*r->H, interpolation, border_mode, border_value, r->equalization, r->antialias)
-        && remap_host_image(out1, image1, width1, height1, channels, dtype, r->map[1], r->W*r->H, interpolation, border_mode, border_value, r->equalization, r->antialias);
+    return remap_host_image(out0, image0, width0, height0, channels, dtype, r->map[0], r->W*r->H, interpolation, border_mode, border_value, r->preparation)
+        && remap_host_image(out1, image1, width1, height1, channels, dtype, r->map[1], r->W*r->H, interpolation, border_mode, border_value, r->preparation);
 }
 
 bool mrcal_amd_rectification_set_equalization(mrcal_amd_rectification_t* r, const mrcal_amd_equalize_params_t* params)
@@ -724,7 +695,7 @@ bool mrcal_amd_rectification_set_equalization(mrcal_amd_rectification_t* r, cons
     std::string why;
     if(!equalize_params_ok(&why, p.tiles_x > 0 ? p.tiles_x : 1, p.tiles_y > 0 ? p.tiles_y : 1, MRCAL_AMD_IMAGE_UINT8, p))
     { set_error("%s", why.c_str()); return false; }
-    r->equalization = p;
+    r->preparation.equalization = p;
     return true;
 }
 
@@ -736,7 +707,7 @@ bool mrcal_amd_rectification_set_antialias(mrcal_amd_rectification_t* r, const m
     // (what can be refused without an image; the rest when one comes)
     std::string why;
     if(!smooth_is_off(p) && !smooth_params_ok(&why, 1, 1, MRCAL_AMD_IMAGE_UINT8, p)) { set_error("%s", why.c_str()); return false; }
-    r->antialias = p;
+    r->preparation.antialias = p;
     return true;
 }
 
@@ -746,6 +717,48 @@ bool mrcal_amd_rectification_range(mrcal_amd_rectification_t* r, double* range, 
     last_error_string().clear();
     if(!rectification_given(r) || !have_device()) return false;
     return range_dense(range, disparity_scaled, r->W, r->H, r->range_args, disparity_scale, disparity_scaled_min, disparity_scaled_max);
+}
+
+// What _disparity_filtered() and _point_cloud_of_images() do alike: the refusals before any device work (the matcher
+// says the same of the speckle pair again), a new matcher (stereo_sgm.hip) with its speckle filter set (a window of 0:
+// no filter, and nothing of it runs), and both images prepared and rectified straight into its device buffers. The raw
+// and the prepared images are tmp's, which may go once the NULL stream has run dry. If they are wanted: *cloud, the
+// rectification's point-cloud object, made before the matcher; *d_unfiltered0, of *dtype_unfiltered0, image0 as it was
+// before the anti-aliasing filter. NULL: a refusal or a failure, and nothing is left running
+static mrcal_amd_stereo_sgm_t* rectified_pair_matcher(mrcal_amd_rectification* r, DeviceBuffers& tmp,
+                                                      const void* image0, int width0, int height0,
+                                                      const void* image1, int width1, int height1, int dtype,
+                                                      const mrcal_amd_stereo_sgm_params_t* params,
+                                                      int speckle_window_size, int speckle_range, mrcal_amd_point_cloud_t** cloud = NULL,
+                                                      const void** d_unfiltered0 = NULL, int* dtype_unfiltered0 = NULL)
+{
+    SpeckleParams p; std::string why;
+    if(!speckle_params_of_matcher(&p, &why, 0, 1, speckle_window_size, speckle_range)) { set_error("%s", why.c_str()); return NULL; }
+    if(!rectification_given(r) || !have_device()) return NULL;
+    if(!pair_arguments_ok(r->preparation, width0, height0, width1, height1, 1, dtype, r->W, r->H,
+                          MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT))
+        return NULL;
+    if(cloud != NULL && (*cloud = rectification_cloud(r)) == NULL) return NULL;
+    mrcal_amd_stereo_sgm_t* m = mrcal_amd_stereo_sgm_create(r->W, r->H, r->preparation.dtype_out(dtype), params);
+    if(m == NULL) return NULL;
+    // (destroy clears nothing: the error of a failure stays)
+    if(!mrcal_amd_stereo_sgm_set_speckle_filter(m, speckle_window_size, speckle_range)) { mrcal_amd_stereo_sgm_destroy(m); return NULL; }
+    const void* image[2] = { image0, image1 };
+    const int   W[2] = { width0, width1 }, H[2] = { height0, height1 };
+    for(int i = 0; i < 2; i++)
+    {
+        const void *d_src = NULL, *d_unfiltered = NULL; int dtype_src = dtype;
+        if(!(r->preparation.upload(tmp, tmp, image[i], W[i], H[i], 1, dtype, &d_src, &dtype_src, &d_unfiltered) &&
+             remap_device(d_src, W[i], H[i], 1, dtype_src, r->map[i], sgm_device_image(m, i), r->W*r->H,
+                          MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT, NULL)))
+        {
+            (void)hipDeviceSynchronize();
+            mrcal_amd_stereo_sgm_destroy(m);
+            return NULL;
+        }
+        if(i == 0 && d_unfiltered0 != NULL) { *d_unfiltered0 = d_unfiltered; *dtype_unfiltered0 = dtype_src; }
+    }
+    return m;
 }
 
 // image pair -> disparity: both images rectified straight into the matcher's device buffers (stereo_sgm.hip)
@@ -764,43 +777,13 @@ bool mrcal_amd_rectification_disparity_filtered(mrcal_amd_rectification_t* r,
                                                 int speckle_window_size, int speckle_range, int16_t* disparity)
 {
     last_error_string().clear();
-    {
-        // (refused before any device work; the matcher says the same again)
-        SpeckleParams p; std::string why;
-        if(!speckle_params_of_matcher(&p, &why, 0, 1, speckle_window_size, speckle_range)) { set_error("%s", why.c_str()); return false; }
-    }
-    if(!rectification_given(r) || !have_device()) return false;
-    if(!remap_arguments_ok(width0, height0, 1, dtype, r->W, r->H, MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT) ||
-       !remap_arguments_ok(width1, height1, 1, dtype, r->W, r->H, MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT))
-        return false;
-    if(!equalization_arguments_ok(r->equalization, width0, height0, 1, dtype) ||
-       !equalization_arguments_ok(r->equalization, width1, height1, 1, dtype))
-        return false;
-    if(!antialias_arguments_ok(r->antialias, r->equalization, width0, height0, 1, dtype) ||
-       !antialias_arguments_ok(r->antialias, r->equalization, width1, height1, 1, dtype))
-        return false;
-    const int dtype_matched = equalize_dtype_out(r->equalization.method, dtype);
-    mrcal_amd_stereo_sgm_t* m = mrcal_amd_stereo_sgm_create(r->W, r->H, dtype_matched, params);
+    DeviceBuffers tmp;
+    mrcal_amd_stereo_sgm_t* m = rectified_pair_matcher(r, tmp, image0, width0, height0, image1, width1, height1, dtype, params,
+                                                       speckle_window_size, speckle_range);
     if(m == NULL) return false;
-    // (a window of 0: no filter, and nothing of it runs)
-    if(!mrcal_amd_stereo_sgm_set_speckle_filter(m, speckle_window_size, speckle_range)) { mrcal_amd_stereo_sgm_destroy(m); return false; }
-    const void* image[2] = { image0, image1 };
-    const int   W[2] = { width0, width1 }, H[2] = { height0, height1 };
-    bool ok = true;
-    {
-        DeviceBuffers tmp;
-        for(int i = 0; i < 2 && ok; i++)
-        {
-            const void* d_src = NULL; int dtype_src = dtype;
-            ok = upload_equalized(tmp, r->equalization, r->antialias, image[i], W[i], H[i], dtype, &d_src, &dtype_src) &&
-                 remap_device(d_src, W[i], H[i], 1, dtype_src, r->map[i], sgm_device_image(m, i), r->W*r->H,
-                              MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT, NULL);
-        }
-        // (its copy waits for the launches: the images may go when this returns)
-        ok = ok && sgm_match_device(m, disparity);
-        if(!ok) (void)hipDeviceSynchronize();
-    }
-    // (destroy clears nothing: the error of a failure stays)
+    // (its copy waits for the launches: the images and the matcher may go when this returns)
+    const bool ok = sgm_match_device(m, disparity);
+    if(!ok) (void)hipDeviceSynchronize();
     mrcal_amd_stereo_sgm_destroy(m);
     return ok;
 }
@@ -832,53 +815,26 @@ bool mrcal_amd_rectification_point_cloud_of_images(mrcal_amd_rectification_t* r,
                   sgm_params->disparity_min);
         return false;
     }
-    {
-        SpeckleParams p; std::string why;
-        if(!speckle_params_of_matcher(&p, &why, 0, 1, speckle_window_size, speckle_range)) { set_error("%s", why.c_str()); return false; }
-    }
-    if(!rectification_given(r) || !have_device()) return false;
-    if(!remap_arguments_ok(width0, height0, 1, dtype, r->W, r->H, MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT) ||
-       !remap_arguments_ok(width1, height1, 1, dtype, r->W, r->H, MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT))
-        return false;
-    if(!equalization_arguments_ok(r->equalization, width0, height0, 1, dtype) ||
-       !equalization_arguments_ok(r->equalization, width1, height1, 1, dtype))
-        return false;
-    if(!antialias_arguments_ok(r->antialias, r->equalization, width0, height0, 1, dtype) ||
-       !antialias_arguments_ok(r->antialias, r->equalization, width1, height1, 1, dtype))
-        return false;
-    const int dtype_matched = equalize_dtype_out(r->equalization.method, dtype);
-    mrcal_amd_point_cloud_t* c = rectification_cloud(r);
-    if(c == NULL) return false;
-    mrcal_amd_stereo_sgm_t* m = mrcal_amd_stereo_sgm_create(r->W, r->H, dtype_matched, sgm_params);
+    DeviceBuffers tmp;
+    mrcal_amd_point_cloud_t* c = NULL;
+    const void* d_unfiltered0 = NULL; int dtype_unfiltered0 = dtype;
+    mrcal_amd_stereo_sgm_t* m = rectified_pair_matcher(r, tmp, image0, width0, height0, image1, width1, height1, dtype, sgm_params,
+                                                       speckle_window_size, speckle_range, &c, &d_unfiltered0, &dtype_unfiltered0);
     if(m == NULL) return false;
-    if(!mrcal_amd_stereo_sgm_set_speckle_filter(m, speckle_window_size, speckle_range)) { mrcal_amd_stereo_sgm_destroy(m); return false; }
     // the disparities are the matcher's: its scale, and everything from its smallest disparity up is valid
     mrcal_amd_point_cloud_params_t p = *params;
     p.disparity_scale      = 16;
     p.disparity_scaled_min = (uint16_t)(16*sgm_params->disparity_min);
     p.disparity_scaled_max = 0x7FFF;
-    const void* image[2] = { image0, image1 };
-    const int   W[2] = { width0, width1 }, H[2] = { height0, height1 };
-    const bool  equalized_colors = r->equalization.method != EQUALIZE_METHOD_NONE && p.image != NULL && p.image == image0 &&
-                                   p.image_width == width0 && p.image_height == height0 && p.image_channels == 1 && p.image_dtype == dtype;
+    // colours from image0 itself: from the equalized one, where it lies, as it was before the anti-aliasing filter
     const void* d_color = NULL;
-    bool ok = true;
-    {
-        DeviceBuffers tmp;
-        for(int i = 0; i < 2 && ok; i++)
-        {
-            const void *d_src = NULL, *d_unfiltered = NULL; int dtype_src = dtype;
-            ok = upload_equalized(tmp, r->equalization, r->antialias, image[i], W[i], H[i], dtype, &d_src, &dtype_src, &d_unfiltered) &&
-                 remap_device(d_src, W[i], H[i], 1, dtype_src, r->map[i], sgm_device_image(m, i), r->W*r->H,
-                              MRCAL_AMD_INTER_LINEAR, MRCAL_AMD_BORDER_CONSTANT, NULL);
-            // colours from image0 itself: from the equalized one, where it lies, as it was before the anti-aliasing filter
-            if(ok && i == 0 && equalized_colors) { d_color = d_unfiltered; p.image_dtype = dtype_src; }
-        }
-        const int16_t* d_disparity = NULL;
-        // (the cloud waits for its launches, and so for these: the images and the matcher may go when this returns)
-        ok = ok && sgm_match_device_resident(m, &d_disparity) && point_cloud_compute_device(c, (const uint16_t*)d_disparity, &p, N, d_color);
-        if(!ok) (void)hipDeviceSynchronize();
-    }
+    if(r->preparation.equalization.method != EQUALIZE_METHOD_NONE && p.image != NULL && p.image == image0 &&
+       p.image_width == width0 && p.image_height == height0 && p.image_channels == 1 && p.image_dtype == dtype)
+    { d_color = d_unfiltered0; p.image_dtype = dtype_unfiltered0; }
+    const int16_t* d_disparity = NULL;
+    // (the cloud waits for its launches, and so for these: the images and the matcher may go when this returns)
+    const bool ok = sgm_match_device_resident(m, &d_disparity) && point_cloud_compute_device(c, (const uint16_t*)d_disparity, &p, N, d_color);
+    if(!ok) (void)hipDeviceSynchronize();
     mrcal_amd_stereo_sgm_destroy(m);
     return ok;
 }
@@ -932,14 +888,16 @@ bool mrcal_amd_transform_image_smoothed(void* out, const void* image, int width,
 {
     last_error_string().clear();
     if(!remap_arguments_ok(width, height, channels, dtype, width_out, height_out, interpolation, border_mode)) return false;
-    const SmoothParams antialias = smooth_params_of(params);
-    if(!antialias_arguments_ok(antialias, EqualizeParams(), width, height, channels, dtype)) return false;
+    ImagePreparation preparation;
+    preparation.antialias = smooth_params_of(params);
+    std::string why;
+    if(!preparation.ok(&why, width, height, channels, dtype)) { set_error("%s", why.c_str()); return false; }
     if(!have_device()) return false;
     DeviceBuffers tmp;
     float* d_map = NULL;
     if(!tmp.upload(&d_map, mapxy, (size_t)2*width_out*height_out)) return false;
     return remap_host_image(out, image, width, height, channels, dtype, d_map, width_out*height_out,
-                            interpolation, border_mode, border_value, EqualizeParams(), antialias);
+                            interpolation, border_mode, border_value, preparation);
 }
 
 bool mrcal_amd_stereo_range_sparse(double* range, double* p, const double* disparity, const mrcal_point2_t* qrect0,

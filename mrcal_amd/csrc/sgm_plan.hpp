@@ -10,6 +10,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include "image_format.hpp"
 
 namespace mrcal_amd {
 
@@ -55,7 +56,7 @@ struct SgmPlan
     unsigned select_grid = 0, check_grid = 0;
 };
 
-inline size_t sgm_pixel_bytes(int dtype) { return dtype == 0 ? 1 : 2; }
+inline size_t sgm_pixel_bytes(int dtype) { return image_pixel_bytes(dtype); }     // (the name sgm_plan_check.cpp asks by)
 inline size_t sgm_aligned(size_t n) { return (n + SGM_ALIGN - 1)/SGM_ALIGN*SGM_ALIGN; }
 
 // the parameters that cannot be matched, for whatever data: false, and why
@@ -64,9 +65,9 @@ inline bool sgm_params_ok(std::string* error, int W, int H, int dtype, const Sgm
     char buf[256];
     buf[0] = 0;
     const long D = (long)p.disparity_max - (long)p.disparity_min;
-    if(!(dtype == 0 || dtype == 1))
+    if(!image_dtype_is_integer(dtype))
         snprintf(buf, sizeof(buf), "stereo_matching_sgm(): images are uint8 or uint16");
-    else if(W <= 0 || H <= 0 || (long)W*H > (1L << 28))
+    else if(!image_size_ok(W, H))
         snprintf(buf, sizeof(buf), "stereo_matching_sgm(): images of %d x %d pixels cannot be matched", W, H);
     else if(D <= 0 || D > SGM_MAX_D || D % 16 != 0)
         snprintf(buf, sizeof(buf), "stereo_matching_sgm(): disparity_max - disparity_min must be a positive multiple of 16, at most %d. Got %ld",
@@ -95,7 +96,7 @@ inline bool sgm_plan(SgmPlan* plan, std::string* error, int W, int H, int dtype,
     plan->per_lane = plan->D/SGM_LANES;
     const size_t N = (size_t)W*(size_t)H;
     size_t at = 0;
-    for(int i = 0; i < 2; i++) { plan->image[i]  = at; at += sgm_aligned(N*sgm_pixel_bytes(dtype)); }
+    for(int i = 0; i < 2; i++) { plan->image[i]  = at; at += sgm_aligned(N*image_pixel_bytes(dtype)); }
     for(int i = 0; i < 2; i++) { plan->census[i] = at; at += sgm_aligned(N*sizeof(uint64_t)); }
     plan->S           = at; at += sgm_aligned(N*(size_t)plan->D*sizeof(uint16_t));
     plan->index_left  = at; at += sgm_aligned(N);

@@ -1,5 +1,5 @@
 // smooth_gaussian(): the anti-aliasing pre-filter of an image that is about to be remapped to fewer pixels
-// (include/mrcal_amd_smooth.h: the definition, to the bit; the reference only has it on its to-do list).
+// (include/mrcal_amd.h, "smoothing": the definition, to the bit; the reference only has it on its to-do list).
 //
 //   smooth_kernel   ONE launch an image, a workgroup a tile of tile_w x tile_h pixels of the result
 //                   (256 x 32 of a uint8 image at sigma = 2; the plan makes the tile lower for a larger radius):
@@ -18,14 +18,11 @@
 #include <stdint.h>
 #include <string.h>
 #include <string>
-#include "../../include/mrcal_amd_smooth.h"
+#include "../../include/mrcal_amd.h"
 #include "host_state.hpp"
 #include "device_memory.hpp"
 #include "smooth_plan.hpp"
 #include "smooth.hpp"
-
-static_assert(SMOOTH_DTYPE_UINT8 == MRCAL_AMD_IMAGE_UINT8 && SMOOTH_DTYPE_UINT16 == MRCAL_AMD_IMAGE_UINT16,
-              "smooth_plan.hpp restates the header's image types");
 
 namespace mrcal_amd {
 
@@ -202,7 +199,7 @@ bool smooth_device(const SmoothPlan& p, const void* d_in, void* d_out, SmoothEve
     if(d_in == d_out) { set_error("smooth(): internal error: the result cannot replace the image"); return false; }
     const SmoothArgs a = args_of(p);
     if(!record(events, 0)) return false;
-    if(p.dtype == SMOOTH_DTYPE_UINT8)
+    if(p.dtype == IMAGE_DTYPE_UINT8)
         hipLaunchKernelGGL((smooth_kernel<uint8_t>),  dim3(p.grid), dim3(SMOOTH_THREADS), p.lds_bytes, NULL, a, (const uint8_t*)d_in,  (uint8_t*)d_out);
     else
         hipLaunchKernelGGL((smooth_kernel<uint16_t>), dim3(p.grid), dim3(SMOOTH_THREADS), p.lds_bytes, NULL, a, (const uint16_t*)d_in, (uint16_t*)d_out);
@@ -220,7 +217,7 @@ bool smooth_resident(DeviceBuffers& result, const SmoothParams& params, const vo
     SmoothPlan plan; std::string why;
     if(!smooth_plan(&plan, &why, W, H, dtype, params, free_bytes, false)) { set_error("%s", why.c_str()); return false; }
     uint8_t* d_out = NULL;
-    if(!result.alloc(&d_out, (size_t)W*H*smooth_pixel_bytes(dtype))) return false;
+    if(!result.alloc(&d_out, (size_t)W*H*image_pixel_bytes(dtype))) return false;
     if(!smooth_device(plan, d_image, d_out)) return false;
     *d_smoothed = d_out;
     return true;
@@ -274,7 +271,7 @@ bool mrcal_amd_smoother_apply(mrcal_amd_smoother_t* s, const void* in, void* out
     if(in == NULL || out == NULL) { set_error("smooth(): an image is NULL"); return false; }
     if(!have_device()) return false;
     const SmoothPlan& p = s->plan;
-    const size_t bytes = (size_t)p.W*(size_t)p.H*smooth_pixel_bytes(p.dtype);
+    const size_t bytes = (size_t)p.W*(size_t)p.H*image_pixel_bytes(p.dtype);
     s->events.timed = false;
     HIP_TRY(hipMemcpy(s->pool + p.image, in, bytes, hipMemcpyHostToDevice), return false);
     if(!smooth_device(p, s->pool + p.image, s->pool + p.result, &s->events)) return false;

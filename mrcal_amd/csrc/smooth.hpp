@@ -1,9 +1,9 @@
 // The Gaussian pre-filter of smooth.hip for the translation unit that has an image on the device already
-// (rectification.hip: the raw images between the upload, the equalization and the remap).
+// (rectification.hip's ImagePreparation::upload(): a raw image between its upload, its equalization and whatever uses it).
 // HOST declarations; the kernel stays where it is.
 #pragma once
 #include <stdint.h>
-#include "../../include/mrcal_amd_smooth.h"
+#include "../../include/mrcal_amd.h"
 #include "device_memory.hpp"
 #include "resident_common.hpp"
 #include "smooth_plan.hpp"

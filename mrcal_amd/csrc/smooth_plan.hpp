@@ -2,26 +2,22 @@
 // of both axes, the tile a workgroup makes with its halo, the LDS it needs for that, the grid, where the image and the
 // result lie in the ONE pooled allocation a smoother owns, and the refusal of an image that does not fit the device's
 // free memory (the caller passes that figure in). Plain structs in and out, no HIP type or call.
-// tests/hostcheck_smooth/smooth_plan_check.cpp runs it under the host sanitizers.
+// tests/hostcheck/smooth_plan_check.cpp runs it under the host sanitizers.
 //
-// What the filter is: include/mrcal_amd_smooth.h.
+// What the filter is: include/mrcal_amd.h, "smoothing".
 #pragma once
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include "image_format.hpp"
 
 namespace mrcal_amd {
-
-// (the values of MRCAL_AMD_IMAGE_*, which this file does not include)
-#define SMOOTH_DTYPE_UINT8    0
-#define SMOOTH_DTYPE_UINT16   1
 
 #define SMOOTH_SIGMA_MIN    0.5
 #define SMOOTH_SIGMA_MAX    8.0
 #define SMOOTH_R_MAX        24          // ceil(3 SMOOTH_SIGMA_MAX)
-#define SMOOTH_MAX_PIXELS   (1L << 28)
 #define SMOOTH_ALIGN        256         // of the parts of the pool, in bytes
 #define SMOOTH_THREADS      256
 #define SMOOTH_QUAD         4           // the pixels of a row one lane makes at a time
@@ -52,12 +48,11 @@ struct SmoothPlan
 };
 
 inline size_t smooth_aligned(size_t n) { return (n + SMOOTH_ALIGN - 1)/SMOOTH_ALIGN*SMOOTH_ALIGN; }
-inline size_t smooth_pixel_bytes(int dtype) { return dtype == SMOOTH_DTYPE_UINT8 ? 1 : 2; }
 // 0, or in [0.5, 8]; a NaN is neither
 inline bool smooth_sigma_ok(double sigma) { return sigma == 0.0 || (sigma >= SMOOTH_SIGMA_MIN && sigma <= SMOOTH_SIGMA_MAX); }
 inline bool smooth_is_off(const SmoothParams& p) { return p.sigma_x == 0.0 && p.sigma_y == 0.0; }
 
-// The integer taps of one axis, w[0..R], summing to 256 with their mirror images (include/mrcal_amd_smooth.h, "taps").
+// The integer taps of one axis, w[0..R], summing to 256 with their mirror images (include/mrcal_amd.h, "smoothing": taps).
 // Any sigma > 0 whose radius is at most SMOOTH_R_MAX is served; sigma == 0: the one tap 256
 inline bool smooth_weights(int* R, int* w, double sigma)
 {
@@ -97,9 +92,9 @@ inline bool smooth_params_ok(std::string* error, int W, int H, int dtype, const 
                  SMOOTH_SIGMA_MIN, SMOOTH_SIGMA_MAX, p.sigma_x, p.sigma_y);
     else if(smooth_is_off(p))
         snprintf(buf, sizeof(buf), "smooth(): both sigmas are 0: there is nothing to run");
-    else if(!(dtype == SMOOTH_DTYPE_UINT8 || dtype == SMOOTH_DTYPE_UINT16))
+    else if(!image_dtype_is_integer(dtype))
         snprintf(buf, sizeof(buf), "smooth(): images are uint8 or uint16");
-    else if(W <= 0 || H <= 0 || (long)W*H > SMOOTH_MAX_PIXELS)
+    else if(!image_size_ok(W, H))
         snprintf(buf, sizeof(buf), "smooth(): images of %d x %d pixels cannot be smoothed", W, H);
     if(buf[0] == 0) return true;
     *error = buf;
@@ -118,7 +113,7 @@ inline bool smooth_plan(SmoothPlan* plan, std::string* error, int W, int H, int 
     if(!smooth_weights(&q.Rx, q.wx, p.sigma_x) || !smooth_weights(&q.Ry, q.wy, p.sigma_y))
     { *error = "smooth(): internal error: a sigma that was accepted has no taps"; return false; }
 
-    const int px = (int)smooth_pixel_bytes(dtype);
+    const int px = (int)image_pixel_bytes(dtype);
     q.tile_w     = SMOOTH_SUM_ROW_BYTES/(2*px);                // a sum has twice the pixel's bytes
     q.halo_x     = (q.Rx + SMOOTH_QUAD - 1)/SMOOTH_QUAD*SMOOTH_QUAD;
     q.raw_dwords = (q.tile_w + 2*q.halo_x)*px/4 + 1;

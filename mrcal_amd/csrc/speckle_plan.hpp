@@ -11,6 +11,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include "image_format.hpp"
 
 namespace mrcal_amd {
 
@@ -18,7 +19,6 @@ namespace mrcal_amd {
 #define SPECKLE_TILE_X 64
 #define SPECKLE_TILE_Y 16
 #define SPECKLE_THREADS 256         // of every kernel
-#define SPECKLE_MAX_PIXELS (1L << 28)
 #define SPECKLE_MAX_DIFF 65535      // the largest difference two int16 can have: a larger max_diff means this
 #define SPECKLE_ALIGN 256           // of the parts of the pool, in bytes
 
@@ -57,7 +57,7 @@ inline bool speckle_params_ok(std::string* error, int W, int H, long new_value, 
 {
     char buf[256];
     buf[0] = 0;
-    if(W <= 0 || H <= 0 || (long)W*H > SPECKLE_MAX_PIXELS)
+    if(!image_size_ok(W, H))
         snprintf(buf, sizeof(buf), "filter_speckles(): images of %d x %d pixels cannot be filtered", W, H);
     else if(new_value < INT16_MIN || new_value > INT16_MAX)
         snprintf(buf, sizeof(buf), "filter_speckles(): new_value must be in %d..%d. Got %ld", INT16_MIN, INT16_MAX, new_value);

@@ -548,7 +548,7 @@ bool mrcal_amd_stereo_sgm_match(mrcal_amd_stereo_sgm_t* m, const void* image0, c
 {
     last_error_string().clear();
     if(!sgm_given(m) || !have_device()) return false;
-    const size_t n = (size_t)m->plan.W*m->plan.H*sgm_pixel_bytes(m->plan.dtype);
+    const size_t n = (size_t)m->plan.W*m->plan.H*image_pixel_bytes(m->plan.dtype);
     HIP_TRY(hipMemcpy(sgm_device_image(m, 0), image0, n, hipMemcpyHostToDevice), return false);
     HIP_TRY(hipMemcpy(sgm_device_image(m, 1), image1, n, hipMemcpyHostToDevice), return false);
     return sgm_match_device(m, disparity);

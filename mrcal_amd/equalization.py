@@ -21,12 +21,12 @@ import numpy as np
 
 from ._cabi import _ptr
 from ._handle import Handle
+from ._images import GREY_DTYPES, grey_shape, grey_dtype, grey_image, out_like, apply_resident
 
 
 EQUALIZE_NONE, EQUALIZE_CLAHE, EQUALIZE_STRETCH = 0, 1, 2
 _METHODS = {None: EQUALIZE_NONE, 'clahe': EQUALIZE_CLAHE, 'stretch': EQUALIZE_STRETCH}
-_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1}
-_MAX_PIXELS = 1 << 28
+_WORDS = ("equalize()", "equalized", "convert a colour image first", "equalizer")
 _MAX_TILES = 4096
 
 
@@ -41,24 +41,6 @@ def _method(method, none_allowed):
     if method is None and none_allowed:
         return EQUALIZE_NONE
     raise Exception(f"equalize(): the method must be {'None, ' if none_allowed else ''}'clahe' or 'stretch', not {method!r}")
-
-
-def _shape(shape):
-    try:    shape = tuple(int(n) for n in shape)
-    except TypeError: shape = ()
-    if len(shape) != 2:
-        raise Exception(f"equalize(): shape must be (H,W), got {shape}")
-    if shape[0] <= 0 or shape[1] <= 0 or shape[0]*shape[1] > _MAX_PIXELS:
-        raise Exception(f"equalize(): images of {shape[1]} x {shape[0]} pixels cannot be equalized")
-    return shape
-
-
-def _dtype(dtype):
-    try:    dtype = np.dtype(dtype)
-    except TypeError: dtype = None
-    if dtype not in _DTYPES or dtype is None:
-        raise Exception(f"equalize(): images are uint8 or uint16, not {dtype}")
-    return dtype
 
 
 def _clahe_arguments(clip_limit, tiles):
@@ -84,21 +66,6 @@ def _tiles_fit(shape, tiles_x, tiles_y):
                         f"({px},{py}) pixels, and a reflection reaches ({W - 1},{H - 1})")
 
 
-def _image(image, what="image", shape=None, dtype=None):
-    """a grey uint8 or uint16 image, or the refusal"""
-    if not isinstance(image, np.ndarray):
-        raise Exception(f"equalize(): '{what}' must be a numpy array")
-    if image.ndim == 3:
-        raise Exception(f"equalize(): '{what}' must be a grayscale image of shape (H,W), got {image.shape}: convert a colour image first")
-    if image.ndim != 2:
-        raise Exception(f"equalize(): '{what}' must be a grayscale image of shape (H,W), got {image.shape}")
-    if image.dtype not in _DTYPES:
-        raise Exception(f"equalize(): '{what}' must have dtype uint8 or uint16, not {image.dtype}")
-    _shape(image.shape)
-    if shape is not None and (image.shape != shape or image.dtype != dtype):
-        raise Exception(f"equalize(): this equalizer was made for images of shape {shape} and dtype {dtype}, got {image.shape} and {image.dtype}")
-
-
 def equalization_params(equalization, clahe_clip_limit, clahe_tiles, images=()):
     """The keywords equalization = None | 'clahe' | 'stretch', clahe_clip_limit, clahe_tiles that Rectification and
     FeatureMatcher take -> (mrcal_amd_equalize_params_t or None, the dtype the equalized images have or None). Every
@@ -108,7 +75,7 @@ def equalization_params(equalization, clahe_clip_limit, clahe_tiles, images=()):
         return None, None
     clip_limit, tiles_x, tiles_y = _clahe_arguments(clahe_clip_limit, clahe_tiles)
     for i, image in enumerate(images):
-        _image(image, f"image{i}")
+        grey_image(_WORDS, image, f"image{i}")
         if method == EQUALIZE_CLAHE:
             _tiles_fit(image.shape, tiles_x, tiles_y)
     dtype = None
@@ -129,38 +96,26 @@ and every apply() reuses them.
     _destroy = "mrcal_amd_equalizer_destroy"
 
     def __init__(self, shape, dtype, method='clahe', *, clip_limit=8.0, tiles=(8, 8)):
-        self.shape, self.dtype = _shape(shape), _dtype(dtype)
+        self.shape, self.dtype = grey_shape(_WORDS, shape), grey_dtype(_WORDS, dtype)
         m = _method(method, False)
         clip_limit, tiles_x, tiles_y = _clahe_arguments(clip_limit, tiles)
         if m == EQUALIZE_CLAHE:
             _tiles_fit(self.shape, tiles_x, tiles_y)
         self.dtype_out = np.dtype(np.uint8) if m == EQUALIZE_STRETCH else self.dtype
         p = _EqualizeParams(m, clip_limit, tiles_x, tiles_y)
-        self._create("equalize()", "mrcal_amd_equalizer_create", self.shape[1], self.shape[0], _DTYPES[self.dtype], C.addressof(p))
+        self._create("equalize()", "mrcal_amd_equalizer_create", self.shape[1], self.shape[0], GREY_DTYPES[self.dtype], C.addressof(p))
 
     def apply(self, image, out=None):
         self._open()
-        _image(image, "image", self.shape, self.dtype)
-        _out(out, self.shape, self.dtype_out)
-        a = np.ascontiguousarray(image)
-        dense = out is not None and out.flags.c_contiguous and out is not image and not np.shares_memory(out, a)
-        o = out if dense else np.zeros(self.shape, dtype=self.dtype_out)
-        self._call("equalize()", "mrcal_amd_equalizer_apply", _ptr(a), _ptr(o))
-        if out is None:
-            return o
-        if o is not out: out[...] = o
-        return out
+        grey_image(_WORDS, image, "image", self.shape, self.dtype)
+        return apply_resident(_WORDS, lambda a, o: self._call("equalize()", "mrcal_amd_equalizer_apply", _ptr(a), _ptr(o)),
+                              image, out, self.shape, self.dtype_out)
 
     def stage_milliseconds(self):
         self._open()
         ms = np.zeros((3,), dtype=np.float32)
         self._call("equalize()", "mrcal_amd_equalizer_stage_milliseconds", _ptr(ms))
         return dict(zip(("histogram", "lut", "apply"), (float(x) for x in ms)))
-
-
-def _out(out, shape, dtype):
-    if out is not None and (not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != dtype):
-        raise Exception(f"equalize(): 'out' must be a numpy array of shape {shape} and dtype {np.dtype(dtype)}")
 
 
 def equalize_clahe(image, *, clip_limit=8.0, tiles=(8, 8), out=None):
@@ -179,10 +134,10 @@ The exact arithmetic, operation by operation, is in include/mrcal_amd.h ("equali
 project: the tests hold the kernels (csrc/equalize.hip) to two numpy transcriptions of that text
 (tests/equalize_checker.py), EQUAL in every pixel, and not to cv2 itself. clip_limit <= 0: nothing is clipped. Integer
 histograms, no floating-point atomics: the same bits on every call. The one-shot form of ImageEqualizer.apply()."""
-    _image(image)
+    grey_image(_WORDS, image)
     clip_limit, tiles_x, tiles_y = _clahe_arguments(clip_limit, tiles)
     _tiles_fit(image.shape, tiles_x, tiles_y)
-    _out(out, image.shape, image.dtype)
+    out_like(_WORDS, out, image.shape, image.dtype)
     with ImageEqualizer(image.shape, image.dtype, 'clahe', clip_limit=clip_limit, tiles=(tiles_x, tiles_y)) as e:
         return e.apply(image, out=out)
 
@@ -193,7 +148,7 @@ min and max over the whole image. uint8 or uint16 (H,W) in, uint8 out: a new arr
 mrcal_image_uint8_load() does to a 16-bit image (image.c), and mrcal-stereo --equalization stretch; unlike it, the true
 extremes are used (its loop misses a maximum that comes before the first smaller pixel) and a constant image, for which
 it divides by zero, gives all zeros. The one-shot form of ImageEqualizer.apply()."""
-    _image(image)
-    _out(out, image.shape, np.uint8)
+    grey_image(_WORDS, image)
+    out_like(_WORDS, out, image.shape, np.uint8)
     with ImageEqualizer(image.shape, image.dtype, 'stretch') as e:
         return e.apply(image, out=out)

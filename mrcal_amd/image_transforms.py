@@ -15,7 +15,9 @@ import ctypes as C
 import numpy as np
 
 from ._cabi import _ptr
+from ._images import _image_arguments, _remap_modes, _border_values, _output_array
 from .poseutils import compose_Rt, invert_Rt
+from .smoothing import antialias_params, antialias_sigma
 
 
 _FIT_MESSAGE = "fit must be either None or a numpy array or one of ('corners','centers-horizontal','centers-vertical')"
@@ -174,8 +176,6 @@ antialias: None, 'auto', a sigma or (sigma_x, sigma_y): the image (grayscale, ui
 device between its upload and the remap (smooth_gaussian()), the same bits as filtering it first. 'auto':
 antialias_sigma(mapxy); where that is 0, and for None, nothing of it runs"""
     from . import _lib, _api
-    from .stereo import _image_arguments, _remap_modes, _border_values, _output_array
-    from .smoothing import antialias_params, antialias_sigma
     if not isinstance(image, np.ndarray): raise Exception("'image' must be a numpy array")
     if not isinstance(mapxy, np.ndarray): raise Exception("'mapxy' must be a numpy array")
     a, w, h, channels, dtype = _image_arguments(image)

@@ -15,7 +15,7 @@ A bilinear remap reads 4 source pixels for an output pixel whatever the scale, s
 as the rectification of a large pair down to the matcher's 256 disparities does, aliases. The reference has this on its
 to-do list only (doc/news-3.0.org: "mrcal-stereo should have an anti-aliasing filter ... when I downsample, just before
 mrcal.transform_image()", with cv2.GaussianBlur(sigmaX = 2)). The definition, to the bit, is in
-include/mrcal_amd_smooth.h; the kernel is csrc/smooth.hip, and there is no CPU fallback for it. Out of scope: colour
+include/mrcal_amd.h ("smoothing"); the kernel is csrc/smooth.hip, and there is no CPU fallback for it. Out of scope: colour
 images, sigmas above 8 (halve the image first).
 """
 import ctypes as C
@@ -25,10 +25,10 @@ import numpy as np
 from . import _handle
 from ._cabi import _ptr
 from ._handle import Handle
+from ._images import GREY_DTYPES, grey_shape, grey_dtype, grey_image, out_like, apply_resident
 
 
-_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1}
-_MAX_PIXELS = 1 << 28
+_WORDS = ("smooth()", "smoothed", "an image that is filtered is grey", "smoother")
 SIGMA_MIN, SIGMA_MAX, R_MAX = 0.5, 8.0, 24
 
 
@@ -62,44 +62,6 @@ def _sigmas_to_run(sigma):
     if s == (0.0, 0.0):
         raise Exception("smooth(): both sigmas are 0: there is nothing to run")
     return s
-
-
-def _shape(shape):
-    try:    shape = tuple(int(n) for n in shape)
-    except TypeError: shape = ()
-    if len(shape) != 2:
-        raise Exception(f"smooth(): shape must be (H,W), got {shape}")
-    if shape[0] <= 0 or shape[1] <= 0 or shape[0]*shape[1] > _MAX_PIXELS:
-        raise Exception(f"smooth(): images of {shape[1]} x {shape[0]} pixels cannot be smoothed")
-    return shape
-
-
-def _dtype(dtype):
-    try:    dtype = np.dtype(dtype)
-    except TypeError: dtype = None
-    if dtype is None or dtype not in _DTYPES:
-        raise Exception(f"smooth(): images are uint8 or uint16, not {dtype}")
-    return dtype
-
-
-def _image(image, what="image", shape=None, dtype=None):
-    """a grey uint8 or uint16 image, or the refusal"""
-    if not isinstance(image, np.ndarray):
-        raise Exception(f"smooth(): '{what}' must be a numpy array")
-    if image.ndim == 3:
-        raise Exception(f"smooth(): '{what}' must be a grayscale image of shape (H,W), got {image.shape}: an image that is filtered is grey")
-    if image.ndim != 2:
-        raise Exception(f"smooth(): '{what}' must be a grayscale image of shape (H,W), got {image.shape}")
-    if image.dtype not in _DTYPES:
-        raise Exception(f"smooth(): '{what}' must have dtype uint8 or uint16, not {image.dtype}")
-    _shape(image.shape)
-    if shape is not None and (image.shape != shape or image.dtype != dtype):
-        raise Exception(f"smooth(): this smoother was made for images of shape {shape} and dtype {dtype}, got {image.shape} and {image.dtype}")
-
-
-def _out(out, shape, dtype):
-    if out is not None and (not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != dtype):
-        raise Exception(f"smooth(): 'out' must be a numpy array of shape {shape} and dtype {np.dtype(dtype)}")
 
 
 def smooth_weights(sigma):
@@ -153,7 +115,7 @@ def antialias_params(antialias, auto_sigma, images=()):
     if s == (0.0, 0.0):
         return None
     for i, image in enumerate(images):
-        _image(image, f"image{i}" if len(images) > 1 else "image")
+        grey_image(_WORDS, image, f"image{i}" if len(images) > 1 else "image")
     return _SmoothParams(*s)
 
 
@@ -168,23 +130,16 @@ them.
     _destroy = "mrcal_amd_smoother_destroy"
 
     def __init__(self, shape, dtype, sigma):
-        self.shape, self.dtype = _shape(shape), _dtype(dtype)
+        self.shape, self.dtype = grey_shape(_WORDS, shape), grey_dtype(_WORDS, dtype)
         self.sigma = _sigmas_to_run(sigma)
         p = _SmoothParams(*self.sigma)
-        self._create("smooth()", "mrcal_amd_smoother_create", self.shape[1], self.shape[0], _DTYPES[self.dtype], C.addressof(p))
+        self._create("smooth()", "mrcal_amd_smoother_create", self.shape[1], self.shape[0], GREY_DTYPES[self.dtype], C.addressof(p))
 
     def apply(self, image, out=None):
         self._open()
-        _image(image, "image", self.shape, self.dtype)
-        _out(out, self.shape, self.dtype)
-        a = np.ascontiguousarray(image)
-        dense = out is not None and out.flags.c_contiguous and out is not image and not np.shares_memory(out, a)
-        o = out if dense else np.zeros(self.shape, dtype=self.dtype)
-        self._call("smooth()", "mrcal_amd_smoother_apply", _ptr(a), _ptr(o))
-        if out is None:
-            return o
-        if o is not out: out[...] = o
-        return out
+        grey_image(_WORDS, image, "image", self.shape, self.dtype)
+        return apply_resident(_WORDS, lambda a, o: self._call("smooth()", "mrcal_amd_smoother_apply", _ptr(a), _ptr(o)),
+                              image, out, self.shape, self.dtype)
 
     def milliseconds(self):
         self._open()
@@ -200,12 +155,12 @@ array, or `out`. sigma: a number or (sigma_x, sigma_y); each is 0 (that axis is 
   1. per axis: R = ceil(3 sigma) and the integer taps w_-R .. w_R of smooth_weights(sigma), which sum to 256
   2. T[y][x] = sum_k wx_k I[y][clamp(x + k)]; O[y][x] = (sum_k wy_k T[clamp(y + k)][x] + 32768) >> 16
 
-The border is replicated; a constant image comes back unchanged. The exact definition is in include/mrcal_amd_smooth.h.
+The border is replicated; a constant image comes back unchanged. The exact definition is in include/mrcal_amd.h ("smoothing").
 cv2 is no part of this project and no equality with cv2.GaussianBlur() is claimed: the tests hold the kernel
 (csrc/smooth.hip) to two numpy transcriptions of that text (tests/smooth_checker.py), EQUAL in every pixel. Integers
 only, no atomics: the same bits on every call. The one-shot form of ImageSmoother.apply()."""
-    _image(image)
+    grey_image(_WORDS, image)
     sigma = _sigmas_to_run(sigma)
-    _out(out, image.shape, image.dtype)
+    out_like(_WORDS, out, image.shape, image.dtype)
     with ImageSmoother(image.shape, image.dtype, sigma) as s:
         return s.apply(image, out=out)

@@ -49,6 +49,7 @@ import numpy as np
 from . import _handle
 from ._cabi import _ptr
 from ._handle import Handle, _failed
+from ._images import MAX_PIXELS, _image_arguments, _output_array
 from .poseutils import compose_Rt
 from .equalization import equalization_params, _EqualizeParams
 from .smoothing import antialias_params, antialias_sigma
@@ -164,50 +165,6 @@ def _baseline(models_rectified):
     return float(np.linalg.norm(Rt01[3, :]))
 
 
-_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1, np.dtype(np.float32): 2}
-
-
-def _image_arguments(image, what="image"):
-    """-> dense array, width, height, channels, dtype code"""
-    if not isinstance(image, np.ndarray):
-        raise Exception(f"'{what}' must be a numpy array")
-    if image.dtype not in _DTYPES:
-        raise Exception(f"'{what}' must have dtype uint8, uint16 or float32, not {image.dtype}")
-    if not (image.ndim == 2 or (image.ndim == 3 and image.shape[2] == 3)) or image.size == 0:
-        raise Exception(f"'{what}' must have shape (H,W) or (H,W,3), got {image.shape}")
-    return np.ascontiguousarray(image), image.shape[1], image.shape[0], (1 if image.ndim == 2 else 3), _DTYPES[image.dtype]
-
-
-def _remap_modes(borderMode, interpolation):
-    if   borderMode is None or borderMode == 'constant'    or (not isinstance(borderMode, str) and borderMode == 0): border = 0
-    elif                       borderMode == 'transparent' or (not isinstance(borderMode, str) and borderMode == 5): border = 5
-    else: raise Exception(f"borderMode must be None, 'constant' (0) or 'transparent' (5), not {borderMode!r}")
-    if   interpolation is None or interpolation == 'linear'  or (not isinstance(interpolation, str) and interpolation == 1): interp = 1
-    elif                          interpolation == 'nearest' or (not isinstance(interpolation, str) and interpolation == 0): interp = 0
-    else: raise Exception(f"interpolation must be None, 'linear' (1) or 'nearest' (0), not {interpolation!r}")
-    return border, interp
-
-
-def _border_values(borderValue, channels):
-    b = np.atleast_1d(np.asarray(borderValue, dtype=np.float64)).ravel()
-    if b.size == 1: b = np.repeat(b, channels)
-    if b.size < channels:
-        raise Exception(f"borderValue must be a scalar or have a value per channel ({channels}), got {b.size}")
-    return np.ascontiguousarray(b[:channels])
-
-
-def _output_array(out, shape, dtype, transparent):
-    """-> (the dense array the library fills, the array to return)"""
-    if out is None:
-        o = np.zeros(shape, dtype=dtype)
-        return o, o
-    if not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != dtype:
-        raise Exception(f"'out' must be a numpy array of shape {shape} and dtype {np.dtype(dtype)}")
-    if out.flags.c_contiguous:
-        return out, out
-    return (np.ascontiguousarray(out) if transparent else np.empty(shape, dtype=dtype)), out
-
-
 class Rectification(Handle):
     """The rectification of a stereo pair, resident: both maps are made on the device once and stay there.
 
@@ -254,30 +211,40 @@ class Rectification(Handle):
                      _rectification_model_type(lib, rectification_model), _ptr(fxycxy), C.addressof(imagersize),
                      _ptr(r_rect0_ref), _baseline(models_rectified))
 
-    def _equalize(self, params):
-        """what the calls that follow do to their raw images; None: nothing, which a handle that was never told
-        otherwise does by itself"""
-        if params is None and not getattr(self, "_equalizing", False):
-            return
-        p = params if params is not None else _EqualizeParams(0, 8.0, 8, 8)
-        self._call("equalize()", "mrcal_amd_rectification_set_equalization", C.addressof(p))
-        self._equalizing = params is not None
+    # what the handle last received of the two settings, as plain values; None: nothing, which a new handle does by itself
+    _sent = (None, None)
+    _antialias_auto_sigma = None
 
     def _antialias_auto(self):
         """antialias_sigma() of the two maps, the larger: computed once"""
-        if getattr(self, "_antialias_auto_sigma", None) is None:
+        if self._antialias_auto_sigma is None:
             maps = self.maps()
             self._antialias_auto_sigma = max(antialias_sigma(maps[0]), antialias_sigma(maps[1]))
         return self._antialias_auto_sigma
 
-    def _antialias(self, antialias, images):
-        """what the calls that follow do to their raw images after the equalization; None: nothing, which a handle
-        that was never told otherwise does by itself"""
-        params = antialias_params(antialias, self._antialias_auto, images)
-        if params is None and not getattr(self, "_antialiasing", False):
-            return
-        self._call("smooth()", "mrcal_amd_rectification_set_antialias", None if params is None else C.addressof(params))
-        self._antialiasing = params is not None
+    def _prepare(self, eq, smooth):
+        """What the calls that follow do to their raw images between the upload and the remap: eq, smooth: what
+        equalization_params() and antialias_params() made of the keywords, after every refusal; None: nothing of it.
+        Each is sent only where it differs from what the handle last received"""
+        settings = (None if eq is None else (eq.method, eq.clip_limit, eq.tiles_x, eq.tiles_y),
+                    None if smooth is None else (smooth.sigma_x, smooth.sigma_y))
+        if settings[0] != self._sent[0]:
+            p = eq if eq is not None else _EqualizeParams(0, 8.0, 8, 8)
+            self._call("equalize()", "mrcal_amd_rectification_set_equalization", C.addressof(p))
+            self._sent = (settings[0], self._sent[1])
+        if settings[1] != self._sent[1]:
+            self._call("smooth()", "mrcal_amd_rectification_set_antialias", None if smooth is None else C.addressof(smooth))
+            self._sent = settings
+
+    @staticmethod
+    def _matcher_pair(image0, image1):
+        """a grayscale pair of one dtype for the matcher -> its dtype code"""
+        for image in (image0, image1):
+            if not isinstance(image, np.ndarray) or image.ndim != 2 or image.size == 0:
+                raise Exception("stereo_matching_sgm() accepts ONLY grayscale images of shape (H,W)")
+        if image0.dtype != image1.dtype:
+            raise Exception(f"stereo_matching_sgm(): image0 and image1 must have the same dtype, got {image0.dtype} and {image1.dtype}")
+        return _SGM_DTYPES[_sgm_dtype(image0.dtype)]
 
     def maps(self):
         self._open()
@@ -289,10 +256,7 @@ class Rectification(Handle):
         """(image0 rectified, image1 rectified): linear interpolation, 0 outside the images. out: the two arrays to fill.
         equalization, antialias: of the raw images, on the device, before the remap (grayscale, uint8 or uint16, then)"""
         self._open()
-        if equalization is None:
-            eq, dtype_out = None, None
-        else:
-            eq, dtype_out = equalization_params(equalization, clahe_clip_limit, clahe_tiles, (image0, image1))
+        eq, dtype_out = equalization_params(equalization, clahe_clip_limit, clahe_tiles, (image0, image1))
         a0, w0, h0, c0, t0 = _image_arguments(image0, "image0")
         a1, w1, h1, c1, t1 = _image_arguments(image1, "image1")
         if (c0, t0) != (c1, t1):
@@ -302,8 +266,7 @@ class Rectification(Handle):
             raise Exception("'out' must be a pair of arrays")
         (o0, r0), (o1, r1) = (_output_array(None if out is None else out[i], shape, a0.dtype if dtype_out is None else dtype_out, False)
                               for i in (0, 1))
-        self._equalize(eq)
-        self._antialias(antialias, (image0, image1))
+        self._prepare(eq, antialias_params(antialias, self._antialias_auto, (image0, image1)))
         self._call("rectify()", "mrcal_amd_rectification_rectify", _ptr(o0), _ptr(o1), _ptr(a0), w0, h0, _ptr(a1), w1, h1,
                    c0, t0, 1, 0, None)
         if r0 is not o0: r0[...] = o0
@@ -328,15 +291,9 @@ class Rectification(Handle):
         self._open()
         speckle = _speckle_keywords(speckle_window_size, speckle_range)
         p = _sgm_params(**params)
-        for image in (image0, image1):
-            if not isinstance(image, np.ndarray) or image.ndim != 2 or image.size == 0:
-                raise Exception("stereo_matching_sgm() accepts ONLY grayscale images of shape (H,W)")
-        if image0.dtype != image1.dtype:
-            raise Exception(f"stereo_matching_sgm(): image0 and image1 must have the same dtype, got {image0.dtype} and {image1.dtype}")
-        dtype = _SGM_DTYPES[_sgm_dtype(image0.dtype)]
-        eq = None if equalization is None else equalization_params(equalization, clahe_clip_limit, clahe_tiles, (image0, image1))[0]
-        self._equalize(eq)
-        self._antialias(antialias, (image0, image1))
+        dtype = self._matcher_pair(image0, image1)
+        eq, _ = equalization_params(equalization, clahe_clip_limit, clahe_tiles, (image0, image1))
+        self._prepare(eq, antialias_params(antialias, self._antialias_auto, (image0, image1)))
         a0, a1 = np.ascontiguousarray(image0), np.ascontiguousarray(image1)
         out = np.zeros((self.Nel, self.Naz), dtype=np.int16)
         images = (_ptr(a0), a0.shape[1], a0.shape[0], _ptr(a1), a1.shape[1], a1.shape[0], dtype, C.addressof(p))
@@ -378,15 +335,9 @@ class Rectification(Handle):
         p_sgm = _sgm_params(**sgm_params)
         if p_sgm.disparity_min < 0:
             raise Exception(f"stereo_point_cloud(): disparity_min must not be negative: the cast to uint16 of stereo_range() has no meaning for negative disparities. Got {p_sgm.disparity_min}")
-        for image in (image0, image1):
-            if not isinstance(image, np.ndarray) or image.ndim != 2 or image.size == 0:
-                raise Exception("stereo_matching_sgm() accepts ONLY grayscale images of shape (H,W)")
-        if image0.dtype != image1.dtype:
-            raise Exception(f"stereo_matching_sgm(): image0 and image1 must have the same dtype, got {image0.dtype} and {image1.dtype}")
-        sgm_dtype = _SGM_DTYPES[_sgm_dtype(image0.dtype)]
-        eq, dtype_equalized = (None, None) if equalization is None else \
-            equalization_params(equalization, clahe_clip_limit, clahe_tiles, (image0, image1))
-        self._antialias(antialias, (image0, image1))
+        sgm_dtype = self._matcher_pair(image0, image1)
+        eq, dtype_equalized = equalization_params(equalization, clahe_clip_limit, clahe_tiles, (image0, image1))
+        smooth = antialias_params(antialias, self._antialias_auto, (image0, image1))
         a0, a1 = np.ascontiguousarray(image0), np.ascontiguousarray(image1)
         # (image0 as its own colour image: the SAME array, which the library then takes equalized, where it lies)
         image = _cloud_image(a0 if color_image is None else color_image, "image0" if color_image is None else "color_image", self._models)
@@ -396,7 +347,7 @@ class Rectification(Handle):
         p, keep = _cloud_params(0, 0, 0, rmin, rmax, Rt, float32, image)       # (the disparity fields: the library's, from the matcher's)
         if eq is not None and color_image is None and dtype_equalized != a0.dtype:
             image = (np.zeros((0,), dtype=dtype_equalized),) + tuple(image[1:])      # (what the colours are read into: 'stretch' makes uint8)
-        self._equalize(eq)
+        self._prepare(eq, smooth)           # (after every refusal)
         N = C.c_int(0)
         self._call("stereo_point_cloud()", "mrcal_amd_rectification_point_cloud_of_images", _ptr(a0), a0.shape[1], a0.shape[0],
                    _ptr(a1), a1.shape[1], a1.shape[0], sgm_dtype, C.addressof(p_sgm), *speckle, C.addressof(p), C.addressof(N))
@@ -653,8 +604,7 @@ of features of image0 in image1.
 
     def __init__(self, image0, image1, *, equalization=None, clahe_clip_limit=8.0, clahe_tiles=(8, 8)):
         (a0, w0, h0), (a1, w1, h1), dtype = _match_images(image0, image1)
-        eq, dtype_equalized = (None, None) if equalization is None else \
-            equalization_params(equalization, clahe_clip_limit, clahe_tiles, (image0, image1))
+        eq, dtype_equalized = equalization_params(equalization, clahe_clip_limit, clahe_tiles, (image0, image1))
         self._dtype = a0.dtype if eq is None else dtype_equalized
         if eq is None:
             self._create("match_feature()", "mrcal_amd_feature_matcher_create", _ptr(a0), w0, h0, _ptr(a1), w1, h1, dtype)
@@ -937,7 +887,6 @@ Sobel-filtered images, its adaptive P2, colour input, and ELAS itself: nothing i
 # ---------------------------------------------------------------------------------------------------------------------
 # filter_speckles(): small regions of a disparity image become invalid (csrc/speckle_filter.hip)
 
-_SPECKLE_MAX_PIXELS = 1 << 28
 _INT32_MAX = (1 << 31) - 1
 
 
@@ -969,7 +918,7 @@ def _speckle_shape(shape):
     except TypeError: shape = ()
     if len(shape) != 2:
         raise Exception(f"filter_speckles(): shape must be (H,W), got {shape}")
-    if shape[0] <= 0 or shape[1] <= 0 or shape[0]*shape[1] > _SPECKLE_MAX_PIXELS:
+    if shape[0] <= 0 or shape[1] <= 0 or shape[0]*shape[1] > MAX_PIXELS:
         raise Exception(f"filter_speckles(): images of {shape[1]} x {shape[0]} pixels cannot be filtered")
     return shape
 
@@ -1059,7 +1008,6 @@ the device. The N = 1 case of SpeckleFilter.filter()."""
 # ---------------------------------------------------------------------------------------------------------------------
 # stereo_point_cloud(): disparities to a compacted, coloured cloud of points (csrc/point_cloud.hip)
 
-_CLOUD_MAX_PIXELS = 1 << 28
 _CLOUD_FRAMES = ('ref', 'cam0', 'rect0')
 _CLOUD_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1}
 
@@ -1079,8 +1027,8 @@ def _cloud_disparity(disparity, shape, disparity_scale, disparity_min, disparity
                         (f", got shape {disparity.shape} and dtype {disparity.dtype}" if isinstance(disparity, np.ndarray) else ""))
     if disparity.shape != shape:
         raise Exception(f"stereo_point_cloud(): the disparity and the rectified images MUST have the same dimensions. I have disparity.shape={disparity.shape} and models_rectified[0].imagersize()={(shape[1], shape[0])}")
-    if shape[0]*shape[1] > _CLOUD_MAX_PIXELS:
-        raise Exception(f"stereo_point_cloud(): a disparity image of {shape[1]} x {shape[0]} pixels cannot be made a cloud of: at most {_CLOUD_MAX_PIXELS} pixels")
+    if shape[0]*shape[1] > MAX_PIXELS:
+        raise Exception(f"stereo_point_cloud(): a disparity image of {shape[1]} x {shape[0]} pixels cannot be made a cloud of: at most {MAX_PIXELS} pixels")
     if disparity_min is not None and disparity_scaled_min is not None and disparity_min != disparity_scaled_min:
         raise Exception("disparity_min and disparity_scaled_min may not both be given")
     if disparity_max is not None and disparity_scaled_max is not None and disparity_max != disparity_scaled_max:
@@ -1182,8 +1130,8 @@ made once, and every point_cloud() reuses them; the output buffers grow when a c
             if not isinstance(map0, np.ndarray) or map0.dtype != np.float32 or map0.shape != (self.Nel, self.Naz, 2):
                 raise Exception(f"stereo_point_cloud(): map0 must be a float32 numpy array of shape {(self.Nel, self.Naz, 2)}")
             map0 = np.ascontiguousarray(map0)
-        if self.Nel*self.Naz > _CLOUD_MAX_PIXELS:
-            raise Exception(f"stereo_point_cloud(): a disparity image of {self.Naz} x {self.Nel} pixels cannot be made a cloud of: at most {_CLOUD_MAX_PIXELS} pixels")
+        if self.Nel*self.Naz > MAX_PIXELS:
+            raise Exception(f"stereo_point_cloud(): a disparity image of {self.Naz} x {self.Nel} pixels cannot be made a cloud of: at most {MAX_PIXELS} pixels")
         lib, _ = _handle._libs()
         rectification_model, fxycxy = models_rectified[0].intrinsics()
         fxycxy = np.ascontiguousarray(fxycxy, dtype=np.float64)

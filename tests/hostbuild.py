@@ -29,12 +29,14 @@ PROGRAMS = {
     "equalize_plan_check":           ((), True),
     "gram_banks_check":              ((), False),       # prints its table first: test_gram_banks.py
     "gram_packing_check":            ((), True),
+    "image_prepare_check":           ((), True),
     "lensfit_plan_check":            ((), True),
     "match_plan_check":              ((), True),
     "point_cloud_plan_check":        ((), True),
     "problem_plan_check":            (("problem_plan.cpp",), True),
     "regional_stats_plan_check":     ((), True),
     "sgm_plan_check":                ((), True),
+    "smooth_plan_check":             ((), True),
     "speckle_plan_check":            ((), True),
     "valid_region_check":            (("region_outline.cpp",), False),      # takes a file of masks: test_valid_region_host.py
 }

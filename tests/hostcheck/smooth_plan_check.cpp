@@ -4,7 +4,7 @@
 // offsets of the parts of the pooled allocation, and the refusal of an image that does not fit the free device memory.
 // Not a product path, and nothing loads it into Python.
 //
-//   built by tests/test_smooth_host.py with hostbuild._build(..., hostbuild.PROGRAM_FLAGS). No arguments
+//   built by tests/hostbuild.py, build_program("smooth_plan_check"): a row of its PROGRAMS. No arguments
 //   (prints "ok"; a sanitizer report or a failed check ends it with a non-zero status)
 #include <stdio.h>
 #include <stdlib.h>

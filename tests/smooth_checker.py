@@ -1,4 +1,4 @@
-"""The definition of the anti-aliasing Gaussian pre-filter (include/mrcal_amd_smooth.h), restated twice: vectorised
+"""The definition of the anti-aliasing Gaussian pre-filter (include/mrcal_amd.h, "smoothing"), restated twice: vectorised
 numpy (smooth) and plain loops (smooth_loops). The kernel of csrc/smooth.hip must EQUAL them in every pixel. Also the
 taps (weights) and the sigma that 'auto' picks for a map (antialias_sigma). A plain module: the tests import it. No
 cv2, and no claim of equality with cv2.GaussianBlur()."""

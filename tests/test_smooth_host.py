@@ -1,21 +1,15 @@
-"""The anti-aliasing Gaussian pre-filter (include/mrcal_amd_smooth.h), the part that needs no GPU: the two restatements of
-the definition against each other, the taps of the library against the checker's, the plan of csrc/smooth_plan.hpp
-under the host sanitizers, the second signature table against its header, the sigma that 'auto' picks, and every
-refusal that is made before any device work."""
-import ctypes
+"""The anti-aliasing Gaussian pre-filter (include/mrcal_amd.h, "smoothing"), the part that needs no GPU: the two
+restatements of the definition against each other, the taps of the library against the checker's, the plan of
+csrc/smooth_plan.hpp under the host sanitizers, the sigma that 'auto' picks, and every refusal that is made before any
+device work."""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
 import hostbuild
 import smooth_checker as chk
-from test_cabi_symbols import kind_in_header, kind_in_table
 
-HEADER = os.path.join(ROOT, "include", "mrcal_amd_smooth.h")
 SIGMAS = (0.5, 0.87, 1.3, 1.936, 3.3, 5, 8)
 
 
@@ -59,42 +53,7 @@ def test_the_librarys_taps(amd, sigma):
 
 def test_smooth_plan_under_the_host_sanitizers():
     """csrc/smooth_plan.hpp driven by a stand-alone program with its own main, built with ASan and UBSan: host code only"""
-    source = os.path.join(ROOT, "tests", "hostcheck_smooth", "smooth_plan_check.cpp")
-    program = hostbuild._build(os.path.join(hostbuild.BUILD, "smooth_plan_check"), [source], hostbuild.PROGRAM_FLAGS)
-    r = hostbuild.subprocess.run([program], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
-
-
-def prototypes():
-    """[(return type, name, [parameter, ...])] of include/mrcal_amd_smooth.h"""
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", " ", text)
-    text = "\n".join(line for line in text.split("\n") if not line.lstrip().startswith("#"))
-    text = re.sub(r'extern\s+"C"\s*\{', " ", text)
-    out = []
-    for m in re.finditer(r"([A-Za-z_][\w\s\*]*?[\s\*])(\w+)\s*\(([^()]*)\)\s*;", text):
-        parameters = m.group(3).strip()
-        out.append((m.group(1).strip(), m.group(2), [] if parameters in ("", "void") else [a.strip() for a in parameters.split(",")]))
-    return out
-
-
-def test_second_signature_table_agrees_with_its_header():
-    """_cabi.SIGNATURES_SMOOTH against include/mrcal_amd_smooth.h: a row for every prototype and no other, the same
-    number of arguments and the same kind of value each; every name exported, and none of them in the first table"""
-    from mrcal_amd._cabi import SIGNATURES, SIGNATURES_SMOOTH
-    declared = {name: (ret, parameters) for ret, name, parameters in prototypes()}
-    assert len(declared) == 7 and "#include \"mrcal_amd.h\"" in open(HEADER).read()
-    assert sorted(declared) == sorted(SIGNATURES_SMOOTH)
-    assert not set(SIGNATURES_SMOOTH) & set(SIGNATURES)
-    for name, (ret, parameters) in declared.items():
-        restype, argtypes = SIGNATURES_SMOOTH[name]
-        assert kind_in_table(restype) == kind_in_header(ret, False), name
-        assert len(argtypes) == len(parameters), name
-        for parameter, argtype in zip(parameters, argtypes):
-            assert kind_in_table(argtype) == kind_in_header(parameter, True), (name, parameter)
-    lib = ctypes.CDLL(os.path.join(ROOT, "mrcal_amd", "libmrcal_amd.so"))
-    assert not [n for n in SIGNATURES_SMOOTH if not hasattr(lib, n)]
+    hostbuild.assert_prints_ok("smooth_plan_check")
 
 
 def decimating_map(shape, step):
